@@ -2,6 +2,7 @@
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: one rank per GPU under torch.distributed.run — started bare, bench.py
                                                             launches the ranks itself; a WORLD_SIZE that differs from N is an error)
+    python bench.py ... --dump-outputs DIR                 (after the K timed steps: what the last one left the caller, DIR/<name>.npy)
 
 One "step" = one full reference training step (ddpm_torch/utils/train.py:148-170: forward, backward, global-norm clip,
 Adam, LR schedule, EMA, loss reduce incl. loss.item()) on B=128 synthetic 32x32 images PER GPU (weak scaling), bf16
@@ -180,9 +181,10 @@ def settle(tr, x0, first_step, limit=40):
     return extra
 
 
-def timed_steps(tr, x0, steps, warmup, sync, blocks=1):
+def timed_steps(tr, x0, steps, warmup, sync, blocks=1, parts=1):
     """`blocks` consecutive timed regions of exactly `steps` steps each, every one bracketed by sync() (barrier + device sync) on both
-    sides.  Returns the list of block times in seconds (the reported figure is the median block)."""
+    sides.  Returns the list of block times in seconds.  With `parts` > 1 the steps of a block are also split into that many consecutive
+    parts by device events (no host synchronisation between them); their times, in seconds, are left in `timed_steps.parts`."""
     for i in range(warmup):
         tr.step(x0, global_steps=i + 1)
     warmup += settle(tr, x0, warmup + 1)
@@ -190,16 +192,53 @@ def timed_steps(tr, x0, steps, warmup, sync, blocks=1):
     sync()
     before = [(d.choice, id(d.graph), id(d.plan), d.captures) for d in tr._direct.values()]
     els = []
+    ends = {steps * (j + 1) // parts for j in range(parts)} if parts > 1 else set()
     for blk in range(blocks):
+        evs = [torch.cuda.Event(enable_timing=True)] if ends else []
+        for e in evs:
+            e.record()
         t0 = time.perf_counter()
         for i in range(steps):
             tr.step(x0, global_steps=warmup + blk * steps + i + 1)
+            if i + 1 in ends:
+                evs.append(torch.cuda.Event(enable_timing=True))
+                evs[-1].record()
         tr.current_stats                 # every step's loss read-back is collected INSIDE the timed region (the last one is still pending)
         sync()
         els.append(time.perf_counter() - t0)
+        timed_steps.parts = [a.elapsed_time(b) * 1e-3 for a, b in zip(evs, evs[1:])]
     after = [(d.choice, id(d.graph), id(d.plan), d.captures) for d in tr._direct.values()]
     assert before == after, f"the step changed form inside the timed region: {before} -> {after}"
     return els
+
+
+def dump_outputs(out_dir, model, tr, n_sample=1 << 21, seed=0):
+    """What the timed training step leaves its caller after its last step, as float32 .npy files under `out_dir` (~32 MB): the
+    parameters, Adam's two moments and the EMA shadow, each as the same fixed, seeded sample of `n_sample` entries of the flattened
+    parameter list (named_parameters order), and the trainer's loss statistic.  Returns {file name: what it holds}."""
+    import numpy as np
+    named = [(k, p) for k, p in model.named_parameters() if p.requires_grad]
+    total = sum(p.numel() for _, p in named)
+    n = min(n_sample, total)
+    idx = torch.randperm(total, generator=torch.Generator().manual_seed(seed))[:n].sort().values
+    dev = named[0][1].device
+    idx_dev = idx.to(dev)
+
+    def sample(tensors):
+        return torch.cat([t.detach().reshape(-1).float() for t in tensors])[idx_dev].cpu().numpy()
+    state = tr.optimizer.state
+    arrays = {"params": sample(p for _, p in named),
+              "adam_exp_avg": sample(state[p]["exp_avg"] for _, p in named),
+              "adam_exp_avg_sq": sample(state[p]["exp_avg_sq"] for _, p in named),
+              "ema_shadow": sample(tr.ema.shadow[k] for k, _ in named),
+              "loss": np.array([tr.current_stats["loss"]], dtype=np.float32)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32))
+    what = f"{n} of the {total} trainable parameter entries (flattened in named_parameters order; torch.randperm, CPU generator seed {seed}, sorted)"
+    return {"params.npy": "parameters after the last timed step: " + what, "adam_exp_avg.npy": "Adam first moment, same entries",
+            "adam_exp_avg_sq.npy": "Adam second moment, same entries", "ema_shadow.npy": "EMA shadow weights, same entries",
+            "loss.npy": "Trainer.current_stats['loss'] after the timed steps (sample-weighted mean over every step the trainer ran)"}
 
 
 def median(v):
@@ -216,10 +255,14 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the fp32 / CelebA / CelebA-HQ lines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one left the caller (sampled parameters, Adam moments, EMA, loss) to DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # Started bare (`python bench.py --gpus N`): become the launcher — one rank per GPU under torch.distributed.run, rendezvous
         # on the loopback address (the reference self-spawns too: train.py:286-301).  The driver's own torchrun command line sets
@@ -301,17 +344,19 @@ def main():
             torch.cuda.synchronize()
 
     net.train()
-    # 5 consecutive blocks of exactly --steps steps, each bracketed by barrier + synchronize; per block the MAX over ranks; the line
-    # reports the MEDIAN block (one 0.2-s block cannot resolve a 2 % change: box jitter is of that order)
-    n_blocks = max(1, int(os.environ.get("BENCH_BLOCKS", "5")))
-    block_s = timed_steps(tr, x0, args.steps, args.warmup, sync, n_blocks)
+    # exactly --steps timed steps, bracketed by barrier + synchronize, the MAX over ranks; device events split them into up to
+    # BENCH_BLOCKS (5) consecutive parts without synchronising in between, whose spread is reported next to the figure
+    n_blocks = max(1, min(int(os.environ.get("BENCH_BLOCKS", "5")), args.steps))
+    elapsed = timed_steps(tr, x0, args.steps, args.warmup, sync, parts=n_blocks)[0]
+    part_s = timed_steps.parts if n_blocks > 1 else [elapsed]
     if distributed:
-        te = torch.tensor(block_s, device=dev)
+        te = torch.tensor([elapsed], device=dev)
         dist.all_reduce(te, op=dist.ReduceOp.MAX)
-        block_s = [float(v) for v in te]
-    elapsed = median(block_s)
+        elapsed = float(te[0])
     ms_per_step = elapsed / args.steps * 1e3
     imgs_per_s = B_PER_GPU * world * args.steps / elapsed
+    part_steps = [args.steps * (j + 1) // n_blocks - args.steps * j // n_blocks for j in range(n_blocks)]
+    dumped = dump_outputs(args.dump_outputs, model, tr) if args.dump_outputs and rank == 0 else None
     loss = tr.current_stats["loss"]
     kinds = {d.last_kind for d in tr._direct.values()}
     form = "graph" if "graph" in kinds else ("plan" if "plan" in kinds else "eager")
@@ -389,10 +434,10 @@ def main():
         f, t = sum(v[1] for v in agg.values()), sum(v[2] for v in agg.values())
         return {"tflops": round(f / t / 1e12, 1), "ms": round(t * 1e3, 3), "frac": round(f / t / 1e12 / pk, 4)}
 
-    agg, shapes, hbm = profile_step(tr, x0, args.warmup + n_blocks * args.steps + 1)
+    agg, shapes, hbm = profile_step(tr, x0, args.warmup + args.steps + 1)
     side_was = unet_mod._SIDE_STREAM
     unet_mod._SIDE_STREAM = False
-    agg_iso, shapes_iso, hbm_iso = profile_step(tr, x0, args.warmup + n_blocks * args.steps + 2)
+    agg_iso, shapes_iso, hbm_iso = profile_step(tr, x0, args.warmup + args.steps + 2)
     unet_mod._SIDE_STREAM = side_was
     # (every rank ran the two extra steps above: with N > 1 they contain the gradient all-reduce and the loss reduce)
     # What the matrix pipe SUSTAINS on this box: an MFMA-only loop on register-resident random bf16 operands, ~0.3 s (the chip clocks to
@@ -506,8 +551,9 @@ def main():
                           "On one GPU the communicator has a single rank: the times show WHEN the exchanges are issued, not what xGMI does with them"}
         out = {"metric": "training imgs/s/GPU + 1000-step DDPM samples/s, CIFAR-10 UNet @1/2/4/8 MI355X",
                "value": round(imgs_per_s, 2), "unit": "imgs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-               "ms_per_step": round(ms_per_step, 3), "ms_per_step_blocks": [round(v / args.steps * 1e3, 3) for v in block_s],
-               "timing": f"median of {n_blocks} consecutive blocks of {args.steps} steps, each bracketed by barrier + device sync (max over ranks per block)",
+               "ms_per_step": round(ms_per_step, 3), "ms_per_step_blocks": [round(v / n * 1e3, 3) for v, n in zip(part_s, part_steps)],
+               "timing": f"{args.steps} consecutive steps bracketed by barrier + device sync (max over ranks); ms_per_step_blocks = the same steps "
+                         f"in {n_blocks} consecutive parts of {part_steps} steps timed by device events (rank 0)",
                "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
                "dtype": args.dtype, "data": "synthetic",
                "config": {"workload": "configs/cifar10.json UNet (35.7M params), full Trainer.step, B=128 per GPU, 32x32, T=1000, dropout 0.1, Adam+clip+EMA",
@@ -520,6 +566,8 @@ def main():
                           "train_model_tflops_per_gpu": round(imgs_per_s / world * 3 * FWD_GFLOP["cifar"] / 1e3, 1),
                           "train_model_frac_of_peak": round(imgs_per_s / world * 3 * FWD_GFLOP["cifar"] / 1e3 / peak, 4), "final_loss": round(loss, 4)},
                "roofline": roofline}
+        if dumped:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "files": dumped}
 
     # ---- sampling + the other BASELINE configurations (rank 0 only: independent work, no collectives)
     S = args.sample_steps

@@ -566,10 +566,80 @@ def g15_metrics():
     save("g15_metrics.pt", out)
 
 
+# ----------------------------------------------------------------------------- G16 oracle checks at their own seeds
+def g16_oracle_checks():
+    """What tests/test_oracle_vs_reference.py holds the oracle to, at seeds of its own (none shared with G1-G15): the reference's seeded
+    initialisation as its key / shape layout and one SHA-256 (bit-exactness needs no values), the UNet forward with every parameter gradient
+    (recipes.pack_grads: int16 fractions of the tensor's max |g|, 1.5e-5 of it, far inside the test's 2e-4 bar; tensors above GRAD_SAMPLE
+    entries as a fixed sample of entries plus the digest of the whole), a 60-step p_sample_progressive chain and the variational-bound
+    terms of loss_type="kl" for every mean / variance type."""
+    from oracle import diffusion_ref as D
+    from tests.golden.recipes import sha256_state, state_layout, pack_grads
+    cfgs = {"conv_resample": dict(in_channels=3, hid_channels=32, out_channels=3, ch_multipliers=[1, 2, 2], num_res_blocks=2,
+                                  apply_attn=[False, True, False], drop_rate=0.0)}
+    cfgs["pool_resample"] = dict(cfgs["conv_resample"], resample_with_conv=False)
+    out = {"init": {}, "fwd": {}, "sampling": {}, "vlb": {}}
+    for name, cfg in cfgs.items():
+        torch.manual_seed(77)
+        init = ref.UNet(**cfg).state_dict()
+        out["init"][name] = dict(layout=state_layout(init), sha256=sha256_state(init))
+        torch.manual_seed(901)
+        m = ref.UNet(**cfg)
+        sd = U.randomize_state_dict(m.state_dict(), 902)
+        m.load_state_dict(sd)
+        g = torch.Generator().manual_seed(902)
+        x, gy = torch.randn(3, 3, 16, 16, generator=g), torch.randn(3, 3, 16, 16, generator=g)
+        m.train()
+        y = m(x, torch.tensor([0, 412, 999]))
+        (y * gy).sum().backward()
+        out["fwd"][name] = dict(state=sha256_state(sd), y=y.detach().clone(),
+                                grads=pack_grads({k: q.grad for k, q in m.named_parameters()}))
+    cfg = cfgs["conv_resample"]
+    torch.manual_seed(911)
+    m = ref.UNet(**cfg)
+    sd = U.randomize_state_dict(m.state_dict(), 912)
+    m.load_state_dict(sd)
+    m.eval()
+    for var_type in ("fixed-small", "fixed-large"):
+        dif = ref.GaussianDiffusion(ref.get_beta_schedule("linear", 1e-4, 0.02, 60), "eps", var_type, "mse")
+        x, preds = dif.p_sample_progressive(m, shape=(2, 3, 16, 16), device=torch.device("cpu"), pred_freq=10, seed=5)
+        out["sampling"][var_type] = dict(state=sha256_state(sd), x=x.clone(), preds=preds.clone())
+    betas = D.beta_schedule("linear", 1e-4, 0.02, 1000)
+    for mean_type in ("eps", "x_0", "mean"):
+        for var_type in ("fixed-small", "fixed-large"):
+            dif = ref.GaussianDiffusion(betas=betas, model_mean_type=mean_type, model_var_type=var_type, loss_type="kl")
+            g = torch.Generator().manual_seed(4242)
+            x_0 = (torch.rand(5, 3, 8, 8, generator=g) * 2 - 1).clamp(-1, 1)
+            x_0[0, 0, 0, :4] = torch.tensor([1.0, -1.0, 0.9995, -0.9995])
+            noise = torch.randn(5, 3, 8, 8, generator=g)
+            t = torch.tensor([0, 0, 1, 500, 999])
+            w = torch.randn(5, 3, 8, 8, generator=g) * 0.3
+            outs = {}
+
+            def net(x_t, tt):
+                o = (0.7 * x_t + w).detach().requires_grad_(True)
+                outs["o"] = o
+                return o
+            losses = dif.train_losses(net, x_0, t, noise=noise)
+            losses.sum().backward()
+            o_ref = outs["o"]
+            try:
+                dif._prior_bpd(x_0)
+                prior_raises = False
+            except RuntimeError:
+                prior_raises = True
+            with torch.no_grad():
+                x_t = D.q_sample(D.ddpm_tables(betas, var_type), x_0, t, noise)
+                l2, p2 = dif._loss_term_bpd(lambda a, b: o_ref.detach(), x_0, x_t, t, clip_denoised=True, return_pred=True)
+            out["vlb"][f"{mean_type}/{var_type}"] = dict(o=o_ref.detach().clone(), losses=losses.detach().clone(), o_grad=o_ref.grad.clone(),
+                                                          clipped_losses=l2.clone(), clipped_pred=p2.clone(), prior_bpd_raises=prior_raises)
+    save("g16_oracle_checks.pt", out)
+
+
 if __name__ == "__main__":
     import sys
     ALL = dict(g1=g1_ops, g2=g2_blocks, g3=g3_model, g4=g4_tables, g5=g5_steps, g6=g6_loops, g7=g7_train, g8=g8_toy, g9=g9_train_lr, g10=g10_config2,
                g11=g11_config2_bench_batch, g12=g12_config2_train_steps, g13=g13_config5_and_4_at_their_batches,
-               g14=g14_config4_ddim50_at_its_batch, g15=g15_metrics)
+               g14=g14_config4_ddim50_at_its_batch, g15=g15_metrics, g16=g16_oracle_checks)
     for name in (sys.argv[1:] or list(ALL)):          # `make_golden.py g9` regenerates one fixture, no argument = all
         ALL[name]()

@@ -4,6 +4,8 @@ A *recipe* regenerates an input from a CPU seed (torch's CPU RNG stream is stabl
 keeps its digest so drift is detected.  A *digest* stands in for a tensor too large to commit:
 (sum, |.|-sum, squares-sum in fp64 + 32-element head/tail).  Small tensors are stored whole.
 """
+import hashlib
+
 import torch
 
 FULL_LIMIT = 4096
@@ -91,3 +93,74 @@ def g15_inputs(D=48, seed=151):
     gen = torch.randn(700, D, generator=g) @ mix + 0.3
     real = torch.randn(900, D, generator=g) @ (mix * 1.1) + torch.linspace(-0.2, 0.4, D)
     return gen, real
+
+
+# ---- fixture G16: bit-exact tensors by hash, gradients as 16-bit fractions of their max magnitude
+GRAD_SAMPLE = 256
+
+
+def state_layout(sd):
+    """[(key, dtype, shape)] in the state dict's order."""
+    return [(k, str(v.dtype), tuple(v.shape)) for k, v in sd.items()]
+
+
+def sha256_state(sd):
+    """SHA-256 over every key, dtype, shape and tensor's bytes in the state dict's order: equal digests <=> same keys, order and bits."""
+    h = hashlib.sha256()
+    for (k, dt, shape), v in zip(state_layout(sd), sd.values()):
+        h.update(repr((k, dt, shape)).encode())
+        h.update(v.detach().cpu().contiguous().numpy().tobytes())
+    return h.hexdigest()
+
+
+def quantize16(t, scale=None):
+    """(scale, int16 q) with t ~= q * scale / 32767 and scale = max |t| unless given (>= it): every element within scale / 65534 of its
+    value."""
+    scale = float(t.detach().abs().max()) if scale is None else scale
+    q = torch.round(t.detach().double() / (scale or 1.0) * 32767).to(torch.int16)
+    return dict(scale=scale, q=q)
+
+
+def dequantize16(rec):
+    """The tensor ``quantize16`` packed (fp64) and the bound on its distance from the original."""
+    return rec["q"].double() * (rec["scale"] / 32767), rec["scale"] / 65534
+
+
+def sample_index(numel, n=GRAD_SAMPLE):
+    """``n`` fixed, sorted entries of a flattened tensor of ``numel`` elements (seeded by ``numel``; torch's CPU generator, so the same
+    entries on every machine)."""
+    return torch.randperm(numel, generator=torch.Generator().manual_seed(numel))[:n].sort().values
+
+
+def pack_grad(t):
+    """A gradient for fixture G16, quantised against its own max |g| (``scale``): whole up to GRAD_SAMPLE entries, else the
+    ``sample_index`` entries plus the digest of the whole tensor."""
+    flat = t.detach().reshape(-1)
+    scale = float(flat.abs().max())
+    if flat.numel() <= GRAD_SAMPLE:
+        return quantize16(flat, scale)
+    return dict(quantize16(flat[sample_index(flat.numel())], scale), digest=digest(t))
+
+
+def pack_grads(grads):
+    """``pack_grad`` of every {key: gradient}, concatenated into a few tensors (one file record each instead of one per tensor)."""
+    recs = {k: pack_grad(t) for k, t in grads.items()}
+    big = [k for k, r in recs.items() if "digest" in r]
+    return dict(keys=list(recs), scale=torch.tensor([r["scale"] for r in recs.values()], dtype=torch.float64),
+                counts=[r["q"].numel() for r in recs.values()], q=torch.cat([r["q"] for r in recs.values()]),
+                digested=big, shapes=[recs[k]["digest"]["shape"] for k in big],
+                sums=torch.tensor([[recs[k]["digest"][f] for f in ("sum", "abs_sum", "sq_sum")] for k in big], dtype=torch.float64),
+                ends=torch.stack([torch.cat([recs[k]["digest"]["head"], recs[k]["digest"]["tail"]]) for k in big]))
+
+
+def unpack_grads(rec):
+    """{key: the ``pack_grad`` record} from ``pack_grads``, in the original order."""
+    out, off = {}, 0
+    for k, scale, n in zip(rec["keys"], rec["scale"].tolist(), rec["counts"]):
+        out[k] = dict(scale=scale, q=rec["q"][off:off + n])
+        off += n
+    for i, k in enumerate(rec["digested"]):
+        total, abs_total, sq_total = rec["sums"][i].tolist()
+        out[k]["digest"] = dict(shape=tuple(rec["shapes"][i]), sum=total, abs_sum=abs_total, sq_sum=sq_total,
+                                head=rec["ends"][i, :32], tail=rec["ends"][i, 32:])
+    return out

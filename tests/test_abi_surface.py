@@ -50,10 +50,13 @@ def test_argument_validation_returns_status_codes_without_a_gpu():
     with pytest.raises(RuntimeError, match="null pointer"):
         _hip.call("ddpm_silu_fwd", 0, 0, 10, 0)
     # maximum sizes: the kernels address an operand with 32-bit byte offsets, so a tensor of 2 GiB or more is refused on the host
-    # (32 x 32 x 384 channels bf16: B = 4096 is 3 GiB; B = 2048 = 1.5 GiB passes validation and only fails here for want of a GPU)
+    # (32 x 32 x 384 channels bf16: B = 4096 is 3 GiB; B = 2048 = 1.5 GiB passes validation).  Only the refused size goes through the
+    # launching entry point: a size that passes would launch a kernel on these fake addresses wherever a GPU is present, so it is put to
+    # the same dispatch with launching switched off (ddpm_conv2d_variant: the id of the kernel it would run, or -status)
     fake = 0x10000
     conv = lambda B: lib.ddpm_conv2d_nhwc(fake, 384, fake, fake, 128, 0, 0, 0, 0, 0, B, 32, 32, 384, 32, 32, 128, 3, 3, 1, 1, 1, 0, 0, 0, 0, 1, 0, 0, 1, 0)
-    assert conv(4096) == 1 and conv(2048) in (0, 4)
+    dry = lambda B: lib.ddpm_conv2d_variant(384, 128, B, 32, 32, 384, 32, 32, 128, 3, 3, 1, 1, 1, 0, 0, 0, 1, 1, 0)
+    assert conv(4096) == 1 and dry(4096) == -1 and dry(2048) >= 0
 
 
 QUERIES = {"ddpm_wgrad_effective_splits", "ddpm_conv3x3_wgrad_splits", "ddpm_conv1x1_wgrad_splits", "ddpm_gn_workspace_floats",

@@ -1,9 +1,19 @@
-"""CPU: the last committed bench.py output (profiles/*_bench_default.json) carries every field of the driver's contract."""
+"""CPU: the last committed bench.py output (profiles/*_bench_default.json) carries every field of the driver's contract; the launcher
+and --dump-outputs behave as documented."""
 import glob
 import json
 import os
 import subprocess
 import sys
+
+import numpy as np
+import pytest
+import torch
+
+import bench
+import ddpm_torch
+from ddpm_torch import _hip
+from tests import abi_emulator
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -69,3 +79,36 @@ def test_world_size_mismatch_is_an_error():
     assert r.returncode != 0 and "--gpus 4 but WORLD_SIZE=1" in (r.stderr + r.stdout)
     r = _bench(["--gpus", "1"], {})
     assert r.returncode == 0 and json.loads(r.stdout.strip().splitlines()[-1])["n_gpus"] == 1
+
+
+@pytest.mark.skipif(not os.path.exists(_hip.LIB_PATH), reason="libddpm_hip.so not built")
+def test_dump_outputs_writes_the_same_seeded_sample_every_run(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR` (CPU, C ABI emulated, a tiny trainer): float32 files of a fixed size, identical for identical inputs,
+    holding the parameters / Adam moments / EMA the trainer actually has at the sampled entries."""
+    abi_emulator.install(monkeypatch, _hip)
+    tiny = dict(in_channels=3, hid_channels=32, out_channels=3, ch_multipliers=[1, 2], num_res_blocks=1, apply_attn=[False, True], drop_rate=0.1)
+
+    def run(out):
+        ddpm_torch.seed_all(1234)
+        model, _, _, tr = bench.make_trainer(ddpm_torch, tiny, torch.device("cpu"), "fp32", (3, 8, 8), "fixed-large")
+        x0 = torch.rand(4, 3, 8, 8, generator=torch.Generator().manual_seed(1234)) * 2 - 1
+        for i in range(3):
+            tr.step(x0, global_steps=i + 1)
+        return model, tr, bench.dump_outputs(str(out), model, tr, n_sample=5000)
+
+    model, tr, files = run(tmp_path / "a")
+    run(tmp_path / "b")
+    assert sorted(files) == sorted(os.listdir(tmp_path / "a"))
+    named = [(k, p) for k, p in model.named_parameters() if p.requires_grad]
+    idx = torch.randperm(sum(p.numel() for _, p in named), generator=torch.Generator().manual_seed(0))[:5000].sort().values
+    flat = {"params": [p for _, p in named], "adam_exp_avg": [tr.optimizer.state[p]["exp_avg"] for _, p in named],
+            "adam_exp_avg_sq": [tr.optimizer.state[p]["exp_avg_sq"] for _, p in named], "ema_shadow": [tr.ema.shadow[k] for k, _ in named]}
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float32 and np.isfinite(a).all() and np.array_equal(a, b), f
+        name = f[:-len(".npy")]
+        if name in flat:
+            assert a.shape == (5000,) and np.array_equal(a, torch.cat([t.detach().reshape(-1) for t in flat[name]])[idx].numpy()), f
+        else:
+            assert a.shape == (1,) and a[0] == np.float32(tr.current_stats["loss"])
+    assert np.abs(np.load(tmp_path / "a" / "adam_exp_avg.npy")).max() > 0         # the steps ran: the moments moved

@@ -1,75 +1,87 @@
-"""CPU, BUILD CONTAINER ONLY (skipped wherever /root/reference is absent — always on the GPU box): the oracle against the live
-reference, beyond what the committed fixtures freeze.  Fresh seeds each run of this file would defeat reproducibility, so the seeds
-are fixed but DIFFERENT from the ones tests/golden/make_golden.py uses: an oracle that merely memorised the fixtures fails here."""
+"""CPU: the oracle against the reference's own numbers at seeds of these checks (fixture G16, tests/golden/make_golden.py g16), beyond
+what the other fixtures freeze.  The seeds are DIFFERENT from the ones every other fixture uses: an oracle that merely memorised those
+fails here.  The reference's inputs (seeded initialisation, randomised state, x, noise) are recreated on this side and pinned bit for bit
+against a SHA-256 of the reference's tensors before anything is compared."""
 import pytest
 import torch
 
 from oracle import diffusion_ref as D
-from oracle import load_reference as LR
 from oracle import unet_ref as U
-
-pytestmark = pytest.mark.skipif(not LR.available(), reason="reference checkout not mounted (build container only)")
+from tests.golden.recipes import check, dequantize16, sample_index, sha256_state, state_layout, unpack_grads
 
 CFG = dict(in_channels=3, hid_channels=32, out_channels=3, ch_multipliers=[1, 2, 2], num_res_blocks=2, apply_attn=[False, True, False], drop_rate=0.0)
 
 
 @pytest.fixture(scope="module")
-def ref():
+def g16(golden):
     torch.set_num_threads(1)
-    return LR.load()
+    return golden("g16_oracle_checks.pt")
 
 
 CFG_POOL = dict(CFG, resample_with_conv=False)          # AvgPool2d(2) / bare nearest Upsample (unet.py:163-170,196-199)
 
 
-def _model(ref, seed, cfg=CFG):
+def _state(seed, cfg=CFG):
+    """The reference's `torch.manual_seed(seed); UNet(**cfg)` + randomisation — its initialisation is the oracle's, bit for bit."""
     torch.manual_seed(seed)
-    m = ref.UNet(**cfg)
-    sd = U.randomize_state_dict(m.state_dict(), seed + 1)
-    m.load_state_dict(sd)
-    return m, sd
+    return U.randomize_state_dict(U.init_state_dict(cfg), seed + 1)
 
 
 @pytest.mark.parametrize("cfg", [CFG, CFG_POOL], ids=["conv_resample", "pool_resample"])
-def test_seeded_init_and_key_order_match(ref, cfg):
-    torch.manual_seed(77)
-    m = ref.UNet(**cfg)
+def test_seeded_init_and_key_order_match(g16, cfg):
     torch.manual_seed(77)
     mine = U.init_state_dict(cfg)
-    theirs = m.state_dict()
-    assert list(mine) == list(theirs)
-    for k in mine:
-        assert torch.equal(mine[k], theirs[k]), k
+    theirs = g16["init"]["pool_resample" if cfg is CFG_POOL else "conv_resample"]
+    assert [k for k, *_ in state_layout(mine)] == [k for k, *_ in theirs["layout"]]
+    assert state_layout(mine) == theirs["layout"]
+    assert sha256_state(mine) == theirs["sha256"]                                 # every tensor bit for bit
 
 
 @pytest.mark.parametrize("cfg", [CFG, CFG_POOL], ids=["conv_resample", "pool_resample"])
-def test_forward_and_every_gradient(ref, cfg):
-    m, sd = _model(ref, 901, cfg)
+def test_forward_and_every_gradient(g16, cfg):
+    rec = g16["fwd"]["pool_resample" if cfg is CFG_POOL else "conv_resample"]
+    sd = _state(901, cfg)
+    assert sha256_state(sd) == rec["state"]
     g = torch.Generator().manual_seed(902)
     x, gy = torch.randn(3, 3, 16, 16, generator=g), torch.randn(3, 3, 16, 16, generator=g)
     t = torch.tensor([0, 412, 999])
-    m.train()
-    y = m(x, t)
-    (y * gy).sum().backward()
+    y = rec["y"]
     p = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
     y2 = U.unet_forward(p, cfg, x, t, training=True)
     (y2 * gy).sum().backward()
     assert float((y - y2).detach().abs().max()) <= 2e-5 * float(y.detach().abs().max())
-    for k, q in m.named_parameters():
-        scale = max(float(q.grad.abs().max()), 1e-6)
-        assert float((q.grad - p[k].grad).abs().max()) <= 2e-4 * scale + 1e-6, k
+    grads = unpack_grads(rec["grads"])
+    assert list(grads) == [k for k in sd if p[k].grad is not None]
+    # Analytically-zero gradients (a per-channel constant in front of a GroupNorm with one channel per group: the 32-channel blocks'
+    # conv1 / time-projection biases and the like) are fp32 rounding noise, 1e-7..1e-6 of the median tensor scale against >= 0.1 for every
+    # other tensor.  Noise is reproduced bit for bit only by the same arithmetic on the same CPU, so on those the oracle is held to being
+    # zero up to rounding as well.  Every other tensor is compared entry by entry: whole up to GRAD_SAMPLE entries; above that on a fixed
+    # sample of entries, and as a whole against the digest of the reference's tensor (sums, sum of squares, first / last 32 entries).
+    noise = 1e-4 * sorted(q["scale"] for q in grads.values())[len(grads) // 2]
+    for k, q in grads.items():
+        mine = p[k].grad
+        if q["scale"] < noise:
+            assert float(mine.abs().max()) < noise, k
+            continue
+        flat = mine.double().reshape(-1)
+        if "digest" in q:
+            check(mine, q["digest"], 2e-4, name=k)
+            flat = flat[sample_index(flat.numel())]
+        ref_grad, qerr = dequantize16(q)
+        scale = max(q["scale"], 1e-6)
+        # |mine - reference| <= |mine - stored| + qerr: the stored gradient is held to the bar less its rounding
+        assert float((ref_grad - flat).abs().max()) <= 2e-4 * scale + 1e-6 - qerr, k
 
 
 @pytest.mark.parametrize("var_type", ["fixed-small", "fixed-large"])
-def test_progressive_sampling_loop(ref, var_type):
+def test_progressive_sampling_loop(g16, var_type):
     """p_sample_progressive (diffusion.py:176-198) on a 60-step chain: final sample and every kept pred_x0 against the oracle's loop
     fed with the noise stream the reference consumed (x_T first, then one z per step)."""
-    m, sd = _model(ref, 911)
-    m.eval()
-    betas = ref.get_beta_schedule("linear", 1e-4, 0.02, 60)
-    dif = ref.GaussianDiffusion(betas, "eps", var_type, "mse")
+    rec = g16["sampling"][var_type]
+    sd = _state(911)
+    assert sha256_state(sd) == rec["state"]
     shape = (2, 3, 16, 16)
-    x, preds = dif.p_sample_progressive(m, shape=shape, device=torch.device("cpu"), pred_freq=10, seed=5)
+    x, preds = rec["x"], rec["preds"]
     g = torch.Generator().manual_seed(5)
     x_T = torch.empty(shape).normal_(generator=g)
     zs = [torch.empty(shape).normal_(generator=g) for _ in range(60)]
@@ -94,11 +106,11 @@ def test_progressive_sampling_loop(ref, var_type):
 
 @pytest.mark.parametrize("mean_type", ["eps", "x_0", "mean"])
 @pytest.mark.parametrize("var_type", ["fixed-small", "fixed-large"])
-def test_variational_bound_terms_and_their_gradient(ref, mean_type, var_type):
+def test_variational_bound_terms_and_their_gradient(g16, mean_type, var_type):
     """loss_type="kl" (diffusion.py:222-224 -> `_loss_term_bpd`, :203-215): the oracle's restatement against the
-    live reference on a batch that mixes t = 0 (decoder NLL) with t > 0 (KL), values and the gradient with respect to the network output."""
+    reference on a batch that mixes t = 0 (decoder NLL) with t > 0 (KL), values and the gradient with respect to the network output."""
+    rec = g16["vlb"][f"{mean_type}/{var_type}"]
     betas = D.beta_schedule("linear", 1e-4, 0.02, 1000)
-    dif = ref.GaussianDiffusion(betas=betas, model_mean_type=mean_type, model_var_type=var_type, loss_type="kl")
     T = D.ddpm_tables(betas, var_type)
     g = torch.Generator().manual_seed(4242)
     x_0 = (torch.rand(5, 3, 8, 8, generator=g) * 2 - 1).clamp(-1, 1)
@@ -106,27 +118,20 @@ def test_variational_bound_terms_and_their_gradient(ref, mean_type, var_type):
     noise = torch.randn(5, 3, 8, 8, generator=g)
     t = torch.tensor([0, 0, 1, 500, 999])
     w = torch.randn(5, 3, 8, 8, generator=g) * 0.3
-    outs = {}
-
-    def net(x_t, tt):                 # a "network" whose output is a leaf we can differentiate with respect to
-        o = (0.7 * x_t + w).detach().requires_grad_(True)
-        outs["o"] = o
-        return o
-    losses = dif.train_losses(net, x_0, t, noise=noise)
-    losses.sum().backward()
-    o_ref = outs["o"]
+    # the reference's "network" output: a leaf 0.7 * x_t + w on its own x_t
+    losses, o_ref = rec["losses"], rec["o"]
     x_t = D.q_sample(T, x_0, t, noise)
+    assert torch.allclose(0.7 * x_t + w, o_ref, rtol=1e-6, atol=1e-6)
     o = o_ref.detach().clone().requires_grad_(True)
     mine, _ = D.loss_term_bpd(T, mean_type, x_0, x_t, t, o, clip_denoised=False)
     mine.sum().backward()
     assert torch.allclose(mine.detach(), losses.detach(), rtol=2e-5, atol=1e-6), (mine, losses)
-    assert float((o.grad - o_ref.grad).abs().max()) <= 1e-4 * float(o_ref.grad.abs().max()) + 1e-9      # (fp32 cancellation in cdf_upper - cdf_lower)
+    assert float((o.grad - rec["o_grad"]).abs().max()) <= 1e-4 * float(rec["o_grad"].abs().max()) + 1e-9      # (fp32 cancellation in cdf_upper - cdf_lower)
     # (`_prior_bpd` / `calc_all_bpd`, diffusion.py:245-267, cannot run in the reference: the jit-scripted `normal_kl` rejects the float
-    #  arguments `_prior_bpd` passes — nothing to pin, and the product does not carry them)
-    with pytest.raises(RuntimeError):
-        dif._prior_bpd(x_0)
+    #  arguments `_prior_bpd` passes — nothing to pin, and the product does not carry them; the fixture recorded the failure)
+    assert rec["prior_bpd_raises"]
     # clip_denoised = True (the evaluation path of calc_all_bpd) and the x_0 estimate
     with torch.no_grad():
-        l2, p2 = dif._loss_term_bpd(lambda a, b: o_ref.detach(), x_0, x_t, t, clip_denoised=True, return_pred=True)
+        l2, p2 = rec["clipped_losses"], rec["clipped_pred"]
         m2, q2 = D.loss_term_bpd(T, mean_type, x_0, x_t, t, o_ref.detach(), clip_denoised=True)
     assert torch.allclose(m2, l2, rtol=2e-5, atol=1e-6) and torch.allclose(q2, p2, rtol=1e-5, atol=1e-6)
