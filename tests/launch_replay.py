@@ -1,0 +1,1112 @@
+"""Launch recording and replay against float64 references (TEST INFRASTRUCTURE).
+
+record()   wraps ddpm_torch._hip._invoke while a workload runs and keeps one SIGNATURE per distinct launch: the entry name, every
+           scalar argument, and for every pointer argument whether it is NULL and its address modulo 256 (the hipStream_t is dropped).
+replay()   re-issues one recorded signature on fresh random inputs at that geometry — same pitches, same pointer offsets modulo 256,
+           the same optional operands present or absent, the same accumulate / output mode / splits — and compares every output with a
+           float64 torch restatement of include/ddpm_hip.h written here (tests/abi_emulator.py is not used as a reference).
+
+The float64 work runs in torch on the device that holds the buffers: the MI355X in the -m gpu test, the host in the CPU test.  Every
+image of every output is compared.
+
+Memory safety: every buffer's extent is computed from the contract (a pitched [rows][cols] operand spans (rows - 1) * ld + cols
+elements), and sits between two 64 KiB guard bands filled with a sentinel byte.  After each launch the guards, and every element of the
+buffer the contract does not let the call write (pitch gaps, read-only operands), must hold what they held before.
+
+Error model: each output element i gets its own bar
+    |got_i - ref_i| <= c * (u_out * M_i + u_acc * sqrt(K) * S_i)
+M_i is the sum of the magnitudes of the terms added into element i (the product sum, bias, row bias, residual, prior content), S_i is
+sqrt(sum_k (a_k b_k)^2) over the K products of a reduction (the same operation on squared operands), u_out is the unit roundoff of the
+stored type (2^-8 bf16, 2^-24 fp32) and u_acc = 2^-24 that of the fp32 accumulator.  Families whose error has another shape state their
+model where they are defined.  A bar is never a fraction of the tensor-wide maximum.
+"""
+import ctypes
+import math
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from ddpm_torch import _hip
+
+F32, BF16 = 0, 1
+U_BF16, U_F32 = 2.0 ** -8, 2.0 ** -24
+U_ACC = 2.0 ** -24
+GUARD = 64 * 1024                   # bytes of sentinel on each side of every buffer
+SENTINEL = 0xA5
+C_GEMM = 4                          # c of the GEMM-shaped families (conv, dgrad, wgrad, gemm, atb, colsum, upsample backward)
+C_NORM = 4                          # GroupNorm forward / backward
+C_ATTN = 4                          # attention forward / backward
+C_ELEM = 8                          # fp32 diffusion elementwise kernels (expf / sqrtf of the tables are a few ulp)
+TINY = 1e-30                        # floor of a bar: an element whose every term is exactly zero must come out exactly zero
+
+
+# ----------------------------------------------------------------------------------------------------------------- recording
+def _is_ptr(t):
+    return t is ctypes.c_void_p
+
+
+def signature(name, args):
+    types = _hip.PROTOTYPES[name]
+    n = len(args) if name == "ddpm_stream_order" else len(args) - 1          # the last argument is the hipStream_t
+    sig = []
+    for a, t in zip(args[:n], types[:n]):
+        if _is_ptr(t):
+            a = int(a or 0)
+            sig.append(("p", a == 0, a % 256))
+        elif t is ctypes.c_float:
+            sig.append(float(a))
+        else:
+            sig.append(int(a))
+    return (name, tuple(sig))
+
+
+class Recorder:
+    """Callable that stands in for _hip._invoke: keeps the distinct signatures (in first-seen order) and calls through."""
+
+    def __init__(self, inner):
+        self.inner = inner
+        self.sigs = {}
+
+    def __call__(self, name, args):
+        self.sigs.setdefault(signature(name, args), None)
+        return self.inner(name, args)
+
+    @property
+    def names(self):
+        return sorted({s[0] for s in self.sigs})
+
+
+# ----------------------------------------------------------------------------------------------------------------- guarded buffers
+_TD = {F32: torch.float32, BF16: torch.bfloat16, "i64": torch.int64, "u64": torch.int64}
+_INT = {torch.float32: torch.int32, torch.bfloat16: torch.int16, torch.int64: torch.int64}
+
+
+class Arena:
+    """All buffers of one replay, each between sentinel guard bands, allocated on `device`."""
+
+    def __init__(self, device, seed):
+        self.device = device
+        self.gen = torch.Generator().manual_seed(seed)                   # host draws (time steps)
+        self.dgen = torch.Generator(device=device).manual_seed(seed)    # buffer contents, drawn where they live
+        self.bufs = []
+
+    def buf(self, name, n, dtype, mod=0):
+        b = Buf(name, n, _TD[dtype], mod, self.device)
+        self.bufs.append(b)
+        return b
+
+    def randn(self, n, mean=0.0, scale=1.0):
+        return torch.randn(n, generator=self.dgen, device=self.device) * scale + mean
+
+    def snapshot(self):
+        for b in self.bufs:
+            b.before = b.raw.clone()
+
+    def check(self):
+        """Guards intact, and nothing outside the declared outputs changed."""
+        for b in self.bufs:
+            lo, hi = b.start, b.start + b.nbytes
+            assert torch.equal(b.raw[:lo], b.before[:lo]) and torch.equal(b.raw[hi:], b.before[hi:]), f"{b.name}: guard band overwritten"
+            keep = ~b.written
+            if bool(keep.any()):
+                now, was = b.t.view(_INT[b.t.dtype]), b.before[lo:hi].view(_INT[b.t.dtype])
+                bad = (now != was) & keep
+                assert not bool(bad.any()), f"{b.name}: {int(bad.sum())} element(s) outside the contract's output changed"
+
+
+class Buf:
+    def __init__(self, name, n, dtype, mod, device):
+        es = torch.empty(0, dtype=dtype).element_size()
+        self.name, self.n = name, max(int(n), 1)
+        self.nbytes = self.n * es
+        self.raw = torch.full((GUARD + 256 + self.nbytes + GUARD,), SENTINEL, dtype=torch.uint8, device=device)
+        self.start = GUARD + (mod - self.raw.data_ptr() - GUARD) % 256          # address of the first element = mod (modulo 256)
+        self.t = self.raw[self.start:self.start + self.nbytes].view(dtype)
+        self.written = torch.zeros(self.n, dtype=torch.bool, device=device)
+        self.ptr = self.raw.data_ptr() + self.start
+
+    def fill(self, values):
+        self.t.copy_(values.to(self.t.dtype).reshape(-1)[:self.n])
+        return self
+
+    def mat(self, rows, cols, ld, off=0):
+        """[rows][cols] view with pitch ld starting `off` elements in."""
+        return self.t.as_strided((rows, cols), (ld, 1), self.t.storage_offset() + off)
+
+    def out(self, rows, cols, ld, off=0):
+        self.written.as_strided((rows, cols), (ld, 1), off).fill_(True)
+        return self.mat(rows, cols, ld, off)
+
+    def all_out(self):
+        self.written.fill_(True)
+        return self.t
+
+
+def pitched(rows, cols, ld):
+    return (rows - 1) * ld + cols if rows > 0 else 0
+
+
+def _d(t):
+    return t.to(torch.float64)
+
+
+class Result:
+    def __init__(self, sig):
+        self.sig, self.worst, self.where = sig, 0.0, ""
+
+    def cmp(self, what, got, ref, bar):
+        got, ref, bar = _d(got), ref.to(got.device), bar.to(got.device)
+        assert bool(torch.isfinite(got).all()), f"{what}: non-finite output"
+        r = float(((got - ref).abs() / (bar + TINY)).max()) if got.numel() else 0.0
+        if r >= self.worst:
+            self.worst, self.where = r, what
+        return r
+
+
+# ----------------------------------------------------------------------------------------------------------------- fp64 convolution
+def canvas(x, Ho, Wo, R, S, stride, pad_t, pad_l, upsample, dilate):
+    """x [B,H,W,C] (NHWC) -> zero canvas [B, (Ho-1)*stride+R, (Wo-1)*stride+S, C] on which a VALID correlation with stride `stride`
+    gathers exactly the contract's  x[b, f(oy*stride + r - pad_t), f(ox*stride + s - pad_l), c]  (zero outside the virtual grid)."""
+    B, H, W, C = x.shape
+    if upsample:
+        xv = x.repeat_interleave(2, 1).repeat_interleave(2, 2)
+    elif dilate:
+        xv = x.new_zeros(B, 2 * H - 1, 2 * W - 1, C)
+        xv[:, ::2, ::2] = x
+    else:
+        xv = x
+    nh, nw = (Ho - 1) * stride + R, (Wo - 1) * stride + S
+    can = x.new_zeros(B, nh, nw, C)
+    hv, wv = xv.shape[1], xv.shape[2]
+    ys, xs = max(0, -pad_t), max(0, -pad_l)
+    ye, xe = min(hv, nh - pad_t), min(wv, nw - pad_l)
+    if ye > ys and xe > xs:
+        can[:, pad_t + ys:pad_t + ye, pad_l + xs:pad_l + xe] = xv[:, ys:ye, xs:xe]
+    return can
+
+
+def _tap(can, r, s, Ho, Wo, stride):
+    return can[:, r:r + (Ho - 1) * stride + 1:stride, s:s + (Wo - 1) * stride + 1:stride]
+
+
+def conv_fp64(can, w, Ho, Wo, stride):
+    """y[b,oy,ox,n] = sum_{r,s,c} can[b, oy*stride+r, ox*stride+s, c] * w[n,r,s,c]  (w: [N,R,S,C], all float64) by R*S matmuls."""
+    N, R, S, C = w.shape
+    y = can.new_zeros(can.shape[0], Ho, Wo, N)
+    for r in range(R):
+        for s in range(S):
+            y += _tap(can, r, s, Ho, Wo, stride) @ w[:, r, s, :].T
+    return y
+
+
+def wgrad_fp64(can, dy, R, S, Ho, Wo, stride):
+    """dw[n,r,s,c] = sum_{b,oy,ox} dy[b,oy,ox,n] * can[b, oy*stride+r, ox*stride+s, c]  ->  [N,R,S,C]."""
+    N, C = dy.shape[-1], can.shape[-1]
+    g = dy.reshape(-1, N).T
+    out = can.new_zeros(N, R, S, C)
+    for r in range(R):
+        for s in range(S):
+            out[:, r, s] = g @ _tap(can, r, s, Ho, Wo, stride).reshape(-1, C)
+    return out
+
+
+# ----------------------------------------------------------------------------------------------------------------- replay builders
+def _launch(name, args):
+    _hip._invoke(name, list(args) + [_hip.stream() if torch.device(_DEVICE[0]).type == "cuda" else 0])
+
+
+_DEVICE = ["cpu"]
+
+
+def _ptr(b):
+    return 0 if b is None else b.ptr
+
+
+def _opt(sig_entry):
+    return not sig_entry[1]            # pointer present
+
+
+def _mod(sig_entry):
+    return sig_entry[2]
+
+
+def rep_conv2d(A, sig, res):
+    (px, x_ld, pw, py, y_ld, pb, prb, rb_ld, pres, res_ld, B, H, W, C, Ho, Wo, N, R, S, stride, pad_t, pad_l, ups, dil, acc, mode,
+     splits, pws, pcnt, dt) = sig
+    M = B * Ho * Wo
+    odt = dt if mode == 0 else F32
+    x = A.buf("x", pitched(B * H * W, C, x_ld), dt, _mod(px))
+    w = A.buf("w", N * R * S * C, dt, _mod(pw))
+    ny = B * N * Ho * Wo if mode == 3 else pitched(M, N, y_ld)
+    y = A.buf("y", ny, odt, _mod(py))
+    bias = A.buf("bias", N, F32, _mod(pb)) if _opt(pb) else None
+    rb = A.buf("rowbias", pitched(B, N, rb_ld), F32, _mod(prb)) if _opt(prb) else None
+    r_ = A.buf("residual", pitched(M, N, res_ld), dt, _mod(pres)) if _opt(pres) else None
+    ws = cnt = None
+    if _opt(pws):
+        tiles = max(-(-M // 128) * -(-N // 128) * 16384, -(-M // 64) * -(-N // 64) * 4096) * max(splits, 1)
+        if splits == 2:
+            tiles = max(tiles, 256 * 4096)
+        ws = A.buf("splitk_ws", tiles, F32, _mod(pws))
+        ws.fill(torch.full((ws.n,), float("nan"))).all_out()
+    if _opt(pcnt):
+        cnt = A.buf("splitk_cnt", -(-M // 64) * -(-N // 64), F32, _mod(pcnt))
+        cnt.fill(torch.zeros(cnt.n))
+        cnt.all_out()
+    K = R * S * C
+    x.fill(A.randn(x.n))
+    w.fill(A.randn(w.n, scale=1.0 / math.sqrt(K)))       # products O(1): bias, row bias and residual weigh as much as the sum
+    y.fill(A.randn(y.n))
+    for b in (bias, rb, r_):
+        if b is not None:
+            b.fill(A.randn(b.n))
+    prior = _d(y.t).clone()
+    if mode == 3:
+        y.all_out()
+    else:
+        y.out(M, N, y_ld)
+    A.snapshot()
+    _launch("ddpm_conv2d_nhwc", [x.ptr, x_ld, w.ptr, y.ptr, y_ld, _ptr(bias), _ptr(rb), rb_ld, _ptr(r_), res_ld, B, H, W, C, Ho, Wo, N,
+                                 R, S, stride, pad_t, pad_l, ups, dil, acc, mode, splits, _ptr(ws), _ptr(cnt), dt])
+    sync()
+    A.check()
+    if cnt is not None:
+        assert not bool(cnt.t.view(torch.int32).any()), "split-K counters not left zero"
+    xs = _d(x.mat(B * H * W, C, x_ld)).reshape(B, H, W, C)
+    wt = _d(w.t).reshape(N, R, S, C)
+    can = canvas(xs, Ho, Wo, R, S, stride, pad_t, pad_l, ups, dil)
+    ref = conv_fp64(can, wt, Ho, Wo, stride).reshape(M, N)
+    mag = ref.abs()
+    sq = conv_fp64(can * can, wt * wt, Ho, Wo, stride).reshape(M, N).sqrt()
+    if bias is not None:
+        ref = ref + _d(bias.t)[None]
+        mag = mag + _d(bias.t).abs()[None]
+    if rb is not None:
+        v = _d(rb.mat(B, N, rb_ld)).repeat_interleave(Ho * Wo, 0)
+        ref, mag = ref + v, mag + v.abs()
+    if r_ is not None:
+        v = _d(r_.mat(M, N, res_ld))
+        ref, mag = ref + v, mag + v.abs()
+    if mode == 3:
+        got = _d(y.mat(B * N, Ho * Wo, Ho * Wo)).reshape(B, N, Ho * Wo).permute(0, 2, 1).reshape(M, N)
+        pv = prior.reshape(B, N, Ho * Wo).permute(0, 2, 1).reshape(M, N)
+    else:
+        got = _d(y.mat(M, N, y_ld))
+        pv = prior.as_strided((M, N), (y_ld, 1))
+    if acc:
+        ref, mag = ref + pv, mag + pv.abs()
+    u = U_BF16 if odt == BF16 else U_F32
+    bar = C_GEMM * (u * mag + U_ACC * math.sqrt(K) * sq)
+    res.cmp("y", got, ref, bar)
+
+
+def _slab_setup(A, name, n_one, copies, stride, mod):
+    b = A.buf(name, (copies - 1) * stride + n_one if copies > 1 else n_one, F32, mod)
+    b.fill(torch.full((b.n,), float("nan")))
+    for s in range(copies):
+        b.written[s * stride:s * stride + n_one] = True
+    return b
+
+
+def _reduce_slabs(A, slab, n_one, copies, stride):
+    """ddpm_wgrad_reduce over the copies, as the step runs it; returns the reduced [n_one] floats."""
+    dst = A.buf(slab.name + "_reduced", n_one, F32)
+    dst.all_out()
+    tab = torch.tensor([slab.ptr, dst.ptr, n_one, copies, stride], dtype=torch.int64, device=A.device)
+    A.snapshot()
+    _launch("ddpm_wgrad_reduce", [tab.data_ptr(), 1])
+    sync()
+    A.check()
+    return dst.t
+
+
+def _wgrad_common(A, res, dy_b, x_b, can, dy, R, S, Ho, Wo, stride, Nreal, Creal, dw, slab_stride, copies, prior, dbias=None,
+                  bias_stride=0, bprior=None):
+    n_one = Nreal * R * S * Creal
+    full = wgrad_fp64(can, dy, R, S, Ho, Wo, stride)[:Nreal, :, :, :Creal].reshape(-1)
+    mag = full.abs()
+    sq = wgrad_fp64(can * can, dy * dy, R, S, Ho, Wo, stride)[:Nreal, :, :, :Creal].reshape(-1).sqrt()
+    K = dy.shape[0] * Ho * Wo
+    if slab_stride == 0:
+        got = dw.t[:n_one]
+        full, mag = full + prior, mag + prior.abs()
+    else:
+        got = _reduce_slabs(A, dw, n_one, copies, slab_stride)
+    res.cmp("dw", got, full, C_GEMM * (U_F32 * mag + U_ACC * math.sqrt(K) * sq))
+    if dbias is not None:
+        g = dy.reshape(-1, dy.shape[-1])[:, :Nreal]
+        ref, sq = g.sum(0), (g * g).sum(0).sqrt()
+        mag = ref.abs()
+        if bias_stride == 0 and slab_stride == 0:
+            got = dbias.t[:Nreal]
+            ref, mag = ref + bprior, mag + bprior.abs()
+        else:
+            got = _reduce_slabs(A, dbias, Nreal, copies, bias_stride)
+        res.cmp("dbias", got, ref, C_GEMM * (U_F32 * mag + U_ACC * math.sqrt(K) * sq))
+
+
+def _wgrad_launch(A, name, args):
+    A.snapshot()
+    _launch(name, args)
+    sync()
+    A.check()
+
+
+def rep_conv3x3_wgrad(A, sig, res, up=False):
+    pdy, dy_ld, px, x_ld, pdw, slab_stride, pdb, bias_stride, B, H, W, C, N, Nreal, splits, dt = sig
+    Hs, Ws = (H // 2, W // 2) if up else (H, W)
+    copies = _hip.lib().ddpm_conv3x3_wgrad_splits(B, H, W, C, N, splits) if slab_stride else 1
+    assert copies > 0
+    dy = A.buf("dy", pitched(B * H * W, N, dy_ld), dt, _mod(pdy)).fill(A.randn(pitched(B * H * W, N, dy_ld)))
+    x = A.buf("x", pitched(B * Hs * Ws, C, x_ld), dt, _mod(px)).fill(A.randn(pitched(B * Hs * Ws, C, x_ld)))
+    n_one = Nreal * 9 * C
+    if slab_stride:
+        dw = _slab_setup(A, "dw", n_one, copies, slab_stride, _mod(pdw))
+        db = _slab_setup(A, "dbias", Nreal, copies, bias_stride, _mod(pdb)) if _opt(pdb) else None
+        prior = bprior = None
+    else:
+        dw = A.buf("dw", n_one, F32, _mod(pdw)).fill(A.randn(n_one))
+        dw.all_out()
+        prior = _d(dw.t).clone()
+        db = A.buf("dbias", Nreal, F32, _mod(pdb)).fill(A.randn(Nreal)) if _opt(pdb) else None
+        if db is not None:
+            db.all_out()
+        bprior = None if db is None else _d(db.t).clone()
+    _wgrad_launch(A, "ddpm_conv3x3_wgrad_up_nhwc" if up else "ddpm_conv3x3_wgrad_nhwc",
+                  [dy.ptr, dy_ld, x.ptr, x_ld, dw.ptr, slab_stride, _ptr(db), bias_stride, B, H, W, C, N, Nreal, splits, dt])
+    xs = _d(x.mat(B * Hs * Ws, C, x_ld)).reshape(B, Hs, Ws, C)
+    g = _d(dy.mat(B * H * W, N, dy_ld)).reshape(B, H, W, N)
+    can = canvas(xs, H, W, 3, 3, 1, 1, 1, int(up), 0)
+    _wgrad_common(A, res, dy, x, can, g, 3, 3, H, W, 1, Nreal, C, dw, slab_stride, copies, prior, db, bias_stride, bprior)
+
+
+def rep_conv3x3_wgrad_up(A, sig, res):
+    rep_conv3x3_wgrad(A, sig, res, up=True)
+
+
+def rep_conv1x1_wgrad(A, sig, res):
+    pdy, dy_ld, px, x_ld, pdw, slab_stride, pdb, bias_stride, P, C, N, splits, dt = sig
+    assert slab_stride > 0 and splits >= 1
+    dy = A.buf("dy", pitched(P, N, dy_ld), dt, _mod(pdy)).fill(A.randn(pitched(P, N, dy_ld)))
+    x = A.buf("x", pitched(P, C, x_ld), dt, _mod(px)).fill(A.randn(pitched(P, C, x_ld)))
+    dw = _slab_setup(A, "dw", N * C, splits, slab_stride, _mod(pdw))
+    db = _slab_setup(A, "dbias", N, splits, bias_stride, _mod(pdb)) if _opt(pdb) else None
+    _wgrad_launch(A, "ddpm_conv1x1_wgrad_nhwc", [dy.ptr, dy_ld, x.ptr, x_ld, dw.ptr, slab_stride, _ptr(db), bias_stride, P, C, N, splits, dt])
+    g = _d(dy.mat(P, N, dy_ld)).reshape(1, P, 1, N)
+    can = _d(x.mat(P, C, x_ld)).reshape(1, P, 1, C)
+    _wgrad_common(A, res, dy, x, can, g, 1, 1, P, 1, 1, N, C, dw, slab_stride, splits, None, db, bias_stride, None)
+
+
+def rep_conv2d_wgrad(A, sig, res):
+    (pdy, dy_ld, px, x_ld, pdw, slab_stride, B, H, W, C, Creal, Ho, Wo, N, Nreal, R, S, stride, pad_t, pad_l, ups, splits, dt) = sig
+    dy = A.buf("dy", pitched(B * Ho * Wo, N, dy_ld), dt, _mod(pdy)).fill(A.randn(pitched(B * Ho * Wo, N, dy_ld)))
+    x = A.buf("x", pitched(B * H * W, C, x_ld), dt, _mod(px)).fill(A.randn(pitched(B * H * W, C, x_ld)))
+    n_one = Nreal * R * S * Creal
+    if slab_stride:
+        copies = splits
+        dw = _slab_setup(A, "dw", n_one, copies, slab_stride, _mod(pdw))
+        prior = None
+    else:
+        copies = 1
+        dw = A.buf("dw", n_one, F32, _mod(pdw)).fill(A.randn(n_one))
+        dw.all_out()
+        prior = _d(dw.t).clone()
+    _wgrad_launch(A, "ddpm_conv2d_wgrad_nhwc", [dy.ptr, dy_ld, x.ptr, x_ld, dw.ptr, slab_stride, B, H, W, C, Creal, Ho, Wo, N, Nreal,
+                                               R, S, stride, pad_t, pad_l, ups, splits, dt])
+    xs = _d(x.mat(B * H * W, C, x_ld)).reshape(B, H, W, C)
+    g = _d(dy.mat(B * Ho * Wo, N, dy_ld)).reshape(B, Ho, Wo, N)
+    can = canvas(xs, Ho, Wo, R, S, stride, pad_t, pad_l, ups, 0)
+    _wgrad_common(A, res, dy, x, can, g, R, S, Ho, Wo, stride, Nreal, Creal, dw, slab_stride, copies, prior)
+
+
+def rep_wgrad_reduce(A, sig, res):
+    """Stand-alone check of the fixed-order slab sum (the slab replays above also run it): copies of random partials."""
+    n_one, copies, stride = 1000, 3, 1024
+    slab = A.buf("slabs", (copies - 1) * stride + n_one, F32).fill(A.randn((copies - 1) * stride + n_one))
+    got = _reduce_slabs(A, slab, n_one, copies, stride)
+    parts = torch.stack([_d(slab.t[s * stride:s * stride + n_one]) for s in range(copies)])
+    # a short fixed-order fp32 sum: the worst-case bound u * sum |partials| (M of every added term)
+    res.cmp("sum", got, parts.sum(0), C_GEMM * U_F32 * parts.abs().sum(0))
+
+
+def rep_gemm(A, sig, res):
+    (pa, a_ld, a_bs, a_tr, pb, b_ld, b_bs, b_tr, pc, c_ld, c_bs, pbias, pres, res_ld, res_bs, M, N, K, batch, alpha, acc, mode, splits,
+     dt) = sig
+    odt = dt if mode == 0 else F32
+    na = (batch - 1) * a_bs + (pitched(K, M, a_ld) if a_tr else pitched(M, K, a_ld))
+    nb = (batch - 1) * b_bs + (pitched(K, N, b_ld) if b_tr else pitched(N, K, b_ld))
+    nc = (batch - 1) * c_bs + pitched(M, N, c_ld)
+    a = A.buf("a", na, dt, _mod(pa)).fill(A.randn(na))
+    b = A.buf("b", nb, dt, _mod(pb)).fill(A.randn(nb, scale=1.0 / math.sqrt(K)))
+    c = A.buf("c", nc, odt, _mod(pc)).fill(A.randn(nc))
+    bias = A.buf("bias", N, F32, _mod(pbias)).fill(A.randn(N)) if _opt(pbias) else None
+    r_ = None
+    if _opt(pres):
+        nr = (batch - 1) * res_bs + pitched(M, N, res_ld)
+        r_ = A.buf("residual", nr, dt, _mod(pres)).fill(A.randn(nr))
+    prior = _d(c.t).clone()
+    A.snapshot()
+    _launch("ddpm_gemm", [a.ptr, a_ld, a_bs, a_tr, b.ptr, b_ld, b_bs, b_tr, c.ptr, c_ld, c_bs, _ptr(bias), _ptr(r_), res_ld, res_bs,
+                          M, N, K, batch, alpha, acc, mode, splits, dt])
+    sync()
+    for i in range(batch):
+        c.out(M, N, c_ld, i * c_bs)
+    A.check()
+    u = U_BF16 if odt == BF16 else U_F32
+    for i in range(batch):
+        Am = _d(a.mat(K, M, a_ld, i * a_bs)).T if a_tr else _d(a.mat(M, K, a_ld, i * a_bs))
+        Bm = _d(b.mat(K, N, b_ld, i * b_bs)).T if b_tr else _d(b.mat(N, K, b_ld, i * b_bs))
+        ref = alpha * Am @ Bm.T
+        mag = ref.abs()
+        sq = abs(alpha) * ((Am * Am) @ (Bm * Bm).T).sqrt()
+        if bias is not None:
+            ref, mag = ref + _d(bias.t)[None], mag + _d(bias.t).abs()[None]
+        if r_ is not None:
+            v = _d(r_.mat(M, N, res_ld, i * res_bs))
+            ref, mag = ref + v, mag + v.abs()
+        if acc or mode == 2:
+            v = prior.as_strided((M, N), (c_ld, 1), i * c_bs)
+            ref, mag = ref + v, mag + v.abs()
+        res.cmp(f"c[{i}]", c.mat(M, N, c_ld, i * c_bs), ref, C_GEMM * (u * mag + U_ACC * math.sqrt(K) * sq))
+
+
+def rep_atb(A, sig, res):
+    pa, lda, pb, ldb, pc, ldc, M, N, K = sig
+    a = A.buf("a", pitched(K, M, lda), F32, _mod(pa)).fill(A.randn(pitched(K, M, lda)))
+    b = A.buf("b", pitched(K, N, ldb), F32, _mod(pb)).fill(A.randn(pitched(K, N, ldb)))
+    c = A.buf("c", pitched(M, N, ldc), F32, _mod(pc)).fill(A.randn(pitched(M, N, ldc)))
+    A.snapshot()
+    _launch("ddpm_atb_f32", [a.ptr, lda, b.ptr, ldb, c.ptr, ldc, M, N, K])
+    sync()
+    got = c.out(M, N, ldc)
+    A.check()
+    Am, Bm = _d(a.mat(K, M, lda)), _d(b.mat(K, N, ldb))
+    # K = the batch: a short fixed-order fp32 reduction, held to the worst-case bound of such a sum (M = sum_k |a_k b_k|)
+    ref, sq = Am.T @ Bm, ((Am * Am).T @ (Bm * Bm)).sqrt()
+    mag = Am.abs().T @ Bm.abs()
+    res.cmp("c", got, ref, C_GEMM * (U_F32 * mag + U_ACC * math.sqrt(K) * sq))
+
+
+# GroupNorm ---------------------------------------------------------------------------------------------------------------------------
+_M32 = 0xFFFFFFFF
+
+
+def _mul32(x, c):
+    """(x * c) mod 2^32 for int64 tensors holding uint32 values (split so no product leaves int64)."""
+    return (x * (c & 0xFFFF) + (((x * (c >> 16)) & 0xFFFF) << 16)) & _M32
+
+
+def _mix32(x):
+    x = x ^ (x >> 16)
+    x = _mul32(x, 0x7FEB352D)
+    x = x ^ (x >> 15)
+    x = _mul32(x, 0x846CA68B)
+    return x ^ (x >> 16)
+
+
+def keep_mask(seed, idx, p):
+    """Dropout keep mask for linear element indices idx (int64 tensor): a torch restatement of abi_emulator._keep_mask (the hash of
+    dropout_keep() in csrc/common.h) that runs where idx lives; the host check holds the two bit-equal."""
+    th = p * 65536.0
+    thresh = 0 if th <= 0 else (65536 if th >= 65536.0 else int(th + 0.5))
+    pair = idx >> 1
+    lo, hi = pair & _M32, (pair >> 32) & _M32
+    s_lo, s_hi = seed & _M32, (seed >> 32) & _M32
+    w = _mix32(lo ^ _mix32((hi + s_lo) & _M32) ^ ((s_hi * 0x9E3779B9) & _M32))
+    field = torch.where((idx & 1) == 1, w >> 16, w & 0xFFFF)
+    return field >= thresh
+
+
+def _keep(A, B, HW, C, drop_p, seed):
+    """Keep mask of the dropout after the GroupNorm, linear NHWC index b*HW*C + p*C + c (not the library's mask hook)."""
+    idx = torch.arange(B * HW * C, dtype=torch.int64, device=A.device)
+    return keep_mask(seed & ((1 << 64) - 1), idx, drop_p).to(torch.float64).reshape(B, HW, C)
+
+
+def _gn_stats(x, G, eps):
+    B, HW, C = x.shape
+    xg = x.reshape(B, HW, G, C // G).permute(0, 2, 1, 3).reshape(B, G, -1)
+    mean, var = xg.mean(-1), xg.var(-1, unbiased=False)
+    return mean, 1.0 / torch.sqrt(var + eps)
+
+
+def _per_c(v, B, HW, C, G):
+    """[B,G] -> [B,HW,C]"""
+    return v.repeat_interleave(C // G, 1)[:, None, :].expand(B, HW, C)
+
+
+def _seed(A, pseed, seed, drop_p):
+    if not _opt(pseed):
+        return None, seed
+    word = A.buf("seed_dev", 1, "u64", _mod(pseed))
+    w = 0x5DEECE66D
+    word.t.fill_(w)
+    return word, (seed + w) & ((1 << 64) - 1)
+
+
+def rep_gn_fwd(A, sig, res):
+    """GroupNorm(G) -> SiLU -> dropout.  t = gamma * xh + beta with xh = (x - mean) * rstd; y = drop(silu(t)).
+    Model: M_i = |y_i| (the bf16 / fp32 store) and the fp32 statistics term  sqrt(n) * (|gamma| (|x| + |mean|) rstd + |beta|) * |y'(t)|
+    with y' = silu'(t) * keep / (1 - p)  (n = (C/G) * HW, the statistics are sums of n terms; |x| + |mean| bounds the magnitude of the
+    centred value the kernel forms about its pivot).  Statistics: mean to u_acc * sqrt(n) * (|mean| + std), rstd to u_acc * sqrt(n)."""
+    px, x_ld, py, y_ld, pg, pb, pst, pws, B, HW, C, G, eps, silu, drop_p, seed, pseed, dt = sig
+    x = A.buf("x", pitched(B * HW, C, x_ld), dt, _mod(px)).fill(A.randn(pitched(B * HW, C, x_ld), mean=1.5))
+    y = A.buf("y", pitched(B * HW, C, y_ld), dt, _mod(py)).fill(A.randn(pitched(B * HW, C, y_ld)))
+    g = A.buf("gamma", C, F32, _mod(pg)).fill(1.0 + 0.3 * A.randn(C))
+    b = A.buf("beta", C, F32, _mod(pb)).fill(0.5 * A.randn(C))
+    st = A.buf("stats", B * G * 2, F32, _mod(pst)) if _opt(pst) else None
+    nws = int(_hip.lib().ddpm_gn_workspace_floats(B, HW, C, G, dt))
+    ws = A.buf("workspace", nws, F32, _mod(pws)).fill(torch.zeros(nws))
+    ws.all_out()
+    if st is not None:
+        st.all_out()
+    word, eff = _seed(A, pseed, seed, drop_p)
+    A.snapshot()
+    _launch("ddpm_groupnorm_silu_fwd", [x.ptr, x_ld, y.ptr, y_ld, g.ptr, b.ptr, _ptr(st), ws.ptr, B, HW, C, G, eps, silu, drop_p, seed,
+                                        _ptr(word), dt])
+    sync()
+    got = y.out(B * HW, C, y_ld)
+    A.check()
+    xs = _d(x.mat(B * HW, C, x_ld)).reshape(B, HW, C)
+    mean, rstd = _gn_stats(xs, G, eps)
+    mu, rs = _per_c(mean, B, HW, C, G), _per_c(rstd, B, HW, C, G)
+    gm, bt = _d(g.t), _d(b.t)
+    xh = (xs - mu) * rs
+    t = gm * xh + bt
+    sg = torch.sigmoid(t)
+    yv, dyv = (t * sg, sg * (1 + t * (1 - sg))) if silu else (t, torch.ones_like(t))
+    if drop_p > 0:
+        k = _keep(A, B, HW, C, drop_p, eff) / (1.0 - drop_p)
+        yv, dyv = yv * k, dyv * k
+    n = (C // G) * HW
+    u = U_BF16 if dt == BF16 else U_F32
+    bar = C_NORM * (u * yv.abs() + U_ACC * math.sqrt(n) * (gm.abs() * (xs.abs() + mu.abs()) * rs + bt.abs()) * dyv.abs())
+    res.cmp("y", got.reshape(B, HW, C), yv, bar)
+    if st is not None:
+        s = _d(st.t).reshape(B, G, 2)
+        std = 1.0 / rstd
+        res.cmp("mean", s[..., 0], mean, C_NORM * U_ACC * math.sqrt(n) * (mean.abs() + std))
+        res.cmp("rstd", s[..., 1], rstd, C_NORM * U_ACC * math.sqrt(n) * rstd)
+
+
+def rep_gn_bwd(A, sig, res):
+    """Backward of rep_gn_fwd with (mean, rstd) given:  dz = dy * keep / (1 - p) * silu'(t),
+        dx = rstd * (dz*gamma - xh*c1 - c2) + add (+ prior),  c1 = mean_g(dz*gamma*xh),  c2 = mean_g(dz*gamma)
+        dgamma += sum dz*xh,  dbeta += sum dz,  dx_colsum[b,c] += sum_p dx.
+    Model: M_i = rstd (|dz*gamma| + |xh*c1| + |c2|) + |add| + |prior| for the store; the fp32 part adds u_acc * sqrt(n) * (that bracket
+    without the store + rstd*|c1| (|x| + |mean|) rstd + rstd |gamma| |dy| e_t), which covers the group sums, the recomputed xh and the
+    fp32 error of t (e_t = |gamma| (|x| + |mean|) rstd + |beta|, in units of u_acc) carried through silu'.  dgamma / dbeta add that
+    error of every term linearly.  The pixel sums are GEMM-shaped
+    (M = sum of |terms|, S = root of the sum of squared terms, K = the pixel count), with the per-element error of the summed dx as M."""
+    (px, x_ld, pdy, dy_ld, pdx, dx_ld, pg, pb, pst, pdg, pdb, pws, B, HW, C, G, silu, drop_p, seed, pseed, acc, pcs, cs_ld, padd, add_ld,
+     dt) = sig
+    rows = B * HW
+    x = A.buf("x", pitched(rows, C, x_ld), dt, _mod(px)).fill(A.randn(pitched(rows, C, x_ld), mean=1.5))
+    dy = A.buf("dy", pitched(rows, C, dy_ld), dt, _mod(pdy)).fill(A.randn(pitched(rows, C, dy_ld), mean=0.3))
+    dx = A.buf("dx", pitched(rows, C, dx_ld), dt, _mod(pdx)).fill(A.randn(pitched(rows, C, dx_ld)))
+    g = A.buf("gamma", C, F32, _mod(pg)).fill(1.0 + 0.3 * A.randn(C))
+    b = A.buf("beta", C, F32, _mod(pb)).fill(0.5 * A.randn(C))
+    xs = _d(x.mat(rows, C, x_ld)).reshape(B, HW, C)
+    mean, rstd = _gn_stats(xs, G, 1e-6)
+    st = A.buf("stats", B * G * 2, F32, _mod(pst)).fill(torch.stack([mean, rstd], -1))
+    dg = A.buf("dgamma", C, F32, _mod(pdg)).fill(A.randn(C)) if _opt(pdg) else None
+    db = A.buf("dbeta", C, F32, _mod(pdb)).fill(A.randn(C)) if _opt(pdb) else None
+    nws = int(_hip.lib().ddpm_gn_workspace_floats(B, HW, C, G, dt))
+    ws = A.buf("workspace", nws, F32, _mod(pws)).fill(torch.zeros(nws))
+    ws.all_out()
+    cs = None
+    if _opt(pcs):
+        cs = A.buf("dx_colsum", pitched(B, C, cs_ld), F32, _mod(pcs)).fill(A.randn(pitched(B, C, cs_ld)))
+        cs.mat(B, C, cs_ld).zero_()                        # zero on entry (contract)
+    ad = A.buf("add", pitched(rows, C, add_ld), dt, _mod(padd)).fill(A.randn(pitched(rows, C, add_ld))) if _opt(padd) else None
+    for o in (dg, db):
+        if o is not None:
+            o.all_out()
+    word, eff = _seed(A, pseed, seed, drop_p)
+    prior = _d(dx.mat(rows, C, dx_ld)).reshape(B, HW, C).clone()
+    pdg_v = None if dg is None else _d(dg.t).clone()
+    pdb_v = None if db is None else _d(db.t).clone()
+    A.snapshot()
+    _launch("ddpm_groupnorm_silu_bwd", [x.ptr, x_ld, dy.ptr, dy_ld, dx.ptr, dx_ld, g.ptr, b.ptr, st.ptr, _ptr(dg), _ptr(db), ws.ptr,
+                                        B, HW, C, G, silu, drop_p, seed, _ptr(word), acc, _ptr(cs), cs_ld, _ptr(ad), add_ld, dt])
+    sync()
+    got = dx.out(rows, C, dx_ld)
+    if cs is not None:
+        cs.out(B, C, cs_ld)
+    A.check()
+    s = _d(st.t).reshape(B, G, 2)                        # the fp32 statistics the kernel was given
+    mu, rs = _per_c(s[..., 0], B, HW, C, G), _per_c(s[..., 1], B, HW, C, G)
+    gm, bt = _d(g.t), _d(b.t)
+    xh = (xs - mu) * rs
+    t = gm * xh + bt
+    sg = torch.sigmoid(t)
+    dz = _d(dy.mat(rows, C, dy_ld)).reshape(B, HW, C)
+    if silu:
+        dz = dz * sg * (1 + t * (1 - sg))
+    if drop_p > 0:
+        dz = dz * _keep(A, B, HW, C, drop_p, eff) / (1.0 - drop_p)
+    dyk = _d(dy.mat(rows, C, dy_ld)).reshape(B, HW, C).abs()
+    if drop_p > 0:
+        dyk = dyk * _keep(A, B, HW, C, drop_p, eff) / (1.0 - drop_p)
+    dt_err = dyk * (gm.abs() * (xs.abs() + mu.abs()) * rs + bt.abs()) if silu else 0.0 * dyk   # |dy| * (what bounds t's fp32 error) / u
+    a = dz * gm
+    grp = lambda v: _per_c(v.reshape(B, HW, G, C // G).mean((1, 3)), B, HW, C, G)
+    c1, c2 = grp(a * xh), grp(a)
+    ref = rs * (a - xh * c1 - c2)
+    inner = rs * (a.abs() + (xh * c1).abs() + c2.abs())
+    mag = inner.clone()
+    if ad is not None:
+        v = _d(ad.mat(rows, C, add_ld)).reshape(B, HW, C)
+        ref, mag = ref + v, mag + v.abs()
+    if acc:
+        ref, mag = ref + prior, mag + prior.abs()
+    n = (C // G) * HW
+    u = U_BF16 if dt == BF16 else U_F32
+    fp32_part = U_ACC * math.sqrt(n) * (inner + rs * c1.abs() * (xs.abs() + mu.abs()) * rs + rs * gm.abs() * dt_err)
+    res.cmp("dx", got.reshape(B, HW, C), ref, C_NORM * (u * mag + fp32_part))
+    if cs is not None:
+        # the colsum adds the dx values the kernel forms (before or after the store): their per-element error is part of M
+        dxm = mag * u + fp32_part
+        res.cmp("dx_colsum", cs.mat(B, C, cs_ld), ref.sum(1),
+                C_NORM * (dxm.sum(1) + U_F32 * ref.abs().sum(1) + U_ACC * math.sqrt(HW) * (ref * ref).sum(1).sqrt()))
+    K = B * HW
+    flat = lambda v: v.reshape(K, C)
+    for o, terms, p0, nm in ((dg, dz * xh, pdg_v, "dgamma"), (db, dz, pdb_v, "dbeta")):
+        if o is None:
+            continue
+        tm = flat(terms)
+        ref_c, sq_c = tm.sum(0) + p0, (tm * tm).sum(0).sqrt()
+        mag_c = tm.sum(0).abs() + p0.abs()
+        lin = flat(dt_err * (xh.abs() if nm == "dgamma" else 1.0) + (dz.abs() * (xs.abs() + mu.abs()) * rs if nm == "dgamma" else 0.0)).sum(0)
+        res.cmp(nm, o.t, ref_c, C_NORM * (U_F32 * mag_c + U_ACC * (math.sqrt(K) * sq_c + lin)))
+
+
+# attention ----------------------------------------------------------------------------------------------------------------------------
+def _qkv(A, sig_p, ld, B, L, C, dt):
+    qkv = A.buf("qkv", pitched(B * L, 3 * C, ld), dt, _mod(sig_p)).fill(A.randn(pitched(B * L, 3 * C, ld), scale=1.5))
+    v = _d(qkv.mat(B * L, 3 * C, ld)).reshape(B, L, 3 * C)
+    return qkv, v[..., :C], v[..., C:2 * C], v[..., 2 * C:]
+
+
+def _logit_err(q, k, scale):
+    """per (i, j) fp32 error bound of the logits q_i . k_j * scale: u_acc sqrt(C) sqrt(sum_c (q k)^2) * scale"""
+    C = q.shape[-1]
+    return U_ACC * math.sqrt(C) * ((q * q) @ (k * k).transpose(1, 2)).sqrt() * scale
+
+
+def rep_attn_fwd(A, sig, res, lse_entry=False):
+    """out = softmax(q k^T * scale) v, lse = log sum exp.  Model (csrc/attention.hip rounds P to bf16 in front of the PV product):
+    M_ic = |out_ic| + sum_j P_ij |v_jc| (the bf16 store, and the rounding of P: 2^-8 sum_j P_ij |v_jc|), plus the logit error e_ij
+    carried through exp: 2 max_j e_ij * sum_j P_ij |v_jc|, and the fp32 PV sum u_acc sqrt(L) S.  lse: u_acc (|lse| + log L) + max_j e_ij."""
+    if lse_entry:
+        pq, ld, po, o_ld, plse, B, L, C, scale, dt = sig
+    else:
+        pq, ld, po, o_ld, B, L, C, scale, dt = sig
+        plse = ("p", True, 0)
+    qkv, q, k, v = _qkv(A, pq, ld, B, L, C, dt)
+    o = A.buf("out", pitched(B * L, C, o_ld), dt, _mod(po)).fill(A.randn(pitched(B * L, C, o_ld)))
+    lse = A.buf("lse", B * L, F32, _mod(plse)) if _opt(plse) else None
+    if lse is not None:
+        lse.all_out()
+    A.snapshot()
+    if lse_entry:
+        _launch("ddpm_attention_fwd_lse", [qkv.ptr, ld, o.ptr, o_ld, _ptr(lse), B, L, C, scale, dt])
+    else:
+        _launch("ddpm_attention_fwd", [qkv.ptr, ld, o.ptr, o_ld, B, L, C, scale, dt])
+    sync()
+    got = o.out(B * L, C, o_ld)
+    A.check()
+    s = q @ k.transpose(1, 2) * scale
+    ls = torch.logsumexp(s, -1)
+    P = torch.exp(s - ls[..., None])
+    ref = P @ v
+    pv = P @ v.abs()
+    e = _logit_err(q, k, scale).amax(-1, keepdim=True)
+    sq = ((P * P) @ (v * v)).sqrt()
+    bar = C_ATTN * (U_BF16 * (ref.abs() + pv) + 2 * e * pv + U_ACC * math.sqrt(L) * sq)
+    res.cmp("out", got.reshape(B, L, C), ref, bar)
+    if lse is not None:
+        res.cmp("lse", lse.t.reshape(B, L), ls, C_ATTN * (U_ACC * (ls.abs() + math.log(L)) + e[..., 0]))
+
+
+def rep_attn_fwd_lse(A, sig, res):
+    rep_attn_fwd(A, sig, res, lse_entry=True)
+
+
+def rep_attn_bwd(A, sig, res):
+    """dV = P^T dO, dS = P o (dO V^T - D), D_i = dO_i . O_i, dQ = dS K scale, dK = dS^T Q scale, with P from q, k and the given lse and
+    O the given (bf16) forward output.  Model: the bf16 store (2^-8 |ref|); P rounded to bf16 before dV (2^-8 sum_i P_ij |dO_ic|); dS
+    rounded to bf16 before dQ / dK — independent roundings of the L terms, so 2^-8 sqrt(sum_j (dS_ij k_jc)^2); the fp32 error of
+    dP - D (u_acc sqrt(C) (root of the squared dO V^T terms) + u_acc |D|) and of the logits carried through P and dS; the fp32 sums
+    u_acc sqrt(L) S.  D: GEMM-shaped over C."""
+    pq, ld, po, o_ld, pdo, do_ld, plse, pdv, pdq, dq_ld, B, L, C, scale, dt = sig
+    qkv, q, k, v = _qkv(A, pq, ld, B, L, C, dt)
+    s = q @ k.transpose(1, 2) * scale
+    ls = torch.logsumexp(s, -1)
+    o = A.buf("o", pitched(B * L, C, o_ld), dt, _mod(po)).fill(A.randn(pitched(B * L, C, o_ld)))
+    o.mat(B * L, C, o_ld).copy_((torch.exp(s - ls[..., None]) @ v).reshape(B * L, C))
+    d_o = A.buf("d_o", pitched(B * L, C, do_ld), dt, _mod(pdo)).fill(A.randn(pitched(B * L, C, do_ld)))
+    lse = A.buf("lse", B * L, F32, _mod(plse)).fill(ls)
+    dvec = A.buf("dvec", B * L, F32, _mod(pdv)).fill(torch.full((B * L,), float("nan")))
+    dvec.all_out()
+    dq = A.buf("dqkv", pitched(B * L, 3 * C, dq_ld), dt, _mod(pdq)).fill(A.randn(pitched(B * L, 3 * C, dq_ld)))
+    A.snapshot()
+    _launch("ddpm_attention_bwd", [qkv.ptr, ld, o.ptr, o_ld, d_o.ptr, do_ld, lse.ptr, dvec.ptr, dq.ptr, dq_ld, B, L, C, scale, dt])
+    sync()
+    got = _d(dq.out(B * L, 3 * C, dq_ld)).reshape(B, L, 3 * C)
+    A.check()
+    O = _d(o.mat(B * L, C, o_ld)).reshape(B, L, C)
+    dO = _d(d_o.mat(B * L, C, do_ld)).reshape(B, L, C)
+    P = torch.exp(s - _d(lse.t).reshape(B, L, 1))
+    D = (dO * O).sum(-1)
+    dP = dO @ v.transpose(1, 2)
+    dS = P * (dP - D[..., None])
+    kT = lambda t: t.transpose(1, 2)
+    e_s = _logit_err(q, k, scale)                                                  # logit error -> relative error of P
+    e_dp = U_ACC * math.sqrt(C) * ((dO * dO) @ kT(v * v)).sqrt() + U_ACC * D.abs()[..., None]
+    dS_err = e_s * dS.abs() + P * e_dp                                              # fp32 error of each dS_ij before its rounding
+    res.cmp("dvec", dvec.t.reshape(B, L), D, C_ATTN * (U_F32 * (dO * O).abs().sum(-1) + U_ACC * math.sqrt(C) * ((dO * O) ** 2).sum(-1).sqrt()))
+    outs = (
+        ("dq", dS @ k * scale, (dS * dS) @ (k * k), dS_err @ k.abs() * scale, 0),
+        ("dk", kT(dS) @ q * scale, kT(dS * dS) @ (q * q), kT(dS_err) @ q.abs() * scale, C),
+        ("dv", kT(P) @ dO, kT(P * P) @ (dO * dO), kT(e_s * P) @ dO.abs(), 2 * C),
+    )
+    for nm, ref, sq, prop, c0 in outs:
+        sq = sq.sqrt() * (scale if nm != "dv" else 1.0)
+        rounding = (U_BF16 * (kT(P) @ dO.abs())) if nm == "dv" else U_BF16 * sq
+        bar = C_ATTN * (U_BF16 * ref.abs() + rounding + prop + U_ACC * math.sqrt(L) * sq)
+        res.cmp(nm, got[..., c0:c0 + C], ref, bar)
+
+
+# elementwise, reductions and diffusion -----------------------------------------------------------------------------------------------
+def rep_colsum(A, sig, res):
+    pdy, ld, pps, ps_ld, ptot, B, HW, C, dt = sig
+    dy = A.buf("dy", pitched(B * HW, C, ld), dt, _mod(pdy)).fill(A.randn(pitched(B * HW, C, ld)))
+    ps = A.buf("per_sample", pitched(B, C, ps_ld), F32, _mod(pps)).fill(A.randn(pitched(B, C, ps_ld))) if _opt(pps) else None
+    tot = A.buf("total", C, F32, _mod(ptot)).fill(A.randn(C)) if _opt(ptot) else None
+    p_ps = None if ps is None else _d(ps.mat(B, C, ps_ld)).clone()
+    p_tot = None if tot is None else _d(tot.t).clone()
+    A.snapshot()
+    _launch("ddpm_colsum", [dy.ptr, ld, _ptr(ps), ps_ld, _ptr(tot), B, HW, C, dt])
+    sync()
+    if ps is not None:
+        ps.out(B, C, ps_ld)
+    if tot is not None:
+        tot.all_out()
+    A.check()
+    g = _d(dy.mat(B * HW, C, ld)).reshape(B, HW, C)
+    if ps is not None:
+        res.cmp("per_sample", ps.mat(B, C, ps_ld), g.sum(1) + p_ps,
+                C_GEMM * (U_F32 * (g.sum(1).abs() + p_ps.abs()) + U_ACC * math.sqrt(HW) * (g * g).sum(1).sqrt()))
+    if tot is not None:
+        gg = g.reshape(-1, C)
+        res.cmp("total", tot.t, gg.sum(0) + p_tot,
+                C_GEMM * (U_F32 * (gg.sum(0).abs() + p_tot.abs()) + U_ACC * math.sqrt(B * HW) * (gg * gg).sum(0).sqrt()))
+
+
+def rep_upsample2x_bwd(A, sig, res):
+    pdy, pdx, dx_ld, B, H, W, C, acc, dt = sig
+    dyu = A.buf("dy_up", B * 4 * H * W * C, dt, _mod(pdy)).fill(A.randn(B * 4 * H * W * C))
+    dx = A.buf("dx", pitched(B * H * W, C, dx_ld), dt, _mod(pdx)).fill(A.randn(pitched(B * H * W, C, dx_ld)))
+    prior = _d(dx.mat(B * H * W, C, dx_ld)).clone()
+    A.snapshot()
+    _launch("ddpm_upsample2x_bwd", [dyu.ptr, dx.ptr, dx_ld, B, H, W, C, acc, dt])
+    sync()
+    got = dx.out(B * H * W, C, dx_ld)
+    A.check()
+    blk = _d(dyu.t).reshape(B, H, 2, W, 2, C)
+    ref = blk.sum((2, 4)).reshape(-1, C)
+    mag = ref.abs()
+    sq = (blk * blk).sum((2, 4)).reshape(-1, C).sqrt()
+    if acc:
+        ref, mag = ref + prior, mag + prior.abs()
+    u = U_BF16 if dt == BF16 else U_F32
+    res.cmp("dx", got, ref, C_GEMM * (u * mag + U_ACC * 2 * sq))
+
+
+def _tables(A, T):
+    return torch.linspace(0.05, 1.5, T, dtype=torch.float64)
+
+
+def _t(A, B, T, p):
+    tb = A.buf("t", B, "i64", _mod(p))
+    tv = torch.randint(0, T, (B,), generator=A.gen)
+    tv[0], tv[-1] = 0, T - 1
+    tb.t.copy_(tv)
+    return tb, tv
+
+
+def rep_q_sample(A, sig, res):
+    px0, pn, pt, pa, pb, pxt, B, n, T = sig
+    x0 = A.buf("x0", B * n, F32, _mod(px0)).fill(A.randn(B * n))
+    nz = A.buf("noise", B * n, F32, _mod(pn)).fill(A.randn(B * n))
+    tb, tv = _t(A, B, T, pt)
+    ta = A.buf("sqrt_ab", T, F32, _mod(pa)).fill(A.randn(T).abs())
+    tbb = A.buf("sqrt_1mab", T, F32, _mod(pb)).fill(A.randn(T).abs())
+    xt = A.buf("xt", B * n, F32, _mod(pxt)).fill(A.randn(B * n))
+    A.snapshot()
+    _launch("ddpm_q_sample", [x0.ptr, nz.ptr, tb.ptr, ta.ptr, tbb.ptr, xt.ptr, B, n, T])
+    sync()
+    xt.all_out()
+    A.check()
+    tv = tv.to(A.device)
+    a, b = _d(ta.t)[tv][:, None], _d(tbb.t)[tv][:, None]
+    X, N_ = _d(x0.t).reshape(B, n), _d(nz.t).reshape(B, n)
+    res.cmp("xt", xt.t.reshape(B, n), a * X + b * N_, C_ELEM * U_F32 * ((a * X).abs() + (b * N_).abs()))
+
+
+def rep_mse_fwd(A, sig, res):
+    pp, pt, pl, B, n = sig
+    p = A.buf("pred", B * n, F32, _mod(pp)).fill(A.randn(B * n))
+    tg = A.buf("target", B * n, F32, _mod(pt)).fill(A.randn(B * n))
+    loss = A.buf("loss", B, F32, _mod(pl)).fill(A.randn(B))
+    A.snapshot()
+    _launch("ddpm_mse_fwd", [p.ptr, tg.ptr, loss.ptr, B, n])
+    sync()
+    loss.all_out()
+    A.check()
+    P_, T_ = _d(p.t).reshape(B, n), _d(tg.t).reshape(B, n)
+    d = T_ - P_
+    mag = (d * d + 2 * d.abs() * (P_.abs() + T_.abs())).sum(1) / n
+    res.cmp("loss", loss.t, (d * d).mean(1), C_GEMM * (U_F32 * mag + U_ACC * math.sqrt(n) * (d ** 4).sum(1).sqrt() / n))
+
+
+def rep_mse_bwd(A, sig, res):
+    pp, pt, pg, pgp, B, n = sig
+    p = A.buf("pred", B * n, F32, _mod(pp)).fill(A.randn(B * n))
+    tg = A.buf("target", B * n, F32, _mod(pt)).fill(A.randn(B * n))
+    gl = A.buf("gloss", B, F32, _mod(pg)).fill(A.randn(B))
+    gp = A.buf("gpred", B * n, F32, _mod(pgp)).fill(A.randn(B * n))
+    A.snapshot()
+    _launch("ddpm_mse_bwd", [p.ptr, tg.ptr, gl.ptr, gp.ptr, B, n])
+    sync()
+    gp.all_out()
+    A.check()
+    P_, T_, G_ = _d(p.t).reshape(B, n), _d(tg.t).reshape(B, n), _d(gl.t)[:, None]
+    ref = (P_ - T_) * (2.0 / n) * G_
+    res.cmp("gpred", gp.t.reshape(B, n), ref, C_ELEM * U_F32 * ((P_.abs() + T_.abs()) * (2.0 / n) * G_.abs()))
+
+
+def rep_p_sample_step(A, sig, res):
+    """x0 = clamp(recip[t] x_t - recip_m1[t] out); x_prev = c1[t] x0 + c2[t] x_t + [t > 0] exp(logvar[t] / 2) z.  Model: u_f32 times
+    the magnitudes of every term (x0's terms scaled by |c1|; the clamp is 1-Lipschitz), c = C_ELEM for the fp32 exp."""
+    pxt, po, pz, pt, pr, prm1, pc1, pc2, plv, pxp, ppred, B, n, mean_type, clip, T = sig
+    xt = A.buf("x_t", B * n, F32, _mod(pxt)).fill(A.randn(B * n))
+    out = A.buf("model_out", B * n, F32, _mod(po)).fill(A.randn(B * n))
+    z = A.buf("z", B * n, F32, _mod(pz)).fill(A.randn(B * n))
+    tb, tv = _t(A, B, T, pt)
+    tabs = [A.buf(nm, T, F32, _mod(p)).fill(_tables(A, T) * f) for nm, p, f in
+            (("recip", pr, 1.0), ("recip_m1", prm1, 0.5), ("coef1", pc1, 0.3), ("coef2", pc2, 0.7), ("logvar", plv, -2.0))]
+    xp = A.buf("x_prev", B * n, F32, _mod(pxp)).fill(A.randn(B * n))
+    pred = A.buf("pred_x0", B * n, F32, _mod(ppred)).fill(A.randn(B * n)) if _opt(ppred) else None
+    A.snapshot()
+    _launch("ddpm_p_sample_step", [xt.ptr, out.ptr, z.ptr, tb.ptr] + [tb_.ptr for tb_ in tabs] + [xp.ptr, _ptr(pred), B, n, mean_type,
+                                                                                                  clip, T])
+    sync()
+    xp.all_out()
+    if pred is not None:
+        pred.all_out()
+    A.check()
+    tv = tv.to(A.device)
+    rc, rm, c1, c2, lv = (_d(tb_.t)[tv][:, None] for tb_ in tabs)
+    X, O, Z = (_d(b.t).reshape(B, n) for b in (xt, out, z))
+    assert mean_type == 0, "the recorded workloads predict eps"
+    x0 = rc * X - rm * O
+    x0m = (rc * X).abs() + (rm * O).abs()
+    if clip:
+        x0 = x0.clamp(-1.0, 1.0)
+    sig_ = torch.exp(0.5 * lv) * (tv > 0).to(X.dtype)[:, None]
+    ref = c1 * x0 + c2 * X + sig_ * Z
+    mag = (c1 * x0).abs() + c1.abs() * x0m + (c2 * X).abs() + (sig_ * Z).abs()
+    res.cmp("x_prev", xp.t.reshape(B, n), ref, C_ELEM * U_F32 * mag)
+    if pred is not None:
+        res.cmp("pred_x0", pred.t.reshape(B, n), x0, C_ELEM * U_F32 * x0m)
+
+
+REPLAY = {
+    "ddpm_conv2d_nhwc": rep_conv2d,
+    "ddpm_conv3x3_wgrad_nhwc": rep_conv3x3_wgrad,
+    "ddpm_conv3x3_wgrad_up_nhwc": rep_conv3x3_wgrad_up,
+    "ddpm_conv1x1_wgrad_nhwc": rep_conv1x1_wgrad,
+    "ddpm_conv2d_wgrad_nhwc": rep_conv2d_wgrad,
+    "ddpm_wgrad_reduce": rep_wgrad_reduce,
+    "ddpm_gemm": rep_gemm,
+    "ddpm_atb_f32": rep_atb,
+    "ddpm_groupnorm_silu_fwd": rep_gn_fwd,
+    "ddpm_groupnorm_silu_bwd": rep_gn_bwd,
+    "ddpm_attention_fwd": rep_attn_fwd,
+    "ddpm_attention_fwd_lse": rep_attn_fwd_lse,
+    "ddpm_attention_bwd": rep_attn_bwd,
+    "ddpm_colsum": rep_colsum,
+    "ddpm_upsample2x_bwd": rep_upsample2x_bwd,
+    "ddpm_q_sample": rep_q_sample,
+    "ddpm_mse_fwd": rep_mse_fwd,
+    "ddpm_mse_bwd": rep_mse_bwd,
+    "ddpm_p_sample_step": rep_p_sample_step,
+}
+
+# Entries a step launches that are not replayed here, and the existing test that covers each (tests/test_kernels_gpu.py unless named).
+COVERED_ELSEWHERE = {
+    "ddpm_mt_adam_ema": "test_fused_adam_ema_matches_torch_adam, test_multi_tensor_update_with_scalars_from_device_memory",
+    "ddpm_mt_grad_sumsq": "test_multi_tensor_update_with_scalars_from_device_memory",
+    "ddpm_mt_gather_f32": "test_multi_tensor_gather",
+    "ddpm_wgrad_unpack": "test_wgrad_unpack_and_fused_norm",
+    "ddpm_wgrad_unpack_sumsq": "test_wgrad_unpack_and_fused_norm",
+    "ddpm_pack_weight": "test_timestep_embedding_and_layout_kernels",
+    "ddpm_pack_weight_multi": "test_pack_weight_multi",
+    "ddpm_nchw_to_nhwc": "test_timestep_embedding_and_layout_kernels",
+    "ddpm_timestep_embedding": "test_timestep_embedding_and_layout_kernels",
+    "ddpm_silu_fwd": "test_reductions_and_fanin",
+    "ddpm_silu_bwd": "test_reductions_and_fanin",
+    "ddpm_add_rows": "test_reductions_and_fanin",
+    "ddpm_weighted_sum_f32": "test_diffusion_algebra_kernels",
+    "ddpm_gather_i64": "test_diffusion_algebra_kernels",
+    "ddpm_add_i64": "test_diffusion_algebra_kernels",
+    "ddpm_gather_rows_f32": "test_gather_rows_time_table",
+    "ddpm_softmax_fwd": "test_reductions_and_fanin",
+    "ddpm_softmax_bwd": "test_reductions_and_fanin",
+    "ddpm_stream_order": "not a kernel of arithmetic (stream ordering edge)",
+    "ddpm_fill_zero": "not a kernel of arithmetic (stream-ordered memset)",
+}
+
+
+def sync():
+    if torch.device(_DEVICE[0]).type == "cuda":
+        torch.cuda.synchronize()
+
+
+def replay(sig, device, seed=0):
+    """Replay one signature on `device`; returns a Result (worst err/bar and where)."""
+    _DEVICE[0] = device
+    name, words = sig
+    res = Result(sig)
+    A = Arena(device, seed)
+    REPLAY[name](A, words, res)
+    return res
+
+
+def geometry(sig, offsets=True):
+    """The signature without its dropout seed (every dropout layer draws its own seed; the replay draws masks from the recorded one), and
+    with offsets=False also without the pointer offsets (the host check replays each geometry once)."""
+    name, words = sig
+    types = _hip.PROTOTYPES[name]
+    return (name, tuple(0 if t is ctypes.c_ulonglong else (w[0], w[1], w[2] if offsets else 0) if isinstance(w, tuple) else w
+                        for w, t in zip(words, types)))
+
+
+def short(sig):
+    name, words = sig
+    ws = ",".join(("-" if w[1] else f"@{w[2]}") if isinstance(w, tuple) else (f"{w:g}" if isinstance(w, float) else str(w)) for w in words)
+    return f"{name[5:]}({ws})"
+
+
+# ----------------------------------------------------------------------------------------------------------------- workloads
+def _config(name):
+    import json
+    import os
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ddpm-torch_amd", "configs", name)
+    with open(path) as f:
+        return json.load(f)
+
+
+def _net(cfg, device, seed=0):
+    import ddpm_torch
+    torch.manual_seed(seed)
+    kw = {k: v for k, v in cfg["model"].items() if k != "block_size"}
+    return ddpm_torch.UNet(out_channels=kw["in_channels"], **kw).to(device).set_compute_dtype(torch.bfloat16)
+
+
+def _diffusion(cfg):
+    import ddpm_torch
+    d = cfg["diffusion"]
+    return ddpm_torch.GaussianDiffusion(ddpm_torch.get_beta_schedule(d["beta_schedule"], d["beta_start"], d["beta_end"], d["timesteps"]),
+                                        d["model_mean_type"], d["model_var_type"], d["loss_type"])
+
+
+def _train_step(cfg, device, B, size, drop=None):
+    import ddpm_torch
+    if drop is not None:
+        cfg = dict(cfg, model=dict(cfg["model"], drop_rate=drop))
+    m = _net(cfg, device)
+    tc = cfg["train"]
+    opt = torch.optim.Adam(m.parameters(), lr=tc["lr"], betas=(0.9, 0.999))
+    tr = ddpm_torch.Trainer(m, opt, _diffusion(cfg), epochs=1, trainloader=None, use_ema=tc["use_ema"], grad_norm=tc["grad_norm"],
+                            shape=(3, size, size), device=torch.device(device), ema_decay=tc["ema_decay"])
+    m.train()
+    x = torch.rand(B, 3, size, size, generator=torch.Generator().manual_seed(1)) * 2 - 1
+    return lambda: tr.step(x.to(device), global_steps=1)
+
+
+def _sample_step(cfg, device, B, size, ddim_steps=None):
+    m = _net(cfg, device).eval()
+    dif = _diffusion(cfg)
+    if ddim_steps:
+        import ddim
+        d = cfg["diffusion"]
+        dif = ddim.DDIM(dif.betas if torch.is_tensor(dif.betas) else torch.as_tensor(dif.betas), d["model_mean_type"], "fixed-small",
+                        d["loss_type"], eta=0.0, subsequence=ddim.get_selection_schedule("linear", ddim_steps, d["timesteps"]))
+    g = torch.Generator().manual_seed(2)
+    x = torch.randn(B, 3, size, size, generator=g).to(device)
+    t = torch.full((B,), 500, dtype=torch.int64, device=device)
+    if ddim_steps:
+        t = torch.full((B,), ddim_steps // 2, dtype=torch.int64, device=device)
+
+    def run():
+        with torch.no_grad():
+            dif.p_sample_step(m, x, t)
+    return run
+
+
+# key -> (what it runs, builder(device, B, size)); full size: the geometry the benchmark and the configs run
+WORKLOADS = {
+    "W1": ("cifar10 train step, B=128, dropout 0.1", lambda dev, B=128, s=32: _train_step(_config("cifar10.json"), dev, B, s, drop=0.1), 128, 32),
+    "W2": ("cifar10 ancestral sampling step, B=128", lambda dev, B=128, s=32: _sample_step(_config("cifar10.json"), dev, B, s), 128, 32),
+    "W3": ("celebahq 256x256 train step, B=2", lambda dev, B=2, s=256: _train_step(_config("celebahq.json"), dev, B, s), 2, 256),
+    "W4": ("celeba 64x64 DDIM step, B=128", lambda dev, B=128, s=64: _sample_step(_config("celeba.json"), dev, B, s, ddim_steps=50), 128, 64),
+}
+
+
+def record(monkeypatch, key, device, B=None, size=None):
+    """Run workload `key` once with every _invoke recorded; returns the Recorder."""
+    _, build, B0, S0 = WORKLOADS[key]
+    run = build(device, B or B0, size or S0)
+    rec = Recorder(_hip._invoke)
+    monkeypatch.setattr(_hip, "_invoke", rec)
+    try:
+        run()
+        sync_dev(device)
+    finally:
+        monkeypatch.setattr(_hip, "_invoke", rec.inner)
+    return rec
+
+
+def sync_dev(device):
+    if torch.device(device).type == "cuda":
+        torch.cuda.synchronize()
+
+
+def variant_of(sig):
+    """Kernel the dispatch queries of include/ddpm_hip_debug.h name for a conv / wgrad / GEMM signature (None for other entries)."""
+    lib = _hip.lib()
+    name, w = sig
+    if name == "ddpm_conv2d_nhwc":
+        (_, x_ld, _, _, y_ld, pb, prb, _, pres, _, B, H, W, C, Ho, Wo, N, R, S, stride, pt, pl, ups, dil, acc, mode, splits, _, _, dt) = w
+        epi = int(_opt(pres)) | (2 if acc else 0)            # bit 0: residual operand, bit 1: accumulate (gemm.hip, ddpm_conv2d_variant)
+        # the query stands 16-byte aligned pointers in for the operands and y_ld for the residual pitch: it names the kernel that ran
+        # only when the recorded call meets the same alignment conditions, so hold the recorded call to them
+        assert all(p[2] % 16 == 0 for p in w if isinstance(p, tuple) and not p[1]), f"unaligned operand in {short(sig)}"
+        assert not _opt(pres) or (w[9] % 8 == 0 and y_ld % 8 == 0), f"residual pitch the query cannot stand in for: {short(sig)}"
+        return int(lib.ddpm_conv2d_variant(x_ld, y_ld, B, H, W, C, Ho, Wo, N, R, S, stride, pt, pl, ups, dil, mode, splits, dt, epi))
+    if name == "ddpm_conv2d_wgrad_nhwc":
+        (_, dy_ld, _, x_ld, _, _, B, H, W, C, Creal, Ho, Wo, N, Nreal, R, S, stride, pt, pl, ups, splits, dt) = w
+        return int(lib.ddpm_conv2d_wgrad_variant(dy_ld, x_ld, B, H, W, C, Creal, Ho, Wo, N, Nreal, R, S, stride, pt, pl, ups, splits, dt))
+    if name in ("ddpm_conv3x3_wgrad_nhwc", "ddpm_conv3x3_wgrad_up_nhwc"):
+        B, H, W, C, N = w[8:13]
+        return int(lib.ddpm_conv3x3_wgrad_variant(B, H, W, C, N))
+    if name == "ddpm_conv1x1_wgrad_nhwc":
+        return 9
+    if name == "ddpm_gemm":
+        (_, a_ld, _, a_tr, _, b_ld, _, b_tr, _, c_ld, _, _, _, _, _, M, N, K, batch, _, _, mode, splits, dt) = w
+        return int(lib.ddpm_gemm_variant(a_ld, a_tr, b_ld, b_tr, c_ld, M, N, K, batch, mode, splits, dt))
+    return None

@@ -437,7 +437,8 @@ def test_groupnorm_fwd_bwd(dt, B, HW, C, silu, drop):
 @pytest.mark.parametrize("B,HW,C", [(2, 1024, 128), (2, 256, 256), (3, 64, 256), (2, 4096, 128)])
 def test_groupnorm_statistics_with_mean_far_from_zero(dt, B, HW, C):
     """|mean| / std = 500 (50 +- 0.1, the case a single-pass sum / sum-of-squares loses in fp32): every path — streaming
-    two-launch, staged, register-resident — must reproduce the two-pass fp64 statistics."""
+    two-launch, staged, register-resident — must reproduce the two-pass fp64 statistics, and the backward at those means must match its
+    fp64 restatement."""
     x = (r(B * HW, C, seed=1, scale=0.1) + 50.0)
     x = x + torch.arange(C).float()[None, :] * 0.01                       # channels of a group differ a little
     xq = x.to(DT[dt])
@@ -461,6 +462,33 @@ def test_groupnorm_statistics_with_mean_far_from_zero(dt, B, HW, C):
         got = stats.cpu()
         assert float((got[..., 0] - want[..., 0]).abs().max()) < 1e-4 * 50, entry
         assert float(((got[..., 1] - want[..., 1]) / want[..., 1]).abs().max()) < 1e-3, (entry, got[0, :3], want[0, :3])
+    # the backward at the same means, from the two-pass statistics: dx = rstd * (dy*gamma - xh*c1 - c2) (no SiLU / dropout), dgamma, dbeta
+    dy = r(B * HW, C, seed=4).to(DT[dt])
+    xd, dyd, st = xq.cuda(), dy.cuda(), want.cuda()
+    dx, dg, db, ws = torch.empty_like(xd), torch.zeros(C, device="cuda"), torch.zeros(C, device="cuda"), torch.zeros(nws, device="cuda")
+    _hip.call("ddpm_groupnorm_silu_bwd", xd.data_ptr(), C, dyd.data_ptr(), C, dx.data_ptr(), C, gd.data_ptr(), bd.data_ptr(), st.data_ptr(),
+              dg.data_ptr(), db.data_ptr(), ws.data_ptr(), B, HW, C, 32, 0, 0.0, 0, 0, 0, 0, 0, 0, 0, dt, _hip.stream())
+    m64 = want[..., 0].double().repeat_interleave(C // 32, 1)[:, None, :]
+    r64 = want[..., 1].double().repeat_interleave(C // 32, 1)[:, None, :]
+    xh = (xq.double().reshape(B, HW, C) - m64) * r64
+    a = dy.double().reshape(B, HW, C) * gamma.double()
+    grp = lambda v: v.reshape(B, HW, 32, C // 32).mean((1, 3)).repeat_interleave(C // 32, 1)[:, None, :]
+    c1, c2 = grp(a * xh), grp(a)
+    ref = r64 * (a - xh * c1 - c2)
+    # per-element bars, the GroupNorm backward model of tests/launch_replay.py (rep_gn_bwd): the store rounds the terms of
+    # rstd * (dz*gamma - xh*c1 - c2); the fp32 part covers the group sums and xh recomputed from |x| + |mean| ~ 100 at rstd ~ 10
+    u, n, K = (2.0 ** -8 if dt == 1 else 2.0 ** -24), (C // 32) * HW, B * HW
+    inner = r64 * (a.abs() + (xh * c1).abs() + c2.abs())
+    xm = xq.double().reshape(B, HW, C).abs() + m64.abs()
+    bar = 4 * (u * inner + 2.0 ** -24 * math.sqrt(n) * (inner + r64 * c1.abs() * xm * r64))
+    ratio = float(((dx.cpu().double().reshape(B, HW, C) - ref).abs() / bar).max())
+    assert ratio <= 1.0, ("bwd dx err/bar", ratio)
+    dz = dy.double().reshape(K, C)
+    for got_c, terms, lin, nm in ((dg, dz * xh.reshape(K, C), (dz.abs() * (xm * r64).reshape(K, C)).sum(0), "dgamma"), (db, dz, 0.0, "dbeta")):
+        ref_c = terms.sum(0)
+        bar_c = 4 * 2.0 ** -24 * (ref_c.abs() + math.sqrt(K) * (terms * terms).sum(0).sqrt() + lin)
+        ratio = float(((got_c.cpu().double() - ref_c).abs() / bar_c).max())
+        assert ratio <= 1.0, (nm + " err/bar", ratio)
 
 
 @pytest.mark.parametrize("B,L,C", [(3, 256, 256), (2, 128, 128), (2, 384, 256)])

@@ -1,0 +1,103 @@
+"""Host check (CPU) of tests/launch_replay.py, the replay-against-float64 machinery of tests/test_step_launches_gpu.py.
+
+The four workloads of the GPU test run through the host-emulated engine (tests/abi_emulator.py) at batch 2 (CelebA-HQ at 128x128 instead of
+256x256: its geometry does not change how the contract is read), their launches are recorded, and every recorded signature of a
+replayed entry is replayed against the emulator.  This shows, before any GPU time, that the replay builders size their buffers, read
+pitches, epilogue terms, output modes and slab workspaces the way include/ddpm_hip.h states them — two independent restatements
+(the emulator and the float64 references) must agree within the per-element bars — and that no emulated write leaves the extents the
+builders computed (the guard bands and the untouched elements are checked after every launch).  Every recorded entry is accounted for."""
+import os
+import time
+
+import pytest
+import torch
+
+from ddpm_torch import _hip
+from tests import abi_emulator
+from tests import launch_replay as LR
+
+pytestmark = pytest.mark.skipif(not os.path.exists(_hip.LIB_PATH), reason="libddpm_hip.so not built")
+
+# The emulator is itself an fp32 restatement (torch's CPU group-norm backward forms dgamma as sum(dz x) - mean sum(dz), which cancels
+# where |mean| >> std): its own rounding may exceed a bar written for the kernels by a small factor.  A misread pitch, operand or
+# epilogue term is off by the size of the value itself, 10^3..10^7 bars.
+HOST_SLACK = 4.0
+HOST_SIZE = {"W1": (2, 32), "W2": (2, 32), "W3": (2, 128), "W4": (2, 64)}
+
+
+def test_replay_builders_agree_with_the_emulator_on_every_recorded_signature(monkeypatch):
+    abi_emulator.install(monkeypatch, _hip)
+    t0 = time.perf_counter()
+    sigs, names = {}, set()
+    for key, (B, size) in HOST_SIZE.items():
+        rec = LR.record(monkeypatch, key, "cpu", B, size)
+        names |= set(rec.names)
+        for s in rec.sigs:
+            sigs.setdefault(LR.geometry(s, offsets=False), key)
+    unaccounted = sorted(names - set(LR.REPLAY) - set(LR.COVERED_ELSEWHERE))
+    assert not unaccounted, f"recorded entries neither replayed nor mapped to a covering test: {unaccounted}"
+    for must in ("ddpm_conv2d_nhwc", "ddpm_groupnorm_silu_fwd", "ddpm_groupnorm_silu_bwd", "ddpm_attention_fwd_lse", "ddpm_attention_bwd",
+                 "ddpm_q_sample", "ddpm_p_sample_step"):
+        assert must in names, must
+    worst = []
+    for s, key in sigs.items():
+        if s[0] not in LR.REPLAY:
+            continue
+        r = LR.replay(s, "cpu")
+        worst.append((r.worst, key, LR.short(s), r.where))
+        assert r.worst <= HOST_SLACK, f"{key} {LR.short(s)}: {r.where} err/bar {r.worst:.3g}"
+    worst.sort(reverse=True)
+    for w in worst[:8]:
+        print(f"{w[1]} {w[2]} -> {w[3]} err/bar {w[0]:.3f}")
+    print(f"{len(worst)} signatures replayed in {time.perf_counter() - t0:.1f} s")
+
+
+def test_keep_mask_restatement_is_bit_equal_to_the_numpy_hash():
+    import numpy as np
+    for seed in (0, 12345, 0x5DEECE66D + 977, (1 << 63) + 99):
+        idx = np.concatenate([np.arange(70000, dtype=np.uint64), np.uint64(1 << 33) + np.arange(5000, dtype=np.uint64)])
+        for p in (0.1, 0.5):
+            want = abi_emulator._keep_mask(seed, idx, abi_emulator._thresh(p))
+            got = LR.keep_mask(seed, torch.from_numpy(idx.astype(np.int64)), p).numpy()
+            assert (got == want).all(), (seed, p)
+
+
+def test_guard_band_and_untouched_elements_catch_a_stray_write():
+    """The checks the replays rely on: a write one element past a pitched row, or into a guard band, is reported."""
+    A = LR.Arena("cpu", 0)
+    b = A.buf("m", LR.pitched(4, 8, 16), LR.F32, 48)
+    assert b.ptr % 256 == 48
+    b.fill(torch.zeros(b.n))
+    b.out(4, 8, 16)
+    A.snapshot()
+    b.mat(4, 8, 16)[...] = 1.0
+    A.check()                                          # writes inside the declared output: fine
+    b.t[8] = 2.0                                       # pitch gap
+    with pytest.raises(AssertionError, match="outside the contract"):
+        A.check()
+    b.t[8] = 0.0
+    A.check()
+    b.raw[b.start + b.nbytes + 5] = 0
+    with pytest.raises(AssertionError, match="guard band"):
+        A.check()
+
+
+def test_error_model_bars_bite_at_the_scale_of_a_one_percent_kernel_error(monkeypatch):
+    """A conv result off by 2^-4 of one bias term in one output channel must exceed its bar: the bars are per element, not a fraction of
+    the tensor maximum."""
+    emu = abi_emulator.install(monkeypatch, _hip)
+    sig = ("ddpm_conv2d_nhwc", (("p", False, 0), 64, ("p", False, 0), ("p", False, 0), 64, ("p", False, 0), ("p", True, 0), 0,
+                                ("p", False, 0), 64, 2, 8, 8, 64, 8, 8, 64, 3, 3, 1, 1, 1, 0, 0, 0, 0, 1, ("p", True, 0),
+                                ("p", True, 0), 1))
+    assert LR.replay(sig, "cpu").worst <= 1.0
+    real = emu.ddpm_conv2d_nhwc
+
+    def skewed(*a):
+        real(*a)
+        bias, y, y_ld = a[5], a[3], a[4]
+        ys = abi_emulator.Mat(y, 2 * 64, 64, y_ld, abi_emulator.BF16)
+        v = ys.get()
+        v[:, 63] += abi_emulator.f32(bias, 64)[63] * 2.0 ** -4
+        ys.set(v)
+    monkeypatch.setattr(emu, "ddpm_conv2d_nhwc", skewed)
+    assert LR.replay(sig, "cpu").worst > 1.0
