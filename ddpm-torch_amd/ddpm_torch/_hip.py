@@ -82,6 +82,11 @@ PROTOTYPES = {
     "ddpm_set_reserved_cus": [I],
     "ddpm_get_reserved_cus": [],
     "ddpm_copy_probe": [P, P, L, I, P],
+    # the toy denoiser (csrc/toymlp.hip; driven by toy/toy_model.py)
+    "ddpm_toy_time_table": [P, P, P, P, P, P, I, I, P],
+    "ddpm_toy_decoder_fwd": [P] * 16 + [I] * 5 + [P],
+    "ddpm_toy_decoder_bwd": [P] * 19 + [L] + [I] * 5 + [P],
+    "ddpm_toy_time_table_bwd": [P] * 7 + [L, I, I, I, P],
     # launch plans (csrc/plan.hip; driven by _plan.LaunchPlan)
     "ddpm_stream_order": [P, P],
     "ddpm_fill_zero": [P, L, P],

@@ -100,6 +100,10 @@ class _AutogradVLB(torch.autograd.Function):
 
 
 class GaussianDiffusion:
+    # whether the sampling loops (eager and captured) clamp the x_0 estimate to [-1, 1] (diffusion.py:152-158 pass clip_denoised=True);
+    # the 2-D toy subclass never clips (toy/diffusion.py:32)
+    clip_sampling = True
+
     def __init__(self, betas, model_mean_type, model_var_type, loss_type, **kwargs):
         assert isinstance(betas, torch.Tensor) and betas.dtype == _F64          # diffusion.py:42-43
         assert (betas > 0).all() and (betas <= 1).all()
@@ -302,7 +306,7 @@ class GaussianDiffusion:
             t.fill_(ti)
             out = denoise_fn(x_t, self._model_t(t))
             z = torch.empty_like(x_t).normal_(generator=rng) if z_stream is None else next(z_stream).to(x_t)
-            x_t, pred = self._step(x_t, out, z, t, True, on_step is not None)
+            x_t, pred = self._step(x_t, out, z, t, self.clip_sampling, on_step is not None)
             if on_step is not None:
                 on_step(ti, pred)
         return x_t
@@ -407,7 +411,7 @@ class GaussianDiffusion:
             if not external_z:
                 z.normal_(generator=rng)
             _hip.call("ddpm_p_sample_step", x_t.data_ptr(), out.data_ptr(), z.data_ptr(), t.data_ptr(), *[tb.data_ptr() for tb in tabs],
-                      x_t.data_ptr(), 0, B, n, mean_code, 1, T, _hip.stream())         # in place: each element is read once, then written
+                      x_t.data_ptr(), 0, B, n, mean_code, int(self.clip_sampling), T, _hip.stream())   # in place: each element is read once, then written
             _hip.call("ddpm_add_i64", t.data_ptr(), B, -1, _hip.stream())
 
         gen = rng if rng is not None else torch.cuda.default_generators[dev.index if dev.index is not None else torch.cuda.current_device()]

@@ -1,7 +1,9 @@
 """Host-side functional helpers mirroring ``ddpm_torch/functions.py`` of the reference for the hot path:
-``get_timestep_embedding`` (functions.py:10-26) and ``flat_mean`` (functions.py:99-101).  Device work goes
-through the C-ABI; CPU tensors raise (no fallback)."""
+``get_timestep_embedding`` (functions.py:10-26) and ``flat_mean`` (functions.py:99-101), plus the toy evaluator's NumPy histograms
+``hist2d`` / ``discrete_klv2d`` (functions.py:75-97).  Device work goes through the C-ABI; CPU tensors raise (no fallback)."""
 import math
+
+import numpy as np
 
 import torch
 
@@ -32,3 +34,27 @@ def get_timestep_embedding(timesteps, embed_dim, dtype=torch.float32):
 
 def flat_mean(x, start_dim=1):
     return torch.mean(x, dim=list(range(start_dim, x.ndim)))
+
+
+def _axis_ranges(value_range):
+    """None | r (both axes [-r, r]) | (lo, hi) for both axes | ((xlo, xhi), (ylo, yhi))  ->  numpy.histogram2d's ``range``."""
+    if value_range is None:
+        return None
+    if isinstance(value_range, (int, float)):
+        return ((-value_range, value_range), (-value_range, value_range))
+    first = next(iter(value_range))
+    return tuple(value_range) if hasattr(first, "__iter__") else (tuple(value_range), tuple(value_range))
+
+
+def hist2d(data, bins, value_range=None):
+    """Counts of the 2-D points ``data`` [N, 2] on a bins x bins grid (``bins="auto"``: floor(sqrt(N // 10)))."""
+    pts = np.asarray(data)
+    nb = math.floor(math.sqrt(len(pts) // 10)) if bins == "auto" else bins
+    counts, _, _ = np.histogram2d(pts[:, 0], pts[:, 1], bins=nb, range=_axis_ranges(value_range))
+    return counts
+
+
+def discrete_klv2d(hist1, hist2, eps=1e-9):
+    """KL(hist2 || hist1) of two normalised histograms, each cell regularised by ``eps``."""
+    log_ratio = np.log(hist2 + eps) - np.log(hist1 + eps)
+    return np.sum(hist2 * log_ratio)

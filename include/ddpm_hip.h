@@ -255,6 +255,40 @@ int ddpm_mt_adam_ema(const long long* table, int n_tensors, const float* total_s
  * concatenated time-bias projection (all ResidualBlock.fc weights; fc.bias + conv1.bias, ddpm_torch/models/unet.py:77,85-86). */
 int ddpm_mt_gather_f32(const long long* table, int n_tensors, void* stream);
 
+/* ---- the 2-D toy denoiser, BASELINE config 1 (upstream toy/toy_model.py:17-62, csrc/toymlp.hip), fp32 only.
+ *   Decoder(D, M, L):  h_0 = x W_in^T (toy_model.py:44,59);  e[t] = enc(lrelu(t_proj(temb(t)))) (:53-55,57-58; TemporalLayer.enc :26,35);
+ *   h_{l+1} = h_l + fc2(lrelu(LN2(fc1(lrelu(LN1(h_l))) + e[t])))  with ONE TemporalLayer object used L times (:32-37,47-48,60);
+ *   y = out_fc(LN_out(h_L)) + out_fc.b (:49-50,61).  LayerNorm eps 1e-5 (affine), LeakyReLU slope 0.02 (:14), temb as ddpm_timestep_embedding.
+ * Geometry: 1 <= D <= 16, M % 32 == 0 with 32 <= M <= 256, L >= 1, B >= 1, 1 <= T <= 4096; anything else DDPM_ERR_SHAPE.  Weights are the
+ * module's fp32 tensors (nn.Linear layout [out][in]); fc1_w / fc2_w 16-byte aligned.  t outside [0, T) makes that row NaN.
+ *
+ * ddpm_toy_time_table (toy_model.py:57-58 + :35 `self.enc(t_emb)`): tabs [2][T][M] = {E[t] = enc(c[t]), c[t] = lrelu(t_proj(temb(t)))} for
+ * every t < T, computed from the live parameters on every call (c is the enc input and the LeakyReLU mask of the backward).
+ * freqs: the M/2 fp32 frequencies of ddpm_timestep_embedding. */
+int ddpm_toy_time_table(const float* freqs, const float* tproj_w, const float* tproj_b, const float* enc_w, const float* enc_b,
+                        float* tabs, int T, int M, void* stream);
+/* Decoder.forward (toy_model.py:56-62) for x [B][D], t [B] int64, one launch: y [B][D].  saved (null: inference) receives what the
+ * backward needs: [L+1][B][M] h_0..h_L, then [B][2L+1][2] (mean, rstd) of LN1 / LN2 of every layer and of LN_out (toy_model.py:33-34,61). */
+int ddpm_toy_decoder_fwd(const float* x, const long long* t, const float* w_in, const float* n1_w, const float* n1_b, const float* fc1_w,
+                         const float* n2_w, const float* n2_b, const float* fc2_w, const float* on_w, const float* on_b, const float* out_w,
+                         const float* out_b, const float* tabs, float* y, float* saved, int B, int D, int M, int L, int T, void* stream);
+/* autograd of Decoder.forward (toy_model.py:56-62) except the time path: from dy [B][D] and the forward's saved buffer,
+ *   dx [B][D] (null: not wanted);
+ *   grads = [in_fc.w M*D][norm1.w M][norm1.b M][fc1.w M*M][norm2.w M][norm2.b M][fc2.w M*M][out_norm.w M][out_norm.b M][out_fc.w D*M][out_fc.b D]
+ *           (the shared layer's gradients summed over its L uses);
+ *   dzsum [B][M] = sum over layers of the gradient at the fc1 output (= at e[t] of that row; input of ddpm_toy_time_table_bwd).
+ * Every output is overwritten.  ws: ws_floats >= 4*r(L*B*M) + r(2*S*M*M) + r(ceil(B/32)*(6M + 2MD + D)) with r(n) = n rounded up to a
+ * multiple of 64 and S = min(64, max(1, ceil(L*B/512))) — per-row operands of the weight gradients and per-block partial slabs, summed in
+ * a fixed order (no atomics: bit-identical on repetition). */
+int ddpm_toy_decoder_bwd(const float* x, const long long* t, const float* dy, const float* w_in, const float* n1_w, const float* n1_b,
+                         const float* fc1_w, const float* n2_w, const float* n2_b, const float* fc2_w, const float* on_w, const float* on_b,
+                         const float* out_w, const float* tabs, const float* saved, float* dx, float* grads, float* dzsum, float* ws,
+                         long long ws_floats, int B, int D, int M, int L, int T, void* stream);
+/* autograd of the time table (toy_model.py:57-58, :26,35): dE[t] = sum of dzsum over the rows with that t (row order), then
+ * gtab = [enc.w M*M][enc.b M][t_proj.0.w M*M][t_proj.0.b M] (overwritten).  ws: ws_floats >= 3*T*M. */
+int ddpm_toy_time_table_bwd(const long long* t, const float* dzsum, const float* freqs, const float* enc_w, const float* tabs, float* gtab,
+                            float* ws, long long ws_floats, int B, int M, int T, void* stream);
+
 /* ---- launch plans (no upstream counterpart: the reference issues its step op by op from Python, ddpm_torch/utils/train.py:148-170).
  * The training step is a fixed sequence of the calls above; a plan records it once — entry-point name + argument words + the
  * hipStream_t each call was given — and ddpm_plan_run re-issues a whole segment from C: eager semantics (two concurrent streams,
