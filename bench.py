@@ -3,12 +3,15 @@
     python bench.py --gpus N --steps K --warmup W          (N > 1: one rank per GPU under torch.distributed.run — started bare, bench.py
                                                             launches the ranks itself; a WORLD_SIZE that differs from N is an error)
     python bench.py ... --dump-outputs DIR                 (after the K timed steps: what the last one left the caller, DIR/<name>.npy)
+    python bench.py ... --full                             (after them, everything else listed below; --sample-steps S, --no-extras and
+                                                            --no-cpu-baseline trim that part)
 
 One "step" = one full reference training step (ddpm_torch/utils/train.py:148-170: forward, backward, global-norm clip,
 Adam, LR schedule, EMA, loss reduce incl. loss.item()) on B=128 synthetic 32x32 images PER GPU (weak scaling), bf16
 compute with fp32 master weights / gradients / optimizer state, dropout 0.1 active — configs/cifar10.json of the
 reference (BASELINE config 2; config 3 at N > 1).  Inputs are resident in HBM before the timed region.
-Rank 0 prints ONE JSON line.  Beyond the driver's contract it carries:
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps, dumps if asked and prints the line: the headline figure,
+`ms_per_step`, its blocks and the step's configuration.  With --full the line also carries:
   roofline     — the MFMA kernel with the most GPU time per step (ranked with every kernel alone on the chip): algorithmic
                  FLOPs of its launches / their summed HIP-event durations in the product step (events recorded on the launch
                  stream — main or side — around every MFMA launch of one extra step), vs the dense bf16 peak; `isolated` = the
@@ -246,130 +249,12 @@ def median(v):
     return v[len(v) // 2] if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2])
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100)
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--sample-steps", type=int, default=1000, help="length of the timed p_sample chain (1000 = the real thing; 0 = skip sampling and the other configs)")
-    ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the fp32 / CelebA / CelebA-HQ lines")
-    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
-                    help="after the timed steps, write what the last one left the caller (sampled parameters, Adam moments, EMA, loss) to DIR/<name>.npy")
-    args = ap.parse_args()
-
-    if args.gpus < 1:
-        raise SystemExit("bench.py: --gpus must be >= 1")
-    if args.steps < 1:
-        raise SystemExit("bench.py: --steps must be >= 1")
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # Started bare (`python bench.py --gpus N`): become the launcher — one rank per GPU under torch.distributed.run, rendezvous
-        # on the loopback address (the reference self-spawns too: train.py:286-301).  The driver's own torchrun command line sets
-        # WORLD_SIZE and lands in the branch below.
-        import socket
-        import subprocess
-        with socket.socket() as sk:
-            sk.bind(("127.0.0.1", 0))
-            port = sk.getsockname()[1]
-        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
-               "--master-port", str(port), os.path.abspath(__file__), *sys.argv[1:]]
-        env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
-        raise SystemExit(subprocess.call(cmd, env=env))
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = int(os.environ.get("RANK", "0"))
-    local = int(os.environ.get("LOCAL_RANK", "0"))
-    if world != args.gpus:
-        raise SystemExit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}: the line would be mislabelled; launch one rank per GPU "
-                         f"(python -m torch.distributed.run --nproc-per-node {args.gpus} bench.py --gpus {args.gpus} ...) or run bench.py bare")
-    distributed = world > 1
-    if os.environ.get("BENCH_LAUNCH_PROBE"):
-        # test hook (tests/test_bench_contract.py, no GPU): prove that N ranks were started and can talk, then stop before any GPU work
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        if distributed:
-            dist.init_process_group("gloo", init_method="env://", world_size=world, rank=rank)
-        seen = torch.ones(1)
-        if distributed:
-            dist.all_reduce(seen)
-            dist.destroy_process_group()
-        if rank == 0:
-            print(json.dumps({"launch_probe": True, "n_gpus": world, "ranks_in_collective": int(seen)}))
-        return
-    # The JSON line must be the only thing on stdout.  RCCL prints a version banner ("RCCL version : ... / Librccl path : ...") through C
-    # stdio when a communicator comes up; on a pipe or a file that buffer is flushed at process exit, i.e. AFTER Python's own line — seen on
-    # the one-rank RCCL run (profiles/r05h_bench_ddp1.json was followed by five banner lines), and with N ranks every rank would add its own.
-    # So the process-level stdout (fd 1) of every rank is pointed at stderr from here on and Python keeps the original for its one print.
-    sys.stdout.flush()
-    json_out = os.fdopen(os.dup(1), "w")
-    os.dup2(2, 1)
-    torch.cuda.set_device(local)
-    dev = torch.device("cuda", local)
-    ranks_seen = 1
-    # BENCH_DDP=native on ONE GPU: a world-size-1 RCCL communicator, so that the exchange path (chunked all-reduces issued from inside the
-    # backward, loss reduce, barrier) runs and config.dp can be read before a node is available
-    self_ddp = world == 1 and os.environ.get("BENCH_DDP") == "native"
-    if self_ddp:
-        import socket
-        with socket.socket() as sk:
-            sk.bind(("127.0.0.1", 0))
-            port1 = sk.getsockname()[1]
-        dist.init_process_group("nccl", init_method=f"tcp://127.0.0.1:{port1}", world_size=1, rank=0)
-        distributed = True
-    elif distributed:
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        dist.init_process_group("nccl", init_method="env://", world_size=world, rank=rank)     # "nccl" is RCCL on ROCm
-        probe = torch.ones(1, device=dev)
-        dist.all_reduce(probe)                                                                 # every rank present on the RCCL communicator
-        ranks_seen = int(probe)
-        assert ranks_seen == world, f"RCCL communicator has {ranks_seen} ranks, expected {world}"
-
-    import ddim
-    import ddpm_torch
+def roofline_leg(args, model, tr, x0, dev, rank, world):
+    """--full: per-launch figures of two more training steps, which every rank runs (with N > 1 they contain the collectives).
+    Returns (roofline, dp) on rank 0, (None, None) on the other ranks."""
     import ddpm_torch.models.unet as unet_mod
     import ddpm_torch.utils.train as train_mod
     from ddpm_torch import _ops
-    ddpm_torch.seed_all(1234)
-    # Data parallelism: the engine's own reducer (parameters broadcast from rank 0; gradient staging buffer all-reduced over
-    # RCCL in chunks from inside the hand-written backward, overlapped with the rest of it).  BENCH_DDP=torch falls back to
-    # the reference's DistributedDataParallel wrapper (train.py:110), which also works but only starts reducing after backward.
-    native = os.environ.get("BENCH_DDP", "native") != "torch"
-    model, net, dif, tr = make_trainer(ddpm_torch, CIFAR, dev, args.dtype, (3, 32, 32), "fixed-large", distributed, rank, native, local)
-    g = torch.Generator().manual_seed(1234 + rank)
-    x0 = (torch.rand(B_PER_GPU, 3, 32, 32, generator=g) * 2 - 1).to(dev)            # resident before timing
-
-    def sync():
-        torch.cuda.synchronize()
-        if distributed:
-            dist.barrier()
-            torch.cuda.synchronize()
-
-    net.train()
-    # exactly --steps timed steps, bracketed by barrier + synchronize, the MAX over ranks; device events split them into up to
-    # BENCH_BLOCKS (5) consecutive parts without synchronising in between, whose spread is reported next to the figure
-    n_blocks = max(1, min(int(os.environ.get("BENCH_BLOCKS", "5")), args.steps))
-    elapsed = timed_steps(tr, x0, args.steps, args.warmup, sync, parts=n_blocks)[0]
-    part_s = timed_steps.parts if n_blocks > 1 else [elapsed]
-    if distributed:
-        te = torch.tensor([elapsed], device=dev)
-        dist.all_reduce(te, op=dist.ReduceOp.MAX)
-        elapsed = float(te[0])
-    ms_per_step = elapsed / args.steps * 1e3
-    imgs_per_s = B_PER_GPU * world * args.steps / elapsed
-    part_steps = [args.steps * (j + 1) // n_blocks - args.steps * j // n_blocks for j in range(n_blocks)]
-    dumped = dump_outputs(args.dump_outputs, model, tr) if args.dump_outputs and rank == 0 else None
-    loss = tr.current_stats["loss"]
-    kinds = {d.last_kind for d in tr._direct.values()}
-    form = "graph" if "graph" in kinds else ("plan" if "plan" in kinds else "eager")
-    step_mode = "direct step, " + {"graph": "hipGraph replay", "plan": "launch plan (ddpm_plan_run: the step's C-ABI calls re-issued from C on both streams)",
-                                   "eager": "eager launches"}[form] + (" (chosen by measurement)" if any(d.choice for d in tr._direct.values()) else "") \
-        if tr._direct else "autograd step"
-    # what the auto-probe measured for each form of the step on THIS box (ms per step, 4 pipelined steps each, before the timed region)
-    step_probe = {}
-    for d in tr._direct.values():
-        step_probe = {k + "_ms": round(v * 1e3, 3) for k, v in d.times.items()}
-        if d.plan is not None:
-            step_probe["plan_launches"] = d.plan.launches
-
     # ---- roofline of the dominant kernel: per-launch HIP events (recorded on the stream each kernel is launched on) over
     # one more training step.  The product runs the weight-gradient kernels on a side stream NEXT to the critical path, so
     # a launch's duration includes the slowdown from sharing the chip; `isolated` repeats the measurement with that
@@ -458,7 +343,6 @@ def main():
         practical = {"tflops": round(6 * it_p * 16 * 32768.0 * 1024 / (ea.elapsed_time(eb) * 1e-3) / 1e12, 1),
                      "what": "ddpm_mfma_probe: MFMA-only loop (v_mfma_f32_32x32x16_bf16, 8 accumulators per wave, one wave per SIMD, all 256 CUs) on random bf16 "
                              "operands held in registers, sustained ~0.3 s after warm-up on this box; zero operands reach the nominal peak"}
-    out = None
     if rank == 0:
         if os.environ.get("BENCH_SHAPES"):
             with open(os.environ["BENCH_SHAPES"], "w") as f:
@@ -549,29 +433,18 @@ def main():
                   "chunk_target": os.environ.get("DDPM_DP_CHUNK_MB", "conv-weight region / 6 (~24 MB)") ,
                   "note": "timestamps on the compute stream of the profiled eager step (side stream off); the last chunk is the small-tensor tail. "
                           "On one GPU the communicator has a single rank: the times show WHEN the exchanges are issued, not what xGMI does with them"}
-        out = {"metric": "training imgs/s/GPU + 1000-step DDPM samples/s, CIFAR-10 UNet @1/2/4/8 MI355X",
-               "value": round(imgs_per_s, 2), "unit": "imgs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-               "ms_per_step": round(ms_per_step, 3), "ms_per_step_blocks": [round(v / n * 1e3, 3) for v, n in zip(part_s, part_steps)],
-               "timing": f"{args.steps} consecutive steps bracketed by barrier + device sync (max over ranks); ms_per_step_blocks = the same steps "
-                         f"in {n_blocks} consecutive parts of {part_steps} steps timed by device events (rank 0)",
-               "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-               "dtype": args.dtype, "data": "synthetic",
-               "config": {"workload": "configs/cifar10.json UNet (35.7M params), full Trainer.step, B=128 per GPU, 32x32, T=1000, dropout 0.1, Adam+clip+EMA",
-                          "global_batch": B_PER_GPU * world, "rccl_ranks": ranks_seen, "dp": dp,
-                          "parallelism": f"dp{world}" + ("" if world == 1 else (" (native chunked RCCL all-reduce inside backward)" if native else " (torch DDP)")),
-                          "step_execution": step_mode, "step_probe": step_probe,
-                          "hbm_gb": {"reserved": round(torch.cuda.memory_reserved() / 2 ** 30, 2), "allocated_peak": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2),
-                                     "of": 288, "note": "whole bench process at the end of the run (training state + the step form's private pool + the sampler's graphs + the other-configs legs)"},
-                          "imgs_per_s_per_gpu": round(imgs_per_s / world, 2),
-                          "train_model_tflops_per_gpu": round(imgs_per_s / world * 3 * FWD_GFLOP["cifar"] / 1e3, 1),
-                          "train_model_frac_of_peak": round(imgs_per_s / world * 3 * FWD_GFLOP["cifar"] / 1e3 / peak, 4), "final_loss": round(loss, 4)},
-               "roofline": roofline}
-        if dumped:
-            out["dump_outputs"] = {"dir": args.dump_outputs, "files": dumped}
+        return roofline, dp
+    return None, None
 
-    # ---- sampling + the other BASELINE configurations (rank 0 only: independent work, no collectives)
+
+def sampling_and_other_configs(args, out, model, net, dif, x0, dev, world):
+    """--full, rank 0 only (independent work, no collectives): the sampling figures and the other BASELINE configurations, added
+    to `out`."""
+    import ddim
+    import ddpm_torch
+    peak = PEAK[args.dtype]
     S = args.sample_steps
-    if rank == 0 and S > 0:
+    if S > 0:
         net.eval()
         # the reference's p_sample (EMA weights are what generate.py samples with; same cost), B=128, eval mode, fixed-large,
         # seed 131071.  --sample-steps 1000 (default) runs the real 1000-step chain end to end; a smaller S times an S-step
@@ -653,8 +526,160 @@ def main():
                 "dtype": args.dtype, "note": "20-step chain timed, scaled to 1000 steps"}
             del mh, nh, th
             out["other_configs"] = extras
-    if rank == 0 and not args.no_cpu_baseline and world == 1:
-        out["cpu_baseline"] = cpu_baseline()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--sample-steps", type=int, default=1000,
+                    help="--full: length of the timed p_sample chain (1000 = the real thing; 0 = skip sampling and the other configs)")
+    ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the fp32 / CelebA / CelebA-HQ lines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one left the caller (sampled parameters, Adam moments, EMA, loss) to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the roofline, sampling, the other configurations and the CPU baseline")
+    args = ap.parse_args()
+
+    if args.gpus < 1:
+        raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        # Started bare (`python bench.py --gpus N`): become the launcher — one rank per GPU under torch.distributed.run, rendezvous
+        # on the loopback address (the reference self-spawns too: train.py:286-301).  The driver's own torchrun command line sets
+        # WORLD_SIZE and lands in the branch below.
+        import socket
+        import subprocess
+        with socket.socket() as sk:
+            sk.bind(("127.0.0.1", 0))
+            port = sk.getsockname()[1]
+        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
+               "--master-port", str(port), os.path.abspath(__file__), *sys.argv[1:]]
+        env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
+        raise SystemExit(subprocess.call(cmd, env=env))
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    rank = int(os.environ.get("RANK", "0"))
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    if world != args.gpus:
+        raise SystemExit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}: the line would be mislabelled; launch one rank per GPU "
+                         f"(python -m torch.distributed.run --nproc-per-node {args.gpus} bench.py --gpus {args.gpus} ...) or run bench.py bare")
+    distributed = world > 1
+    if os.environ.get("BENCH_LAUNCH_PROBE"):
+        # test hook (tests/test_bench_contract.py, no GPU): prove that N ranks were started and can talk, then stop before any GPU work
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        if distributed:
+            dist.init_process_group("gloo", init_method="env://", world_size=world, rank=rank)
+        seen = torch.ones(1)
+        if distributed:
+            dist.all_reduce(seen)
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps({"launch_probe": True, "n_gpus": world, "ranks_in_collective": int(seen)}))
+        return
+    # The JSON line must be the only thing on stdout.  RCCL prints a version banner ("RCCL version : ... / Librccl path : ...") through C
+    # stdio when a communicator comes up; on a pipe or a file that buffer is flushed at process exit, i.e. AFTER Python's own line — seen on
+    # the one-rank RCCL run (profiles/r05h_bench_ddp1.json was followed by five banner lines), and with N ranks every rank would add its own.
+    # So the process-level stdout (fd 1) of every rank is pointed at stderr from here on and Python keeps the original for its one print.
+    sys.stdout.flush()
+    json_out = os.fdopen(os.dup(1), "w")
+    os.dup2(2, 1)
+    torch.cuda.set_device(local)
+    dev = torch.device("cuda", local)
+    ranks_seen = 1
+    # BENCH_DDP=native on ONE GPU: a world-size-1 RCCL communicator, so that the exchange path (chunked all-reduces issued from inside the
+    # backward, loss reduce, barrier) runs and config.dp can be read before a node is available
+    self_ddp = world == 1 and os.environ.get("BENCH_DDP") == "native"
+    if self_ddp:
+        import socket
+        with socket.socket() as sk:
+            sk.bind(("127.0.0.1", 0))
+            port1 = sk.getsockname()[1]
+        dist.init_process_group("nccl", init_method=f"tcp://127.0.0.1:{port1}", world_size=1, rank=0)
+        distributed = True
+    elif distributed:
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        dist.init_process_group("nccl", init_method="env://", world_size=world, rank=rank)     # "nccl" is RCCL on ROCm
+        probe = torch.ones(1, device=dev)
+        dist.all_reduce(probe)                                                                 # every rank present on the RCCL communicator
+        ranks_seen = int(probe)
+        assert ranks_seen == world, f"RCCL communicator has {ranks_seen} ranks, expected {world}"
+
+    import ddpm_torch
+    ddpm_torch.seed_all(1234)
+    # Data parallelism: the engine's own reducer (parameters broadcast from rank 0; gradient staging buffer all-reduced over
+    # RCCL in chunks from inside the hand-written backward, overlapped with the rest of it).  BENCH_DDP=torch falls back to
+    # the reference's DistributedDataParallel wrapper (train.py:110), which also works but only starts reducing after backward.
+    native = os.environ.get("BENCH_DDP", "native") != "torch"
+    model, net, dif, tr = make_trainer(ddpm_torch, CIFAR, dev, args.dtype, (3, 32, 32), "fixed-large", distributed, rank, native, local)
+    g = torch.Generator().manual_seed(1234 + rank)
+    x0 = (torch.rand(B_PER_GPU, 3, 32, 32, generator=g) * 2 - 1).to(dev)            # resident before timing
+
+    def sync():
+        torch.cuda.synchronize()
+        if distributed:
+            dist.barrier()
+            torch.cuda.synchronize()
+
+    net.train()
+    # exactly --steps timed steps, bracketed by barrier + synchronize, the MAX over ranks; device events split them into up to
+    # BENCH_BLOCKS (5) consecutive parts without synchronising in between, whose spread is reported next to the figure
+    n_blocks = max(1, min(int(os.environ.get("BENCH_BLOCKS", "5")), args.steps))
+    elapsed = timed_steps(tr, x0, args.steps, args.warmup, sync, parts=n_blocks)[0]
+    part_s = timed_steps.parts if n_blocks > 1 else [elapsed]
+    if distributed:
+        te = torch.tensor([elapsed], device=dev)
+        dist.all_reduce(te, op=dist.ReduceOp.MAX)
+        elapsed = float(te[0])
+    ms_per_step = elapsed / args.steps * 1e3
+    imgs_per_s = B_PER_GPU * world * args.steps / elapsed
+    part_steps = [args.steps * (j + 1) // n_blocks - args.steps * j // n_blocks for j in range(n_blocks)]
+    dumped = dump_outputs(args.dump_outputs, model, tr) if args.dump_outputs and rank == 0 else None
+    loss = tr.current_stats["loss"]
+    kinds = {d.last_kind for d in tr._direct.values()}
+    form = "graph" if "graph" in kinds else ("plan" if "plan" in kinds else "eager")
+    step_mode = "direct step, " + {"graph": "hipGraph replay", "plan": "launch plan (ddpm_plan_run: the step's C-ABI calls re-issued from C on both streams)",
+                                   "eager": "eager launches"}[form] + (" (chosen by measurement)" if any(d.choice for d in tr._direct.values()) else "") \
+        if tr._direct else "autograd step"
+    # what the auto-probe measured for each form of the step on THIS box (ms per step, 4 pipelined steps each, before the timed region)
+    step_probe = {}
+    for d in tr._direct.values():
+        step_probe = {k + "_ms": round(v * 1e3, 3) for k, v in d.times.items()}
+        if d.plan is not None:
+            step_probe["plan_launches"] = d.plan.launches
+
+    # everything beyond the headline figure runs with --full only
+    roofline, dp = roofline_leg(args, model, tr, x0, dev, rank, world) if args.full else (None, None)
+    peak = PEAK[args.dtype]
+    out = None
+    if rank == 0:
+        out = {"metric": "training imgs/s/GPU + 1000-step DDPM samples/s, CIFAR-10 UNet @1/2/4/8 MI355X",
+               "value": round(imgs_per_s, 2), "unit": "imgs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+               "ms_per_step": round(ms_per_step, 3), "ms_per_step_blocks": [round(v / n * 1e3, 3) for v, n in zip(part_s, part_steps)],
+               "timing": f"{args.steps} consecutive steps bracketed by barrier + device sync (max over ranks); ms_per_step_blocks = the same steps "
+                         f"in {n_blocks} consecutive parts of {part_steps} steps timed by device events (rank 0)",
+               "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+               "dtype": args.dtype, "data": "synthetic",
+               "config": {"workload": "configs/cifar10.json UNet (35.7M params), full Trainer.step, B=128 per GPU, 32x32, T=1000, dropout 0.1, Adam+clip+EMA",
+                          "global_batch": B_PER_GPU * world, "rccl_ranks": ranks_seen, "dp": dp,
+                          "parallelism": f"dp{world}" + ("" if world == 1 else (" (native chunked RCCL all-reduce inside backward)" if native else " (torch DDP)")),
+                          "step_execution": step_mode, "step_probe": step_probe,
+                          "hbm_gb": {"reserved": round(torch.cuda.memory_reserved() / 2 ** 30, 2), "allocated_peak": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2),
+                                     "of": 288, "note": "whole bench process after the timed steps (training state + the step form's private pool; with --full also the two profiled steps)"},
+                          "imgs_per_s_per_gpu": round(imgs_per_s / world, 2),
+                          "train_model_tflops_per_gpu": round(imgs_per_s / world * 3 * FWD_GFLOP["cifar"] / 1e3, 1),
+                          "train_model_frac_of_peak": round(imgs_per_s / world * 3 * FWD_GFLOP["cifar"] / 1e3 / peak, 4), "final_loss": round(loss, 4)}}
+        if roofline is not None:
+            out["roofline"] = roofline
+        if dumped:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "files": dumped}
+    if args.full and rank == 0:
+        sampling_and_other_configs(args, out, model, net, dif, x0, dev, world)
+        if not args.no_cpu_baseline and world == 1:
+            out["cpu_baseline"] = cpu_baseline()
     if distributed:
         dist.barrier()
         dist.destroy_process_group()

@@ -4,14 +4,14 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/${1:-prof}; mkdir -p $O
 export TMPDIR=/tmp DDPM_TORCH_AMD_TRAIN_GRAPH=${PROFILE_STEP_FORM:-plan}
-CMD="python $R/bench.py --steps 10 --warmup 3 --sample-steps 0 --no-cpu-baseline --no-extras"
+CMD="python $R/bench.py --full --steps 10 --warmup 3 --sample-steps 0 --no-cpu-baseline --no-extras"
 cd /tmp
 rm -rf /tmp/kt; timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -- $CMD > $O/kt.log 2>&1
 cp $(find /tmp/kt -name "*kernel_stats.csv" | head -1) $O/kernel_stats.csv
 rm -rf /tmp/pf /tmp/pw /tmp/pm
 timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d /tmp/pf -- $CMD > $O/pf.log 2>&1
 timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d /tmp/pw -- $CMD > $O/pw.log 2>&1
-python $R/scripts/pmc_traffic.py /tmp/pf /tmp/pw $O/hbm_traffic.json "bench.py --steps 10 --warmup 3 --sample-steps 0 --no-cpu-baseline --no-extras (DDPM_TORCH_AMD_TRAIN_GRAPH=plan: the launch-plan form of the step)"
+python $R/scripts/pmc_traffic.py $TMPDIR/pf $TMPDIR/pw $O/hbm_traffic.json "bench.py --full --steps 10 --warmup 3 --sample-steps 0 --no-cpu-baseline --no-extras (DDPM_TORCH_AMD_TRAIN_GRAPH=plan: the launch-plan form of the step)"
 timeout 600 rocprofv3 --pmc SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES --kernel-trace --output-format csv -d /tmp/pm -- $CMD > $O/pm.log 2>&1
 python - $O/mfma_busy.csv <<'PY'
 import csv, glob, sys, collections
@@ -33,5 +33,5 @@ with open(sys.argv[1], "w") as o:
 PY
 cd $R
 unset DDPM_TORCH_AMD_TRAIN_GRAPH
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 head -25 $O/kernel_stats.csv | cut -c1-200; head -12 $O/mfma_busy.csv | cut -c1-220; tail -c 600 $O/bench_default.json

@@ -1,5 +1,5 @@
-"""CPU: the last committed bench.py output (profiles/*_bench_default.json) carries every field of the driver's contract; the launcher
-and --dump-outputs behave as documented."""
+"""CPU: the last committed bench.py output (profiles/*_bench_default.json) carries every field of the driver's contract; the launcher,
+--full and --dump-outputs behave as documented."""
 import glob
 import json
 import os
@@ -69,6 +69,14 @@ def _bench(args, env_extra, timeout=300):
 def test_bare_gpus_n_starts_n_ranks():
     """`python bench.py --gpus 2` with no WORLD_SIZE launches two ranks itself (gloo stand-in for the communicator: no GPU here)."""
     r = _bench(["--gpus", "2"], {})
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line == {"launch_probe": True, "n_gpus": 2, "ranks_in_collective": 2}
+
+
+def test_full_is_passed_to_every_rank():
+    """`--full` (the measurements beyond the headline figure) is an option of the launcher and of each rank it starts."""
+    r = _bench(["--gpus", "2", "--full"], {})
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert line == {"launch_probe": True, "n_gpus": 2, "ranks_in_collective": 2}
