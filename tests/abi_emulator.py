@@ -120,6 +120,8 @@ class Emulator:
         xin = torch.from_numpy(Mat(x, B * H * W, C, x_ld, dt).get()).reshape(B, H, W, C).permute(0, 3, 1, 2)
         wt = torch.from_numpy(Mat(w, N, R * S * C, R * S * C, dt).get()).reshape(N, R, S, C).permute(0, 3, 1, 2)
         can = _canvas(xin, Ho, Wo, R, S, stride, pad_t, pad_l, ups, dil)
+        if dt == F32:                                               # fp32: accumulate in float64, so the emulator's own rounding stays
+            can, wt = can.double(), wt.double()                     # far inside the bars the fp32 kernels are held to
         out = F.conv2d(can, wt, stride=stride)                      # [B, N, Ho, Wo]
         assert out.shape[2:] == (Ho, Wo), (out.shape, Ho, Wo)
         out = out.permute(0, 2, 3, 1).reshape(B * Ho * Wo, N).numpy().copy()
@@ -146,6 +148,8 @@ class Emulator:
         xin = torch.from_numpy(Mat(x, B * H * W, C, x_ld, dt).get()).reshape(B, H, W, C).permute(0, 3, 1, 2)
         g = torch.from_numpy(Mat(dy, B * Ho * Wo, N, dy_ld, dt).get()).reshape(B, Ho, Wo, N).permute(0, 3, 1, 2)[:, :Nreal]
         can = _canvas(xin, Ho, Wo, R, S, stride, pad_t, pad_l, ups, 0)
+        if dt == F32:                                               # fp32: float64 accumulation, as in ddpm_conv2d_nhwc
+            can, g = can.double(), g.double()
         gw = torch.nn.grad.conv2d_weight(can.contiguous(), (Nreal, C, R, S), g.contiguous(), stride=stride)
         val = gw[:, :Creal].permute(0, 2, 3, 1).numpy()                            # packed layout [n][r][s][c]
         if slab_stride == 0:

@@ -39,6 +39,12 @@ C_NORM = 4                          # GroupNorm forward / backward
 C_ATTN = 4                          # attention forward / backward
 C_ELEM = 8                          # fp32 diffusion elementwise kernels (expf / sqrtf of the tables are a few ulp)
 TINY = 1e-30                        # floor of a bar: an element whose every term is exactly zero must come out exactly zero
+# fp32 operands on the matrix cores (v_mfma_f32_32x32x2_f32, csrc/gemm.hip Mma<float>) fold two products into the fp32 accumulator per
+# step, and the ISA does not specify that step as a correctly rounded addition; a faithful one (error below one ulp of the accumulated
+# value, 2 u_acc) is what bounds it.  Measured on the MI355X (W5-W8): the fp32 convs miss a float64 sum by 1.6x what a round-to-nearest
+# sequential fp32 sum of the same products misses (1.19 of the u_acc bar at 16 M outputs, where round-to-nearest sums reach 0.72).
+# The accumulation term of fp32 GEMM-shaped replays therefore uses 2 u_acc; bf16 products keep u_acc (their bars are set by the store).
+U_ACC_MFMA_F32 = 2 * U_ACC
 
 
 # ----------------------------------------------------------------------------------------------------------------- recording
@@ -151,9 +157,19 @@ def _d(t):
     return t.to(torch.float64)
 
 
+F64_SLICE = 8 << 30                 # bytes of float64 working set per slice of images in the largest references (W13: B = 2048)
+
+
+def image_slices(B, per_image):
+    """[(b0, b1)] covering the B images so that a slice's float64 working set (per_image elements an image) stays near F64_SLICE:
+    the references of operands >= 1 GiB run in several passes instead of one pass that would need tens of GB of device memory."""
+    n = max(1, int(F64_SLICE // (8 * max(per_image, 1))))
+    return [(b0, min(B, b0 + n)) for b0 in range(0, B, n)]
+
+
 class Result:
     def __init__(self, sig):
-        self.sig, self.worst, self.where = sig, 0.0, ""
+        self.sig, self.worst, self.where, self.max_bytes = sig, 0.0, "", 0
 
     def cmp(self, what, got, ref, bar):
         got, ref, bar = _d(got), ref.to(got.device), bar.to(got.device)
@@ -273,32 +289,38 @@ def rep_conv2d(A, sig, res):
     A.check()
     if cnt is not None:
         assert not bool(cnt.t.view(torch.int32).any()), "split-K counters not left zero"
-    xs = _d(x.mat(B * H * W, C, x_ld)).reshape(B, H, W, C)
     wt = _d(w.t).reshape(N, R, S, C)
-    can = canvas(xs, Ho, Wo, R, S, stride, pad_t, pad_l, ups, dil)
-    ref = conv_fp64(can, wt, Ho, Wo, stride).reshape(M, N)
-    mag = ref.abs()
-    sq = conv_fp64(can * can, wt * wt, Ho, Wo, stride).reshape(M, N).sqrt()
-    if bias is not None:
-        ref = ref + _d(bias.t)[None]
-        mag = mag + _d(bias.t).abs()[None]
-    if rb is not None:
-        v = _d(rb.mat(B, N, rb_ld)).repeat_interleave(Ho * Wo, 0)
-        ref, mag = ref + v, mag + v.abs()
-    if r_ is not None:
-        v = _d(r_.mat(M, N, res_ld))
-        ref, mag = ref + v, mag + v.abs()
-    if mode == 3:
-        got = _d(y.mat(B * N, Ho * Wo, Ho * Wo)).reshape(B, N, Ho * Wo).permute(0, 2, 1).reshape(M, N)
-        pv = prior.reshape(B, N, Ho * Wo).permute(0, 2, 1).reshape(M, N)
-    else:
-        got = _d(y.mat(M, N, y_ld))
-        pv = prior.as_strided((M, N), (y_ld, 1))
-    if acc:
-        ref, mag = ref + pv, mag + pv.abs()
+    HWo = Ho * Wo
+    nh, nw = (Ho - 1) * stride + R, (Wo - 1) * stride + S
     u = U_BF16 if odt == BF16 else U_F32
-    bar = C_GEMM * (u * mag + U_ACC * math.sqrt(K) * sq)
-    res.cmp("y", got, ref, bar)
+    ua = U_ACC_MFMA_F32 if dt == F32 else U_ACC
+    for b0, b1 in image_slices(B, 3 * nh * nw * C + 8 * HWo * N):
+        r0, r1 = b0 * HWo, b1 * HWo
+        xs = _d(x.mat(B * H * W, C, x_ld)[b0 * H * W:b1 * H * W]).reshape(b1 - b0, H, W, C)
+        can = canvas(xs, Ho, Wo, R, S, stride, pad_t, pad_l, ups, dil)
+        ref = conv_fp64(can, wt, Ho, Wo, stride).reshape(-1, N)
+        mag = ref.abs()
+        sq = conv_fp64(can * can, wt * wt, Ho, Wo, stride).reshape(-1, N).sqrt()
+        del can
+        if bias is not None:
+            ref = ref + _d(bias.t)[None]
+            mag = mag + _d(bias.t).abs()[None]
+        if rb is not None:
+            v = _d(rb.mat(B, N, rb_ld)[b0:b1]).repeat_interleave(HWo, 0)
+            ref, mag = ref + v, mag + v.abs()
+        if r_ is not None:
+            v = _d(r_.mat(M, N, res_ld)[r0:r1])
+            ref, mag = ref + v, mag + v.abs()
+        if mode == 3:
+            got = _d(y.mat(B * N, HWo, HWo)[b0 * N:b1 * N]).reshape(b1 - b0, N, HWo).permute(0, 2, 1).reshape(-1, N)
+            pv = prior.reshape(B, N, HWo)[b0:b1].permute(0, 2, 1).reshape(-1, N)
+        else:
+            got = _d(y.mat(M, N, y_ld)[r0:r1])
+            pv = prior.as_strided((M, N), (y_ld, 1))[r0:r1]
+        if acc:
+            ref, mag = ref + pv, mag + pv.abs()
+        bar = C_GEMM * (u * mag + ua * math.sqrt(K) * sq)
+        res.cmp("y", got, ref, bar)
 
 
 def _slab_setup(A, name, n_one, copies, stride, mod):
@@ -328,12 +350,13 @@ def _wgrad_common(A, res, dy_b, x_b, can, dy, R, S, Ho, Wo, stride, Nreal, Creal
     mag = full.abs()
     sq = wgrad_fp64(can * can, dy * dy, R, S, Ho, Wo, stride)[:Nreal, :, :, :Creal].reshape(-1).sqrt()
     K = dy.shape[0] * Ho * Wo
+    ua = U_ACC_MFMA_F32 if dy_b.t.dtype == torch.float32 else U_ACC
     if slab_stride == 0:
         got = dw.t[:n_one]
         full, mag = full + prior, mag + prior.abs()
     else:
         got = _reduce_slabs(A, dw, n_one, copies, slab_stride)
-    res.cmp("dw", got, full, C_GEMM * (U_F32 * mag + U_ACC * math.sqrt(K) * sq))
+    res.cmp("dw", got, full, C_GEMM * (U_F32 * mag + ua * math.sqrt(K) * sq))
     if dbias is not None:
         g = dy.reshape(-1, dy.shape[-1])[:, :Nreal]
         ref, sq = g.sum(0), (g * g).sum(0).sqrt()
@@ -454,6 +477,7 @@ def rep_gemm(A, sig, res):
         c.out(M, N, c_ld, i * c_bs)
     A.check()
     u = U_BF16 if odt == BF16 else U_F32
+    ua = U_ACC_MFMA_F32 if dt == F32 else U_ACC
     for i in range(batch):
         Am = _d(a.mat(K, M, a_ld, i * a_bs)).T if a_tr else _d(a.mat(M, K, a_ld, i * a_bs))
         Bm = _d(b.mat(K, N, b_ld, i * b_bs)).T if b_tr else _d(b.mat(N, K, b_ld, i * b_bs))
@@ -468,7 +492,7 @@ def rep_gemm(A, sig, res):
         if acc or mode == 2:
             v = prior.as_strided((M, N), (c_ld, 1), i * c_bs)
             ref, mag = ref + v, mag + v.abs()
-        res.cmp(f"c[{i}]", c.mat(M, N, c_ld, i * c_bs), ref, C_GEMM * (u * mag + U_ACC * math.sqrt(K) * sq))
+        res.cmp(f"c[{i}]", c.mat(M, N, c_ld, i * c_bs), ref, C_GEMM * (u * mag + ua * math.sqrt(K) * sq))
 
 
 def rep_atb(A, sig, res):
@@ -518,9 +542,10 @@ def keep_mask(seed, idx, p):
     return field >= thresh
 
 
-def _keep(A, B, HW, C, drop_p, seed):
-    """Keep mask of the dropout after the GroupNorm, linear NHWC index b*HW*C + p*C + c (not the library's mask hook)."""
-    idx = torch.arange(B * HW * C, dtype=torch.int64, device=A.device)
+def _keep(A, B, HW, C, drop_p, seed, b0=0):
+    """Keep mask of the dropout after the GroupNorm for images b0 .. b0 + B - 1, linear NHWC index b*HW*C + p*C + c (not the
+    library's mask hook)."""
+    idx = torch.arange(b0 * HW * C, (b0 + B) * HW * C, dtype=torch.int64, device=A.device)
     return keep_mask(seed & ((1 << 64) - 1), idx, drop_p).to(torch.float64).reshape(B, HW, C)
 
 
@@ -549,7 +574,11 @@ def rep_gn_fwd(A, sig, res):
     """GroupNorm(G) -> SiLU -> dropout.  t = gamma * xh + beta with xh = (x - mean) * rstd; y = drop(silu(t)).
     Model: M_i = |y_i| (the bf16 / fp32 store) and the fp32 statistics term  sqrt(n) * (|gamma| (|x| + |mean|) rstd + |beta|) * |y'(t)|
     with y' = silu'(t) * keep / (1 - p)  (n = (C/G) * HW, the statistics are sums of n terms; |x| + |mean| bounds the magnitude of the
-    centred value the kernel forms about its pivot).  Statistics: mean to u_acc * sqrt(n) * (|mean| + std), rstd to u_acc * sqrt(n)."""
+    centred value the kernel forms about its pivot).  Statistics: mean to u_acc * sqrt(n) * (|mean| + std), rstd to u_acc * sqrt(n).
+    fp32 stores add the fp32 evaluation of silu(t) and of the dropout scale, relative to |y|:  e_silu = _sigmoid_err(t) - 1 (the fast exp
+    and 1 + e, see rep_silu_fwd) + 2 (the hardware reciprocal of silu_fast_, 1 ulp) + 1 (t * s) + 1 (* keep / (1 - p)), in units of
+    u_acc.  Where silu'(t) = 0 (t = -1.28) the statistics term vanishes and this is the whole error; a bf16 store is 2^16 times coarser
+    and its bar is left as it was."""
     px, x_ld, py, y_ld, pg, pb, pst, pws, B, HW, C, G, eps, silu, drop_p, seed, pseed, dt = sig
     x = A.buf("x", pitched(B * HW, C, x_ld), dt, _mod(px)).fill(A.randn(pitched(B * HW, C, x_ld), mean=1.5))
     y = A.buf("y", pitched(B * HW, C, y_ld), dt, _mod(py)).fill(A.randn(pitched(B * HW, C, y_ld)))
@@ -568,26 +597,33 @@ def rep_gn_fwd(A, sig, res):
     sync()
     got = y.out(B * HW, C, y_ld)
     A.check()
-    xs = _d(x.mat(B * HW, C, x_ld)).reshape(B, HW, C)
-    mean, rstd = _gn_stats(xs, G, eps)
-    mu, rs = _per_c(mean, B, HW, C, G), _per_c(rstd, B, HW, C, G)
-    gm, bt = _d(g.t), _d(b.t)
-    xh = (xs - mu) * rs
-    t = gm * xh + bt
-    sg = torch.sigmoid(t)
-    yv, dyv = (t * sg, sg * (1 + t * (1 - sg))) if silu else (t, torch.ones_like(t))
-    if drop_p > 0:
-        k = _keep(A, B, HW, C, drop_p, eff) / (1.0 - drop_p)
-        yv, dyv = yv * k, dyv * k
     n = (C // G) * HW
     u = U_BF16 if dt == BF16 else U_F32
-    bar = C_NORM * (u * yv.abs() + U_ACC * math.sqrt(n) * (gm.abs() * (xs.abs() + mu.abs()) * rs + bt.abs()) * dyv.abs())
-    res.cmp("y", got.reshape(B, HW, C), yv, bar)
-    if st is not None:
-        s = _d(st.t).reshape(B, G, 2)
-        std = 1.0 / rstd
-        res.cmp("mean", s[..., 0], mean, C_NORM * U_ACC * math.sqrt(n) * (mean.abs() + std))
-        res.cmp("rstd", s[..., 1], rstd, C_NORM * U_ACC * math.sqrt(n) * rstd)
+    gm, bt = _d(g.t), _d(b.t)
+    for b0, b1 in image_slices(B, 14 * HW * C):
+        nb = b1 - b0
+        xs = _d(x.mat(B * HW, C, x_ld)[b0 * HW:b1 * HW]).reshape(nb, HW, C)
+        mean, rstd = _gn_stats(xs, G, eps)
+        mu, rs = _per_c(mean, nb, HW, C, G), _per_c(rstd, nb, HW, C, G)
+        xh = (xs - mu) * rs
+        t = gm * xh + bt
+        sg = torch.sigmoid(t)
+        yv, dyv = (t * sg, sg * (1 + t * (1 - sg))) if silu else (t, torch.ones_like(t))
+        del xh, sg
+        if drop_p > 0:
+            k = _keep(A, nb, HW, C, drop_p, eff, b0) / (1.0 - drop_p)
+            yv, dyv = yv * k, dyv * k
+            del k
+        bar = C_NORM * (u * yv.abs() + U_ACC * math.sqrt(n) * (gm.abs() * (xs.abs() + mu.abs()) * rs + bt.abs()) * dyv.abs())
+        if dt == F32:
+            bar = bar + C_NORM * U_ACC * ((_sigmoid_err(t) + 3) if silu else 1.0) * yv.abs()
+        res.cmp("y", got[b0 * HW:b1 * HW].reshape(nb, HW, C), yv, bar)
+        del xs, t, yv, dyv, bar
+        if st is not None:
+            s_ = _d(st.t).reshape(B, G, 2)[b0:b1]
+            std = 1.0 / rstd
+            res.cmp("mean", s_[..., 0], mean, C_NORM * U_ACC * math.sqrt(n) * (mean.abs() + std))
+            res.cmp("rstd", s_[..., 1], rstd, C_NORM * U_ACC * math.sqrt(n) * rstd)
 
 
 def rep_gn_bwd(A, sig, res):
@@ -924,6 +960,195 @@ def rep_p_sample_step(A, sig, res):
         res.cmp("pred_x0", pred.t.reshape(B, n), x0, C_ELEM * U_F32 * x0m)
 
 
+def rep_softmax_fwd(A, sig, res):
+    """P = softmax(s) over rows of L (s fp32 [rows][L], P [rows][L] of dtype).  The kernel forms m = max_j s_j, e_i = expf(s_i - m),
+    Z = sum_j e_j (lane-strided fp32 sums, then a wave tree) and stores e_i * (1 / Z).  Model, relative to each p_i:
+        e_i:  the fp32 rounding of s_i - m is u_acc |s_i - m| in the exponent, the fast exp (exp2 of (s_i - m) log2 e) another
+              u_acc |s_i - m| from that product and ~2 ulp of its own:  r_i = u_acc (2 |s_i - m| + 4);
+        Z:    sum_j p_j r_j from its terms, u_acc sqrt(L) sqrt(sum_j p_j^2) from the fp32 sum, u_acc for the reciprocal;
+        p_i:  u_acc for the product and u_out for the store.
+    |got_i - p_i| <= c * p_i * (u_out + r_i + sum_j p_j r_j + u_acc (sqrt(L) sqrt(sum_j p_j^2) + 2)), never relative to the row maximum.
+    The logits are N(0, 3^2): the smallest p_i stay far above the fp32 normal range, so no term flushes."""
+    ps, pp, rows, L, dt = sig
+    s_ = A.buf("s", rows * L, F32, _mod(ps)).fill(A.randn(rows * L, scale=3.0))
+    p = A.buf("p", rows * L, dt, _mod(pp)).fill(A.randn(rows * L))
+    A.snapshot()
+    _launch("ddpm_softmax_fwd", [s_.ptr, p.ptr, rows, L, dt])
+    sync()
+    got = p.all_out()
+    A.check()
+    S = _d(s_.t).reshape(rows, L)
+    d = S - S.amax(-1, keepdim=True)
+    P = torch.softmax(d, -1)
+    r = U_ACC * (2 * d.abs() + 4)
+    zr = (P * r).sum(-1, keepdim=True) + U_ACC * (math.sqrt(L) * (P * P).sum(-1, keepdim=True).sqrt() + 2)
+    u = U_BF16 if dt == BF16 else U_F32
+    res.cmp("p", got.reshape(rows, L), P, C_ATTN * P * (u + r + zr))
+
+
+def rep_softmax_bwd(A, sig, res):
+    """dS_i = p_i (dp_i - D), D = sum_j p_j dp_j, with P (dtype) and dP (fp32) as given.  Model: D is an fp32 sum of L products
+    (u_acc (sum_j |p_j dp_j| + sqrt(L) sqrt(sum_j (p_j dp_j)^2))), the difference adds u_acc (|dp_i| + |D|) <= u_acc (|dp_i| +
+    sum_j |p_j dp_j|), and both scale with p_i through the product; the product and the store add u_acc |dS_i| and u_out |dS_i|:
+        |got_i - dS_i| <= c * ((u_out + u_acc) |dS_i| + u_acc p_i (|dp_i| + 2 sum_j |p_j dp_j| + sqrt(L) sqrt(sum_j (p_j dp_j)^2)))."""
+    pp, pdp, pds, rows, L, dt = sig
+    p = A.buf("p", rows * L, dt, _mod(pp)).fill(torch.softmax(A.randn(rows * L, scale=3.0).reshape(rows, L), -1))
+    dp = A.buf("dp", rows * L, F32, _mod(pdp)).fill(A.randn(rows * L))
+    ds = A.buf("ds", rows * L, dt, _mod(pds)).fill(A.randn(rows * L))
+    A.snapshot()
+    _launch("ddpm_softmax_bwd", [p.ptr, dp.ptr, ds.ptr, rows, L, dt])
+    sync()
+    got = ds.all_out()
+    A.check()
+    P, G = _d(p.t).reshape(rows, L), _d(dp.t).reshape(rows, L)
+    pg = P * G
+    ref = P * (G - pg.sum(-1, keepdim=True))
+    dot_err = 2 * pg.abs().sum(-1, keepdim=True) + math.sqrt(L) * (pg * pg).sum(-1, keepdim=True).sqrt()
+    u = U_BF16 if dt == BF16 else U_F32
+    res.cmp("ds", got.reshape(rows, L), ref, C_ATTN * ((u + U_ACC) * ref.abs() + U_ACC * P * (G.abs() + dot_err)))
+
+
+def _sigmoid_err(x):
+    """relative fp32 error of sigmoidf_ (csrc/common.h: 1 / (1 + expf(-x)), fast exp) in units of u: the exp's r = |x| + 2 (argument
+    product and the exp itself) damped by 1 - s in 1 + e, one rounding for the sum and one for the division"""
+    return 2 + (x.abs() + 2) * (1 - torch.sigmoid(x))
+
+
+def rep_silu_fwd(A, sig, res):
+    """y = x sigmoid(x) (fp32).  Model: |got - y| <= c u (1 + e_s) |y| with e_s = _sigmoid_err(x): relative to each element."""
+    px, py, n = sig
+    x = A.buf("x", n, F32, _mod(px)).fill(A.randn(n, scale=4.0))
+    y = A.buf("y", n, F32, _mod(py)).fill(A.randn(n))
+    A.snapshot()
+    _launch("ddpm_silu_fwd", [x.ptr, y.ptr, n])
+    sync()
+    got = y.all_out()
+    A.check()
+    X = _d(x.t)
+    ref = X * torch.sigmoid(X)
+    res.cmp("y", got, ref, C_ELEM * U_F32 * (1 + _sigmoid_err(X)) * ref.abs())
+
+
+def rep_silu_bwd(A, sig, res):
+    """dx (+)= dy silu'(x), silu'(x) = s (1 + x (1 - s)), s = sigmoid(x) (fp32, csrc/common.h silu_gradf_).  Model: s carries
+    e_s = _sigmoid_err(x) (relative, units of u); 1 - s then carries s e_s + (1 - s) absolutely, x (1 - s) |x| times that plus its own
+    rounding, and the bracket and the product one rounding each:
+        E' = |silu'| (e_s + 2) + s |x| (s e_s + 2 (1 - s))     (units of u, absolute)
+        |got - ref| <= c u (|dy| E' + 2 |dy silu'| + |prior|)   (prior only with accumulate)."""
+    px, pdy, pdx, n, acc = sig
+    x = A.buf("x", n, F32, _mod(px)).fill(A.randn(n, scale=4.0))
+    dy = A.buf("dy", n, F32, _mod(pdy)).fill(A.randn(n))
+    dx = A.buf("dx", n, F32, _mod(pdx)).fill(A.randn(n))
+    prior = _d(dx.t).clone()
+    A.snapshot()
+    _launch("ddpm_silu_bwd", [x.ptr, dy.ptr, dx.ptr, n, acc])
+    sync()
+    got = dx.all_out()
+    A.check()
+    X, G = _d(x.t), _d(dy.t)
+    sg = torch.sigmoid(X)
+    d1 = sg * (1 + X * (1 - sg))
+    es = _sigmoid_err(X)
+    e1 = d1.abs() * (es + 2) + sg * X.abs() * (sg * es + 2 * (1 - sg))
+    ref = G * d1
+    mag = G.abs() * e1 + 2 * ref.abs()
+    if acc:
+        ref, mag = ref + prior, mag + prior.abs() + ref.abs()
+    res.cmp("dx", got, ref, C_ELEM * U_F32 * mag)
+
+
+def rep_add_rows(A, sig, res):
+    """y (+)= x over [rows][C] with pitches.  A copy (accumulate = 0) is exact: bar 0.  With accumulate the fp32 sum and the store
+    round once each: c u_out (|x| + |prior|)."""
+    px, x_ld, py, y_ld, rows, C, acc, dt = sig
+    x = A.buf("x", pitched(rows, C, x_ld), dt, _mod(px)).fill(A.randn(pitched(rows, C, x_ld)))
+    y = A.buf("y", pitched(rows, C, y_ld), dt, _mod(py)).fill(A.randn(pitched(rows, C, y_ld)))
+    prior = _d(y.mat(rows, C, y_ld)).clone()
+    A.snapshot()
+    _launch("ddpm_add_rows", [x.ptr, x_ld, y.ptr, y_ld, rows, C, acc, dt])
+    sync()
+    got = y.out(rows, C, y_ld)
+    A.check()
+    X = _d(x.mat(rows, C, x_ld))
+    if acc:
+        u = U_BF16 if dt == BF16 else U_F32
+        res.cmp("y", got, X + prior, C_GEMM * u * (X.abs() + prior.abs()))
+    else:
+        res.cmp("y", got, X, torch.zeros_like(X))
+
+
+def rep_timestep_embedding(A, sig, res):
+    """out[b] = [sin(a_b), cos(a_b)] (+ a zero column when dim is odd) with a_bi = fl32(t_b * f_i): the kernel's fp32 product is part of
+    the contract (functions.py's torch.outer), so the reference rounds it exactly as fp32 does (t_b * f_i is exact in float64) and
+    evaluates sin / cos of that argument in float64.  Model: the fp32 sinf / cosf with full range reduction, a few ulp of the result:
+    c u |ref|; the pad column must be exactly zero.  freqs is the host's table exp(-i ln(1e4) / (half - 1)) in fp32."""
+    pt, pf, po, B, dim = sig
+    half = dim // 2
+    tb = A.buf("t", B, "i64", _mod(pt))
+    tv = torch.randint(0, 1000, (B,), generator=A.gen)
+    tv[0] = 0
+    tv[-1] = 999
+    tb.t.copy_(tv)
+    f = torch.exp(-torch.arange(half, dtype=torch.float64) * math.log(1e4) / (half - 1)).to(torch.float32)
+    fr = A.buf("freqs", half, F32, _mod(pf)).fill(f)
+    out = A.buf("out", B * dim, F32, _mod(po)).fill(A.randn(B * dim))
+    A.snapshot()
+    _launch("ddpm_timestep_embedding", [tb.ptr, fr.ptr, out.ptr, B, dim])
+    sync()
+    got = out.all_out()
+    A.check()
+    arg = (_d(tb.t)[:, None] * _d(fr.t)[None, :]).to(torch.float32).to(torch.float64)
+    ref = torch.zeros(B, dim, dtype=torch.float64, device=arg.device)
+    ref[:, :half], ref[:, half:2 * half] = torch.sin(arg), torch.cos(arg)
+    res.cmp("out", got.reshape(B, dim), ref, C_ELEM * U_F32 * ref.abs())
+
+
+def rep_gather_rows(A, sig, res):
+    """out[r] = table[idx[r]], bit-exact (bar 0); an index outside [0, table_rows) must give a NaN row.  Two launches: every index
+    valid (first and last table row included), then every even row's index out of range (-1, table_rows, 2^40 in turn)."""
+    ptab, pidx, pout, rows, row_len, table_rows = sig
+    tab = A.buf("table", table_rows * row_len, F32, _mod(ptab)).fill(A.randn(table_rows * row_len))
+    ib = A.buf("idx", rows, "i64", _mod(pidx))
+    out = A.buf("out", rows * row_len, F32, _mod(pout))
+    T = _d(tab.t).reshape(table_rows, row_len)
+    for bad in (False, True):
+        iv = torch.randint(0, table_rows, (rows,), generator=A.gen)
+        iv[0], iv[-1] = (0, table_rows - 1) if rows > 1 else (iv[0], iv[0])
+        poison = torch.zeros(rows, dtype=torch.bool)
+        if bad:
+            poison[::2] = True
+            oob = torch.tensor([-1, table_rows, 1 << 40], dtype=torch.int64)
+            iv[::2] = oob[torch.arange(0, rows, 2) // 2 % 3]
+        ib.t.copy_(iv)
+        out.fill(A.randn(out.n))
+        A.snapshot()
+        _launch("ddpm_gather_rows_f32", [tab.ptr, ib.ptr, out.ptr, rows, row_len, table_rows])
+        sync()
+        got = out.all_out().reshape(rows, row_len)
+        A.check()
+        poison = poison.to(got.device)
+        assert bool(torch.isnan(got[poison]).all()), "an index outside the table did not give a NaN row"
+        keep = ~poison
+        ref = T[iv.clamp(0, table_rows - 1).to(T.device)][keep]
+        res.cmp("out" if not bad else "out(oob)", got[keep], ref, torch.zeros_like(ref))
+
+
+def rep_weighted_sum(A, sig, res):
+    """out = sum_i x_i w_i, one block in a fixed order: a short fp32 sum held, like ddpm_atb_f32, to
+    c (u sum_i |x_i w_i| + u_acc sqrt(n) sqrt(sum_i (x_i w_i)^2))."""
+    px, pw, po, n = sig
+    x = A.buf("x", n, F32, _mod(px)).fill(A.randn(n))
+    w = A.buf("w", n, F32, _mod(pw)).fill(A.randn(n))
+    out = A.buf("out", 1, F32, _mod(po)).fill(A.randn(1))
+    A.snapshot()
+    _launch("ddpm_weighted_sum_f32", [x.ptr, w.ptr, out.ptr, n])
+    sync()
+    got = out.all_out()
+    A.check()
+    pr = _d(x.t) * _d(w.t)
+    res.cmp("out", got, pr.sum().reshape(1), (C_GEMM * (U_F32 * pr.abs().sum() + U_ACC * math.sqrt(n) * (pr * pr).sum().sqrt())).reshape(1))
+
+
 REPLAY = {
     "ddpm_conv2d_nhwc": rep_conv2d,
     "ddpm_conv3x3_wgrad_nhwc": rep_conv3x3_wgrad,
@@ -944,28 +1169,61 @@ REPLAY = {
     "ddpm_mse_fwd": rep_mse_fwd,
     "ddpm_mse_bwd": rep_mse_bwd,
     "ddpm_p_sample_step": rep_p_sample_step,
+    "ddpm_softmax_fwd": rep_softmax_fwd,
+    "ddpm_softmax_bwd": rep_softmax_bwd,
+    "ddpm_silu_fwd": rep_silu_fwd,
+    "ddpm_silu_bwd": rep_silu_bwd,
+    "ddpm_add_rows": rep_add_rows,
+    "ddpm_timestep_embedding": rep_timestep_embedding,
+    "ddpm_gather_rows_f32": rep_gather_rows,
+    "ddpm_weighted_sum_f32": rep_weighted_sum,
 }
 
-# Entries a step launches that are not replayed here, and the existing test that covers each (tests/test_kernels_gpu.py unless named).
+def _p(mod=0, null=False):
+    return ("p", null, mod)
+
+
+# Signatures of the replayed elementwise / softmax entries at edge geometries of their own (both dtypes, accumulate on and off, pitched
+# rows, odd lengths, a single row), replayed next to the recorded ones: ddpm_gather_rows_f32 (the graph-captured sampler's time table)
+# and ddpm_add_rows (gradient fan-in) are launched by no recorded workload.
+SYNTHETIC = [
+    ("ddpm_softmax_fwd", (_p(), _p(16), 1000, 256, F32)),
+    ("ddpm_softmax_fwd", (_p(), _p(), 3, 4096, BF16)),
+    ("ddpm_softmax_fwd", (_p(48), _p(8), 77, 52, F32)),
+    ("ddpm_softmax_bwd", (_p(), _p(), _p(32), 1000, 256, F32)),
+    ("ddpm_softmax_bwd", (_p(), _p(), _p(), 5, 1024, BF16)),
+    ("ddpm_silu_fwd", (_p(), _p(4), 100003)),
+    ("ddpm_silu_bwd", (_p(), _p(), _p(), 100003, 0)),
+    ("ddpm_silu_bwd", (_p(8), _p(), _p(4), 5000, 1)),
+    ("ddpm_add_rows", (_p(), 264, _p(), 256, 1000, 256, 1, BF16)),
+    ("ddpm_add_rows", (_p(16), 384, _p(), 128, 777, 128, 0, BF16)),
+    ("ddpm_add_rows", (_p(), 132, _p(48), 260, 333, 128, 1, F32)),
+    ("ddpm_add_rows", (_p(), 128, _p(), 128, 1, 128, 0, F32)),
+    ("ddpm_timestep_embedding", (_p(), _p(), _p(), 300, 128)),
+    ("ddpm_timestep_embedding", (_p(8), _p(4), _p(), 7, 127)),
+    ("ddpm_gather_rows_f32", (_p(), _p(), _p(), 128, 4992, 1000)),
+    ("ddpm_gather_rows_f32", (_p(), _p(8), _p(), 1, 4992, 1000)),
+    ("ddpm_gather_rows_f32", (_p(), _p(), _p(), 7, 4, 3)),
+    ("ddpm_weighted_sum_f32", (_p(), _p(), _p(), 128)),
+    ("ddpm_weighted_sum_f32", (_p(4), _p(), _p(8), 1)),
+    ("ddpm_weighted_sum_f32", (_p(), _p(), _p(), 100003)),
+]
+
+
+# Entries a step launches that are not replayed here, the existing test that covers each (tests/test_kernels_gpu.py unless named) and
+# what that test holds it to: [torch] a plain torch reference (Adam + clip_grad_norm_, or a float64 restatement), [exact] a bit-exact
+# copy or integer comparison.
 COVERED_ELSEWHERE = {
-    "ddpm_mt_adam_ema": "test_fused_adam_ema_matches_torch_adam, test_multi_tensor_update_with_scalars_from_device_memory",
-    "ddpm_mt_grad_sumsq": "test_multi_tensor_update_with_scalars_from_device_memory",
-    "ddpm_mt_gather_f32": "test_multi_tensor_gather",
-    "ddpm_wgrad_unpack": "test_wgrad_unpack_and_fused_norm",
-    "ddpm_wgrad_unpack_sumsq": "test_wgrad_unpack_and_fused_norm",
-    "ddpm_pack_weight": "test_timestep_embedding_and_layout_kernels",
-    "ddpm_pack_weight_multi": "test_pack_weight_multi",
-    "ddpm_nchw_to_nhwc": "test_timestep_embedding_and_layout_kernels",
-    "ddpm_timestep_embedding": "test_timestep_embedding_and_layout_kernels",
-    "ddpm_silu_fwd": "test_reductions_and_fanin",
-    "ddpm_silu_bwd": "test_reductions_and_fanin",
-    "ddpm_add_rows": "test_reductions_and_fanin",
-    "ddpm_weighted_sum_f32": "test_diffusion_algebra_kernels",
-    "ddpm_gather_i64": "test_diffusion_algebra_kernels",
-    "ddpm_add_i64": "test_diffusion_algebra_kernels",
-    "ddpm_gather_rows_f32": "test_gather_rows_time_table",
-    "ddpm_softmax_fwd": "test_reductions_and_fanin",
-    "ddpm_softmax_bwd": "test_reductions_and_fanin",
+    "ddpm_mt_adam_ema": "test_fused_adam_ema_matches_torch_adam, test_multi_tensor_update_with_scalars_from_device_memory [torch]",
+    "ddpm_mt_grad_sumsq": "test_multi_tensor_update_with_scalars_from_device_memory [torch]",
+    "ddpm_mt_gather_f32": "test_multi_tensor_gather [exact]",
+    "ddpm_wgrad_unpack": "test_wgrad_unpack_and_fused_norm [exact]",
+    "ddpm_wgrad_unpack_sumsq": "test_wgrad_unpack_and_fused_norm [exact, torch]",
+    "ddpm_pack_weight": "test_timestep_embedding_and_layout_kernels [exact]",
+    "ddpm_pack_weight_multi": "test_pack_weight_multi [exact]",
+    "ddpm_nchw_to_nhwc": "test_timestep_embedding_and_layout_kernels [exact]",
+    "ddpm_gather_i64": "test_diffusion_algebra_kernels [exact]",
+    "ddpm_add_i64": "test_diffusion_algebra_kernels [exact]",
     "ddpm_stream_order": "not a kernel of arithmetic (stream ordering edge)",
     "ddpm_fill_zero": "not a kernel of arithmetic (stream-ordered memset)",
 }
@@ -983,6 +1241,7 @@ def replay(sig, device, seed=0):
     res = Result(sig)
     A = Arena(device, seed)
     REPLAY[name](A, words, res)
+    res.max_bytes = max((b.nbytes for b in A.bufs), default=0)
     return res
 
 
@@ -1010,11 +1269,11 @@ def _config(name):
         return json.load(f)
 
 
-def _net(cfg, device, seed=0):
+def _net(cfg, device, seed=0, dtype=torch.bfloat16):
     import ddpm_torch
     torch.manual_seed(seed)
     kw = {k: v for k, v in cfg["model"].items() if k != "block_size"}
-    return ddpm_torch.UNet(out_channels=kw["in_channels"], **kw).to(device).set_compute_dtype(torch.bfloat16)
+    return ddpm_torch.UNet(out_channels=kw["in_channels"], **kw).to(device).set_compute_dtype(dtype)
 
 
 def _diffusion(cfg):
@@ -1024,11 +1283,11 @@ def _diffusion(cfg):
                                         d["model_mean_type"], d["model_var_type"], d["loss_type"])
 
 
-def _train_step(cfg, device, B, size, drop=None):
+def _train_step(cfg, device, B, size, drop=None, dtype=torch.bfloat16):
     import ddpm_torch
     if drop is not None:
         cfg = dict(cfg, model=dict(cfg["model"], drop_rate=drop))
-    m = _net(cfg, device)
+    m = _net(cfg, device, dtype=dtype)
     tc = cfg["train"]
     opt = torch.optim.Adam(m.parameters(), lr=tc["lr"], betas=(0.9, 0.999))
     tr = ddpm_torch.Trainer(m, opt, _diffusion(cfg), epochs=1, trainloader=None, use_ema=tc["use_ema"], grad_norm=tc["grad_norm"],
@@ -1038,8 +1297,8 @@ def _train_step(cfg, device, B, size, drop=None):
     return lambda: tr.step(x.to(device), global_steps=1)
 
 
-def _sample_step(cfg, device, B, size, ddim_steps=None):
-    m = _net(cfg, device).eval()
+def _sample_step(cfg, device, B, size, ddim_steps=None, dtype=torch.bfloat16):
+    m = _net(cfg, device, dtype=dtype).eval()
     dif = _diffusion(cfg)
     if ddim_steps:
         import ddim
@@ -1058,12 +1317,28 @@ def _sample_step(cfg, device, B, size, ddim_steps=None):
     return run
 
 
-# key -> (what it runs, builder(device, B, size)); full size: the geometry the benchmark and the configs run
+# key -> (what it runs, builder(device, B, size), B, size); full size: the geometry the benchmark, the configs and the CLIs run
+_F32 = torch.float32
 WORKLOADS = {
     "W1": ("cifar10 train step, B=128, dropout 0.1", lambda dev, B=128, s=32: _train_step(_config("cifar10.json"), dev, B, s, drop=0.1), 128, 32),
     "W2": ("cifar10 ancestral sampling step, B=128", lambda dev, B=128, s=32: _sample_step(_config("cifar10.json"), dev, B, s), 128, 32),
     "W3": ("celebahq 256x256 train step, B=2", lambda dev, B=2, s=256: _train_step(_config("celebahq.json"), dev, B, s), 2, 256),
     "W4": ("celeba 64x64 DDIM step, B=128", lambda dev, B=128, s=64: _sample_step(_config("celeba.json"), dev, B, s, ddim_steps=50), 128, 64),
+    # the fp32 compute mode (bench.py --full's fp32 leg, the parity configurations): its convs, weight gradients, GroupNorm backward
+    # instantiations and the gemm + softmax + gemm attention are kernels the bf16 mode never reaches
+    "W5": ("cifar10 train step, fp32, B=128, dropout 0.1",
+           lambda dev, B=128, s=32: _train_step(_config("cifar10.json"), dev, B, s, drop=0.1, dtype=_F32), 128, 32),
+    "W6": ("cifar10 ancestral sampling step, fp32, B=128", lambda dev, B=128, s=32: _sample_step(_config("cifar10.json"), dev, B, s, dtype=_F32), 128, 32),
+    "W7": ("celebahq 256x256 train step, fp32, B=2", lambda dev, B=2, s=256: _train_step(_config("celebahq.json"), dev, B, s, dtype=_F32), 2, 256),
+    "W8": ("celeba 64x64 DDIM step, fp32, B=128",
+           lambda dev, B=128, s=64: _sample_step(_config("celeba.json"), dev, B, s, ddim_steps=50, dtype=_F32), 128, 64),
+    # batch sizes the CLIs run besides the benchmark's: dispatch depends on the pixel count
+    "W9": ("cifar10 train step, B=32 (train.py --num-accum 4), dropout 0.1",
+           lambda dev, B=32, s=32: _train_step(_config("cifar10.json"), dev, B, s, drop=0.1), 32, 32),
+    "W10": ("cifar10 sampling step, B=106 (generate.py's ragged last chain)", lambda dev, B=106, s=32: _sample_step(_config("cifar10.json"), dev, B, s), 106, 32),
+    "W11": ("cifar10 sampling step, B=1", lambda dev, B=1, s=32: _sample_step(_config("cifar10.json"), dev, B, s), 1, 32),
+    "W12": ("celeba 64x64 train step, B=128 (config 4)", lambda dev, B=128, s=64: _train_step(_config("celeba.json"), dev, B, s), 128, 64),
+    "W13": ("cifar10 sampling step, B=2048 (operands >= 1 GiB)", lambda dev, B=2048, s=32: _sample_step(_config("cifar10.json"), dev, B, s), 2048, 32),
 }
 
 
@@ -1110,3 +1385,28 @@ def variant_of(sig):
         (_, a_ld, _, a_tr, _, b_ld, _, b_tr, _, c_ld, _, _, _, _, _, M, N, K, batch, _, _, mode, splits, dt) = w
         return int(lib.ddpm_gemm_variant(a_ld, a_tr, b_ld, b_tr, c_ld, M, N, K, batch, mode, splits, dt))
     return None
+
+
+# Kernel ids (variant_of) the dispatch reaches only with bf16 operands.  csrc/gemm.hip ddpm_conv2d_nhwc puts the edge convs (11, 12), the
+# persistent 3x3 stream / wave-specialised kernels (8, 10, 13), the halo kernel (5) and the streaming 1x1 kernel (7) behind
+# `dtype == DDPM_BF16`; csrc/wgrad.hip (6, 14) and csrc/wgrad1x1.hip (9) return DDPM_ERR_DTYPE for anything else.  What stays for fp32
+# is the templated gemm_kernel (1, 2, 3) and gemm64_kernel (4).
+BF16_ONLY = {5, 6, 7, 8, 9, 10, 11, 12, 13, 14}
+
+
+def dtype_index(name):
+    """Position of the `dtype` parameter in the declaration of `name` (include/ddpm_hip.h), None if it has none."""
+    import os
+    import re
+    if not _DTYPE_INDEX:
+        inc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
+        src = "".join(open(os.path.join(inc, f)).read() for f in ("ddpm_hip.h", "ddpm_hip_debug.h"))
+        src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+        for m in re.finditer(r"\b(?:int|long long)\s+(ddpm_\w+)\s*\(([^;{]*?)\)\s*;", src, re.S):
+            names = [re.findall(r"(\w+)\s*$", a.strip()) for a in m.group(2).split(",")]
+            names = [n[0] if n else "" for n in names]
+            _DTYPE_INDEX[m.group(1)] = names.index("dtype") if "dtype" in names else None
+    return _DTYPE_INDEX[name]
+
+
+_DTYPE_INDEX = {}

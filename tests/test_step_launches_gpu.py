@@ -1,11 +1,15 @@
-"""-m gpu: every launch of the benchmarked steps, replayed on the MI355X against a float64 reference at the geometry the step uses.
+"""-m gpu: every launch of the benchmarked steps, and of the fp32 mode and the CLIs' other batch sizes, replayed on the MI355X against a
+float64 reference at the geometry the step uses.
 
-The workloads (tests/launch_replay.py WORKLOADS, bf16 compute mode) are recorded live through ddpm_torch._hip._invoke — the geometry
-list is taken from the step every time the test runs, not from a committed snapshot.  Each distinct signature of a replayed entry is
-(dropout seeds aside) re-issued once on fresh random inputs (same pitches, pointer offsets modulo 256, optional operands, modes, splits and workspaces) and
-every output element is held to its own error-model bar; the float64 references run in torch on the GPU, over every image.
+The workloads (tests/launch_replay.py WORKLOADS: W1-W4 the benchmarked bf16 steps, W5-W8 the same configurations in the fp32 compute
+mode, W9-W13 bf16 steps at the batch sizes train.py --num-accum and generate.py run, up to operands >= 1 GiB) are recorded live through
+ddpm_torch._hip._invoke — the geometry list is taken from the step every time the test runs, not from a committed snapshot.  Each
+distinct signature of a replayed entry is (dropout seeds aside) re-issued once on fresh random inputs (same pitches, pointer offsets
+modulo 256, optional operands, modes, splits and workspaces) and every output element is held to its own error-model bar; the float64
+references run in torch on the GPU, over every image (in slices of images where one pass would need tens of GB).
 Every recorded entry must be either replayed or mapped to the existing test that covers it (launch_replay.COVERED_ELSEWHERE)."""
 import collections
+import time
 
 import pytest
 import torch
@@ -19,6 +23,9 @@ DEV = "cuda:0"
 # kernels the benchmark line is made of (include/ddpm_hip_debug.h): 13 conv3x3_pc, 10 / 8 conv3x3_stream<8> / <16>, 7 pw_conv,
 # 4 gemm64, 11 / 12 edge convs, 14 wgrad3x3_ws, 6 wgrad3x3 (patch-stationary)
 W1_VARIANTS = {13, 10, 8, 7, 4, 11, 12, 14, 6}
+FP32 = ("W5", "W6", "W7", "W8")
+# recorded launches of the fp32 workloads that may pass a dtype other than fp32 (none: every operand of the fp32 mode is fp32)
+FP32_DTYPE_EXEMPT = {}
 
 
 def _table(key, rows):
@@ -27,8 +34,52 @@ def _table(key, rows):
         print(f"  {LR.short(sig):<150s} v{'' if var is None else var:<3} {r.where:<10s} err/bar {r.worst:.3f}")
 
 
+def _check_fp32_mode(key, rec, variants):
+    for s in rec.sigs:
+        i = LR.dtype_index(s[0])
+        if i is not None and s[0] not in FP32_DTYPE_EXEMPT:
+            assert s[1][i] == LR.F32, f"{key}: fp32 mode launched {LR.short(s)} with dtype {s[1][i]}"
+    bf16_only = sorted(set(variants) & LR.BF16_ONLY)
+    assert not bf16_only, f"{key}: fp32 signatures dispatched to bf16-only kernels {bf16_only}"
+    assert "ddpm_softmax_fwd" in rec.names, f"{key}: fp32 attention ran no ddpm_softmax_fwd"
+    if key in ("W5", "W7"):
+        assert "ddpm_softmax_bwd" in rec.names, f"{key}: fp32 attention backward ran no ddpm_softmax_bwd"
+
+
+def _check_w9(rec):
+    """At B = 32 the pixel-count thresholds of the 3x3 dispatch fall at other levels than at B = 128."""
+    moved = []
+    for s in rec.sigs:
+        w = s[1]
+        if s[0] == "ddpm_conv2d_nhwc" and w[17] == 3 and w[18] == 3:
+            at128 = LR.variant_of((s[0], w[:10] + (128,) + w[11:]))
+            if at128 != LR.variant_of(s):
+                moved.append((s, LR.variant_of(s), at128))
+    for s, v, v128 in moved:
+        print(f"W9: {LR.short(s)}  B=32 -> v{v}, B=128 -> v{v128}")
+    assert moved, "W9: every 3x3 conv dispatches as it does at B = 128"
+
+
+def _check_w12(rec):
+    gn = [s for s in rec.sigs if s[0] == "ddpm_groupnorm_silu_bwd" and s[1][13] == 64 * 64]
+    assert gn, "W12: no GroupNorm backward at HW = 4096"
+
+    def pixels_3x3_wgrad(s):
+        w = s[1]
+        if s[0] in ("ddpm_conv3x3_wgrad_nhwc", "ddpm_conv3x3_wgrad_up_nhwc"):
+            return w[8] * w[9] * w[10]
+        if s[0] == "ddpm_conv2d_wgrad_nhwc" and w[15] == 3 and w[16] == 3:
+            return w[6] * w[11] * w[12]
+        return 0
+    wg = [s for s in rec.sigs if pixels_3x3_wgrad(s) == 128 * 64 * 64]
+    assert wg, "W12: no 3x3 weight gradient over B*64*64 pixels"
+    print(f"W12: {len(gn)} GroupNorm backward signature(s) at HW = 4096, {len(wg)} 3x3 weight gradient(s) over 128*64*64 pixels")
+
+
 @pytest.mark.parametrize("key", list(LR.WORKLOADS))
 def test_every_launch_of_the_step_matches_float64(key, monkeypatch):
+    t0 = time.perf_counter()
+    torch.cuda.reset_peak_memory_stats()
     rec = LR.record(monkeypatch, key, DEV)
     torch.cuda.empty_cache()
     unaccounted = sorted(set(rec.names) - set(LR.REPLAY) - set(LR.COVERED_ELSEWHERE))
@@ -43,14 +94,40 @@ def test_every_launch_of_the_step_matches_float64(key, monkeypatch):
     if key == "W1":
         assert W1_VARIANTS <= set(variants), f"W1 did not reach variants {sorted(W1_VARIANTS - set(variants))}"
         assert any(s[0] == "ddpm_conv1x1_wgrad_nhwc" for s in rec.sigs), "W1 ran no 1x1 slab weight gradient"
+    if key in FP32:
+        _check_fp32_mode(key, rec, variants)
+    if key == "W9":
+        _check_w9(rec)
+    if key == "W12":
+        _check_w12(rec)
     rows, bad, seen = [], [], set()
     for i, s in enumerate(rec.sigs):
         if s[0] not in LR.REPLAY or LR.geometry(s) in seen:
             continue
         seen.add(LR.geometry(s))
         r = LR.replay(s, DEV, seed=i)
+        torch.cuda.empty_cache()
         rows.append((s, LR.variant_of(s), r))
         if r.worst > 1.0:
             bad.append(f"{LR.short(s)}: {r.where} err/bar {r.worst:.3g}")
     _table(key, rows)
+    biggest = max(rows, key=lambda x: x[2].max_bytes)
+    worst = max(rows, key=lambda x: x[2].worst)
+    print(f"{key}: {len(rec.sigs)} recorded / {len(rows)} replayed signatures, worst err/bar {worst[2].worst:.3f} ({LR.short(worst[0])[:60]}, "
+          f"{worst[2].where}), largest operand {biggest[2].max_bytes / 2 ** 30:.2f} GiB ({LR.short(biggest[0])[:60]}), "
+          f"peak device memory {torch.cuda.max_memory_allocated() / 1e9:.1f} GB, record + replay {time.perf_counter() - t0:.1f} s")
+    if key == "W13":
+        assert biggest[2].max_bytes >= 2 ** 30, f"W13: largest replayed operand {biggest[2].max_bytes} bytes < 1 GiB"
     assert not bad, f"{key}: {len(bad)} signature(s) beyond their bar:\n" + "\n".join(bad)
+
+
+def test_synthetic_signatures_match_float64():
+    """The replayed entries at edge geometries of their own (launch_replay.SYNTHETIC): ddpm_gather_rows_f32 and ddpm_add_rows are
+    launched by none of the workloads above."""
+    bad = []
+    for i, s in enumerate(LR.SYNTHETIC):
+        r = LR.replay(s, DEV, seed=i)
+        print(f"  {LR.short(s):<90s} {r.where:<10s} err/bar {r.worst:.3f}")
+        if r.worst > 1.0:
+            bad.append(f"{LR.short(s)}: {r.where} err/bar {r.worst:.3g}")
+    assert not bad, "\n".join(bad)

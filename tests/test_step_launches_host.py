@@ -9,8 +9,10 @@ builders computed (the guard bands and the untouched elements are checked after 
 import os
 import time
 
+import numpy as np
 import pytest
 import torch
+import torch.nn.functional as F
 
 from ddpm_torch import _hip
 from tests import abi_emulator
@@ -22,7 +24,7 @@ pytestmark = pytest.mark.skipif(not os.path.exists(_hip.LIB_PATH), reason="libdd
 # where |mean| >> std): its own rounding may exceed a bar written for the kernels by a small factor.  A misread pitch, operand or
 # epilogue term is off by the size of the value itself, 10^3..10^7 bars.
 HOST_SLACK = 4.0
-HOST_SIZE = {"W1": (2, 32), "W2": (2, 32), "W3": (2, 128), "W4": (2, 64)}
+HOST_SIZE = {"W1": (2, 32), "W2": (2, 32), "W3": (2, 128), "W4": (2, 64), "W5": (2, 32), "W6": (2, 32), "W7": (2, 128), "W8": (2, 64)}
 
 
 def test_replay_builders_agree_with_the_emulator_on_every_recorded_signature(monkeypatch):
@@ -52,8 +54,16 @@ def test_replay_builders_agree_with_the_emulator_on_every_recorded_signature(mon
     print(f"{len(worst)} signatures replayed in {time.perf_counter() - t0:.1f} s")
 
 
+@pytest.mark.parametrize("sig", LR.SYNTHETIC, ids=LR.short)
+def test_synthetic_signatures_agree_with_the_emulator(sig, monkeypatch):
+    """Every replayer, including those of entries no recorded workload launches, meets the emulator at its edge geometries."""
+    abi_emulator.install(monkeypatch, _hip)
+    assert sig[0] in LR.REPLAY and sig[0] not in LR.COVERED_ELSEWHERE
+    r = LR.replay(sig, "cpu")
+    assert r.worst <= HOST_SLACK, f"{LR.short(sig)}: {r.where} err/bar {r.worst:.3g}"
+
+
 def test_keep_mask_restatement_is_bit_equal_to_the_numpy_hash():
-    import numpy as np
     for seed in (0, 12345, 0x5DEECE66D + 977, (1 << 63) + 99):
         idx = np.concatenate([np.arange(70000, dtype=np.uint64), np.uint64(1 << 33) + np.arange(5000, dtype=np.uint64)])
         for p in (0.1, 0.5):
@@ -100,4 +110,52 @@ def test_error_model_bars_bite_at_the_scale_of_a_one_percent_kernel_error(monkey
         v[:, 63] += abi_emulator.f32(bias, 64)[63] * 2.0 ** -4
         ys.set(v)
     monkeypatch.setattr(emu, "ddpm_conv2d_nhwc", skewed)
+    assert LR.replay(sig, "cpu").worst > 1.0
+
+
+def _round_bits(a, bits):
+    """a rounded to `bits` significant bits (round half to even), as float32"""
+    m, e = np.frexp(np.asarray(a, dtype=np.float64))
+    return np.ldexp(np.round(m * 2.0 ** bits), e - bits).astype(np.float32)
+
+
+def test_fp32_conv_bar_bites_on_operands_rounded_to_11_bits(monkeypatch):
+    """An fp32 conv whose product ran on operands rounded to 11 significant bits (an fp16-like or tf32-like path, ~5e-4 per operand)
+    must exceed its bar; the same signature computed from the unrounded operands must pass."""
+    emu = abi_emulator.install(monkeypatch, _hip)
+    B, H, W, C, N = 2, 8, 8, 64, 64
+    sig = ("ddpm_conv2d_nhwc", (("p", False, 0), C, ("p", False, 0), ("p", False, 0), N, ("p", False, 0), ("p", True, 0), 0,
+                                ("p", True, 0), 0, B, H, W, C, H, W, N, 3, 3, 1, 1, 1, 0, 0, 0, 0, 1, ("p", True, 0), ("p", True, 0),
+                                abi_emulator.F32))
+    assert LR.replay(sig, "cpu").worst <= 1.0
+    real = emu.ddpm_conv2d_nhwc
+
+    def rounded(*a):
+        real(*a)
+        x, w, y = a[0], a[2], a[3]
+        xin = abi_emulator.Mat(x, B * H * W, C, C, abi_emulator.F32).get()
+        wt = abi_emulator.f32(w, N * 9 * C)
+
+        def conv(xv, wv):
+            xt = torch.from_numpy(xv.astype(np.float64)).reshape(B, H, W, C).permute(0, 3, 1, 2)
+            wk = torch.from_numpy(wv.astype(np.float64)).reshape(N, 3, 3, C).permute(0, 3, 1, 2)
+            return F.conv2d(xt, wk, padding=1).permute(0, 2, 3, 1).reshape(B * H * W, N).numpy()
+        ys = abi_emulator.Mat(y, B * H * W, N, N, abi_emulator.F32)
+        ys.set(ys.get() + (conv(_round_bits(xin, 11), _round_bits(wt, 11)) - conv(xin, wt)))
+    monkeypatch.setattr(emu, "ddpm_conv2d_nhwc", rounded)
+    assert LR.replay(sig, "cpu").worst > 1.0
+
+
+def test_softmax_bar_bites_on_one_row_normaliser_off_by_2_to_the_minus_12(monkeypatch):
+    """ddpm_softmax_fwd (fp32) with one row's normaliser off by 2^-12 relative must exceed the per-element bar; exact rows pass."""
+    emu = abi_emulator.install(monkeypatch, _hip)
+    rows, L = 512, 256
+    sig = ("ddpm_softmax_fwd", (("p", False, 0), ("p", False, 0), rows, L, abi_emulator.F32))
+    assert LR.replay(sig, "cpu").worst <= 1.0
+    real = emu.ddpm_softmax_fwd
+
+    def skewed(s, p, rows_, L_, dt, st):
+        real(s, p, rows_, L_, dt, st)
+        abi_emulator.f32(p, rows_ * L_)[77 * L_:78 * L_] /= np.float32(1.0 + 2.0 ** -12)
+    monkeypatch.setattr(emu, "ddpm_softmax_fwd", skewed)
     assert LR.replay(sig, "cpu").worst > 1.0
