@@ -87,6 +87,9 @@ PROTOTYPES = {
     "ddpm_toy_decoder_fwd": [P] * 16 + [I] * 5 + [P],
     "ddpm_toy_decoder_bwd": [P] * 19 + [L] + [I] * 5 + [P],
     "ddpm_toy_time_table_bwd": [P] * 7 + [L, I, I, I, P],
+    # precision / recall manifolds (csrc/manifold.hip; driven by metrics/precision_recall.py)
+    "ddpm_manifold_kth_f16": [P, L, I, P, L, I, I, I, P, P, L, P],
+    "ddpm_manifold_cover_f16": [P, L, I, P, L, I, I, P, P, P, L, P],
     # launch plans (csrc/plan.hip; driven by _plan.LaunchPlan)
     "ddpm_stream_order": [P, P],
     "ddpm_fill_zero": [P, L, P],

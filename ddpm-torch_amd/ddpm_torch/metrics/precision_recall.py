@@ -1,7 +1,11 @@
 """Improved precision / recall (Kynkäänniemi et al., 2019) as the reference computes it (``ddpm_torch/metrics/precision_recall.py:42-206``
 of tqch/ddpm-torch): a sample set is represented by its feature vectors and, per vector, the distance to its k-th nearest neighbour;
 precision = share of generated features inside at least one real hypersphere, recall the converse.  The VGG-16 feature network is
-pluggable (the reference downloads a TorchScript file): ``ManifoldBuilder(..., extractor=callable)`` or precomputed ``features=``."""
+pluggable (the reference downloads a TorchScript file): ``ManifoldBuilder(..., extractor=callable)`` or precomputed ``features=``.
+
+On the GPU the two manifold computations run as fused kernels (``csrc/manifold.hip``): the pairwise-distance product keeps, per row, the
+smallest distances or one "covered" bit and no block of distances is ever materialised or copied to the host.  The block loop below is the
+CPU path and the fallback for what the kernels do not serve; ``DDPM_TORCH_AMD_FUSED_PR=0`` (read at call time) forces it on the GPU too."""
 import math
 import os
 from collections import namedtuple
@@ -9,7 +13,11 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-__all__ = ["Manifold", "ManifoldBuilder", "calc_pr", "compute_distance", "to_uint8", "load_manifold"]
+from .. import _hip
+
+__all__ = ["Manifold", "ManifoldBuilder", "calc_pr", "compute_distance", "to_uint8", "load_manifold", "kth_radii", "coverage_hits"]
+
+MAX_FUSED_RANK = 16                 # candidates the radius kernel keeps per row (include/ddpm_hip.h)
 
 Manifold = namedtuple("Manifold", ["features", "kth"])
 
@@ -30,6 +38,68 @@ def compute_distance(row_features, col_features, row_batch_size, col_batch_size,
         r = r.to(device)
         rows.append(torch.cat([_pairwise(r, c.to(device)).cpu() for c in col_features.split(col_batch_size, dim=0)], dim=1))
     return torch.cat(rows, dim=0)
+
+
+def _column_splits(nr, nc):
+    """The column split of the fused kernels (include/ddpm_hip.h): the radii's workspace holds one candidate list per split and row."""
+    rt, ct = -(-nr // 128), -(-nc // 128)
+    s0, half = min(ct, 64, -(-4096 // rt)), -(-ct // 2)
+    if rt * half >= 512:
+        s0 = min(s0, half)
+    return -(-ct // -(-ct // s0))
+
+
+def _operand(t):
+    """fp16 [N, D] with unit inner stride, addressed by its row pitch."""
+    if t.dtype != torch.float16 or t.dim() != 2:
+        raise TypeError("the fused manifold kernels take fp16 [N, D] features")
+    return t if t.stride(1) == 1 and t.stride(0) >= t.shape[1] else t.contiguous()
+
+
+def kth_radii(rows, cols, rank):
+    """fp16 [Nr]: per row of ``rows`` the ``rank``-th smallest distance to the rows of ``cols`` (both fp16 [N, D], already on the device).
+    One ``ddpm_manifold_kth_f16`` call on the current stream; output and workspace are torch allocations."""
+    rows, cols = _operand(rows), _operand(cols)
+    _hip.require_cuda(rows, cols)
+    if rows.shape[1] != cols.shape[1]:
+        raise ValueError("feature widths differ")
+    (nr, d), nc = rows.shape, cols.shape[0]
+    out = torch.empty(nr, dtype=torch.float16, device=rows.device)
+    ws = torch.empty(4 * (nr + nc) + 64 * _column_splits(nr, nc) * nr, dtype=torch.uint8, device=rows.device)
+    _hip.call("ddpm_manifold_kth_f16", _hip.ptr(rows), rows.stride(0), nr, _hip.ptr(cols), cols.stride(0), nc, d, int(rank), _hip.ptr(out),
+              _hip.ptr(ws), ws.numel(), _hip.stream())
+    return out
+
+
+def coverage_hits(probe, support, support_kth):
+    """bool [Np]: does probe feature i lie inside at least one support hypersphere (``d(i, j) <= support_kth[j]``, compared in fp16)?
+    One ``ddpm_manifold_cover_f16`` call on the current stream."""
+    probe, support = _operand(probe), _operand(support)
+    _hip.require_cuda(probe, support, support_kth)
+    if probe.shape[1] != support.shape[1] or support_kth.shape != (support.shape[0],) or support_kth.dtype != torch.float16:
+        raise ValueError("support_kth must be fp16 [len(support)] and the feature widths equal")
+    (n_p, d), ns = probe.shape, support.shape[0]
+    support_kth = support_kth.contiguous()
+    hit = torch.empty(n_p, dtype=torch.uint8, device=probe.device)
+    ws = torch.empty(4 * (n_p + ns), dtype=torch.uint8, device=probe.device)
+    _hip.call("ddpm_manifold_cover_f16", _hip.ptr(probe), probe.stride(0), n_p, _hip.ptr(support), support.stride(0), ns, d,
+              _hip.ptr(support_kth), _hip.ptr(hit), _hip.ptr(ws), ws.numel(), _hip.stream())
+    return hit.bool()
+
+
+def _upload(t, device):
+    return t.to(device)
+
+
+def _fused(device, rows, cols, rank=1):
+    """Do the fused kernels serve this call?  A GPU device, fp16 features, D % 8 == 0, rank <= min(16, columns), operands below 2 GiB; and
+    DDPM_TORCH_AMD_FUSED_PR != 0 (read here, at call time).  Everything else keeps the block loop."""
+    if os.environ.get("DDPM_TORCH_AMD_FUSED_PR", "1") == "0" or torch.device(device).type != "cuda":
+        return False
+    for t in (rows, cols):
+        if t.dtype != torch.float16 or t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 8 or t.shape[1] % 8 or t.numel() * 2 >= 2 ** 31:
+            return False
+    return rows.shape[1] == cols.shape[1] and 1 <= rank <= min(MAX_FUSED_RANK, cols.shape[0])
 
 
 def to_uint8(x):
@@ -96,6 +166,12 @@ class ManifoldBuilder:
     def compute_kth(self, row_features, col_features=None):
         """Distance of every row feature to its ``nhood_size``-th nearest OTHER feature (k + 1 smallest: the feature itself is at 0)."""
         cols = row_features if col_features is None else col_features
+        if _fused(self.op_device, row_features, cols, self.nhood_size + 1):
+            dev = torch.device(self.op_device)
+            with torch.cuda.device(dev):
+                r = _upload(row_features, dev)                              # once per call; the same tensor serves both sides of a self-query
+                c = r if col_features is None else _upload(col_features, dev)
+                return kth_radii(r, c, self.nhood_size + 1).cpu()
         out = []
         for block in row_features.split(self.row_batch_size, dim=0):
             d = self.compute_distance(block, cols).to(torch.float32)
@@ -121,6 +197,11 @@ def load_manifold(fpath):
 
 def _coverage(probe, support, row_batch_size, col_batch_size, device):
     """Share of probe features that fall inside at least one support hypersphere."""
+    if _fused(device, probe.features, support.features) and support.kth.dtype == torch.float16:
+        dev = torch.device(device)
+        with torch.cuda.device(dev):
+            hit = coverage_hits(_upload(probe.features, dev), _upload(support.features, dev), _upload(support.kth, dev))
+            return hit.cpu().to(torch.float32).mean()
     hit = []
     for block in probe.features.split(row_batch_size):
         d = compute_distance(block, support.features, row_batch_size, col_batch_size, device)

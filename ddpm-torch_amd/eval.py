@@ -38,8 +38,9 @@ def parse_args(argv=None):
     add("--eval-total-size", default=50000, type=int)
     add("--num-workers", default=4, type=int)
     add("--nhood-size", default=3, type=int)
-    add("--row-batch-size", default=10000, type=int)
-    add("--col-batch-size", default=10000, type=int)
+    blocks = "block size of the host-gathered distance loop (CPU device, fp32 features, nhood-size > 15); ignored by the fused GPU kernels"
+    add("--row-batch-size", default=10000, type=int, help=blocks)
+    add("--col-batch-size", default=10000, type=int, help=blocks)
     add("--device", default="cuda:0", type=str)
     add("--precomputed-dir", default="./precomputed", type=str)
     add("--metrics", nargs="+", default=["fid", "pr"], type=str)

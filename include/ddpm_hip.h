@@ -289,6 +289,29 @@ int ddpm_toy_decoder_bwd(const float* x, const long long* t, const float* dy, co
 int ddpm_toy_time_table_bwd(const long long* t, const float* dzsum, const float* freqs, const float* enc_w, const float* tabs, float* gtab,
                             float* ws, long long ws_floats, int B, int M, int T, void* stream);
 
+/* ---- improved precision / recall (csrc/manifold.hip): the two manifold computations without the N x N distance matrix.
+ * Operands are fp16, row-major [N][ld] with ld in elements (ld >= D, ld % 8 == 0, 16-byte aligned base), D % 8 == 0, every operand below
+ * 2 GiB.  The distance is the one of the block path (widen to fp32, round the result to fp16):
+ *   d2(i,j) = max(|r_i|^2 + |c_j|^2 - 2 <r_i, c_j>, 0) in fp32 (fp16 products accumulated in fp32 on the matrix cores),
+ *   d(i,j)  = fp16_rne(sqrtf(d2(i,j))), overflow -> inf.
+ * Both calls are stream-ordered, allocate nothing and are bit-deterministic (no floating-point atomics).  Scratch is the caller's
+ * `workspace` (16-byte aligned, workspace_bytes = its capacity; DDPM_ERR_SHAPE when it is too small).  With
+ *   RT = ceil(Nr / 128), CT = ceil(Nc / 128), H = ceil(CT / 2), S0 = min(CT, 64, ceil(4096 / RT)), S1 = min(S0, H) if RT * H >= 512 else S0,
+ *   S = ceil(CT / ceil(CT / S1))   (the column split: grid = RT x S workgroups)
+ * the radii need 4 * (Nr + Nc) + 64 * S * Nr bytes and the coverage needs 4 * (Np + Ns) bytes.
+ * Refused on the host before any launch: null pointer 5; D % 8 != 0, ld < D, N < 1, rank outside [1, min(16, Nc)], an operand of 2 GiB
+ * or more, a short workspace 1; a misaligned base or pitch 3.
+ *
+ * ManifoldBuilder.compute_distance + kthvalue (metrics/precision_recall.py:43-55,156-164):
+ *   out[i] (fp16) = the rank-th smallest of d(i, 0 .. Nc-1), rank = nhood_size + 1, equal values counted with multiplicity; a row that
+ *   is also a column is an ordinary column (its distance to itself takes part, as upstream). */
+int ddpm_manifold_kth_f16(const void* rows, long long rows_ld, int Nr, const void* cols, long long cols_ld, int Nc, int D, int rank,
+                          void* out, void* workspace, long long workspace_bytes, void* stream);
+/* calc_pr's membership test (metrics/precision_recall.py:188-204):
+ *   hit[i] (uint8, 0 or 1) = any_j d(i,j) <= support_kth[j], compared as fp16 values; support_kth is fp16 [Ns]. */
+int ddpm_manifold_cover_f16(const void* probe, long long probe_ld, int Np, const void* support, long long support_ld, int Ns, int D,
+                            const void* support_kth, void* hit, void* workspace, long long workspace_bytes, void* stream);
+
 /* ---- launch plans (no upstream counterpart: the reference issues its step op by op from Python, ddpm_torch/utils/train.py:148-170).
  * The training step is a fixed sequence of the calls above; a plan records it once — entry-point name + argument words + the
  * hipStream_t each call was given — and ddpm_plan_run re-issues a whole segment from C: eager semantics (two concurrent streams,
