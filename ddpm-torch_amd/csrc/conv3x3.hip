@@ -36,7 +36,6 @@ struct CsArgs {
     int B, H, W, C, N, K;                                 // H, W: OUTPUT (= virtual input) image; ups = 1: x is stored at half that size (nearest 2x)
     int ups;
     int tiles_y, tiles_x, tiles_n, total_tiles, xcd;
-    int flags;                                            // conv3x3_pc_kernel: bit 0 = consumers at s_setprio 1
     FastDiv d_tiles_n, d_tpi, d_tiles_x;
 };
 
@@ -647,14 +646,11 @@ __device__ __forceinline__ void pc_fault(unsigned addr, unsigned target, unsigne
     __builtin_trap();
 }
 __device__ __forceinline__ void pc_wait_all_ge(unsigned addr, unsigned target) {
-#ifdef PC_ABL_NO_SYNC
-    return;
-#endif
     // bounded: a protocol error must end the launch with an error the host sees (trap), never hang the GPU.  The bound is WALL time
     // (s_memrealtime, 100 MHz): ~5 s, so that a profiler's thread trace, a debugger or a stalled co-tenant cannot turn a slow wait into
     // a fault; the clock is looked at every 4096 polls only.  pc_fault() leaves {block, counter address, target, 1 + kind} in
     // g_pc_fault before the trap (rocgdb / a core file name the wait that tripped; ddpm_conv3x3_pc_last_fault reads it where the
-    // context survives).  DDPM_CONV_NO_PC=1 runs every call on conv3x3_stream_kernel<16>, which has no such waits.
+    // context survives).
     unsigned long long t_first = 0;
     for (unsigned spins = 0;; ++spins) {
         u32x4 v;
@@ -665,9 +661,6 @@ __device__ __forceinline__ void pc_wait_all_ge(unsigned addr, unsigned target) {
     }
 }
 __device__ __forceinline__ void pc_wait_ge(unsigned addr, unsigned target) {          // one (summed) counter: the consumers' rendezvous
-#ifdef PC_ABL_NO_SYNC
-    return;
-#endif
     unsigned long long t_first = 0;
     for (unsigned spins = 0;; ++spins) {
         unsigned v;
@@ -680,9 +673,6 @@ __device__ __forceinline__ void pc_wait_ge(unsigned addr, unsigned target) {    
 // +1 on a counter: one ds_add_u32 of the whole wave, lane 0 on the counter, every other lane on its own word of the junk area (no exec
 // masking, no bank conflict); `lane_addr` is built once per wave
 __device__ __forceinline__ void pc_signal(unsigned lane_addr) {
-#ifdef PC_ABL_NO_SYNC
-    return;
-#endif
     const unsigned one = 1u;
     asm volatile("ds_add_u32 %0, %1" :: "v"(lane_addr), "v"(one) : "memory");
 }
@@ -690,11 +680,7 @@ __device__ __forceinline__ void pc_signal(unsigned lane_addr) {
 #ifdef C3_TIMING
 // debug builds only (scripts/pc_timeline.py): consumer wave 0's phase stamps [block][8] as for the kernel above, then [block][64] clocks at the end of its first 64 K-steps
 #define PC_STAMP(slot) do { if (g_c3_timing && threadIdx.x == 0) g_c3_timing[blockIdx.x * 8 + (slot)] = (slot) == 0 || (slot) == 7 ? wall_clock64() : clock64(); } while (0)
-#ifdef PC_ABL_NO_STEPSTAMP
-#define PC_STEP()
-#else
 #define PC_STEP() do { if (g_c3_timing && threadIdx.x == 0 && tstep < 64) g_c3_timing[2048 + blockIdx.x * 64 + tstep] = clock64(); ++tstep; } while (0)
-#endif
 #else
 #define PC_STAMP(slot)
 #define PC_STEP()
@@ -799,9 +785,6 @@ void conv3x3_pc_kernel(CsArgs a) {
         const unsigned sig_ready = lane == 0 ? cnt0 + PC_READY + (unsigned)(lw * 4) : junk;
         wait_vm<8>();                                       // the halo, the rows and weight tile 0 are in; tiles 1 and 2 may be on their way
         pc_signal(sig_ready);
-#ifdef PC_ABL_NO_LOADERS
-        return;
-#endif
         int slot = 0, hb = 0;
         unsigned gstep = 0;                                 // flat step index
         for (int k = 0; k < my_tiles; ++k) {
@@ -823,18 +806,14 @@ void conv3x3_pc_kernel(CsArgs a) {
                     pc_wait_all_ge(cnt0 + PC_FREED, gstep);
                     // requests of this step, in queue order: parts of the next halo (taps 0-5: 2 2 2 2 2 1), the next tile's rows (tap 6 of a
                     // tile's last chunk), then the weight tile three steps ahead
-#ifndef PC_ABL_NO_HALO
                     if (prefetch && tap < 6) {
                         if (tap < 5) { issue_halo_part(same_tile ? cur : nxt, 2 * tap, ncc, hnxt); issue_halo_part(same_tile ? cur : nxt, 2 * tap + 1, ncc, hnxt); }
                         else issue_halo_part(same_tile ? cur : nxt, 10, ncc, hnxt);
                     }
-#endif
                     if (tap == 6 && rows_here) issue_rows(nxt, (k + 1) & 1);
                     const int wslot = slot + RING - 1 >= RING ? slot - 1 : slot + RING - 1;
-#ifndef PC_ABL_NO_W
                     if (tap + RING - 1 < 9) issue_w(cur.tn, cc, tap + RING - 1, wslot);
                     else if (prefetch) issue_w(ntn, ncc, tap + RING - 1 - 9, wslot);
-#endif
                     slot = slot + 1 == RING ? 0 : slot + 1;
                     // The next step's weight tile (requested two steps back, LAST in its step) has to be in; everything requested in the
                     // previous step and in this one is newer and may stay in flight.  When the next step opens a chunk, that chunk's halo
@@ -862,7 +841,6 @@ void conv3x3_pc_kernel(CsArgs a) {
     // =================================================================== consumers
     constexpr int NIB = 2, NJ = 4;
     const int wn = wave >> 1, wm = wave & 1;              // 64 channels x 128 pixels (patch rows 8 wm .. 8 wm + 7)
-    if (a.flags & 1) __builtin_amdgcn_s_setprio(1);
     // Fragment addresses.  Pixel block j of the wave = patch rows 8 wm + 2 j, 2 j + 1: lane l reads pixel (2 j + (l % 32) / 16, l % 16), so the
     // four blocks sit at a CONSTANT 2 x 18 x 128 bytes from each other, their chunk key ((px + s) >> 1) is the same, and ONE address
     // register + ds_read's immediate offset serves all four; likewise the two 32-row weight blocks (4096 bytes apart).  The sub-step
@@ -947,25 +925,16 @@ void conv3x3_pc_kernel(CsArgs a) {
                     const int rd = kc >= 0 ? 1 : 0;            // new reads are issued in this sub-step
                     auto rd_w = [&](int i) {
                         if (kc < 0) return;
-#ifdef PC_ABL_NO_READS
-                        return;
-#endif
                         asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(nw[i]) : "v"(aw), "n"(i * WI) : "memory");
                         __builtin_amdgcn_sched_barrier(0);
                     };
                     auto rd_x = [&](int j) {
                         if (kc < 0) return;
-#ifdef PC_ABL_NO_READS
-                        return;
-#endif
                         asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(nx[j]) : "v"(ax), "n"(j * XJ) : "memory");
                         __builtin_amdgcn_sched_barrier(0);
                     };
                     auto mm = [&](int i, int j) {
                         if (!mf) return;
-#ifdef PC_ABL_NO_MFMA
-                        return;
-#endif
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, cw[i]), __builtin_bit_cast(bf16x8, cx[j]), acc[i][j], 0, 0, 0);
                         __builtin_amdgcn_sched_barrier(0);
                     };
@@ -994,9 +963,7 @@ void conv3x3_pc_kernel(CsArgs a) {
                     wl(2 + pre + 4 * rd);                    // x1
                     mm(0, 1); rd_x(2); rd_x(3);
                     if (post == 1) {
-#ifndef PC_ABL_NO_SYNC
                         asm volatile("ds_read_b128 %0, %1" : "=v"(rcp) : "v"(cnt0 + PC_READY) : "memory");
-#endif
                         __builtin_amdgcn_sched_barrier(0);
                     } else if (post == 2) {
                         pc_signal(sig);                      // (behind this step's last reads in the wave's LDS queue)
@@ -1016,13 +983,11 @@ void conv3x3_pc_kernel(CsArgs a) {
                 // sub-step 1: the previous step's last fragments (behind them in the queue: that step's signal) | reads kc = 0.  The `ready`
                 // counter read in the previous step's third sub-step is older than those fragments: valid once the first wait is through,
                 // and checked BEFORE this step's first read is issued
-#ifndef PC_ABL_NO_SYNC
                 if (tap > 0 || pend) {
                     asm volatile("s_waitcnt lgkmcnt(5)" ::: "memory");
                     __builtin_amdgcn_sched_barrier(0);
                     if (pc_min_dist(rcp, need) < 0) pc_wait_all_ge(cnt0 + PC_READY, need);
                 }
-#endif
                 sub_step(tap > 0 || pend, fw[1], fx[1], 0, fw[0], fx[0], 1, 0, 0u, false);
                 sub_step(true, fw[0], fx[0], 1, fw[1], fx[1], 0, 0, 0u, false);
                 sub_step(true, fw[1], fx[1], 2, fw[0], fx[0], 0, 1, 0u, false);
@@ -1141,26 +1106,20 @@ extern "C" int ddpm_conv3x3_pc_last_fault(unsigned* out4) {
 int ddpm_conv3x3_stream_launch(const void* x, long long x_ld, const void* w, void* y, long long y_ld, const float* bias, const float* rowbias,
                                long long rowbias_ld, const void* residual, long long res_ld, int accumulate, int B, int H, int W, int C, int N,
                                int upsample, int xcd, int dry, void* stream) {
-    static const bool off = getenv("DDPM_CONV_NO_STREAM3") != nullptr, off8 = getenv("DDPM_CONV_NO_STREAM3_8") != nullptr;
     const long long M = (long long)B * H * W;
-    const int patch = (H % 16 == 0 && W % 16 == 0 && M >= 16384) ? 16 : ((H % 8 == 0 && W % 8 == 0 && M >= 4096 && !off8) ? 8 : 0);
-    if (off || !patch || (residual && accumulate) || C % 64 || N % 64 || x_ld % 8 || y_ld % 8 || (residual && res_ld % 4) || (rowbias && rowbias_ld % 4)) return -1;
+    const int patch = (H % 16 == 0 && W % 16 == 0 && M >= 16384) ? 16 : ((H % 8 == 0 && W % 8 == 0 && M >= 4096) ? 8 : 0);
+    if (!patch || (residual && accumulate) || C % 64 || N % 64 || x_ld % 8 || y_ld % 8 || (residual && res_ld % 4) || (rowbias && rowbias_ld % 4)) return -1;
     if (!aligned16(x) || !aligned16(w) || !aligned16(y) || (residual && (((uintptr_t)residual) & 7)) || (bias && !aligned16(bias)) || (rowbias && !aligned16(rowbias))) return -1;
     if (upsample && ((H | W) & 1)) return -1;
     const long long xbytes = ((long long)B * (H >> upsample) * (W >> upsample) * x_ld - (x_ld - C)) * 2, wbytes = (long long)N * 9 * C * 2;
     const long long rbbytes = rowbias ? ((long long)(B - 1) * rowbias_ld + N) * 4 : 0;
     if (xbytes > 0x7ffffff0ll || wbytes > 0x7ffffff0ll || rbbytes > 0x7ffffff0ll) return -1;
-    // 16 x 16 patches: the wave-specialised kernel (loaders + consumers) unless DDPM_CONV_NO_PC is set; DDPM_C3_PC_FLAGS: bit 0 = consumers at priority 1
-#ifdef PC_DEFAULT_OFF
-    static const bool use_pc = false;                       // (scripts/build_variant.sh prev: the round-3 kernel for same-process A/Bs)
-#else
-    static const bool use_pc = getenv("DDPM_CONV_NO_PC") == nullptr;
-#endif
-    static const int pc_flags = getenv("DDPM_C3_PC_FLAGS") ? atoi(getenv("DDPM_C3_PC_FLAGS")) : 0;
+    // 16 x 16 patches: the wave-specialised kernel (loaders + consumers)
     // (a residual / "+=" epilogue stays on the kernel above: its rows have to be requested a K-step ahead, into registers the
     //  wave-specialised kernel does not have — acc 128 + fragments 48 — and requested late they cost 5-12 %; the two kernels give
     //  bit-identical results, so the choice is invisible)
-    if (dry) return patch == 16 && use_pc && !residual && !accumulate ? 17 : patch;
+    const bool use_pc = patch == 16 && !residual && !accumulate;
+    if (dry) return use_pc ? 17 : patch;
     CsArgs a; memset(&a, 0, sizeof(a));
     a.x = (const bf16_t*)x; a.x_ld = x_ld; a.x_extent = (unsigned)xbytes;
     a.w = (const bf16_t*)w; a.w_extent = (unsigned)wbytes;
@@ -1172,8 +1131,7 @@ int ddpm_conv3x3_stream_launch(const void* x, long long x_ld, const void* w, voi
     a.total_tiles = B * a.tiles_y * a.tiles_x * a.tiles_n;
     a.xcd = xcd;
     a.d_tiles_n = make_fastdiv((unsigned)a.tiles_n); a.d_tpi = make_fastdiv((unsigned)(a.tiles_y * a.tiles_x)); a.d_tiles_x = make_fastdiv((unsigned)a.tiles_x);
-    static const int max_grid = getenv("DDPM_C3_GRID") ? atoi(getenv("DDPM_C3_GRID")) : 256;      // (timing experiments: > 256 = fewer tiles per block)
-    const int cus = max_grid == 256 ? ddpm_cu_budget(256) : max_grid;                             // (256 - DDPM_DP_RESERVED_CUS when a collective runs beside the step)
+    const int cus = ddpm_cu_budget(256);                   // one block per CU (256 - DDPM_DP_RESERVED_CUS when a collective runs beside the step)
     const int grid = a.total_tiles < cus ? a.total_tiles : cus;
 #define C3_LAUNCH(PATCHV)                                                                                                              \
     do {                                                                                                                               \
@@ -1185,8 +1143,7 @@ int ddpm_conv3x3_stream_launch(const void* x, long long x_ld, const void* w, voi
         }                                                                                                                              \
         hipLaunchKernelGGL(conv3x3_stream_kernel<PATCHV>, dim3(grid), dim3(512), Lds<PATCHV>::BYTES, (hipStream_t)stream, a);           \
     } while (0)
-    if (patch == 16 && use_pc && !residual && !accumulate) {
-        a.flags = pc_flags;
+    if (use_pc) {
         static DevOnce pc_attr_set;
         if (!pc_attr_set) {
             if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_pc_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, PC_BYTES) != hipSuccess) return DDPM_ERR_LAUNCH;

@@ -191,8 +191,7 @@ void conv3x3_few_in_kernel(EdgeArgs a) {
 // Launchers for ddpm_conv2d_nhwc (gemm.hip).  -1: geometry not covered (the caller falls through to the tile kernels).
 int ddpm_edgeconv_few_out_launch(const void* x, long long x_ld, const void* w, void* y, const float* bias, int B, int H, int W, int C, int N,
                                  int dry, void* stream) {
-    static const bool off = getenv("DDPM_CONV_NO_EDGE") != nullptr;
-    if (off || N < 1 || N > 16 || C % 64 || C > 512 || H % 16 || W % 16 || x_ld % 8 || !aligned16(x) || !aligned16(w)) return -1;
+    if (N < 1 || N > 16 || C % 64 || C > 512 || H % 16 || W % 16 || x_ld % 8 || !aligned16(x) || !aligned16(w)) return -1;
     const long long xbytes = ((long long)B * H * W * x_ld - (x_ld - C)) * 2;
     if (xbytes > 0x7ffffff0ll) return -1;
     const size_t lds = (size_t)FO_HALO + (size_t)9 * (C / 8) * 256;
@@ -212,8 +211,7 @@ int ddpm_edgeconv_few_out_launch(const void* x, long long x_ld, const void* w, v
 
 int ddpm_edgeconv_few_in_launch(const void* x, long long x_ld, const void* w, void* y, long long y_ld, const float* bias, int B, int H, int W,
                                 int C, int N, int dry, void* stream) {
-    static const bool off = getenv("DDPM_CONV_NO_EDGE") != nullptr;
-    if (off || C != 8 || N % 16 || N < 16 || N > 128 || H % 16 || W % 16 || x_ld % 8 || y_ld % 8 || !aligned16(x) || !aligned16(w) || !aligned16(y) ||
+    if (C != 8 || N % 16 || N < 16 || N > 128 || H % 16 || W % 16 || x_ld % 8 || y_ld % 8 || !aligned16(x) || !aligned16(w) || !aligned16(y) ||
         (bias && !aligned16(bias))) return -1;
     if (dry) return 0;
     EdgeArgs a; memset(&a, 0, sizeof(a));

@@ -229,7 +229,7 @@ void pack_weight_multi_kernel(const long long* __restrict__ descs) {
 extern "C" int ddpm_pack_weight_multi(const long long* descs, int n_tensors, int dtype, void* stream) {
     if (!descs) return DDPM_ERR_NULL;
     if (n_tensors <= 0) return DDPM_OK;                 // (kernel sizes: R <= 3 — the LDS tile holds 32 x 32 x 9 floats; the caller only has 1x1 and 3x3)
-    static const int pk_blocks = getenv("DDPM_PACK_BLOCKS") ? atoi(getenv("DDPM_PACK_BLOCKS")) : 256;    // (blocks per tensor: 64 left the 128-tile tensors two serial load -> store rounds per block)
+    constexpr int pk_blocks = 256;    // (blocks per tensor: 64 left the 128-tile tensors two serial load -> store rounds per block)
     if (dtype == DDPM_BF16) hipLaunchKernelGGL(pack_weight_multi_kernel<bf16_t>, dim3(pk_blocks, n_tensors), dim3(256), 0, (hipStream_t)stream, descs);
     else if (dtype == DDPM_F32) hipLaunchKernelGGL(pack_weight_multi_kernel<float>, dim3(pk_blocks, n_tensors), dim3(256), 0, (hipStream_t)stream, descs);
     else return DDPM_ERR_DTYPE;
@@ -685,9 +685,8 @@ __global__ __launch_bounds__(256) void atb_f32_short_kernel(const float* __restr
 extern "C" int ddpm_atb_f32(const float* a, long long lda, const float* b, long long ldb, float* c, long long ldc, int M, int N, int K, void* stream) {
     if (!a || !b || !c) return DDPM_ERR_NULL;
     if (M <= 0 || N <= 0 || K <= 0 || lda < M || ldb < N || ldc < N) return DDPM_ERR_SHAPE;
-    static const bool no_short = getenv("DDPM_ATB_NO_SHORT") != nullptr;
     const bool vec = ((M | N | (int)(lda & 3) | (int)(ldb & 3) | (int)(ldc & 3)) & 3) == 0 && aligned16(a) && aligned16(b) && aligned16(c);
-    if (K <= 128 && vec && !no_short)
+    if (K <= 128 && vec)
         hipLaunchKernelGGL(atb_f32_short_kernel, dim3((N + 63) / 64, (M + 31) / 32), dim3(256), 0, (hipStream_t)stream, a, lda, b, ldb, c, ldc, M, N, K);
     else
         hipLaunchKernelGGL(atb_f32_kernel, dim3((N + 63) / 64, (M + 63) / 64), dim3(256), 0, (hipStream_t)stream, a, lda, b, ldb, c, ldc, M, N, K);

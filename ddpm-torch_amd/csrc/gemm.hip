@@ -590,7 +590,7 @@ __device__ __forceinline__ void wait_tiles_in_flight(int tiles) {
 // on 8 different XCDs and every L2 fetches the same lines again (measured on wgrad: the LDS-DMA stream alone took as long
 // as the whole kernel).  Logical id = (id % 8) * (total / 8) + id / 8 gives each XCD a CONTIGUOUS range of logical ids, so
 // neighbours in the logical order — which share data — run on the same XCD at about the same time.  The (< 8) ids past
-// the last multiple of 8 keep their own id.  DDPM_NO_XCD_SWIZZLE=1 (host side) passes xcd = 0 and turns it off.
+// the last multiple of 8 keep their own id.  The host passes xcd = 1 (g_xcd_swizzle).
 __device__ __forceinline__ int xcd_logical_id(int id, int total, int xcd) {
     if (!xcd) return id;
     const int per = total >> 3;
@@ -712,12 +712,8 @@ void gemm_kernel(MatDesc A, MatDesc B, Epilogue ep, int M, int N, int K, int k_p
         if (NBUF == 2) {
             if (more) {       // the other buffer was last read in step s-1: every wave is past that barrier
                 const int kn = kmap(s + 1);
-#ifndef GABL_NOISSUE_A              // GABL_*: timing-only ablations (scripts/ablate_gemm.sh), never defined in product builds
                 if constexpr (DMA_A) stage_a(kn, nxt); else la.load(kn, k_end, va);
-#endif
-#ifndef GABL_NOISSUE_B
                 if constexpr (DMA_B) stage_b(kn, nxt + TILE_BYTES); else lb.load(kn, k_end, vb);
-#endif
             }
         }
         const char* ta = cur;
@@ -725,28 +721,14 @@ void gemm_kernel(MatDesc A, MatDesc B, Epilogue ep, int M, int N, int K, int k_p
 #pragma unroll
         for (int kc = 0; kc < BK / KF; ++kc) {
             u32x4 fa[MI], fb[2];
-#ifndef GABL_NOREAD
 #pragma unroll
             for (int i = 0; i < MI; ++i) fa[i] = read_frag<T, TA>(ta, wm * (32 * MI) + i * 32, kc, lane);
 #pragma unroll
             for (int j = 0; j < 2; ++j) fb[j] = read_frag<T, TB>(tb, wn * 64 + j * 32, kc, lane);
-#else
-#pragma unroll
-            for (int i = 0; i < MI; ++i) fa[i] = u32x4{(unsigned)s, (unsigned)kc, (unsigned)i, (unsigned)lane};
-#pragma unroll
-            for (int j = 0; j < 2; ++j) fb[j] = u32x4{(unsigned)s, (unsigned)kc, (unsigned)j, (unsigned)lane};
-#endif
-#ifndef GABL_NOMFMA
 #pragma unroll
             for (int i = 0; i < MI; ++i)
 #pragma unroll
                 for (int j = 0; j < 2; ++j) Mma<T>::run(fa[i], fb[j], acc[i][j]);
-#else
-#pragma unroll
-            for (int i = 0; i < MI; ++i) asm volatile("" :: "v"(fa[i]));
-#pragma unroll
-            for (int j = 0; j < 2; ++j) asm volatile("" :: "v"(fb[j]));
-#endif
             if constexpr (NBUF != 2 && DMA_A && DMA_B) {
                 // deep ring: the tile NBUF-1 steps ahead is requested in the MIDDLE of the step (its slot — the one of step
                 // s-1 — has been free since the last barrier), so the address arithmetic and the LDS-DMA issue overlap
@@ -1258,11 +1240,9 @@ extern "C" int ddpm_debug_set_halo_timing(void* p) {
 
 // Explicit instantiations: every (dtype, operand layout, ring depth, wave count) the launcher can pick.
 #define INST(T, TA, TB, NB, NWV) template __global__ void gemm_kernel<T, TA, TB, NB, NWV>(MatDesc, MatDesc, Epilogue, int, int, int, int, int, int, FastDiv);
-INST(bf16_t, false, false, 2, 4) INST(bf16_t, false, false, 2, 8) INST(bf16_t, false, false, 5, 4) INST(bf16_t, false, false, 5, 8)
-INST(bf16_t, false, true, 2, 4) INST(bf16_t, false, true, 2, 8)
-INST(bf16_t, true, false, 2, 4) INST(bf16_t, true, false, 2, 8)
-INST(bf16_t, true, true, 2, 4) INST(bf16_t, true, true, 2, 8)
-INST(float, false, false, 2, 4) INST(float, false, false, 2, 8) INST(float, false, false, 5, 4) INST(float, false, false, 5, 8)
+INST(bf16_t, false, false, 2, 8) INST(bf16_t, false, false, 5, 8)
+INST(bf16_t, false, true, 2, 8) INST(bf16_t, true, false, 2, 8) INST(bf16_t, true, true, 2, 8)
+INST(float, false, false, 2, 8) INST(float, false, false, 5, 8)
 INST(float, false, true, 2, 4) INST(float, true, false, 2, 4) INST(float, true, true, 2, 4)
 #undef INST
 template __global__ void gemm_kernel<bf16_t, true, true, 2, 8, true>(MatDesc, MatDesc, Epilogue, int, int, int, int, int, int, FastDiv);
@@ -1420,7 +1400,7 @@ template __global__ void attn_fwd_kernel<8>(MatDesc, MatDesc, MatDesc, bf16_t*, 
 // Kernel ids reported by the ddpm_*_variant queries (bench.py attributes its per-launch timings with them):
 // 1 gemm_kernel 4-wave, 2 gemm_kernel 8-wave, 3 gemm_kernel deep ring, 4 gemm64_kernel, 5 conv3x3_halo_kernel, 7 pw_conv_kernel (pointwise.hip), 8 / 10 conv3x3_stream_kernel (conv3x3.hip, 16 x 16 / 8 x 8 patches), 13 conv3x3_pc_kernel (conv3x3.hip, loader / consumer waves), 11 / 12 conv3x3_few_out / few_in (edgeconv.hip).
 // The queries run the SAME dispatch code with `dry` set (nothing is launched): the library keeps no mutable state.
-static const int g_xcd_swizzle = getenv("DDPM_NO_XCD_SWIZZLE") ? 0 : 1;
+static constexpr int g_xcd_swizzle = 1;      // the kernels' `xcd` argument: XCD-aware block order (see xcd_logical_id), always on
 static thread_local int g_variant_query = 0, g_variant_result = 0;      // scoped to ONE ddpm_*_variant call (set and cleared inside it)
 
 struct GemmArgs {          // plain-C mirror filled by the extern "C" entry points
@@ -1490,8 +1470,6 @@ static int finish_desc(MatDesc& d, int esize) {
     return DDPM_OK;
 }
 
-static bool g_use_w8 = getenv("DDPM_GEMM_W4") == nullptr;      // A/B switch for experiments: DDPM_GEMM_W4=1 forces 4-wave blocks
-
 template <typename T>
 static int launch_t(GemmArgs& g, hipStream_t st) {
     constexpr int BK = 8 * Elem<T>::VEC;
@@ -1505,9 +1483,8 @@ static int launch_t(GemmArgs& g, hipStream_t st) {
     if (g.ep.mode == 2 || g.ep.mode == 4 || g.ep.mode == 5) { g.ep.splitk_ws = nullptr; g.ep.splitk_cnt = nullptr; }
     dim3 grid(tiles_m * tiles_n, splits, g.batch);
     // small grids of k-contiguous products: 64x64 tiles put 4x as many CUs to work (see gemm64_kernel)
-    static const bool no_t64 = getenv("DDPM_GEMM_NO_T64") != nullptr;
-    static const int t64_max_tiles = getenv("DDPM_GEMM_T64_TILES") ? atoi(getenv("DDPM_GEMM_T64_TILES")) : 64;
-    if (!no_t64 && !g.A.phase && !g.A.trans && !g.B.trans && (splits == 1 || (splits == 2 && g.ep.splitk_ws && g.ep.splitk_cnt)) &&
+    constexpr int t64_max_tiles = 64;
+    if (!g.A.phase && !g.A.trans && !g.B.trans && (splits == 1 || (splits == 2 && g.ep.splitk_ws && g.ep.splitk_cnt)) &&
         (g.ep.mode == 0 || g.ep.mode == 1) && (long long)tiles_m * tiles_n * g.batch <= t64_max_tiles) {
         const int t64n = (g.N + T64 - 1) / T64;
         // two K runs per tile when the caller offers the workspace (splits == 2), the tiles alone leave half the CUs idle and every
@@ -1518,7 +1495,7 @@ static int launch_t(GemmArgs& g, hipStream_t st) {
         int sp64 = 1;
         if (splits == 2) {
             const long long tiles64 = (long long)((g.M + T64 - 1) / T64) * t64n * g.batch;
-            static const int max_runs = getenv("DDPM_SPLITK64_RUNS") ? atoi(getenv("DDPM_SPLITK64_RUNS")) : 8;
+            constexpr int max_runs = 8;
             while (sp64 * 2 <= max_runs && tiles64 * sp64 * 2 <= 256 && groups64 / (sp64 * 2) >= 4) sp64 *= 2;
         }
         const dim3 grid64(((g.M + T64 - 1) / T64) * t64n, sp64, g.batch);
@@ -1560,20 +1537,17 @@ static int launch_t(GemmArgs& g, hipStream_t st) {
     } while (0)
     // 8-wave blocks whenever both operands take the DMA path (all bf16 products, fp32 with k-contiguous operands)
     constexpr bool BF = sizeof(T) == 2;
-    const bool w8 = g_use_w8;
+    constexpr int NWT = BF ? 8 : 4;                           // wave count with a k-slow (transposed) operand
     if (!g.A.trans && !g.B.trans) {
-        if (deep && w8) LAUNCH(false, false, 5, 8, lds3);
-        else if (deep) LAUNCH(false, false, 5, 4, lds3);
-        else if (w8) LAUNCH(false, false, 2, 8, lds2);
-        else LAUNCH(false, false, 2, 4, lds2);
+        if (deep) LAUNCH(false, false, 5, 8, lds3);
+        else LAUNCH(false, false, 2, 8, lds2);
     } else if (!g.A.trans && g.B.trans) {
-        if constexpr (BF) { if (w8) LAUNCH(false, true, 2, 8, lds2); else LAUNCH(false, true, 2, 4, lds2); } else LAUNCH(false, true, 2, 4, lds2);
+        LAUNCH(false, true, 2, NWT, lds2);
     } else if (g.A.trans && !g.B.trans) {
-        if constexpr (BF) { if (w8) LAUNCH(true, false, 2, 8, lds2); else LAUNCH(true, false, 2, 4, lds2); } else LAUNCH(true, false, 2, 4, lds2);
+        LAUNCH(true, false, 2, NWT, lds2);
     } else {
         if constexpr (BF) {
-            static const bool no_scat = getenv("DDPM_GEMM_NO_SCAT") != nullptr;
-            if (w8 && g.ep.mode >= 2 && !no_scat) {          // weight gradients: the scatter-only instantiation
+            if (g.ep.mode >= 2) {          // weight gradients: the scatter-only instantiation
                 g.variant = 2;
                 if (g.dry) return DDPM_OK;
                 static DevOnce attr_set;
@@ -1583,8 +1557,7 @@ static int launch_t(GemmArgs& g, hipStream_t st) {
                     attr_set = true;
                 }
                 hipLaunchKernelGGL((gemm_kernel<T, true, true, 2, 8, true>), grid, dim3(512), lds2, st, g.A, g.B, g.ep, g.M, g.N, g.K, kps, tiles_n, g_xcd_swizzle, make_fastdiv((unsigned)tiles_n));
-            } else if (w8) LAUNCH(true, true, 2, 8, lds2);
-            else LAUNCH(true, true, 2, 4, lds2);
+            } else LAUNCH(true, true, 2, 8, lds2);
         } else LAUNCH(true, true, 2, 4, lds2);
     }
 #undef LAUNCH
@@ -1665,9 +1638,8 @@ extern "C" int ddpm_conv2d_nhwc(const void* x, long long x_ld, const void* w, vo
     g.splits = splits; g.ep.splitk_ws = splitk_ws; g.ep.splitk_cnt = splitk_cnt;
     // data gradient of a stride-2 conv (dilate): parity-phase form when every 128-row tile can stay inside one phase — 9/4 taps per output
     // pixel on average instead of 9 over a three-quarters-zero operand.  One K run (the reduction is short), the caller's split offer unused.
-    static const bool no_phase = getenv("DDPM_NO_PHASE_DGRAD") != nullptr;
     const int bk = dtype == DDPM_BF16 ? 64 : 32;
-    if (!no_phase && dilate && R == 3 && S == 3 && stride == 1 && !(Ho & 1) && !(Wo & 1) && C % bk == 0 && (out_mode == 0 || out_mode == 1) &&
+    if (dilate && R == 3 && S == 3 && stride == 1 && !(Ho & 1) && !(Wo & 1) && C % bk == 0 && (out_mode == 0 || out_mode == 1) &&
         ((long long)B * (Ho / 2) * (Wo / 2)) % TILE == 0) {
         MatDesc& d = g.A;
         d.phase = 1; d.Hh = Ho / 2; d.Wh = Wo / 2; d.Mp = B * d.Hh * d.Wh; d.spt = C / bk;
@@ -1692,9 +1664,8 @@ extern "C" int ddpm_conv2d_nhwc(const void* x, long long x_ld, const void* w, vo
         if (rc >= 0) { if (g.dry) { g_variant_result = rc == 8 ? 10 : (rc == 17 ? 13 : 8); return DDPM_OK; } return rc; }
     }
     // ... or the one-tile-per-block form (what conv3x3.hip does not cover)
-    static const bool no_halo = getenv("DDPM_CONV_NO_HALO") != nullptr;
-    static const int halo_min_c = getenv("DDPM_CONV_HALO_MINC") ? atoi(getenv("DDPM_CONV_HALO_MINC")) : 64;
-    if (!no_halo && C >= halo_min_c && dtype == DDPM_BF16 && R == 3 && S == 3 && stride == 1 && pad_t == 1 && pad_l == 1 && !upsample && !dilate &&
+    constexpr int halo_min_c = 64;
+    if (C >= halo_min_c && dtype == DDPM_BF16 && R == 3 && S == 3 && stride == 1 && pad_t == 1 && pad_l == 1 && !upsample && !dilate &&
         out_mode == 0 && splits <= 1 && C % 64 == 0 && Ho == H && Wo == W && g.M >= 16384 && aligned16(x) && aligned16(w) && x_ld % 8 == 0) {
         set_vec_ok(g, 2);
         const int rc = conv3x3_halo_launch(g, x, x_ld, w, B, H, W, C, N, (hipStream_t)stream);

@@ -1414,12 +1414,10 @@ void gn_lds_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, GnShape s, Gn
     GN_STAMP(6); GN_STAMP(7);
 }
 
-constexpr int GN_FUSED_SLICE = 64 * 1024;     // LDS bytes of activations per block: two blocks per CU
-
-// picks the group chunk; false when no chunk of this geometry fits (falls back to the two-launch path)
-static const long long gn_fused_max_bytes = getenv("DDPM_GN_FUSED_MAX_KB") ? atoll(getenv("DDPM_GN_FUSED_MAX_KB")) * 1024 : GN_FUSED_SLICE;
-// (128 KiB slices = 512-thread blocks work and make the 32^2 x 128-channel forward 10 % faster in isolation, but the training
-//  step measured 0.25 ms slower with them — A/B in one session, scripts/step_jitter.py — so the default stays at 64 KiB.)
+// register-resident kernels: bytes of activations per 256-thread block (16 vectors per thread), two blocks per CU
+// (128 KiB slices = 512-thread blocks made the 32^2 x 128-channel forward 10 % faster in isolation, but the training
+//  step measured 0.25 ms slower with them — A/B in one session, scripts/step_jitter.py — so the slice stays at 64 KiB.)
+constexpr int GN_FUSED_SLICE = 64 * 1024;
 
 // LDS-staged kernels: largest group chunk whose x slice fits 64 KiB with <= 8 vectors per thread; prefers >= 512 blocks
 // (two per CU) as long as a pixel segment stays >= 128 bytes
@@ -1450,11 +1448,11 @@ static bool gn_lds_plan(const GnShape& s, int esize, GnFused& f, size_t& lds_byt
     if (f.nv < 2 || f.seg_vecs > 32) return false;
     const int nvt = f.nv <= 1 ? 1 : f.nv <= 2 ? 2 : f.nv <= 4 ? 4 : 8;
     lds_bytes = gn_lds_bytes(nvt, 512, f.seg_ch);
-    static const bool no_remap = getenv("DDPM_GN_NO_XCD_REMAP") != nullptr;
-    f.xcd_remap = no_remap ? 0 : 1;
+    f.xcd_remap = 1;
     return lds_bytes <= 160 * 1024 && (long long)s.B * s.HW * s.C < (1ll << 32);
 }
 
+// picks the group chunk; false when no chunk of this geometry fits (falls back to the two-launch path)
 static bool gn_fused_plan(const GnShape& s, int esize, GnFused& f, size_t& lds_bytes) {
     const int vec = 16 / esize;
     int best = 0;
@@ -1462,7 +1460,7 @@ static bool gn_fused_plan(const GnShape& s, int esize, GnFused& f, size_t& lds_b
         if (s.G % gpb) continue;
         const int seg_ch = gpb * s.cpg;
         if (seg_ch % vec) continue;
-        if ((long long)s.HW * seg_ch * esize > gn_fused_max_bytes) break;       // 512 threads x 16 vectors at most
+        if ((long long)s.HW * seg_ch * esize > GN_FUSED_SLICE) break;           // 256 threads x 16 vectors at most
         if (seg_ch / vec > 256) break;
         best = gpb;
     }
@@ -1474,7 +1472,7 @@ static bool gn_fused_plan(const GnShape& s, int esize, GnFused& f, size_t& lds_b
     // XCDs) fetch every line twice and the two streaming launches win (measured: 32^2 x 128 ch bf16 in 64-byte segments 26
     // vs 25 us, 384 ch 106 vs 57 us; at >= 128 B the single launch wins: 16^2 x 256 ch 12.7 vs 16.8 us, 8^2 6.9 vs 11.4 us)
     if (f.seg_ch * esize < 128) return false;
-    f.nt = (long long)s.HW * f.seg_ch * esize > GN_FUSED_SLICE ? 512 : 256;
+    f.nt = 256;
     f.nta = (f.nt / f.seg_vecs) * f.seg_vecs; f.rows_per_iter = f.nta / f.seg_vecs;
     f.nv = (s.HW + f.rows_per_iter - 1) / f.rows_per_iter;
     if (f.nv > 16) return false;
@@ -1652,15 +1650,12 @@ extern "C" int ddpm_groupnorm_silu_fwd(const void* x, long long x_ld, void* y, l
     GnApply a = make_apply(gamma, beta, eps, silu, drop_p, seed, stats, seed_dev);
     hipStream_t st = (hipStream_t)stream;
     GnFused f; size_t lds = 0;
-    static const bool no_fused = getenv("DDPM_GN_NO_FUSED") != nullptr;
-    static const bool no_lds = getenv("DDPM_GN_NO_LDS_FWD") != nullptr;
     GnFused fl; size_t lds_l = 0;
-    const bool reg_ok = !no_fused && gn_fused_plan(s, es, f, lds);
+    const bool reg_ok = gn_fused_plan(s, es, f, lds);
     // small slices (<= 2 vectors per thread of a 256-thread block): the staged kernel in its 256-thread form
-    static const bool small_reg = getenv("DDPM_GN_SMALL_REG") != nullptr;
-    const bool small = reg_ok && f.nv <= 2 && f.nt == 256 && f.seg_vecs <= 32 && !small_reg && !no_lds;
+    const bool small = reg_ok && f.nv <= 2 && f.seg_vecs <= 32;
     if (small) { fl = f; fl.xcd_remap = 0; lds_l = gn_lds_bytes(f.nv <= 1 ? 1 : 2, 256, f.seg_ch); }
-    if (small || (!no_lds && !(reg_ok && f.nv <= 2) && gn_lds_plan(s, es, fl, lds_l))) {        // x staged in LDS: single launch, 1 read + 1 write of HBM
+    if (small || (!(reg_ok && f.nv <= 2) && gn_lds_plan(s, es, fl, lds_l))) {        // x staged in LDS: single launch, 1 read + 1 write of HBM
         const dim3 fgrid(G / fl.GPB, B);
 #define GN_LF(T, NV, NT, FLV) do { static DevOnce attr; if (!attr) { if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gn_lds_fwd_kernel<T, NV, NT, FLV>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return DDPM_ERR_LAUNCH; attr = true; } \
         hipLaunchKernelGGL((gn_lds_fwd_kernel<T, NV, NT, FLV>), fgrid, dim3(NT), lds_l, st, (const T*)x, (T*)y, s, fl, a); } while (0)
@@ -1675,8 +1670,7 @@ extern "C" int ddpm_groupnorm_silu_fwd(const void* x, long long x_ld, void* y, l
     }
     if (reg_ok) {      // register-resident single launch (1 read + 1 write of HBM)
         const dim3 fgrid(G / f.GPB, B);
-#define GN_FWD(T, NV) do { if (f.nt == 512) hipLaunchKernelGGL((gn_reg_fwd_kernel<T, NV, 512>), fgrid, dim3(512), lds, st, (const T*)x, (T*)y, s, f, a); \
-                           else hipLaunchKernelGGL((gn_reg_fwd_kernel<T, NV, 256>), fgrid, dim3(256), lds, st, (const T*)x, (T*)y, s, f, a); } while (0)
+#define GN_FWD(T, NV) hipLaunchKernelGGL((gn_reg_fwd_kernel<T, NV, 256>), fgrid, dim3(256), lds, st, (const T*)x, (T*)y, s, f, a)
 #define GN_FWD_NV(T) do { if (f.nv <= 1) GN_FWD(T, 1); else if (f.nv <= 2) GN_FWD(T, 2); else if (f.nv <= 4) GN_FWD(T, 4); else if (f.nv <= 8) GN_FWD(T, 8); else GN_FWD(T, 16); } while (0)
         if (dtype == DDPM_BF16) GN_FWD_NV(bf16_t); else GN_FWD_NV(float);
 #undef GN_FWD_NV
@@ -1712,19 +1706,16 @@ extern "C" int ddpm_groupnorm_silu_bwd(const void* x, long long x_ld, const void
     GnApply a = make_apply(gamma, beta, 0.f, silu, drop_p, seed, nullptr, seed_dev);
     hipStream_t st = (hipStream_t)stream;
     GnFused f; size_t lds = 0;
-    static const bool no_fused = getenv("DDPM_GN_NO_FUSED") != nullptr || getenv("DDPM_GN_NO_FUSED_BWD") != nullptr;
     // register-resident single launch (x, dy read once, dx written once) — for the small slices only: with x AND dy held in
     // registers the kernel needs > 128 VGPRs from 8 vectors per thread on and then cannot share a CU with the weight-gradient
     // blocks of the side stream; measured end to end (6 alternating pairs) the two streaming launches are 0.13 ms per step
     // faster on the 16^2 / 32^2 tensors, while the 4^2 / 8^2 tensors (<= 2 vectors per thread) keep the single launch.
-    static const bool no_lds = getenv("DDPM_GN_NO_LDS_BWD") != nullptr;
     // 1) slices too big for two register vectors per thread: (x, dy) staged in LDS, one launch, one HBM read of each input
     GnFused fl; size_t lds_l = 0;
-    const bool small = !no_fused && gn_fused_plan(s, es, f, lds) && f.nv <= 2;
-    static const bool small_reg = getenv("DDPM_GN_SMALL_REG") != nullptr;
-    const bool small_lds = small && f.nt == 256 && f.seg_vecs <= 32 && !small_reg && !no_lds;
+    const bool small = gn_fused_plan(s, es, f, lds) && f.nv <= 2;
+    const bool small_lds = small && f.seg_vecs <= 32;
     if (small_lds) { fl = f; fl.xcd_remap = 0; lds_l = gn_lds_bytes(f.nv <= 1 ? 1 : 2, 256, f.seg_ch); }
-    if (small_lds || (!small && !no_lds && gn_lds_plan(s, es, fl, lds_l))) {
+    if (small_lds || (!small && gn_lds_plan(s, es, fl, lds_l))) {
         const dim3 fgrid(G / fl.GPB, B);
 #define GN_LDS(K, NT, ...) do { static DevOnce attr; if (!attr) { if (hipFuncSetAttribute(reinterpret_cast<const void*>(&K<__VA_ARGS__>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return DDPM_ERR_LAUNCH; attr = true; } \
         hipLaunchKernelGGL((K<__VA_ARGS__>), fgrid, dim3(NT), lds_l, st, (const T_*)x, (const T_*)dy, (T_*)dx, s, fl, dy_ld, dx_ld, stats, dgamma, dbeta, a, accumulate, dx_colsum, colsum_ld, (const T_*)add, add_ld); } while (0)
@@ -1758,9 +1749,8 @@ extern "C" int ddpm_groupnorm_silu_bwd(const void* x, long long x_ld, const void
     } colsum_after{dx, dx_ld, dx_colsum, colsum_ld, B, HW, C, dtype, stream};
     if (small) {
         const dim3 fgrid(G / f.GPB, B);
-#define GN_BWD(T, NV) do { if (f.nt == 512) hipLaunchKernelGGL((gn_reg_bwd_kernel<T, NV, 512>), fgrid, dim3(512), lds, st, (const T*)x, (const T*)dy, (T*)dx, s, f, dy_ld, dx_ld, stats, dgamma, dbeta, a, accumulate, (const T*)add, add_ld, dx_colsum, colsum_ld); \
-                           else hipLaunchKernelGGL((gn_reg_bwd_kernel<T, NV, 256>), fgrid, dim3(256), lds, st, (const T*)x, (const T*)dy, (T*)dx, s, f, dy_ld, dx_ld, stats, dgamma, dbeta, a, accumulate, (const T*)add, add_ld, dx_colsum, colsum_ld); } while (0)
-#define GN_BWD_NV(T) do { if (f.nv <= 1) GN_BWD(T, 1); else if (f.nv <= 2) GN_BWD(T, 2); else if (f.nv <= 4) GN_BWD(T, 4); else if (f.nv <= 8) GN_BWD(T, 8); else GN_BWD(T, 16); } while (0)
+#define GN_BWD(T, NV) hipLaunchKernelGGL((gn_reg_bwd_kernel<T, NV, 256>), fgrid, dim3(256), lds, st, (const T*)x, (const T*)dy, (T*)dx, s, f, dy_ld, dx_ld, stats, dgamma, dbeta, a, accumulate, (const T*)add, add_ld, dx_colsum, colsum_ld)
+#define GN_BWD_NV(T) do { if (f.nv <= 1) GN_BWD(T, 1); else GN_BWD(T, 2); } while (0)      // (small: <= 2 vectors per thread)
         if (dtype == DDPM_BF16) GN_BWD_NV(bf16_t); else GN_BWD_NV(float);
 #undef GN_BWD_NV
 #undef GN_BWD

@@ -34,7 +34,6 @@ struct PwArgs {
     const float* bias;
     const bf16_t* res; long long res_ld;
     int accumulate;
-    int ablate;                                             // timing experiments (DDPM_PW_ABLATE): 1 no stores, 2 no MFMA
     int M, N, K, tiles_m, tiles_n, ksteps;
     int spread;                                             // 1: blocks walk (pixel tile, channel tile) pairs (fewer pixel tiles than CUs)
 };
@@ -185,8 +184,7 @@ void pw_conv_kernel(PwArgs a) {
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int j = 0; j < MJ; ++j)
-                    if (!(a.ablate & 2))
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fw[i]), __builtin_bit_cast(bf16x8, fx[j]), acc[i][j], 0, 0, 0);
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fw[i]), __builtin_bit_cast(bf16x8, fx[j]), acc[i][j], 0, 0, 0);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // this wave's LDS reads of stage q are complete before it reaches the next barrier
         if (pre) {
@@ -238,7 +236,7 @@ void pw_conv_kernel(PwArgs a) {
                         const u32x2 sx = __builtin_amdgcn_permlane32_swap(pk[2 * q2].x, pk[2 * q2 + 1].x, false, false);
                         const u32x2 sy = __builtin_amdgcn_permlane32_swap(pk[2 * q2].y, pk[2 * q2 + 1].y, false, false);
                         const int n = n0 + i * 32 + 16 * q2 + 8 * (lane >> 5);
-                        if (p < a.M && n < a.N && !(a.ablate & 1)) {
+                        if (p < a.M && n < a.N) {
                             u32x4 o; o.x = sx.x; o.y = sy.x; o.z = sx.y; o.w = sy.y;
                             *reinterpret_cast<u32x4*>(a.out + (long long)p * a.out_ld + n) = o;
                         }
@@ -250,7 +248,7 @@ void pw_conv_kernel(PwArgs a) {
 #pragma unroll
                 for (int j = 0; j < MJ; ++j) acc[i][j] = (f32x16)(0.f);
             // (full 64-channel range stored by this wave -> exactly ST stores; epilogues at least RING - 1 stages apart -> one window at a time)
-            st_window = (a.ksteps >= RING - 1 && c_nt * TN + wn * 64 + 64 <= a.N && !(a.ablate & 1)) ? RING - 1 : 0;
+            st_window = (a.ksteps >= RING - 1 && c_nt * TN + wn * 64 + 64 <= a.N) ? RING - 1 : 0;
             c_ks = 0; ++c_tile;
             if (a.spread) { c_vt += gridDim.x; c_mt = c_vt / a.tiles_n; c_nt = c_vt - c_mt * a.tiles_n; }
             else if (++c_nt == a.tiles_n) { c_nt = 0; c_mt += gridDim.x; }
@@ -264,9 +262,8 @@ void pw_conv_kernel(PwArgs a) {
 // Returns -1 when the geometry is not covered (the caller keeps the generic kernel), a status code otherwise.  dry: decide only.
 int ddpm_pointwise_launch(const void* x, long long x_ld, const void* w, void* y, long long y_ld, const float* bias, const void* residual,
                           long long res_ld, int accumulate, int M, int N, int K, int dry, void* stream) {
-    static const bool off = getenv("DDPM_CONV_NO_POINTWISE") != nullptr;
-    static const int min_m = getenv("DDPM_POINTWISE_MIN_M") ? atoi(getenv("DDPM_POINTWISE_MIN_M")) : 8192;      // below: too few tiles even as (pixel, channel) pairs (the 64x64-tile kernel with its split-K serves those)
-    if (off || M < min_m || K % 64 || N % 8 || x_ld % 8 || y_ld % 8 || (residual && res_ld % 4)) return -1;
+    constexpr int min_m = 8192;      // below: too few tiles even as (pixel, channel) pairs (the 64x64-tile kernel with its split-K serves those)
+    if (M < min_m || K % 64 || N % 8 || x_ld % 8 || y_ld % 8 || (residual && res_ld % 4)) return -1;
     if (!aligned16(x) || !aligned16(w) || !aligned16(y) || (residual && (((uintptr_t)residual) & 7)) || (bias && !aligned16(bias))) return -1;
     if ((long long)M * x_ld * 2 > 0x7ffffff0ll || (long long)N * K * 2 > 0x7ffffff0ll) return -1;
     if (dry) return DDPM_OK;
@@ -274,19 +271,17 @@ int ddpm_pointwise_launch(const void* x, long long x_ld, const void* w, void* y,
     a.x = (const bf16_t*)x; a.x_ld = x_ld; a.x_extent = (unsigned)(((long long)(M - 1) * x_ld + K) * 2);
     a.w = (const bf16_t*)w; a.w_extent = (unsigned)((long long)N * K * 2);
     a.out = (bf16_t*)y; a.out_ld = y_ld; a.bias = bias; a.res = (const bf16_t*)residual; a.res_ld = res_ld; a.accumulate = accumulate;
-    { const char* e = getenv("DDPM_PW_ABLATE"); a.ablate = e ? atoi(e) : 0; }
     a.M = M; a.N = N; a.K = K; a.ksteps = K / 64;
     hipStream_t st = (hipStream_t)stream;
     // Tile choice.  N >= 256 (the attention projections, the 2C-wide skips and their data gradients): 128 pixels x 256 channels — the
     // activation stage is fetched once for twice the channels, half as many stage hand-overs (barrier + DMA wait) per FLOP and one LDS
     // fragment read per MFMA instead of 1.5: the 16 x 16 layers went from 19.9 / 46.4 / 50.7 us to 10.7 / 19.6 / 23.9 us (256 -> 256,
-    // 768 -> 256, 256 -> 768; isolated bursts, scripts/pw_ab.py), the step from 10.10 to 9.60 ms on the same box.  N = 384 takes two such
+    // 768 -> 256, 256 -> 768; isolated bursts, profiles/r04_pw_tiles.txt), the step from 10.10 to 9.60 ms on the same box.  N = 384 takes two such
     // tiles with the second half empty (16.4 vs 28.3 us at 16 x 16).  Otherwise 128-channel tiles: 256 pixels when they give every CU
     // at least one, else 128 pixels.  Layers with fewer 128-pixel tiles than CUs (the 8 x 8 level, M = 8192) spread (pixel, channel)
     // tile pairs over the blocks: 11.9 / 9.1 us against 13.1 / 11.3 us on the generic tile kernel (512 -> 256, 256 -> 512).
-    static const bool no_wide = getenv("DDPM_PW_NO_WIDE") != nullptr;        // A/B switch: the round-3 tiling
     const bool small_m = (M + 127) / 128 < 256;
-    const bool wide = !no_wide && N >= 256;
+    const bool wide = N >= 256;
     const bool big = (M + 255) / 256 >= 256;
     a.spread = small_m ? 1 : 0;
 #define PW_LAUNCH(TM, TN, RINGV)                                                                                                  \

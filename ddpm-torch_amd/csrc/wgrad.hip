@@ -689,9 +689,8 @@ struct Plan { int ok, stage_px, PW, PH, NB, stages, splits, per, tiles_n, tiles_
 static Plan make_plan(int B, int H, int W, int C, int N, int want_splits) {
     Plan p; memset(&p, 0, sizeof(p));
     if (C % TC || N % 8 || H <= 0 || W <= 0) return p;
-    // the wave-specialised kernel (64-wide in-channel tiles): DDPM_WGRAD3_NO_WS=1 keeps every geometry on the kernel above
-    static const bool no_ws = getenv("DDPM_WGRAD3_NO_WS") != nullptr;
-    p.ws = !no_ws && W >= 16 && W % 16 == 0 && H % 16 == 0 && C % WS_TC == 0 && N % TN == 0;
+    // the wave-specialised kernel (64-wide in-channel tiles) where the geometry allows, else the kernel above
+    p.ws = W >= 16 && W % 16 == 0 && H % 16 == 0 && C % WS_TC == 0 && N % TN == 0;
     if (W >= 16) { if (W % 16 || H % 16) return p; p.stage_px = 256; p.PW = 16; p.PH = 16; p.NB = 1; }
     else if (W == 8 && H == 8) { p.stage_px = 128; p.PW = 8; p.PH = 8; p.NB = 2; }
     else if (W == 4 && H == 4) { p.stage_px = 128; p.PW = 4; p.PH = 4; p.NB = 8; }
@@ -709,8 +708,7 @@ static Plan make_plan(int B, int H, int W, int C, int N, int want_splits) {
         // 96 -> 10.3, 64 -> 11.0 ms; CelebA-HQ B = 2: 12.36 -> 11.97 ms), which also halves the slab copies ddpm_wgrad_reduce sums.
         // Keep >= 4 stages per slice so that the block's prologue / final reduction amortise.
         static const int cu_budget = getenv("DDPM_WGRAD3_CUS") ? atoi(getenv("DDPM_WGRAD3_CUS")) : 128;
-        static const int cu_budget_small = getenv("DDPM_WGRAD3_CUS_SMALL") ? atoi(getenv("DDPM_WGRAD3_CUS_SMALL")) : cu_budget;   // the 8 x 8 / 4 x 4 levels
-        splits = ddpm_cu_budget(W <= 8 ? cu_budget_small : cu_budget) / tiles;
+        splits = ddpm_cu_budget(cu_budget) / tiles;            // (the 8 x 8 / 4 x 4 levels share the budget)
         const int cap = p.stages >= 4 ? p.stages / 4 : 1;
         if (splits > cap) splits = cap;
         if (splits < 1) splits = 1;

@@ -167,7 +167,7 @@ static bool make_plan(int P, int C, int N, Plan& p) {
     const int tiles = p.tiles_c * p.tiles_n;
     // half the chip, like the 3x3 weight-gradient kernel: a launch on every CU makes the main stream's next kernel wait for a whole
     // block of this one (round 5, under the launch-plan step: 256 -> 9.81, 192 -> 9.66, 128 -> 9.65 / 9.73, 96 -> 9.70, 64 -> 9.86 ms per step)
-    static const int cu_budget = getenv("DDPM_WGRAD1_CUS") ? atoi(getenv("DDPM_WGRAD1_CUS")) : 128;
+    constexpr int cu_budget = 128;
     int splits = ddpm_cu_budget(cu_budget) / tiles;             // one block per CU
     if (splits < 1) splits = 1;
     const int max_splits = p.ksteps / 4 > 0 ? p.ksteps / 4 : 1; // a slice keeps >= 4 K-steps
@@ -181,12 +181,11 @@ static bool make_plan(int P, int C, int N, Plan& p) {
 
 // Slab copies ddpm_conv1x1_wgrad_nhwc writes for this geometry (0: geometry not covered — the caller keeps ddpm_conv2d_wgrad_nhwc).
 extern "C" int ddpm_conv1x1_wgrad_splits(int P, int C, int N) {
-    static const bool off = getenv("DDPM_NO_WGRAD1X1") != nullptr;
     // (round 5, under the launch-plan step: the 8 x 8 and 4 x 4 levels' 1x1 weight gradients — P = 8192 / 2048 — on this kernel too:
     //  16384 -> 9.41, 8192 -> 9.39, 2048 -> 9.34 ms per step; the generic kernel's 512-block grids held the main stream up more)
-    static const int min_p = getenv("DDPM_WGRAD1_MIN_P") ? atoi(getenv("DDPM_WGRAD1_MIN_P")) : 2048;
+    constexpr int min_p = 2048;
     Plan p;
-    if (off || P < min_p || !make_plan(P, C, N, p)) return 0;
+    if (P < min_p || !make_plan(P, C, N, p)) return 0;
     return p.splits;
 }
 

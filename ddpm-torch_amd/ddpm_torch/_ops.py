@@ -83,7 +83,6 @@ def conv2d(x, w_ptr, y_ptr, y_ld, N, R, S, Ho, Wo, stride=1, pad_t=0, pad_l=0, u
         lambda: _hip.lib().ddpm_conv2d_variant(x.ld, y_ld, x.B, x.H, x.W, x.C, Ho, Wo, N, R, S, stride, pad_t, pad_l, upsample, dilate, out_mode, splits, x.dtype, (1 if res_ptr else 0) | (2 if accumulate else 0)))
 
 
-_USE_SPLITK = bool(os.environ.get("DDPM_SPLITK"))
 _SPLITK64 = os.environ.get("DDPM_SPLITK64", "1") != "0"
 
 
@@ -93,40 +92,29 @@ class SplitK:
     engine issues every conv forward / data gradient on the main stream).
     Default: TWO K runs per tile for the layers whose 64x64-tile grid has <= 128 blocks (the 4x4 level): the loop of that
     kernel is bound by what one CU can move into its LDS, so the second half of the chip halves it (scripts/g64_timeline.py;
-    DDPM_SPLITK64=0 switches it off).  DDPM_SPLITK=1 additionally brings back the old 128x128-tile split-K for comparisons."""
-    TARGET_BLOCKS = 128
+    DDPM_SPLITK64=0 switches it off)."""
 
     def __init__(self, device):
         self.device = device
         self.ws = None
         self.cnt = None
 
-    # every plan of the small-grid kernel fits (2 / 4 / 8 runs, tiles x runs <= 256 slabs of 64 x 64): <= 128 tiles x 2 runs x one 128x128 fp32 tile.  Reserved in one piece at first use so that the
-    # pointers a captured graph holds stay valid; a buffer that does get outgrown (DDPM_SPLITK=1 only) is retired, never freed.
+    # every plan fits (<= 128 tiles of 64 x 64, so <= 128 of 128 x 128 too): 128 tiles x 2 runs x one 128x128 fp32 tile, 128 counters.
+    # Reserved in one piece at first use so that the pointers a captured graph holds stay valid.
     FLOATS64 = 128 * 2 * 16384
 
-    def _reserve(self, floats, tiles):
-        if self.ws is None or self.ws.numel() < floats:
-            self._retired = getattr(self, "_retired", []) + [self.ws]
-            self.ws = torch.empty(max(floats, self.FLOATS64), dtype=torch.float32, device=self.device)
-        if self.cnt is None or self.cnt.numel() < tiles:
-            self._retired = getattr(self, "_retired", []) + [self.cnt]
-            self.cnt = torch.zeros(max(tiles, 1024), dtype=torch.int32, device=self.device)
+    def _reserve(self):
+        if self.ws is None:
+            self.ws = torch.empty(self.FLOATS64, dtype=torch.float32, device=self.device)
+            self.cnt = torch.zeros(1024, dtype=torch.int32, device=self.device)
         return self.ws.data_ptr(), self.cnt.data_ptr()
 
     def plan(self, M, N, K, dtype):
         ksteps = -(-K // (64 if dtype == _hip.BF16 else 32))
-        tiles = -(-M // 128) * -(-N // 128)
         tiles64 = -(-M // 64) * -(-N // 64)
         if _SPLITK64 and tiles64 <= 128 and ksteps >= 16:
-            # sized for either kernel the library may pick for these arguments (64x64 or 128x128 tiles)
-            return (2,) + self._reserve(max(tiles64 * 2 * 4096, tiles * 2 * 16384), max(tiles64, tiles))
-        if not _USE_SPLITK:
-            return 1, 0, 0
-        splits = min(self.TARGET_BLOCKS // tiles, ksteps // 8)
-        if splits < 2:
-            return 1, 0, 0
-        return (splits,) + self._reserve(tiles * splits * 16384, tiles)
+            return (2,) + self._reserve()          # (the workspace serves either kernel the library may pick: 64x64 or 128x128 tiles)
+        return 1, 0, 0
 
 
 def conv2d_wgrad(dy, x, dw_ptr, Creal, Nreal, R, S, stride=1, pad_t=0, pad_l=0, upsample=0, splits=1, slab_stride=0):

@@ -242,32 +242,21 @@ class _ConvW:
         self.up = False                # conv behind a nearest-2x upsample: its dgrad pack is the 4x4 / stride-2 effective kernel
 
 
-_WGRAD_TARGET_BLOCKS = int(os.environ.get("DDPM_WGRAD_BLOCKS", "512"))
-_FUSED_ATTENTION = os.environ.get("DDPM_FUSED_ATTENTION", "1") != "0"
-_FLASH_ATTENTION = os.environ.get("DDPM_FLASH_ATTENTION", "1") != "0"     # 0: the five-product path with L x L tensors (A/B only)
-_FLASH_INFERENCE = os.environ.get("DDPM_FLASH_INFERENCE", "1") != "0"     # inference attention through the training forward kernel (no lse stored)
-_UP_DGRAD_FUSED = os.environ.get("DDPM_UP_DGRAD_FUSED", "1") != "0"    # upsample convs: dgrad as one 4x4 stride-2 conv
+_WGRAD_TARGET_BLOCKS = 512                                         # generic weight-gradient GEMM: tiles x splits (see _Engine._splits)
+_WGRAD_MINSTEPS = 20                                               # ... and the K-steps a split keeps
 _SIDE_STREAM = os.environ.get("DDPM_SIDE_STREAM", "1") != "0"      # weight / bias gradients on a second HIP stream
-_SIDE_PRIORITY = int(os.environ.get("DDPM_SIDE_PRIORITY", "0"))    # its priority (lower number = dispatched first; clamped to the device's range)
-_WGRAD_MINSTEPS = int(os.environ.get("DDPM_WGRAD_MINSTEPS", "20"))
 _WGRAD_SLABS = os.environ.get("DDPM_WGRAD_SLABS", "0") != "0"      # deterministic slab reduction instead of atomics
-_WGRAD3 = os.environ.get("DDPM_WGRAD3", "1") != "0"                # patch-stationary kernel for the 3x3 / stride-1 weight gradients
-_WGRAD3_UP = os.environ.get("DDPM_WGRAD3_UP", "1") != "0"          # ... also for the Upsample blocks' conv (nearest-2x gather folded into the halo loads)
-_SLAB_FLUSH_ROWS = int(os.environ.get("DDPM_SLAB_FLUSH_ROWS", "3"))   # slab reductions queued on the side stream every so many rows
+_WGRAD3 = os.environ.get("DDPM_WGRAD3", "1") != "0"                # patch-stationary kernel for the 3x3 / stride-1 weight gradients (Upsample blocks' conv included)
+_SLAB_FLUSH_ROWS = 3                                               # slab reductions queued on the side stream every so many rows
 # The backward ends at the network's first layers, and the step ends when the side stream has drained: the weight gradients of the LAST
 # residual blocks of the backward (the first in execution order) find the main stream with little left to run — they take the whole chip
 # instead of the usual half (twice the K slices).  Same-box sweeps on two boxes (profiles/r05_tail_boost_sweep.txt): 0 / 4 / 8 blocks ->
-# 9.87 / 9.81 / 9.83 ms per step (every one of nine 0-vs-4 pairs in favour of 4); 0 = off.
-_TAIL_BLOCKS = int(os.environ.get("DDPM_WGRAD3_TAIL_BLOCKS", "4"))
-_TAIL_ANY = os.environ.get("DDPM_WGRAD3_TAIL_ANY", "0") != "0"
+# 9.87 / 9.81 / 9.83 ms per step (every one of nine 0-vs-4 pairs in favour of 4).
+_TAIL_BLOCKS = 4
 # Data parallel: 1 = chunk exchanges ordered behind the side stream, no main-stream joins (-7.5 % on the one-rank RCCL step, round 5).
 # Default 0 = the round-4 form (join + issue on the main stream): a one-rank all-reduce is the identity and gloo stages through the host, so
 # the ordering of the fast form has never been observable on this one-GPU pool.  Opt in after tests/test_multi_gpu.py passed on >= 2 GPUs.
 _DP_ISSUE_ON_SIDE = os.environ.get("DDPM_DP_ISSUE_ON_SIDE", "0") != "0"
-_TEMB_LEAVES = os.environ.get("DDPM_TEMB_LEAVES", "0") != "0"          # A/B switch: the embedding MLP's parameter gradients as side-stream leaves (see _temb_bwd)
-_ABL_NO_LEAF_ORDER = os.environ.get("DDPM_ABL_NO_LEAF_ORDER", "0") != "0"   # TIMING-ONLY ablation (wrong results): leaves are not ordered behind the main stream
-_WGRAD1 = os.environ.get("DDPM_WGRAD1", "1") != "0"                # slab kernel for the 1x1 weight gradients
-_WGRAD3_ATOMIC = os.environ.get("DDPM_WGRAD3_ATOMIC", "0") != "0"  # ... with fp32 atomics instead of slab copies
 
 
 class _Engine:
@@ -376,7 +365,7 @@ class _Engine:
                 regblock(mods[j])
             if i != 0 and m.resample_with_conv:
                 reg(mods[self.n + 1][1])
-                self.convs[id(mods[self.n + 1][1])].up = _UP_DGRAD_FUSED
+                self.convs[id(mods[self.n + 1][1])].up = True
         reg(m.out_conv[2])
 
     # ---------------------------------------------------------------- derived weight caches
@@ -578,15 +567,14 @@ class _Engine:
             # encoder weights that had been final for milliseconds — behind in_conv's gradient: profiles/r05_dp_one_rank.json), and the
             # 10-18 MB of d(fc.weight), which round 4 produced in one piece after the backward, travel with the chunks.
             # ~6 chunks of ~24 MB for the CIFAR / CelebA nets (143 MB of gradients); DDPM_DP_CHUNK_MB overrides the chunk size — xGMI rings
-            # are per-link bound, so the right size is a property of the node and is to be swept there (bench.py prints config.dp);
-            # DDPM_DP_CHUNK_RAMP=0: uniform chunks.
+            # are per-link bound, so the right size is a property of the node and is to be swept there (bench.py prints config.dp).
             E = self.E
             convs = list(self.convs.values())
             conv_floats = sum((cw.mod.weight.numel() + 3) // 4 * 4 for cw in convs) + self.tb_total * E
             target = max(conv_floats // 6, 1 << 20)
             if os.environ.get("DDPM_DP_CHUNK_MB"):
                 target = max(int(float(os.environ["DDPM_DP_CHUNK_MB"]) * (1 << 18)), 1 << 16)
-            ramp = [16, 4] if os.environ.get("DDPM_DP_CHUNK_RAMP", "1") != "0" else []
+            ramp = [16, 4]
             rb_of_conv1 = {id(rb.conv1): rb for rb in self.res_blocks}
             self.chunks, self.chunk_fc, start, members, blocks = [], [], 0, [], []
             for i, cw in enumerate(convs):
@@ -646,8 +634,7 @@ class _Engine:
             yield
             return
         ctx["keep"].extend(views)
-        if not _ABL_NO_LEAF_ORDER:
-            _hip.call("ddpm_stream_order", ctx["side_handle"], ctx["main_handle"])     # inputs are final on the main stream here
+        _hip.call("ddpm_stream_order", ctx["side_handle"], ctx["main_handle"])     # inputs are final on the main stream here
         # The kernels take their stream as an argument: routing _hip.stream() to the side stream's handle is all a leaf needs (no
         # torch.cuda.stream() context: two stream switches and several device look-ups per leaf, ~190 leaves per step).  Nothing
         # inside a leaf allocates temporaries (the slab copies are persistent), so the allocator's stream bookkeeping is not involved.
@@ -673,14 +660,23 @@ class _Engine:
         if ctx.get("side") is not None:
             _hip.call("ddpm_stream_order", ctx["main_handle"], ctx["side_handle"])
 
+    def _slab(self, weight, copies, n, nb=0):
+        """Persistent slab workspace of one weight: ``copies`` partial gradients of ``n`` floats, then as many partial bias
+        gradients of ``nb`` floats.  Returns (tensor, stride of a weight copy, stride of a bias copy)."""
+        stride, bstride = (n + 3) // 4 * 4, (nb + 3) // 4 * 4
+        slab = self._slabs.get(id(weight))
+        if slab is None or slab.numel() < copies * (stride + bstride):
+            slab = self._slabs[id(weight)] = torch.empty(copies * (stride + bstride), dtype=torch.float32, device=self.device)
+        return slab, stride, bstride
+
     def _wgrad(self, ctx, weight, dy, x, Creal, Nreal, R, S, splits=1, bias=None, **kw):
         """Weight gradient into the staging buffer; then hand finished all-reduce chunks to the communicator.  ``bias`` = staging
         key of the bias gradient when it is the plain column sum of the same ``dy``: returns True when this call produced it too.
 
         3x3 / stride 1 / pad 1, bf16 (the bulk of the FLOPs): the patch-stationary kernel (csrc/wgrad.hip).  Its small output
         tiles need few reduction slices; every slice STORES its partial into its own slab copy (persistent per-weight workspace)
-        and one multi-tensor launch sums the copies in a fixed order — bit-deterministic gradients (DDPM_WGRAD3_ATOMIC=1: fp32
-        atomics instead).  It also accumulates the bias gradient from the dy fragments it reads.
+        and one multi-tensor launch sums the copies in a fixed order — bit-deterministic gradients.  It also accumulates the
+        bias gradient from the dy fragments it reads.  1x1 / stride 1, bf16: the slab kernel of csrc/wgrad1x1.hip, same scheme.
 
         Everything else: the transposed-operand GEMM; its split-K slices add into the staging buffer with fp32 atomics, or
         (DDPM_WGRAD_SLABS=1) store slab copies as above."""
@@ -688,7 +684,7 @@ class _Engine:
         patch = 0
         boost_req = kw.pop("boost", False)
         up = bool(kw.get("upsample"))                    # Upsample block: x stored at half of dy's size, gathered in place by the kernel
-        if (_WGRAD3 and self.T == torch.bfloat16 and R == 3 and S == 3 and (not up or (_WGRAD3_UP and dy.H == 2 * x.H and dy.W == 2 * x.W))
+        if (_WGRAD3 and self.T == torch.bfloat16 and R == 3 and S == 3 and (not up or (dy.H == 2 * x.H and dy.W == 2 * x.W))
                 and kw.get("stride", 1) == 1 and kw.get("pad_t") == 1 and kw.get("pad_l") == 1 and Creal == x.C):
             boost = bool(boost_req)
             pkey = ("w3", x.B, dy.H, dy.W, x.C, dy.C, boost)
@@ -699,45 +695,26 @@ class _Engine:
                     patch = ops.conv3x3_wgrad_splits(x.B, dy.H, dy.W, x.C, dy.C, 2 * patch)
                 self._eff_splits[pkey] = patch
         point = 0
-        if (not patch and _WGRAD1 and self.T == torch.bfloat16 and R == 1 and S == 1 and not kw.get("upsample") and kw.get("stride", 1) == 1
+        if (not patch and self.T == torch.bfloat16 and R == 1 and S == 1 and not up and kw.get("stride", 1) == 1
                 and not kw.get("pad_t") and not kw.get("pad_l") and Creal == x.C and Nreal == dy.C):
             pkey = ("w1", dy.rows, x.C, dy.C)
             point = self._eff_splits.get(pkey)
             if point is None:
                 point = self._eff_splits[pkey] = ops.conv1x1_wgrad_splits(dy.rows, x.C, dy.C)
-        if point:
-            # 1x1: slab kernel (csrc/wgrad1x1.hip) — one block per CU, partial tiles stored from registers, bias gradient folded in
+        if point or patch:
+            # slab kernels (1x1: csrc/wgrad1x1.hip, 3x3: csrc/wgrad.hip) — partial tiles stored from registers, bias gradient folded in
+            copies, n = point or patch, Nreal * R * S * Creal
             bias_ptr = self._pptr(ctx, bias) if bias is not None else 0
             with self._leaf(ctx, dy, x):
-                n = Nreal * Creal
-                stride = (n + 3) // 4 * 4
-                bstride = (Nreal + 3) // 4 * 4
-                slab = self._slabs.get(id(weight))
-                if slab is None or slab.numel() < point * (stride + bstride):
-                    slab = self._slabs[id(weight)] = torch.empty(point * (stride + bstride), dtype=torch.float32, device=self.device)
-                bslab = slab.data_ptr() + 4 * point * stride
-                ops.conv1x1_wgrad(dy, x, slab.data_ptr(), stride, bslab if bias is not None else 0, bstride, Nreal, point)
-                ctx["slab_rows"].append((slab.data_ptr(), self._pptr(ctx, weight), n, point, stride))
-                if bias is not None:
-                    ctx["slab_rows"].append((bslab, bias_ptr, Nreal, point, bstride))
-            did_bias = bias is not None
-        elif patch:
-            bias_ptr = self._pptr(ctx, bias) if bias is not None else 0
-            with self._leaf(ctx, dy, x):
-                if _WGRAD3_ATOMIC:
-                    ops.conv3x3_wgrad(dy, x, self._pptr(ctx, weight), 0, bias_ptr, 0, Nreal, patch, upsample=up)
+                slab, stride, bstride = self._slab(weight, copies, n, Nreal)
+                bslab = slab.data_ptr() + 4 * copies * stride
+                if point:
+                    ops.conv1x1_wgrad(dy, x, slab.data_ptr(), stride, bslab if bias is not None else 0, bstride, Nreal, point)
                 else:
-                    n = Nreal * 9 * Creal
-                    stride = (n + 3) // 4 * 4
-                    bstride = (Nreal + 3) // 4 * 4
-                    slab = self._slabs.get(id(weight))
-                    if slab is None or slab.numel() < patch * (stride + bstride):
-                        slab = self._slabs[id(weight)] = torch.empty(patch * (stride + bstride), dtype=torch.float32, device=self.device)
-                    bslab = slab.data_ptr() + 4 * patch * stride
                     ops.conv3x3_wgrad(dy, x, slab.data_ptr(), stride, bslab if bias is not None else 0, bstride, Nreal, patch, upsample=up)
-                    ctx["slab_rows"].append((slab.data_ptr(), self._pptr(ctx, weight), n, patch, stride))
-                    if bias is not None:
-                        ctx["slab_rows"].append((bslab, bias_ptr, Nreal, patch, bstride))
+                ctx["slab_rows"].append((slab.data_ptr(), self._pptr(ctx, weight), n, copies, stride))
+                if bias is not None:
+                    ctx["slab_rows"].append((bslab, bias_ptr, Nreal, copies, bstride))
             did_bias = bias is not None
         else:
             key = (dy.rows, splits, x.dtype)
@@ -747,10 +724,7 @@ class _Engine:
             with self._leaf(ctx, dy, x):
                 if _WGRAD_SLABS and eff > 1:
                     n = Nreal * R * S * Creal
-                    stride = (n + 3) // 4 * 4
-                    slab = self._slabs.get(id(weight))
-                    if slab is None or slab.numel() < eff * stride:
-                        slab = self._slabs[id(weight)] = torch.empty(eff * stride, dtype=torch.float32, device=self.device)
+                    slab, stride, _ = self._slab(weight, eff, n)
                     ops.conv2d_wgrad(dy, x, slab.data_ptr(), Creal, Nreal, R, S, splits=eff, slab_stride=stride, **kw)
                     ctx["slab_rows"].append((slab.data_ptr(), self._pptr(ctx, weight), n, eff, stride))
                 else:
@@ -1062,11 +1036,11 @@ class _Engine:
         o = self._new(B, x.H, x.W, C)
         prob = lse = None
         scale = 1.0 / math.sqrt(C)
-        flash = _FLASH_ATTENTION and self.T == torch.bfloat16 and Lk <= 256 and Lk % 16 == 0 and C <= 512 and C % 32 == 0
-        if not save and _FUSED_ATTENTION and not (flash and _FLASH_INFERENCE) and self.T == torch.bfloat16 and Lk % 128 == 0 and C in (128, 256):
-            # inference: one kernel, the L x L logits / probabilities stay in LDS and registers (unet.py:41-52); since the training
-            # forward got its DMA rings and the one-butterfly softmax it is the faster one (27 vs 32 us at B=128, L=256, C=256) and serves
-            # inference too; DDPM_FLASH_INFERENCE=0 brings this kernel back
+        flash = self.T == torch.bfloat16 and Lk <= 256 and Lk % 16 == 0 and C <= 512 and C % 32 == 0
+        if not save and not flash and self.T == torch.bfloat16 and Lk % 128 == 0 and C in (128, 256):
+            # inference over more tokens than the kernel below serves: one kernel, the L x L logits / probabilities stay in LDS and
+            # registers (unet.py:41-52).  (Up to 256 tokens the training forward — DMA rings, one-butterfly softmax — is the faster
+            # one, 27 vs 32 us at B=128, L=256, C=256, and serves inference too.)
             _hip.call("ddpm_attention_fwd", qkv.ptr, qkv.ld, o.ptr, o.ld, B, Lk, C, scale, self.dcode, _hip.stream())
         elif flash:
             # training (and the geometries the kernel above does not serve): same, plus the row log-sum-exp the backward
@@ -1110,10 +1084,9 @@ class _Engine:
                    seed_dev=st.get("seed_dev", 0), world=1, sumsq=0)
         if _SIDE_STREAM and gflat.is_cuda:
             if self._side is None:
-                # Default priority 0 = the main stream's own: measured, a lower-priority side stream (DDPM_SIDE_PRIORITY=1..) did not move
-                # the step (the weight-gradient stream has ~3.6 ms of work per ~9.6 ms step and is confined to half the CUs by the
-                # kernels' own grids, DDPM_WGRAD3_CUS); the switch stays for experiments.
-                self._side = torch.cuda.Stream(device=self.device, priority=_SIDE_PRIORITY)
+                # Priority 0 = the main stream's own: measured, a lower-priority side stream did not move the step (the weight-gradient
+                # stream has ~3.6 ms of work per ~9.6 ms step and is confined to half the CUs by the kernels' own grids, DDPM_WGRAD3_CUS).
+                self._side = torch.cuda.Stream(device=self.device, priority=0)
             ctx["side"] = self._side
             ctx["side_handle"] = self._side.cuda_stream
             ctx["main"] = torch.cuda.current_stream()
@@ -1247,16 +1220,11 @@ class _Engine:
                            splitk=self.splitk)
                 self.last_dx = dx
             return
-        if upsample and cw.up:
+        if upsample:
             # d/dx of (nearest-2x upsample -> 3x3 conv) = one 4x4 / stride-2 / pad-1 conv over dy with the summed taps the pack
             # kernel prepared: 16 taps on a quarter of the pixels, no full-resolution intermediate, no 2x2 reduction pass
             g, acc = self._grad_target(x)
             ops.conv2d(dy, cw.wd.data_ptr(), g.ptr, g.ld, cw.C, 4, 4, x.H, x.W, stride=2, pad_t=1, pad_l=1, accumulate=acc, splitk=self.splitk)
-        elif upsample:
-            tmp = self._new(B, dy.H, dy.W, cw.C)            # dgrad at the upsampled resolution, then 2x2 sum
-            ops.conv2d(dy, cw.wd.data_ptr(), tmp.ptr, tmp.ld, cw.C, k, k, dy.H, dy.W, pad_t=k - 1 - pt, pad_l=k - 1 - pl, splitk=self.splitk)
-            g, acc = self._grad_target(x)
-            _hip.call("ddpm_upsample2x_bwd", tmp.ptr, g.ptr, g.ld, B, x.H, x.W, cw.C, acc, self.dcode, _hip.stream())
         else:
             g, acc = self._grad_target(x)
             ops.conv2d(dy, cw.wd.data_ptr(), g.ptr, g.ld, cw.C, k, k, x.H, x.W, pad_t=k - 1 - pt, pad_l=k - 1 - pl,
@@ -1275,8 +1243,8 @@ class _Engine:
         ops.conv2d(dout, c2.wd.data_ptr(), da2.ptr, da2.ld, Cout, 3, 3, x.H, x.W, pad_t=1, pad_l=1, splitk=self.splitk)
         b2 = ("b2", id(rb)) if rb.has_skip else rb.conv2.bias
         # (... on images up to 64 x 64 only: on the CelebA-HQ step the same boost COSTS 1.4 % — 11.71 against 11.55 ms — its first blocks sit
-        #  at 256 x 256 / 128 x 128 with a long main-stream chain still to come; DDPM_WGRAD3_TAIL_ANY=1 lifts the limit)
-        boost = _TAIL_BLOCKS > 0 and (x.H * x.W <= 4096 or _TAIL_ANY) and any(rb is q for q in self.res_blocks[:_TAIL_BLOCKS])
+        #  at 256 x 256 / 128 x 128 with a long main-stream chain still to come)
+        boost = x.H * x.W <= 4096 and any(rb is q for q in self.res_blocks[:_TAIL_BLOCKS])
 
         if not self._wgrad(ctx, rb.conv2.weight, dout, a2, Cout, Cout, 3, 3, pad_t=1, pad_l=1, splits=self._splits(Cout, 9 * Cout, dout.rows), bias=b2, boost=boost):
             self._bias_grad(ctx, dout, [rb.conv2.bias], Cout, slot=("b2", id(rb)) if rb.has_skip else None)
@@ -1384,9 +1352,7 @@ class _Engine:
         # The embedding MLP's parameter gradients stay on THIS stream, behind the chain that produced their inputs: the chain ends here while the
         # side stream still has the first layers' weight gradients, the last chunk's time-projection rows and a run of bias sums queued — as
         # leaves these four launches sat at the end of that queue and the join below waited ~90 us longer for them (profiles/r06_step_tail.txt).
-        # (DDPM_TEMB_LEAVES=1: as leaves on the side stream again, for A/B runs)
-        with (self._leaf(ctx, dt_emb, s1, de1, temb) if _TEMB_LEAVES else contextlib.nullcontext()):
-            _hip.call("ddpm_atb_f32", dt_emb.data_ptr(), E, s1.data_ptr(), E, self._pptr(ctx, lin2.weight), E, E, E, B, _hip.stream())
-            ops.colsum(View(dt_emb, 1, B, 1, E), 0, 0, self._pptr(ctx, lin2.bias))
-            _hip.call("ddpm_atb_f32", de1.data_ptr(), E, temb.data_ptr(), self.hid, self._pptr(ctx, lin1.weight), self.hid, E, self.hid, B, _hip.stream())
-            ops.colsum(View(de1, 1, B, 1, E), 0, 0, self._pptr(ctx, lin1.bias))
+        _hip.call("ddpm_atb_f32", dt_emb.data_ptr(), E, s1.data_ptr(), E, self._pptr(ctx, lin2.weight), E, E, E, B, _hip.stream())
+        ops.colsum(View(dt_emb, 1, B, 1, E), 0, 0, self._pptr(ctx, lin2.bias))
+        _hip.call("ddpm_atb_f32", de1.data_ptr(), E, temb.data_ptr(), self.hid, self._pptr(ctx, lin1.weight), self.hid, E, self.hid, B, _hip.stream())
+        ops.colsum(View(de1, 1, B, 1, E), 0, 0, self._pptr(ctx, lin1.bias))

@@ -35,9 +35,9 @@ int ddpm_mfma_probe(float* sink, int iters, int zero_operands, void* stream);
 
 /* diagnostic (no upstream counterpart): the wave-specialised 3x3 kernel's LDS-semaphore waits are bounded in wall time (~5 s); one that
  * expires records {block, counter address, value waited for, kind} and traps (the launch fails instead of hanging the GPU).  out4 is HOST
- * memory; kind 0 = no wait has ever expired.  Setting DDPM_CONV_NO_PC=1 runs those calls on the barrier-synchronised kernel instead. */
+ * memory; kind 0 = no wait has ever expired. */
 int ddpm_conv3x3_pc_last_fault(unsigned* out4);
-/* ... the same record for the wave-specialised 3x3 weight-gradient kernel (DDPM_WGRAD3_NO_WS=1 runs those calls on the barrier-synchronised one). */
+/* ... the same record for the wave-specialised 3x3 weight-gradient kernel. */
 int ddpm_wgrad3x3_ws_last_fault(unsigned* out4);
 
 /* Data-parallel training (upstream: DistributedDataParallel's all-reduce beside the backward, train.py:110): the persistent kernels size

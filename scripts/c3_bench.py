@@ -1,5 +1,4 @@
-"""3x3 conv forward timings on the CIFAR UNet's big shapes (B = 128, bf16): persistent stationary-halo kernel (conv3x3.hip) vs the
-one-tile-per-block form (DDPM_CONV_NO_STREAM3=1 python scripts/c3_bench.py)."""
+"""3x3 conv forward timings on the CIFAR UNet's big shapes (B = 128, bf16): the persistent stationary-halo kernels (conv3x3.hip)."""
 import math, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "ddpm-torch_amd")]

@@ -1,4 +1,4 @@
-"""3x3 conv forward timings on the 8x8 level (B = 128, bf16): 8x8-patch persistent kernel vs the 64x64-tile GEMM (DDPM_CONV_NO_STREAM3_8=1)."""
+"""3x3 conv forward timings on the 8x8 level (B = 128, bf16): the 8x8-patch persistent kernel."""
 import math, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "ddpm-torch_amd")]

@@ -1,5 +1,5 @@
 #!/bin/bash
-# round 4: LDS / wait counters of the 3x3 kernels (isolated launches), for the wave-specialised kernel, the round-3 kernel and the 3x3 weight gradient
+# round 4: LDS / wait counters of the 3x3 kernels (isolated launches), for the wave-specialised kernel and the 3x3 weight gradient
 cd "$GRAFT_REPO_ROOT" || exit 1
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/${1:-r4cnt}; mkdir -p $O
 export TMPDIR=/tmp
@@ -21,7 +21,6 @@ PY
   done
 }
 run "conv3x3_pc_kernel 128->128 @ 32x32 B=128" "X=1" fwd "128 32 128 128" conv3x3_pc
-run "conv3x3_stream_kernel<16> (round 3) 128->128 @ 32x32 B=128" "DDPM_CONV_NO_PC=1" fwd "128 32 128 128" conv3x3_stream
 run "conv3x3_pc_kernel 512->256 @ 16x16 B=128" "X=1" fwd "128 16 512 256" conv3x3_pc
 run "wgrad3x3_kernel 128x128 @ 32x32 B=128" "X=1" wgrad "128 32 128 128" wgrad3x3
 run "wgrad3x3_kernel 256x256 @ 16x16 B=128" "X=1" wgrad "128 16 256 256" wgrad3x3

@@ -3,7 +3,7 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 O=gpurun_out/${1:-shapes}; mkdir -p $O
 export BENCH_NO_SWEEP=1
-for cfg in "pc:" "old:DDPM_CONV_NO_PC=1" "pc_nogate:BENCH_NO_GATE=1"; do
+for cfg in "pc:" "pc_nogate:BENCH_NO_GATE=1"; do
   name=${cfg%%:*}; envs=${cfg#*:}
   env $envs BENCH_SHAPES=$O/shapes_$name.txt timeout 600 python bench.py --full --steps 60 --warmup 12 --sample-steps 0 --no-cpu-baseline --no-extras 2>/dev/null | tail -1 > $O/bench_$name.json
   python - $O/bench_$name.json $name <<'PY'

@@ -1,5 +1,4 @@
-"""1x1-conv forward timings on the CIFAR UNet's shapes (B = 128, bf16): persistent streaming kernel vs the generic tile GEMM
-(DDPM_CONV_NO_POINTWISE=1 python scripts/pw_bench.py for the latter)."""
+"""1x1-conv forward timings on the CIFAR UNet's shapes (B = 128, bf16): the persistent streaming kernel (pointwise.hip)."""
 import math, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "ddpm-torch_amd")]

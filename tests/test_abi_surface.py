@@ -99,3 +99,39 @@ def test_plan_api_validates_on_the_host():
     assert lib.ddpm_plan_run(h, 7) == 1                                         # no such segment
     assert lib.ddpm_fill_zero(0, 16, 0) == 5 and lib.ddpm_fill_zero(0, 0, 0) == 0 and lib.ddpm_fill_zero(0, -1, 0) == 1
     assert lib.ddpm_plan_destroy(h) == 0
+
+
+PKG = os.path.join(ROOT, "ddpm-torch_amd")
+RETIRED_MACROS = ("PC_ABL_", "PC_DEFAULT_OFF", "GN_ABL_", "GABL_")
+
+
+def _sources(top, suffixes):
+    for d, _, files in os.walk(top):
+        for f in files:
+            if f.endswith(suffixes):
+                yield os.path.join(d, f)
+
+
+def test_every_environment_switch_is_in_the_integration_table_and_no_ablation_macro_is_back():
+    """The project's switches are the rows of INTEGRATION.md's "Environment" table, no more and no fewer: every DDPM_* name a getenv( call
+    under csrc/ or an environ read in the package mentions is documented there, and every documented name is still read.  A kernel
+    experiment is a second build of the library (DDPM_HIP_LIB), not a new branch in the product's dispatch."""
+    read = set()
+    for path in _sources(os.path.join(PKG, "csrc"), (".hip", ".h", ".py")):
+        for line in open(path):
+            if "getenv(" in line or "environ" in line:
+                read |= set(re.findall(r"DDPM_[A-Z0-9_]+", line.split("//")[0]))
+    for path in _sources(PKG, (".py",)):
+        for line in open(path):
+            if "environ" in line:
+                read |= set(re.findall(r"DDPM_[A-Z0-9_]+", line.split("#")[0]))
+    section = open(os.path.join(ROOT, "INTEGRATION.md")).read().split("\n## 4. Environment", 1)[1].split("\n## ", 1)[0]
+    table = set()
+    for row in section.splitlines():
+        if row.startswith("| `"):
+            table |= set(re.findall(r"`(DDPM_[A-Z0-9_]+)`", row.split("|")[1]))
+    assert len(table) >= 10
+    assert read == table, (sorted(read - table), sorted(table - read))
+    for path in _sources(os.path.join(PKG, "csrc"), (".hip", ".h")):
+        src = open(path).read()
+        assert not [m for m in RETIRED_MACROS if m in src], path
