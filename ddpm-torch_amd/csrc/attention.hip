@@ -59,8 +59,10 @@ struct AttnArgs {
 };
 
 // ---- LDS layout
-// tile : bf16 [RB][Lpad], 16-byte chunks XOR-swizzled by (row & KM) (KM = min(Lpad / 8, 16) - 1): the 16 rows a ds_read_b128
-//        lane group touches at one k position fall on 16 different 16-byte slots
+// tile : bf16 [RB][Lpad], 16-byte chunks XOR-swizzled by (row & KM), KM + 1 = the largest power of two <= 16 that divides the
+//        Lpad / 8 chunks of a row (the XOR must map a row's chunks onto themselves: with Lpad = 96, 160, 192 or 224 a 16-chunk key
+//        would send chunks past the end of the row, into the next row's): the 16 rows a ds_read_b128 lane group touches at one
+//        k position fall on KM + 1 different 16-byte slots (16 for Lpad = 128 and 256)
 // stage: 2 buffers; P1 chunk = X [RB][64 c] + Y [Lpad][64 c] with 128-byte rows and the gemm kernels' swizzle ((row >> 1) & 7);
 //        P2 chunk = Y [KR][C] as stored (rows of 2C bytes), chunks XOR-swizzled by (krow & 3) << 2 for the transpose reads
 __device__ __forceinline__ int tile_addr(int row, int col, int pitch_b, int km) {
@@ -390,8 +392,10 @@ struct Lds {
 __device__ __forceinline__ Lds carve(char* smem, int Lpad) {
     Lds l;
     l.pitch_b = Lpad * 2;
-    const int nch = Lpad >> 3;
-    l.km = (nch < 16 ? nch : 16) - 1;
+    const int nch = Lpad >> 3;                       // a multiple of 4
+    int span = 4;
+    while (span < 16 && nch % (span * 2) == 0) span *= 2;
+    l.km = span - 1;
     l.tile = smem;
     l.stage = smem + RB * l.pitch_b;
     l.red = nullptr;

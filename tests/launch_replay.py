@@ -410,6 +410,8 @@ def rep_conv3x3_wgrad_up(A, sig, res):
 
 def rep_conv1x1_wgrad(A, sig, res):
     pdy, dy_ld, px, x_ld, pdw, slab_stride, pdb, bias_stride, P, C, N, splits, dt = sig
+    if splits <= 0:                    # a hand-written signature (ODD_GEOMETRY): the slab count the library plans for this geometry
+        splits = int(_hip.lib().ddpm_conv1x1_wgrad_splits(P, C, N))
     assert slab_stride > 0 and splits >= 1
     dy = A.buf("dy", pitched(P, N, dy_ld), dt, _mod(pdy)).fill(A.randn(pitched(P, N, dy_ld)))
     x = A.buf("x", pitched(P, C, x_ld), dt, _mod(px)).fill(A.randn(pitched(P, C, x_ld)))
@@ -1210,6 +1212,117 @@ SYNTHETIC = [
 ]
 
 
+# ----------------------------------------------------------------------------------------------------------------- odd geometries
+# Hand-written signatures at non-square images and pixel / token counts that are no power of two: the smallest shapes at which each
+# kernel is still dispatched, so that tiles_x != tiles_y (1 x 3, 3 x 1, 3 x 3, 2 x 3 patches), Ho != Wo in the implicit-GEMM index
+# arithmetic, ragged last iterations in the GroupNorm forms and token counts between the tested ones reach the kernels.  Operands are
+# pitched as tests/test_kernels_gpu.py pitches them (x_ld = C + 16, y_ld = N + 32, row bias N + 8), every pointer 16-byte aligned.
+# Each row is (signature, kernel id variant_of must name, or None for the entries without a dispatch query).
+def _conv_sig(B, H, W, C, N, Ho=None, Wo=None, R=3, S=3, stride=1, pad=(1, 1), ups=0, dil=0, bias=0, rowbias=0, res=0, acc=0, mode=0,
+              splits=1, dt=BF16, x_ld=None):
+    Ho, Wo = (H << ups if Ho is None else Ho), (W << ups if Wo is None else Wo)
+    ws = splits > 1
+    return ("ddpm_conv2d_nhwc", (_p(), C + 16 if x_ld is None else x_ld, _p(), _p(), N + 32, _p(null=not bias), _p(null=not rowbias),
+                                 N + 8 if rowbias else 0, _p(null=not res), N + 32 if res else 0, B, H, W, C, Ho, Wo, N, R, S, stride,
+                                 pad[0], pad[1], ups, dil, acc, mode, splits, _p(null=not ws), _p(null=not ws), dt))
+
+
+def _wg3_sig(B, H, W, C, N, up=False, slab=False):
+    n_one = N * 9 * C
+    return ("ddpm_conv3x3_wgrad_up_nhwc" if up else "ddpm_conv3x3_wgrad_nhwc",
+            (_p(), N + 32, _p(), C + 16, _p(), n_one + 64 if slab else 0, _p(), N + 4 if slab else 0, B, H, W, C, N, N, 0, BF16))
+
+
+def _wg_sig(B, H, W, C, N, R=3, S=3, splits=1, slab=False):
+    return ("ddpm_conv2d_wgrad_nhwc", (_p(), N + 32, _p(), C + 16, _p(), N * R * S * C + 64 if slab else 0, B, H, W, C, C, H, W, N, N, R, S,
+                                       1, R // 2, S // 2, 0, splits, BF16))
+
+
+def _gn_sigs(HW, C, dt, silu, drop, full, B=3, G=32):
+    """(forward, backward) of one GroupNorm geometry; full: the backward accumulates and has `add` and `dx_colsum` operands."""
+    seed = 977 + HW + C
+    fwd = ("ddpm_groupnorm_silu_fwd", (_p(), C + 16, _p(), C + 8, _p(), _p(), _p(), _p(), B, HW, C, G, 1e-6, silu, drop, seed,
+                                       _p(null=not full), dt))
+    bwd = ("ddpm_groupnorm_silu_bwd", (_p(), C + 16, _p(), C + 8, _p(), C + 24, _p(), _p(), _p(), _p(), _p(), _p(), B, HW, C, G, silu, drop,
+                                       seed, _p(null=not full), int(full), _p(null=not full), C + 4 if full else 0, _p(null=not full),
+                                       C + 32 if full else 0, dt))
+    return [(fwd, None), (bwd, None)]
+
+
+def _attn_sigs(B, L, C):
+    scale = float(C) ** -0.5
+    return [(("ddpm_attention_fwd_lse", (_p(), 3 * C + 16, _p(), C + 8, _p(), B, L, C, scale, BF16)), None),
+            (("ddpm_attention_bwd", (_p(), 3 * C + 16, _p(), C + 8, _p(), C + 8, _p(), _p(), _p(), 3 * C + 24, B, L, C, scale, BF16)), None)]
+
+
+ODD_GEOMETRY = [
+    # ---- ddpm_conv2d_nhwc, forward and data gradient
+    # 13 conv3x3_pc (wave-specialised, 16 x 16 patches)
+    (_conv_sig(22, 16, 48, 64, 64, bias=1), 13),                            # 1 x 3 patches
+    (_conv_sig(22, 48, 16, 64, 128), 13),                                   # 3 x 1 patches
+    (_conv_sig(8, 48, 48, 64, 64), 13),                                     # 3 x 3 patches
+    (_conv_sig(22, 8, 24, 64, 64, ups=1, bias=1), 13),                      # input stored at 8 x 24, gathered as 16 x 48
+    # 8 conv3x3_stream<16> (the residual / "+=" epilogues of the 16 x 16 patches)
+    (_conv_sig(22, 16, 48, 64, 64, bias=1, rowbias=1, res=1), 8),
+    (_conv_sig(11, 48, 32, 64, 64, acc=1), 8),                              # 3 x 2 patches
+    # 10 conv3x3_stream<8> (8 x 8 patches)
+    (_conv_sig(22, 8, 24, 64, 64, bias=1, rowbias=1), 10),                  # 1 x 3
+    (_conv_sig(8, 24, 24, 64, 128, res=1), 10),                             # 3 x 3
+    (_conv_sig(22, 24, 8, 128, 64, acc=1), 10),                             # 3 x 1, two channel chunks
+    (_conv_sig(11, 16, 24, 64, 64, bias=1), 10),                            # 2 x 3
+    (_conv_sig(22, 12, 4, 64, 64, ups=1), 10),                              # input stored at 12 x 4, gathered as 24 x 8
+    # 5 conv3x3_halo (N no multiple of 64)
+    (_conv_sig(22, 16, 48, 64, 96, bias=1, res=1), 5),
+    (_conv_sig(22, 48, 16, 64, 96, bias=1), 5),
+    # 11 / 12 edge convs
+    (_conv_sig(22, 16, 48, 64, 3, bias=1, mode=3), 11),
+    (_conv_sig(22, 48, 16, 8, 64, bias=1, x_ld=8), 12),
+    # 7 pw_conv (streaming 1x1)
+    (_conv_sig(22, 24, 16, 128, 192, R=1, S=1, pad=(0, 0), bias=1, res=1), 7),
+    # 4 gemm64 (generic implicit GEMM, 64 x 64 tiles): Ho != Wo in dHoWo / dWo
+    (_conv_sig(3, 12, 20, 64, 96, bias=1, rowbias=1, res=1, acc=1), 4),
+    (_conv_sig(3, 6, 10, 32, 64, bias=1, dt=F32), 4),
+    (_conv_sig(2, 8, 12, 64, 64, Ho=4, Wo=6, stride=2, pad=(0, 0), bias=1), 4),       # the Downsample form (SamePad2d(3, 2))
+    (_conv_sig(2, 10, 6, 64, 64, Ho=5, Wo=3, stride=2, pad=(0, 0), bias=1), 4),       # ... with odd output sides
+    (_conv_sig(3, 6, 10, 64, 64, R=1, S=1, pad=(0, 0), bias=1, rowbias=1), 4),
+    # 3 gemm_kernel, deep ring: the parity-phase data gradient of a stride-2 conv (dHhWh / dWh)
+    (_conv_sig(4, 4, 8, 64, 64, Ho=8, Wo=16, pad=(2, 2), dil=1, acc=1), 3),
+    (_conv_sig(8, 6, 8, 64, 64, Ho=12, Wo=16, pad=(1, 1), dil=1, acc=1), 3),
+    # ---- weight gradients and reductions
+    (_wg3_sig(4, 16, 48, 64, 64), 14),                                      # wgrad3x3_ws, atomics
+    (_wg3_sig(4, 16, 48, 64, 64, slab=True), 14),                           # ... slabs
+    (_wg3_sig(3, 48, 16, 64, 128, up=True), 14),                            # x stored at 24 x 8
+    (_wg3_sig(3, 48, 16, 64, 128, up=True, slab=True), 14),
+    (_wg_sig(3, 12, 20, 64, 64, splits=4), 2),                              # generic: K = 720 pixels in 4 slices, atomics
+    (_wg_sig(3, 12, 20, 64, 64, splits=4, slab=True), 2),
+    (_wg_sig(22, 8, 24, 64, 64, splits=6), 2),                              # W = 8 needs H = 8 for the patch kernel: generic, K = 4224
+    (_wg_sig(22, 8, 24, 64, 64, splits=6, slab=True), 2),
+    (("ddpm_conv1x1_wgrad_nhwc", (_p(), 64 + 32, _p(), 64 + 16, _p(), 64 * 64 + 64, _p(), 64 + 4, 22 * 8 * 24, 64, 64, 0, BF16)), 9),
+    (("ddpm_upsample2x_bwd", (_p(), _p(), 64 + 16, 3, 4, 6, 64, 1, BF16)), None),
+    (("ddpm_upsample2x_bwd", (_p(), _p(), 32 + 16, 3, 4, 6, 32, 0, F32)), None),
+    (("ddpm_colsum", (_p(), 64 + 8, _p(), 64 + 4, _p(), 3, 192, 64, BF16)), None),
+    (("ddpm_colsum", (_p(), 128 + 8, _p(), 128 + 4, _p(), 3, 192, 128, F32)), None),
+]
+# ---- GroupNorm forward / backward, B = 3, G = 32: HW chosen so that the last iteration of every form is ragged (HW is no multiple of
+# the rows a block sweeps per iteration).  Form by the plan arithmetic of csrc/norm.hip (gn_fused_plan / gn_lds_plan), the same for the
+# forward and the backward and for both dtypes: "256 x v" the 256-thread staged kernel with v vectors per thread, "512 x v" the
+# 512-thread one, "streaming" the two-launch form.  P2: the backward takes the power-of-two-group instantiation.
+for _dt in (BF16, F32):
+    for _HW, _C, _silu, _drop, _full in (
+            (9, 128, 1, 0.0, False),            # 256 x 1, P2
+            (36, 256, 1, 0.1, True),            # 256 x 2, P2
+            (96, 64, 1, 0.0, False),            # 512 x 2 (bf16: 2 channels per group, not P2)
+            (96, 256, 0, 0.0, True),            # 512 x 2, P2
+            (144, 512, 1, 0.1, False),          # 512 x 4, P2
+            (576, 128, 1, 0.0, True),           # 512 x 8, P2
+            (2304, 64, 1, 0.1, True),           # streaming
+            (48, 384, 0, 0.0, True)):           # 512 x 2 with 12-channel groups (3 / 6 vector columns per group chunk: strided wave tree)
+        ODD_GEOMETRY += _gn_sigs(_HW, _C, _dt, _silu, _drop, _full)
+# ---- the fused attention pair at token counts between the tested ones
+for _B, _L, _C in ((2, 96, 128), (2, 144, 256), (1, 192, 512), (2, 240, 64), (3, 48, 256), (2, 80, 128)):
+    ODD_GEOMETRY += _attn_sigs(_B, _L, _C)
+
+
 # Entries a step launches that are not replayed here, the existing test that covers each (tests/test_kernels_gpu.py unless named) and
 # what that test holds it to: [torch] a plain torch reference (Adam + clip_grad_norm_, or a float64 restatement), [exact] a bit-exact
 # copy or integer comparison.
@@ -1283,21 +1396,28 @@ def _diffusion(cfg):
                                         d["model_mean_type"], d["model_var_type"], d["loss_type"])
 
 
+def _hw(size):
+    """size: the side of a square image, or an (H, W) pair"""
+    return (size, size) if isinstance(size, int) else tuple(size)
+
+
 def _train_step(cfg, device, B, size, drop=None, dtype=torch.bfloat16):
     import ddpm_torch
+    H, W = _hw(size)
     if drop is not None:
         cfg = dict(cfg, model=dict(cfg["model"], drop_rate=drop))
     m = _net(cfg, device, dtype=dtype)
     tc = cfg["train"]
     opt = torch.optim.Adam(m.parameters(), lr=tc["lr"], betas=(0.9, 0.999))
     tr = ddpm_torch.Trainer(m, opt, _diffusion(cfg), epochs=1, trainloader=None, use_ema=tc["use_ema"], grad_norm=tc["grad_norm"],
-                            shape=(3, size, size), device=torch.device(device), ema_decay=tc["ema_decay"])
+                            shape=(3, H, W), device=torch.device(device), ema_decay=tc["ema_decay"])
     m.train()
-    x = torch.rand(B, 3, size, size, generator=torch.Generator().manual_seed(1)) * 2 - 1
+    x = torch.rand(B, 3, H, W, generator=torch.Generator().manual_seed(1)) * 2 - 1
     return lambda: tr.step(x.to(device), global_steps=1)
 
 
 def _sample_step(cfg, device, B, size, ddim_steps=None, dtype=torch.bfloat16):
+    H, W = _hw(size)
     m = _net(cfg, device, dtype=dtype).eval()
     dif = _diffusion(cfg)
     if ddim_steps:
@@ -1306,7 +1426,7 @@ def _sample_step(cfg, device, B, size, ddim_steps=None, dtype=torch.bfloat16):
         dif = ddim.DDIM(dif.betas if torch.is_tensor(dif.betas) else torch.as_tensor(dif.betas), d["model_mean_type"], "fixed-small",
                         d["loss_type"], eta=0.0, subsequence=ddim.get_selection_schedule("linear", ddim_steps, d["timesteps"]))
     g = torch.Generator().manual_seed(2)
-    x = torch.randn(B, 3, size, size, generator=g).to(device)
+    x = torch.randn(B, 3, H, W, generator=g).to(device)
     t = torch.full((B,), 500, dtype=torch.int64, device=device)
     if ddim_steps:
         t = torch.full((B,), ddim_steps // 2, dtype=torch.int64, device=device)
@@ -1317,7 +1437,16 @@ def _sample_step(cfg, device, B, size, ddim_steps=None, dtype=torch.bfloat16):
     return run
 
 
-# key -> (what it runs, builder(device, B, size), B, size); full size: the geometry the benchmark, the configs and the CLIs run
+def _reduced(mult=(1, 2, 2), drop=0.0):
+    """cifar10.json with a reduced network (hid 64, one res block per level, attention at level 1 and in the middle block): the
+    non-square workloads W14-W17 keep the levels, the kernels and the dispatch of a real configuration at a few seconds a test."""
+    cfg = _config("cifar10.json")
+    return dict(cfg, model=dict(cfg["model"], hid_channels=64, ch_multipliers=list(mult), num_res_blocks=1,
+                                apply_attn=[i == 1 for i in range(len(mult))], drop_rate=drop))
+
+
+# key -> (what it runs, builder(device, B, size), B, size); full size: the geometry the benchmark, the configs and the CLIs run; size is
+# the side of a square image or an (H, W) pair
 _F32 = torch.float32
 WORKLOADS = {
     "W1": ("cifar10 train step, B=128, dropout 0.1", lambda dev, B=128, s=32: _train_step(_config("cifar10.json"), dev, B, s, drop=0.1), 128, 32),
@@ -1339,6 +1468,15 @@ WORKLOADS = {
     "W11": ("cifar10 sampling step, B=1", lambda dev, B=1, s=32: _sample_step(_config("cifar10.json"), dev, B, s), 1, 32),
     "W12": ("celeba 64x64 train step, B=128 (config 4)", lambda dev, B=128, s=64: _train_step(_config("celeba.json"), dev, B, s), 128, 64),
     "W13": ("cifar10 sampling step, B=2048 (operands >= 1 GiB)", lambda dev, B=2048, s=32: _sample_step(_config("cifar10.json"), dev, B, s), 2048, 32),
+    # non-square images on the reduced network: 16 x 48 -> 8 x 24 (192 tokens) -> 4 x 12 (48 tokens in the middle block); 1 x 3 / 3 x 1
+    # patches at level 0, 8 x 8 patches at level 1, the generic kernels below
+    "W14": ("reduced net train step, B=22, 16x48, dropout 0.1", lambda dev, B=22, s=(16, 48): _train_step(_reduced(drop=0.1), dev, B, s), 22, (16, 48)),
+    "W15": ("reduced net train step, fp32, B=22, 16x48, dropout 0.1",
+            lambda dev, B=22, s=(16, 48): _train_step(_reduced(drop=0.1), dev, B, s, dtype=_F32), 22, (16, 48)),
+    "W16": ("reduced net ancestral sampling step, B=22, 48x16", lambda dev, B=22, s=(48, 16): _sample_step(_reduced(), dev, B, s), 22, (48, 16)),
+    # every level off the 8-pixel grid; 12 x 10 = 120 tokens, a multiple of 8 but not of 16: the bf16 gemm + softmax + gemm attention
+    "W17": ("reduced net [1, 2] train step, B=2, 24x20, dropout 0.1",
+            lambda dev, B=2, s=(24, 20): _train_step(_reduced(mult=(1, 2), drop=0.1), dev, B, s), 2, (24, 20)),
 }
 
 

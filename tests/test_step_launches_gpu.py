@@ -2,7 +2,8 @@
 float64 reference at the geometry the step uses.
 
 The workloads (tests/launch_replay.py WORKLOADS: W1-W4 the benchmarked bf16 steps, W5-W8 the same configurations in the fp32 compute
-mode, W9-W13 bf16 steps at the batch sizes train.py --num-accum and generate.py run, up to operands >= 1 GiB) are recorded live through
+mode, W9-W13 bf16 steps at the batch sizes train.py --num-accum and generate.py run, up to operands >= 1 GiB, W14-W17 a reduced network
+on non-square 16 x 48, 48 x 16 and 24 x 20 images) are recorded live through
 ddpm_torch._hip._invoke — the geometry list is taken from the step every time the test runs, not from a committed snapshot.  Each
 distinct signature of a replayed entry is (dropout seeds aside) re-issued once on fresh random inputs (same pitches, pointer offsets
 modulo 256, optional operands, modes, splits and workspaces) and every output element is held to its own error-model bar; the float64
@@ -60,6 +61,27 @@ def _check_w9(rec):
     assert moved, "W9: every 3x3 conv dispatches as it does at B = 128"
 
 
+# kernels a non-square step must still reach: 13 / 10 conv3x3 in 1 x 3 patches of 16 x 16 and of 8 x 8, 14 wgrad3x3_ws, 11 / 12 edge convs
+W14_VARIANTS = {13, 10, 14, 11, 12}
+
+
+def _check_w14(rec, variants):
+    """16 x 48 at B = 22 keeps the patch kernels (tiles_x = 3, tiles_y = 1) and the fused attention pair, at 8 x 24 = 192 tokens."""
+    assert W14_VARIANTS <= set(variants), f"W14 did not reach variants {sorted(W14_VARIANTS - set(variants))}"
+    for name in ("ddpm_attention_fwd_lse", "ddpm_attention_bwd"):
+        at = sorted({s[1][-5:-2] for s in rec.sigs if s[0] == name})          # (B, L, C)
+        print(f"W14: {name[5:]} at (B, L, C) = {at}")
+        assert any(L == 192 for _, L, _ in at), f"W14: no {name} over 192 tokens"
+
+
+def _check_w17(rec):
+    """12 x 10 = 120 tokens: a multiple of 8 but not of 16, so the bf16 step runs gemm + softmax + gemm instead of the fused pair."""
+    assert "ddpm_softmax_fwd" in rec.names and "ddpm_softmax_bwd" in rec.names, "W17: no ddpm_softmax_fwd / _bwd"
+    assert "ddpm_attention_fwd_lse" not in rec.names and "ddpm_attention_bwd" not in rec.names
+    sm = sorted({s[1][-3:] for s in rec.sigs if s[0] == "ddpm_softmax_fwd"})
+    assert all(L == 120 and dt == LR.BF16 for _, L, dt in sm), sm
+
+
 def _check_w12(rec):
     gn = [s for s in rec.sigs if s[0] == "ddpm_groupnorm_silu_bwd" and s[1][13] == 64 * 64]
     assert gn, "W12: no GroupNorm backward at HW = 4096"
@@ -100,6 +122,10 @@ def test_every_launch_of_the_step_matches_float64(key, monkeypatch):
         _check_w9(rec)
     if key == "W12":
         _check_w12(rec)
+    if key == "W14":
+        _check_w14(rec, variants)
+    if key == "W17":
+        _check_w17(rec)
     rows, bad, seen = [], [], set()
     for i, s in enumerate(rec.sigs):
         if s[0] not in LR.REPLAY or LR.geometry(s) in seen:

@@ -1,7 +1,8 @@
 """Host check (CPU) of tests/launch_replay.py, the replay-against-float64 machinery of tests/test_step_launches_gpu.py.
 
-The four workloads of the GPU test run through the host-emulated engine (tests/abi_emulator.py) at batch 2 (CelebA-HQ at 128x128 instead of
-256x256: its geometry does not change how the contract is read), their launches are recorded, and every recorded signature of a
+The benchmarked workloads of the GPU test, their fp32 twins and the non-square workloads W14-W17 run through the host-emulated engine
+(tests/abi_emulator.py) at batch 2 (CelebA-HQ at 128x128 instead of 256x256: its geometry does not change how the contract is read),
+their launches are recorded, and every recorded signature of a
 replayed entry is replayed against the emulator.  This shows, before any GPU time, that the replay builders size their buffers, read
 pitches, epilogue terms, output modes and slab workspaces the way include/ddpm_hip.h states them — two independent restatements
 (the emulator and the float64 references) must agree within the per-element bars — and that no emulated write leaves the extents the
@@ -24,7 +25,8 @@ pytestmark = pytest.mark.skipif(not os.path.exists(_hip.LIB_PATH), reason="libdd
 # where |mean| >> std): its own rounding may exceed a bar written for the kernels by a small factor.  A misread pitch, operand or
 # epilogue term is off by the size of the value itself, 10^3..10^7 bars.
 HOST_SLACK = 4.0
-HOST_SIZE = {"W1": (2, 32), "W2": (2, 32), "W3": (2, 128), "W4": (2, 64), "W5": (2, 32), "W6": (2, 32), "W7": (2, 128), "W8": (2, 64)}
+HOST_SIZE = {"W1": (2, 32), "W2": (2, 32), "W3": (2, 128), "W4": (2, 64), "W5": (2, 32), "W6": (2, 32), "W7": (2, 128), "W8": (2, 64),
+             "W14": (2, (16, 48)), "W15": (2, (16, 48)), "W16": (2, (48, 16)), "W17": (2, (24, 20))}      # the non-square workloads
 
 
 def test_replay_builders_agree_with_the_emulator_on_every_recorded_signature(monkeypatch):
@@ -59,6 +61,19 @@ def test_synthetic_signatures_agree_with_the_emulator(sig, monkeypatch):
     """Every replayer, including those of entries no recorded workload launches, meets the emulator at its edge geometries."""
     abi_emulator.install(monkeypatch, _hip)
     assert sig[0] in LR.REPLAY and sig[0] not in LR.COVERED_ELSEWHERE
+    r = LR.replay(sig, "cpu")
+    assert r.worst <= HOST_SLACK, f"{LR.short(sig)}: {r.where} err/bar {r.worst:.3g}"
+
+
+@pytest.mark.parametrize("row", LR.ODD_GEOMETRY, ids=lambda row: LR.short(row[0]))
+def test_odd_geometry_signatures_agree_with_the_emulator_and_name_their_kernel(row, monkeypatch):
+    """launch_replay.ODD_GEOMETRY (non-square images, pixel and token counts that are no power of two) before any GPU time: the float64
+    replayers meet the emulator at these shapes, and the dispatch queries (pure host functions) send each row to the kernel the table
+    names, so that the GPU test of the same rows runs the kernels it means to."""
+    sig, variant = row
+    abi_emulator.install(monkeypatch, _hip)
+    assert sig[0] in LR.REPLAY
+    assert LR.variant_of(sig) == variant, f"{LR.short(sig)}: dispatched to {LR.variant_of(sig)}, the table names {variant}"
     r = LR.replay(sig, "cpu")
     assert r.worst <= HOST_SLACK, f"{LR.short(sig)}: {r.where} err/bar {r.worst:.3g}"
 
@@ -110,6 +125,22 @@ def test_error_model_bars_bite_at_the_scale_of_a_one_percent_kernel_error(monkey
         v[:, 63] += abi_emulator.f32(bias, 64)[63] * 2.0 ** -4
         ys.set(v)
     monkeypatch.setattr(emu, "ddpm_conv2d_nhwc", skewed)
+    assert LR.replay(sig, "cpu").worst > 1.0
+
+
+def test_conv_bar_bites_on_height_and_width_swapped(monkeypatch):
+    """A 3x3 conv that reads its 16 x 48 image as 48 x 16 (H and W swapped: same pixel count, same extents, nothing out of bounds) must
+    exceed its bar; on a square image the swap is invisible, which is why the non-square rows exist."""
+    emu = abi_emulator.install(monkeypatch, _hip)
+    sig = next(s for s, _ in LR.ODD_GEOMETRY if s[0] == "ddpm_conv2d_nhwc" and s[1][11:13] == (16, 48))
+    assert LR.replay(sig, "cpu").worst <= 1.0
+    real = emu.ddpm_conv2d_nhwc
+
+    def swapped(*a):
+        a = list(a)
+        a[11], a[12], a[14], a[15] = a[12], a[11], a[15], a[14]          # H <-> W, Ho <-> Wo
+        real(*a)
+    monkeypatch.setattr(emu, "ddpm_conv2d_nhwc", swapped)
     assert LR.replay(sig, "cpu").worst > 1.0
 
 
