@@ -2,6 +2,7 @@
 // Wave = 64 lanes everywhere in this tree; nothing here is meant to build for another target.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 #include <stdint.h>
 
 #define DDPM_OK 0
@@ -148,6 +149,34 @@ struct DevOnce {
     bool operator!() const { return !(mask.load(std::memory_order_acquire) & bit()); }
     DevOnce& operator=(bool) { mask.fetch_or(bit(), std::memory_order_release); return *this; }
 };
+
+// ---- every kernel launch of the library goes through ddpm_launch (the hipLaunchKernelGGL spelling at the launch sites maps to it).
+// Outside the plan executor it is the plain launch.  The executor (plan.hip) arms g_ddpm_launch_edge around an entry whose kernels a
+// later ddpm_stream_order of the same segment waits for: a launch on the armed stream then carries the edge's event as its completion
+// event (hipExtLaunchKernel's stopEvent), so the waiting stream is released by the producing kernel's own dispatch instead of by a
+// marker enqueued behind it.  An entry that launches several kernels attaches the event to each; a wait binds to the last.
+// (Only ddpm_plan_run arms it, and a hipGraph capture never runs under the executor: a captured launch is always the plain one.)
+struct DdpmLaunchEdge {
+    hipStream_t stream = nullptr;
+    hipEvent_t event = nullptr;
+    bool armed = false;
+    bool attached = false;       // set by the wrapper: at least one launch carried the event
+};
+extern thread_local DdpmLaunchEdge g_ddpm_launch_edge;
+
+template <class... P> static inline void ddpm_launch_with_event(DdpmLaunchEdge& edge, void (*kernel)(P...), dim3 grid, dim3 block, unsigned lds,
+                                                                hipStream_t st, P... formal) {
+    void* args[sizeof...(P) + 1] = {(void*)&formal..., nullptr};
+    if (hipExtLaunchKernel((const void*)kernel, grid, block, args, lds, st, nullptr, edge.event, 0) == hipSuccess) edge.attached = true;
+}
+template <class... P, class... A> static inline void ddpm_launch(void (*kernel)(P...), dim3 grid, dim3 block, unsigned lds, hipStream_t st, A&&... args) {
+    static_assert(sizeof...(P) == sizeof...(A), "kernel argument count");
+    DdpmLaunchEdge& edge = g_ddpm_launch_edge;
+    if (edge.armed && edge.stream == st) ddpm_launch_with_event<P...>(edge, kernel, grid, block, lds, st, static_cast<P>(args)...);
+    else kernel<<<grid, block, lds, st>>>(args...);
+}
+#undef hipLaunchKernelGGL
+#define hipLaunchKernelGGL(kernel, grid, block, lds, stream, ...) ddpm_launch(kernel, dim3(grid), dim3(block), (unsigned)(lds), stream, __VA_ARGS__)
 
 static inline int check_launch() { return hipGetLastError() == hipSuccess ? DDPM_OK : DDPM_ERR_LAUNCH; }
 static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
