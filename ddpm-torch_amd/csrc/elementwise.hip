@@ -4,6 +4,7 @@
 // no synchronisation — all entry points enqueue on the caller's stream and return.
 #include "common.h"
 #include <stdlib.h>
+#include <math.h>
 
 static inline int grid_for(long long n, int block = 256, int cap = 256 * 16) {
     long long g = (n + block - 1) / block;
@@ -572,6 +573,181 @@ extern "C" int ddpm_vlb_terms_bwd(const float* x_0, const float* x_t, const floa
     VlbTables tb{sqrt_recip_ab, sqrt_recip_m1_ab, post_coef1, post_coef2, post_logvar, model_logvar};
     hipLaunchKernelGGL(vlb_terms_bwd_kernel, dim3(grid_for((long long)B * n)), dim3(256), 0, (hipStream_t)stream, x_0, x_t, model_out, t, tb, gloss, gout,
                        B, n, mean_type, T);
+    return check_launch();
+}
+
+// ------------------------------------------------------------------ bits/dim evaluation (GaussianDiffusion.calc_all_bpd, diffusion.py:252-268)
+// One step of the evaluation loop behind the network: the bound term L_t of vlb_terms_kernel (same vlb_model_mean, same expressions, and in
+// the 256-thread layout the same reduction) AND mean_i (pred_x_0 - x_0)^2 from the one pass over x_0, x_t, model_out; pred_x_0 is never
+// stored.  Both land in column t[b] of their [B][ld] tables, so the T-step loop needs no host round trip and no column copy.  A sample whose
+// t is outside [0, T) has no column: it writes nothing (the caller pre-fills the tables with NaN).  decoder 1 = the toy pipeline's
+// continuous Gaussian likelihood at t = 0 (functions.py:68-72).  No atomics, fixed reduction order.
+struct BpdConst { VlbCoef k; float dlv, e_dlv, inv_var2, inv_std; };
+__device__ __forceinline__ BpdConst bpd_const(const VlbTables& tb, long long tt) {
+    BpdConst c;
+    c.k = VlbCoef{tb.recip[tt], tb.recip_m1[tt], tb.coef1[tt], tb.coef2[tt], tb.post_logvar[tt], tb.model_logvar[tt]};
+    c.dlv = c.k.lv1 - c.k.lv2; c.e_dlv = expf(c.dlv); c.inv_var2 = expf(-c.k.lv2); c.inv_std = expf(-0.5f * c.k.lv2);
+    return c;
+}
+__device__ __forceinline__ void bpd_elem(const BpdConst& c, long long tt, int mean_type, int clip, int decoder, float x, float xti, float o,
+                                         float& term, float& sq) {
+    const VlbCoef& k = c.k;
+    float mean, x0p;
+    vlb_model_mean(k, mean_type, clip, xti, o, mean, x0p);
+    if (tt > 0) {
+        const float m1 = __fadd_rn(__fmul_rn(k.c1, x), __fmul_rn(k.c2, xti)), d = m1 - mean;
+        term = 0.5f * ((-1.0f - c.dlv) + d * d * c.inv_var2 + c.e_dlv);
+    } else if (decoder == 0) {
+        const float xc = x - mean;
+        const float cu = x > 0.999f ? 1.0f : vlb_cdf(c.inv_std * (xc + (1.0f / 255.0f)));
+        const float cl = x < -0.999f ? 0.0f : vlb_cdf(c.inv_std * (xc - (1.0f / 255.0f)));
+        term = -logf(fmaxf(cu - cl - 1e-12f, 0.f) + 1e-12f);
+    } else {
+        const float xc = x - mean;
+        term = 0.5f * (xc * xc * c.inv_var2 + 1.8378770664093453f + k.lv2);          // ln(2 pi)
+    }
+    const float e = x0p - x;
+    sq = e * e;
+}
+struct BpdArgs {
+    const float *x0, *xt, *out;
+    const long long* t;
+    VlbTables tb;
+    float *losses, *mses;
+    int B, n, ld, mean_type, clip, decoder, T;
+};
+// rows of n <= 64 elements: one wave per row, four rows per block (the toy evaluates tens of thousands of 2-element rows)
+__global__ __launch_bounds__(256) void bpd_terms_wave_kernel(BpdArgs a) {
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (b >= a.B) return;
+    const long long tt = a.t[b];
+    if ((unsigned long long)tt >= (unsigned long long)a.T) return;
+    const long long base = (long long)b * a.n;
+    const BpdConst c = bpd_const(a.tb, tt);
+    float acc = 0.f, acc2 = 0.f;
+    for (int i = lane; i < a.n; i += 64) {
+        float term, sq;
+        bpd_elem(c, tt, a.mean_type, a.clip, a.decoder, a.x0[base + i], a.xt[base + i], a.out[base + i], term, sq);
+        acc += term; acc2 += sq;
+    }
+    acc = wave_sum(acc); acc2 = wave_sum(acc2);
+    if (lane == 0) {
+        a.losses[(long long)b * a.ld + tt] = acc / (float)a.n / 0.6931471805599453f;
+        a.mses[(long long)b * a.ld + tt] = acc2 / (float)a.n;
+    }
+}
+// one block per row.  256 threads (n < 16384): element order and reduction tree of vlb_terms_kernel.  1024 threads (n >= 16384): 16-byte
+// loads, two vectors of each operand in flight per thread, when the three row bases are 16-byte aligned; the scalar form otherwise.
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void bpd_terms_kernel(BpdArgs a) {
+    constexpr int WAVES = THREADS / 64;
+    __shared__ float sh[2][WAVES];
+    const int b = blockIdx.x;
+    const long long tt = a.t[b];
+    if ((unsigned long long)tt >= (unsigned long long)a.T) return;          // uniform over the block
+    const long long base = (long long)b * a.n;
+    const float *x0 = a.x0 + base, *xt = a.xt + base, *out = a.out + base;
+    const BpdConst c = bpd_const(a.tb, tt);
+    float acc = 0.f, acc2 = 0.f;
+    int nv = 0;
+    if (THREADS == 1024) {
+        const bool al = ((reinterpret_cast<unsigned long long>(x0) | reinterpret_cast<unsigned long long>(xt) | reinterpret_cast<unsigned long long>(out)) & 15) == 0;
+        nv = al ? a.n >> 2 : 0;
+        int i = threadIdx.x;
+        for (; i + THREADS < nv; i += 2 * THREADS) {
+            f32x4 vx[2], vt[2], vo[2];
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                vx[u] = reinterpret_cast<const f32x4*>(x0)[i + u * THREADS];
+                vt[u] = reinterpret_cast<const f32x4*>(xt)[i + u * THREADS];
+                vo[u] = reinterpret_cast<const f32x4*>(out)[i + u * THREADS];
+            }
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    float term, sq;
+                    bpd_elem(c, tt, a.mean_type, a.clip, a.decoder, vx[u][e], vt[u][e], vo[u][e], term, sq);
+                    acc += term; acc2 += sq;
+                }
+        }
+        for (; i < nv; i += THREADS) {
+            const f32x4 vx = reinterpret_cast<const f32x4*>(x0)[i], vt = reinterpret_cast<const f32x4*>(xt)[i], vo = reinterpret_cast<const f32x4*>(out)[i];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float term, sq;
+                bpd_elem(c, tt, a.mean_type, a.clip, a.decoder, vx[e], vt[e], vo[e], term, sq);
+                acc += term; acc2 += sq;
+            }
+        }
+    }
+    for (int i = (nv << 2) + threadIdx.x; i < a.n; i += THREADS) {
+        float term, sq;
+        bpd_elem(c, tt, a.mean_type, a.clip, a.decoder, x0[i], xt[i], out[i], term, sq);
+        acc += term; acc2 += sq;
+    }
+    acc = wave_sum(acc); acc2 = wave_sum(acc2);
+    if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = acc; sh[1][threadIdx.x >> 6] = acc2; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float tot, tot2;
+        if (WAVES == 4) {
+            tot = (sh[0][0] + sh[0][1]) + (sh[0][2] + sh[0][3]);
+            tot2 = (sh[1][0] + sh[1][1]) + (sh[1][2] + sh[1][3]);
+        } else {
+            tot = 0.f; tot2 = 0.f;
+            for (int w = 0; w < WAVES; ++w) { tot += sh[0][w]; tot2 += sh[1][w]; }
+        }
+        a.losses[(long long)b * a.ld + tt] = tot / (float)a.n / 0.6931471805599453f;
+        a.mses[(long long)b * a.ld + tt] = tot2 / (float)a.n;
+    }
+}
+extern "C" int ddpm_bpd_terms(const float* x_0, const float* x_t, const float* model_out, const long long* t,
+                              const float* sqrt_recip_ab, const float* sqrt_recip_m1_ab, const float* post_coef1, const float* post_coef2,
+                              const float* post_logvar, const float* model_logvar, float* losses, float* mses,
+                              int B, int n, int ld, int mean_type, int clip, int decoder, int T, void* stream) {
+    if (!x_0 || !x_t || !model_out || !t || !sqrt_recip_ab || !sqrt_recip_m1_ab || !post_coef1 || !post_coef2 || !post_logvar || !model_logvar || !losses || !mses)
+        return DDPM_ERR_NULL;
+    if (B <= 0 || n <= 0 || T <= 0 || ld < T || mean_type < 0 || mean_type > 2 || decoder < 0 || decoder > 1) return DDPM_ERR_SHAPE;
+    const BpdArgs a{x_0, x_t, model_out, t, VlbTables{sqrt_recip_ab, sqrt_recip_m1_ab, post_coef1, post_coef2, post_logvar, model_logvar},
+                    losses, mses, B, n, ld, mean_type, clip, decoder, T};
+    if (n <= 64) hipLaunchKernelGGL(bpd_terms_wave_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, a);
+    else if (n < 16384) hipLaunchKernelGGL(bpd_terms_kernel<256>, dim3(B), dim3(256), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(bpd_terms_kernel<1024>, dim3(B), dim3(1024), 0, (hipStream_t)stream, a);
+    return check_launch();
+}
+// after the loop: prior[b] = mean_i KL(N(sqrt_ab_last x_0, 1 - ab_last) || N(0, 1)) / ln 2 (diffusion.py:245-250 with the tensors it meant:
+// normal_kl with mean2 = logvar2 = 0) and total[b] = sum_t losses[b][t] + prior[b]; one block per sample, fixed order.
+// normal_kl's 0.5 ((-1 - lv) + m^2 + e^lv) cancels: at T = 1000, lv = log(1 - ab_T) = -4e-5 and the three O(1) terms leave ~1e-5, which
+// fp32 gets to a few percent.  The part that does not depend on the element, e^lv - 1 - lv, is formed once in double on the host;
+// the kernel sums m^2 alone.
+__global__ __launch_bounds__(256) void bpd_finish_kernel(const float* __restrict__ x0, const float* __restrict__ losses, float* __restrict__ prior,
+                                                         float* __restrict__ total, int n, int T, int ld, float sqrt_ab, float var_part) {
+    __shared__ float sh[2][4];
+    const int b = blockIdx.x;
+    const float* x = x0 + (long long)b * n;
+    const float* row = losses + (long long)b * ld;
+    float acc = 0.f, sum = 0.f;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const float m = __fmul_rn(sqrt_ab, x[i]);
+        acc += m * m;
+    }
+    for (int i = threadIdx.x; i < T; i += 256) sum += row[i];
+    acc = wave_sum(acc); sum = wave_sum(sum);
+    if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = acc; sh[1][threadIdx.x >> 6] = sum; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const float pr = 0.5f * (((sh[0][0] + sh[0][1]) + (sh[0][2] + sh[0][3])) / (float)n + var_part) / 0.6931471805599453f;
+        prior[b] = pr;
+        total[b] = ((sh[1][0] + sh[1][1]) + (sh[1][2] + sh[1][3])) + pr;
+    }
+}
+extern "C" int ddpm_bpd_finish(const float* x_0, const float* losses, float* prior, float* total, int B, int n, int T, int ld,
+                               float sqrt_ab_last, float log_1m_ab_last, void* stream) {
+    if (!x_0 || !losses || !prior || !total) return DDPM_ERR_NULL;
+    if (B <= 0 || n <= 0 || T <= 0 || ld < T) return DDPM_ERR_SHAPE;
+    const float var_part = (float)(expm1((double)log_1m_ab_last) - (double)log_1m_ab_last);
+    hipLaunchKernelGGL(bpd_finish_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, x_0, losses, prior, total, n, T, ld, sqrt_ab_last, var_part);
     return check_launch();
 }
 

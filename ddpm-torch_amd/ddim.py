@@ -57,6 +57,10 @@ class DDIM(ddpm_torch.GaussianDiffusion):
         """ddim.py:96-113: S = len(subsequence) steps, same RNG consumption order as the ancestral loop."""
         return self._sample_loop(denoise_fn, shape, device, noise, seed)
 
+    def calc_all_bpd(self, denoise_fn, x_0, clip_denoised=True, seed=None, noise_stream=None):
+        raise NotImplementedError("the variational bound is defined on the full chain; DDIM's tables are those of a sub-sequence — "
+                                  "evaluate bits/dim with the GaussianDiffusion the sampler was derived from")
+
     @classmethod
     def from_ddpm(cls, diffusion, eta, subsequence):
         keys = ("betas", "model_mean_type", "model_var_type", "loss_type")

@@ -186,6 +186,11 @@ class GaussianDiffusion:
              self._tab("sqrt_one_minus_alphas_bar", x_0.device).data_ptr(), out.data_ptr(), B, x_0[0].numel(), len(self.sqrt_alphas_bar), _hip.stream())
         return out
 
+    def q_mean_var(self, x_0, t):
+        """diffusion.py:86-90: mean, variance and log-variance of q(x_t | x_0)."""
+        e = self._extract
+        return e(self.sqrt_alphas_bar, t, x_0) * x_0, e(1.0 - self.alphas_bar, t, x_0), e(torch.log(1.0 - self.alphas_bar), t, x_0)
+
     def q_posterior_mean_var(self, x_0, x_t, t):
         e = self._extract
         mean = e(self.posterior_mean_coef1, t, x_0) * x_0 + e(self.posterior_mean_coef2, t, x_0) * x_t
@@ -335,15 +340,16 @@ class GaussianDiffusion:
             return None
         return [m.engine() for m in denoise_fn.modules() if isinstance(m, UNet)]
 
-    def _graph_entry(self, denoise_fn, shape, device, default_rng, external_z=False):
+    def _graph_entry(self, denoise_fn, shape, device, default_rng, external_z=False, bpd=None):
         """Cached captured step for (denoiser, shape), capturing it on first use; None when capture is not possible.
-        ``external_z`` (parity tests): the step does not draw its noise, the caller fills the captured ``z`` buffer before every replay."""
+        ``external_z`` (parity tests): the step does not draw its noise, the caller fills the captured ``z`` buffer before every replay.
+        ``bpd``: None for the sampling step, ``(clip_denoised,)`` for the bits/dim evaluation step of ``calc_all_bpd``."""
         cache = self.__dict__.setdefault("_sample_graphs", {})
         engines = self._engines_of(denoise_fn)
         # engine serials: model.to() / .float() / set_compute_dtype() re-create the engine (packed weights, workspaces) — a step
         # captured against the previous one points at freed memory and must never be replayed
         # ... and so is the time-bias table the step gathers from: a sampler with a longer schedule re-allocates it
-        key = (id(denoise_fn), shape, str(device), (default_rng, external_z), getattr(denoise_fn, "training", None),
+        key = (id(denoise_fn), shape, str(device), (default_rng, external_z, bpd), getattr(denoise_fn, "training", None),
                tuple((e.serial, e.T, e.tt.data_ptr() if e.tt_on and e.tt is not None else 0) for e in engines) if engines else None)
         ent = cache.get(key)
         if ent is not None and ent["ref"]() is not denoise_fn:
@@ -353,7 +359,10 @@ class GaussianDiffusion:
             for k in [k for k, v in cache.items() if v["ref"]() is denoise_fn and k[5] and {q[0] for q in k[5]} != live]:
                 cache.pop(k)                                      # entries of this denoiser's earlier engines: dead weight (and dead pointers)
         if ent is None:
-            ent = self._capture_sample_step(denoise_fn, shape, device, default_rng, external_z)
+            if bpd is None:
+                ent = self._capture_sample_step(denoise_fn, shape, device, default_rng, external_z)
+            else:
+                ent = self._capture_bpd_step(denoise_fn, shape, device, default_rng, external_z, *bpd)
             if ent is not None and engines is not None:           # arbitrary callables are captured per call: nothing tells us when their weights change
                 import weakref
                 ent["ref"] = weakref.ref(denoise_fn)
@@ -414,6 +423,15 @@ class GaussianDiffusion:
                       x_t.data_ptr(), 0, B, n, mean_code, int(self.clip_sampling), T, _hip.stream())   # in place: each element is read once, then written
             _hip.call("ddpm_add_i64", t.data_ptr(), B, -1, _hip.stream())
 
+        graph = self._capture_step(dev, rng, body, "sampling")
+        if graph is None:
+            return None
+        return {"x_t": x_t, "t": t, "z": z, "rng": rng, "graph": graph, "ref": lambda: denoise_fn}
+
+    @staticmethod
+    def _capture_step(dev, rng, body, what):
+        """Warm ``body`` up on a side stream, then capture it into a SegmentedGraph (None, with a warning, when that is not possible; the
+        generator ``body`` draws from — ``rng``, or the device's default one — is left where it was either way)."""
         gen = rng if rng is not None else torch.cuda.default_generators[dev.index if dev.index is not None else torch.cuda.current_device()]
         snap_rng = gen.get_state()
         try:
@@ -429,11 +447,11 @@ class GaussianDiffusion:
             graph.capture(body)
         except Exception as e:                                   # capture not possible for this denoise_fn: eager loop instead
             import warnings
-            warnings.warn(f"hipGraph capture of the sampling step failed ({type(e).__name__}: {e}); running the eager loop")
+            warnings.warn(f"hipGraph capture of the {what} step failed ({type(e).__name__}: {e}); running the eager loop")
             torch.cuda.synchronize(dev)
             gen.set_state(snap_rng)
             return None
-        return {"x_t": x_t, "t": t, "z": z, "rng": rng, "graph": graph, "ref": lambda: denoise_fn}
+        return graph
 
     def _num_steps(self):
         return self.timesteps
@@ -462,3 +480,93 @@ class GaussianDiffusion:
 
         x = self._sample_loop(denoise_fn, shape, device, noise, seed, on_step=keep, z_stream=z_stream)
         return x.cpu(), preds
+
+    # ------------------------------------------------------------------ negative log-likelihood in bits per dimension
+    # t = 0 likelihood of the evaluation: 0 = discretized Gaussian (functions.py:49-65); the 2-D toy subclass uses 1, the continuous one
+    bpd_decoder = 0
+
+    def _bpd_finish(self, x_0, losses):
+        """(prior [B], total [B]) from x_0 and the [B, T] table of bound terms: one launch (csrc/elementwise.hip `bpd_finish_kernel`)."""
+        B, n = x_0.shape[0], x_0[0].numel()
+        T, last = losses.shape[1], self.timesteps - 1
+        prior = torch.empty(B, dtype=torch.float32, device=x_0.device)
+        total = torch.empty_like(prior)
+        _hip.call("ddpm_bpd_finish", x_0.data_ptr(), losses.data_ptr(), prior.data_ptr(), total.data_ptr(), B, n, T, losses.stride(0),
+                  float(self.sqrt_alphas_bar[last].to(torch.float32)), float(torch.log(1.0 - self.alphas_bar[last]).to(torch.float32)), _hip.stream())
+        return prior, total
+
+    @torch.inference_mode()
+    def _prior_bpd(self, x_0):
+        """diffusion.py:245-250 with the tensors it meant: KL(q(x_T | x_0) || N(0, I)) in bits per dimension, per sample [B]."""
+        x_0, = self._prep(x_0)
+        # the prior is one output of ddpm_bpd_finish: give it a [B, 1] table of zeros to sum, and take the prior alone
+        return self._bpd_finish(x_0, torch.zeros((x_0.shape[0], 1), dtype=torch.float32, device=x_0.device))[0]
+
+    def _bpd_state(self, denoise_fn, shape, dev, rng, external_z, clip_denoised):
+        """Buffers of the evaluation loop and its step body: draw eps, q_sample, network, bound term + MSE into column t, t -= 1."""
+        x_0 = torch.zeros(shape, dtype=torch.float32, device=dev)
+        z, x_t = torch.zeros_like(x_0), torch.empty_like(x_0)       # zeros: with external noise the capture's warm-up runs before the first copy
+        B, n, T = shape[0], x_0[0].numel(), self.timesteps
+        t = torch.full((B,), T - 1, dtype=torch.int64, device=dev)
+        losses = torch.full((B, T), float("nan"), dtype=torch.float32, device=dev)
+        mses = torch.full_like(losses, float("nan"))
+        qtabs = [self._tab(n_, dev) for n_ in ("sqrt_alphas_bar", "sqrt_one_minus_alphas_bar")]
+        tabs = [self._tab(n_, dev) for n_ in _VLB_TABLES]
+        code, clip, decoder = _MEAN_CODE[self.model_mean_type], int(bool(clip_denoised)), self.bpd_decoder
+
+        def body(cut=None):
+            if not external_z:
+                z.normal_(generator=rng)
+            _hip.call("ddpm_q_sample", x_0.data_ptr(), z.data_ptr(), t.data_ptr(), *[tb.data_ptr() for tb in qtabs], x_t.data_ptr(), B, n, T, _hip.stream())
+            out = denoise_fn(x_t, self._model_t(t)).contiguous().float()
+            _hip.call("ddpm_bpd_terms", x_0.data_ptr(), x_t.data_ptr(), out.data_ptr(), t.data_ptr(), *[tb.data_ptr() for tb in tabs],
+                      losses.data_ptr(), mses.data_ptr(), B, n, T, code, clip, decoder, T, _hip.stream())
+            _hip.call("ddpm_add_i64", t.data_ptr(), B, -1, _hip.stream())
+
+        return {"x_0": x_0, "z": z, "t": t, "losses": losses, "mses": mses, "rng": rng, "body": body, "ref": lambda: denoise_fn}
+
+    def _capture_bpd_step(self, denoise_fn, shape, device, default_rng, external_z, clip_denoised):
+        rng = None if default_rng else torch.Generator(device)
+        ent = self._bpd_state(denoise_fn, shape, device, rng, external_z, clip_denoised)
+        ent["graph"] = self._capture_step(device, rng, ent["body"], "bits/dim evaluation")
+        return ent if ent["graph"] is not None else None
+
+    def calc_all_bpd(self, denoise_fn, x_0, clip_denoised=True, seed=None, noise_stream=None):
+        """diffusion.py:252-268 as it was meant: ``(total_bpd [B], losses [B, T], prior_bpd [B], mses [B, T])`` with
+        ``total = L_T + sum_t L_t``, float32 ON ``x_0``'s DEVICE (the reference preallocates on the host and would synchronise T times).
+
+        For t = T-1 ... 0: one standard-normal draw of x_0's shape (from a generator seeded with ``seed`` on x_0's device, else the default
+        one; ``noise_stream`` — parity tests — is an iterator of per-step noise tensors that replaces the draws), q_sample, the network, and
+        one fused kernel that puts L_t and mean (pred_x_0 - x_0)^2 into column t.  The step is captured once and replayed T times like the
+        sampling step (same cache, same fallback to the eager loop; DDPM_TORCH_AMD_GRAPH=0 forces eager); both forms give the same bits."""
+        with torch.inference_mode(), self._time_tables(denoise_fn):
+            return self._calc_all_bpd_impl(denoise_fn, x_0, clip_denoised, seed, noise_stream)
+
+    def _calc_all_bpd_impl(self, denoise_fn, x_0, clip_denoised, seed, noise_stream):
+        x_0, = self._prep(x_0)
+        dev, shape, T = x_0.device, tuple(x_0.shape), self.timesteps
+        clip_denoised, external = bool(clip_denoised), noise_stream is not None
+        ent = None
+        if (T >= 4 and dev.type == "cuda" and os.environ.get("DDPM_TORCH_AMD_GRAPH", "1") != "0"
+                and not torch.cuda.is_current_stream_capturing()):
+            ent = self._graph_entry(denoise_fn, shape, dev, default_rng=seed is None, external_z=external, bpd=(clip_denoised,))
+        if ent is not None:
+            for e in self._engines_of(denoise_fn) or ():
+                e.ensure_fresh()
+            step = ent["graph"].replay
+        else:
+            ent = self._bpd_state(denoise_fn, shape, dev, torch.Generator(dev) if seed is not None else None, external, clip_denoised)
+            step = ent["body"]
+        if ent["rng"] is not None:
+            ent["rng"].manual_seed(seed)
+        ent["x_0"].copy_(x_0)
+        ent["t"].fill_(T - 1)
+        ent["losses"].fill_(float("nan"))          # a sample the kernel refuses (t outside the tables) shows in every total
+        ent["mses"].fill_(float("nan"))
+        for _ in range(T):
+            if external:
+                ent["z"].copy_(next(noise_stream))
+            step()
+        losses, mses = ent["losses"].clone(), ent["mses"].clone()
+        prior, total = self._bpd_finish(x_0, losses)
+        return total, losses, prior, mses

@@ -8,6 +8,7 @@ __all__ = ["GaussianDiffusion"]
 
 class GaussianDiffusion(diffusion.GaussianDiffusion):
     clip_sampling = False
+    bpd_decoder = 1            # t = 0 term of the bound: continuous Gaussian likelihood (toy/diffusion.py:61)
 
     def __init__(self, betas, model_mean_type, model_var_type, loss_type, **kwargs):
         if loss_type == "kl":
@@ -42,3 +43,8 @@ class GaussianDiffusion(diffusion.GaussianDiffusion):
     def _sample_loop(self, denoise_fn, shape, device, noise, seed, on_step=None, z_stream=None):
         self._bind(denoise_fn)
         return super()._sample_loop(denoise_fn, shape, device, noise, seed, on_step, z_stream)
+
+    def calc_all_bpd(self, denoise_fn, x_0, clip_denoised=True, seed=None, noise_stream=None):
+        """The image loop with the continuous-Gaussian decoder at t = 0; the x_0 estimate is never clipped (toy/diffusion.py:31)."""
+        self._bind(denoise_fn)
+        return super().calc_all_bpd(denoise_fn, x_0, clip_denoised=False, seed=seed, noise_stream=noise_stream)

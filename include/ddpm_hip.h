@@ -200,6 +200,20 @@ int ddpm_vlb_terms_bwd(const float* x_0, const float* x_t, const float* model_ou
                        const float* sqrt_recip_ab, const float* sqrt_recip_m1_ab, const float* post_coef1, const float* post_coef2,
                        const float* post_logvar, const float* model_logvar, const float* gloss, float* gout,
                        int B, int n, int mean_type, int T, void* stream);
+/* One step of `calc_all_bpd` (ddpm_torch/diffusion.py:252-268) behind the network.  Per sample b with 0 <= t[b] < T:
+ *   losses[b*ld + t[b]] = the value ddpm_vlb_terms computes (same model mean, same operation order; decoder 0 = the discretized Gaussian
+ *                         at t = 0, decoder 1 = the toy pipeline's continuous Gaussian, functions.py:68-72: 0.5 (d^2 e^-logvar + ln 2pi + logvar))
+ *   mses[b*ld + t[b]]   = mean_i (pred_x_0[b][i] - x_0[b][i])^2, pred_x_0 clipped to [-1, 1] when `clip` is set and never stored
+ * from one pass over x_0, x_t, model_out.  A sample whose t is outside [0, T) writes nothing (the caller pre-fills both tables with NaN).
+ * ld >= T is the row pitch of both tables.  No atomics, fixed reduction order: repeated launches are bit-identical.
+ * ddpm_bpd_finish: prior[b] = mean_i normal_kl(sqrt_ab_last * x_0, log_1m_ab_last, 0, 0) / ln 2 (:245-250),
+ *                  total[b] = (sum_t losses[b*ld + t], fixed order) + prior[b]. */
+int ddpm_bpd_terms(const float* x_0, const float* x_t, const float* model_out, const long long* t,
+                   const float* sqrt_recip_ab, const float* sqrt_recip_m1_ab, const float* post_coef1, const float* post_coef2,
+                   const float* post_logvar, const float* model_logvar, float* losses, float* mses,
+                   int B, int n, int ld, int mean_type, int clip, int decoder, int T, void* stream);
+int ddpm_bpd_finish(const float* x_0, const float* losses, float* prior, float* total, int B, int n, int T, int ld,
+                    float sqrt_ab_last, float log_1m_ab_last, void* stream);
 /* subsequence.gather(0, t) (ddim.py:101) and t += delta (t.fill_ in diffusion.py:172, device-side for graph replay) */
 int ddpm_gather_i64(const long long* idx, const long long* map, long long* out, int B, void* stream);
 int ddpm_add_i64(long long* t, int B, long long delta, void* stream);
