@@ -21,12 +21,8 @@
 
 namespace {
 
-constexpr unsigned OOB = 0x7ffffff0u;
 constexpr int RB = 128;                        // rows of the score block owned by a workgroup
 constexpr int NT = 512;
-
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 struct Opnd {                                   // [L rows][C] bf16, row pitch ld (elements); rsrc spans one image
     __amdgpu_buffer_rsrc_t rsrc;
@@ -34,12 +30,9 @@ struct Opnd {                                   // [L rows][C] bf16, row pitch l
 };
 
 __device__ __forceinline__ Opnd make_opnd(const bf16_t* base, long long ld, int L, int C) {
-    const unsigned long long ad = (unsigned long long)base;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)ad), hi = __builtin_amdgcn_readfirstlane((unsigned)(ad >> 32));
-    const long long bytes = ((long long)(L - 1) * ld + C) * 2;
     Opnd o;
-    o.rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0,
-                                               __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000);
+    const UniformAddr u = uniform_addr(base);
+    o.rsrc = buffer_rsrc_at(u, (unsigned)(((long long)(L - 1) * ld + C) * 2));
     o.ld = ld;
     return o;
 }
@@ -101,19 +94,6 @@ __device__ __forceinline__ void wait_vm_rt(int n) {
     default: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
     }
 }
-__device__ __forceinline__ u32x4 lds_rd16(unsigned addr) {
-    u32x4 v;
-    asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr) : "memory");
-    return v;
-}
-__device__ __forceinline__ uint2 lds_rd_tr(unsigned addr) {          // ds_read_b64_tr_b16: see read_frag<T, true> in gemm.hip
-    uint2 v;
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(addr) : "memory");
-    return v;
-}
-// (the fence keeps hipcc from moving an MFMA, which depends on the reads' registers but not on the wait, ahead of it)
-__device__ __forceinline__ void lds_wait() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_sched_barrier(0); }
-template <int N> __device__ __forceinline__ void lds_wait_n() { asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory"); __builtin_amdgcn_sched_barrier(0); }
 
 #ifdef ATTN_TIMING
 __device__ unsigned long long* g_attn_timing = nullptr;        // debug builds only (scripts/attn_timeline.py): [block][8] stamps
@@ -135,7 +115,7 @@ __device__ __forceinline__ void product_nt(P1<NJ>& t, const Opnd& X, int r0, con
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nyi = (Lpad + 63) / 64;                            // DMA instructions per thread for the Y chunk (rows >= L: zeros)
     const int xs_bytes = RB * 128, slot_bytes = p1_slot_bytes(Lpad), per = 2 + nyi;
-    const unsigned lds0 = (unsigned)(size_t)lds;
+    const unsigned lds0 = lds_addr(lds);
     const int nchunks = (C + 63) / 64;
     // source offsets of this thread's vectors at chunk 0 (LDS position v = tid + 512 i -> row v >> 3, logical chunk (v & 7) ^ ((row >> 1) & 7))
     unsigned xo[2], yo[4]; int xc[2], yc[4];
@@ -149,23 +129,23 @@ __device__ __forceinline__ void product_nt(P1<NJ>& t, const Opnd& X, int r0, con
     for (int i = 0; i < 4; ++i) {
         const int v = tid + NT * i, row = v >> 3;
         yc[i] = ((v & 7) ^ ((row >> 1) & 7)) * 8;
-        yo[i] = row < Lpad ? (unsigned)(((long long)row * Y.ld + yc[i]) * 2) : OOB;
+        yo[i] = row < Lpad ? (unsigned)(((long long)row * Y.ld + yc[i]) * 2) : BUF_OOB;
     }
     auto issue = [&](int ch) {
         char* slot = lds + (ch % P1_RING) * slot_bytes;
         const int c0 = ch * 64;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            unsigned o = c0 + xc[i] < C ? xo[i] + (unsigned)(c0 * 2) : OOB;
+            unsigned o = c0 + xc[i] < C ? xo[i] + (unsigned)(c0 * 2) : BUF_OOB;
             asm volatile("" : "+v"(o));
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(X.rsrc, (__attribute__((address_space(3))) void*)(slot + (i * NT + wave * 64) * 16), 16, o, 0, 0, 0);
+            LDS_DMA16(X.rsrc, slot + (i * NT + wave * 64) * 16, o, 0);
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             if (i < nyi) {
-                unsigned o = (yo[i] != OOB && c0 + yc[i] < C) ? yo[i] + (unsigned)(c0 * 2) : OOB;
+                unsigned o = (yo[i] != BUF_OOB && c0 + yc[i] < C) ? yo[i] + (unsigned)(c0 * 2) : BUF_OOB;
                 asm volatile("" : "+v"(o));
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(Y.rsrc, (__attribute__((address_space(3))) void*)(slot + xs_bytes + (i * NT + wave * 64) * 16), 16, o, 0, 0, 0);
+                LDS_DMA16(Y.rsrc, slot + xs_bytes + (i * NT + wave * 64) * 16, o, 0);
             }
         }
     };
@@ -255,14 +235,14 @@ __device__ __forceinline__ void product_nn(f32x16 (&z)[2][NJ2], const char* tile
         char* slot = ring + (ch % P2_RING) * P2_SLOT;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            unsigned o = ch * KR + vkr[i] < L ? vo[i] + (unsigned)ch * kstep : OOB;
+            unsigned o = ch * KR + vkr[i] < L ? vo[i] + (unsigned)ch * kstep : BUF_OOB;
             asm volatile("" : "+v"(o));
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(Y.rsrc, (__attribute__((address_space(3))) void*)(slot + (i * NT + wave * 64) * 16), 16, o, 0, 0, 0);
+            LDS_DMA16(Y.rsrc, slot + (i * NT + wave * 64) * 16, o, 0);
         }
     };
     for (int c = 0; c < P2_RING - 1 && c < nchunks; ++c) issue(c);
     const int i16 = lane & 15;
-    const unsigned tile0 = (unsigned)(size_t)tile, ring0 = (unsigned)(size_t)ring;
+    const unsigned tile0 = lds_addr(tile), ring0 = lds_addr(ring);
     bool jok[NJ2];
 #pragma unroll
     for (int j = 0; j < NJ2; ++j) jok[j] = (wc + 4 * j) * 32 < C;
@@ -610,7 +590,7 @@ static int check_common(const void* qkv, long long ld, int B, int L, int C, int 
     if (dtype != DDPM_BF16) return DDPM_ERR_DTYPE;
     if (B <= 0 || L <= 0 || L > 256 || L % 16 || C <= 0 || C > 512 || C % 32 || ld < 3 * C) return DDPM_ERR_SHAPE;
     if (!aligned16(qkv) || ld % 8) return DDPM_ERR_ALIGN;
-    if ((long long)L * ld * 2 > 0x7ffffff0ll) return DDPM_ERR_SHAPE;
+    if ((long long)L * ld * 2 > BUF_OOB) return DDPM_ERR_SHAPE;
     return DDPM_OK;
 }
 

@@ -5,6 +5,7 @@
 One shared object, plain C ABI (include/ddpm_hip.h), no torch / pybind types.  The .so is git-ignored but travels
 with the tree to the GPU box.
 """
+import glob
 import os
 import subprocess
 import sys
@@ -24,7 +25,7 @@ def _stale(target, deps):
 
 def build(force=False, verbose=True):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    hdr = os.path.join(HERE, "common.h")
+    hdrs = sorted(glob.glob(os.path.join(HERE, "*.h")))                                  # common.h and what it includes (gfx950.h)
     inc = os.path.join(HERE, "..", "..", "include")
     abi = [os.path.join(inc, "ddpm_hip.h"), os.path.join(inc, "ddpm_hip_debug.h")]      # plan.hip generates its call thunks from these declarations
     objs = []
@@ -32,7 +33,7 @@ def build(force=False, verbose=True):
     for s in SOURCES:
         src, obj = os.path.join(HERE, s), os.path.join(HERE, s.replace(".hip", ".o"))
         objs.append(obj)
-        if force or _stale(obj, [src, hdr, *abi]):
+        if force or _stale(obj, [src, *hdrs, *abi]):
             cmd = [hipcc, *FLAGS, "-c", src, "-o", obj]
             if verbose:
                 print(" ".join(cmd), flush=True)

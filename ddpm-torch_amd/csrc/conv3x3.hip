@@ -21,8 +21,6 @@
 
 namespace {
 
-constexpr unsigned OOB = 0x7ffffff0u;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
@@ -66,17 +64,6 @@ template <int PATCH> struct Lds {
     static_assert(BYTES <= 160 * 1024, "LDS");
 };
 
-template <int N> __device__ __forceinline__ void wait_vm() {
-    static_assert(N >= 0 && N < 64, "vmcnt immediate");
-    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory");
-}
-
-__device__ __forceinline__ int logical_tile(int id, int total, int xcd) {       // see xcd_logical_id in gemm.hip
-    if (!xcd) return id;
-    const int per = total >> 3;
-    return id < (per << 3) ? (id & 7) * per + (id >> 3) : id;
-}
-
 struct TilePos { int img, py0, px0, tn; };
 
 #ifdef C3_TRACE
@@ -112,15 +99,9 @@ void conv3x3_stream_kernel(CsArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wn = wave / WM, wm = wave % WM;             // wave = 32 NIB channels x 32 NJ pixels
 
-    auto rsrc_of = [&](const void* p, unsigned extent) {
-        const unsigned long long ad = (unsigned long long)p;
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)ad), hi = __builtin_amdgcn_readfirstlane((unsigned)(ad >> 32));
-        return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0,
-                                                 __builtin_amdgcn_readfirstlane((int)extent), 0x00020000);
-    };
-    const __amdgpu_buffer_rsrc_t rx = rsrc_of(a.x, a.x_extent), rw = rsrc_of(a.w, a.w_extent);
-    const __amdgpu_buffer_rsrc_t rbias = rsrc_of(a.bias ? (const void*)a.bias : (const void*)a.w, a.bias ? (unsigned)(a.N * 4) : 0u);
-    const __amdgpu_buffer_rsrc_t rrow = rsrc_of(a.rowbias ? (const void*)a.rowbias : (const void*)a.w, a.rowbias ? a.rowbias_extent : 0u);
+    const __amdgpu_buffer_rsrc_t rx = buffer_rsrc(a.x, a.x_extent), rw = buffer_rsrc(a.w, a.w_extent);
+    const __amdgpu_buffer_rsrc_t rbias = buffer_rsrc(a.bias ? (const void*)a.bias : (const void*)a.w, a.bias ? (unsigned)(a.N * 4) : 0u);
+    const __amdgpu_buffer_rsrc_t rrow = buffer_rsrc(a.rowbias ? (const void*)a.rowbias : (const void*)a.w, a.rowbias ? a.rowbias_extent : 0u);
 
     // "+ residual" or "+= out": one extra bf16 tensor added in the epilogue
     const bool extra = a.res || a.accumulate;
@@ -128,7 +109,7 @@ void conv3x3_stream_kernel(CsArgs a) {
     const int my_tiles = a.total_tiles > (int)blockIdx.x ? (a.total_tiles - 1 - (int)blockIdx.x) / G + 1 : 0;
     if (my_tiles == 0) return;
     auto tile_pos = [&](int k) {
-        const int lid = logical_tile(blockIdx.x + k * G, a.total_tiles, a.xcd);
+        const int lid = xcd_logical_id(blockIdx.x + k * G, a.total_tiles, a.xcd);
         const int tmi = (int)fdiv((unsigned)lid, a.d_tiles_n);
         const int tpi = a.tiles_y * a.tiles_x;
         const int img = (int)fdiv((unsigned)tmi, a.d_tpi), pt = tmi - img * tpi;
@@ -154,7 +135,7 @@ void conv3x3_stream_kernel(CsArgs a) {
             const int lc = (v & 7) ^ (PATCH == 16 ? (hx >> 1) & 7 : ((hx >> 1) ^ ((hy & 1) << 2)) & 7);
             // nearest-neighbour 2x up-sampling folded into the gather: virtual pixel (iy, ix) is stored pixel (iy >> 1, ix >> 1)
             const int sy = iy >> a.ups, sx = ix >> a.ups;
-            ho[i] = ok ? ((unsigned)((t.img * (a.H >> a.ups) + sy) * (a.W >> a.ups) + sx) * (unsigned)a.x_ld + (unsigned)(lc * 8)) * 2u : OOB;     // < 2^31: checked by the launcher
+            ho[i] = ok ? ((unsigned)((t.img * (a.H >> a.ups) + sy) * (a.W >> a.ups) + sx) * (unsigned)a.x_ld + (unsigned)(lc * 8)) * 2u : BUF_OOB;     // < 2^31: checked by the launcher
         }
     };
     // one part of a tile's plan (the main loop rebuilds the plan for the NEXT tile part by part, each in the step that requests it —
@@ -169,12 +150,12 @@ void conv3x3_stream_kernel(CsArgs a) {
         const bool ok = hp < HP && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
         const int lc = (v & 7) ^ (PATCH == 16 ? (hx >> 1) & 7 : ((hx >> 1) ^ ((hy & 1) << 2)) & 7);
         const int sy = iy >> a.ups, sx = ix >> a.ups;
-        return ok ? ((unsigned)((t.img * (a.H >> a.ups) + sy) * (a.W >> a.ups) + sx) * (unsigned)a.x_ld + (unsigned)(lc * 8)) * 2u : OOB;
+        return ok ? ((unsigned)((t.img * (a.H >> a.ups) + sy) * (a.W >> a.ups) + sx) * (unsigned)a.x_ld + (unsigned)(lc * 8)) * 2u : BUF_OOB;
     };
     auto issue_halo_part = [&](unsigned ho, int i, int cc, char* dst) {
-        const unsigned o = ho == OOB ? OOB : ho + (unsigned)(cc * 128);
+        const unsigned o = ho == BUF_OOB ? BUF_OOB : ho + (unsigned)(cc * 128);
         char* d = (PATCH == 8 || i < 5) ? dst + (wave * 64 + 512 * i) * 16 : (wave == 0 ? dst + 5 * 512 * 16 : smem + DUMP_AT);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (__attribute__((address_space(3))) void*)d, 16, o, 0, 0, 0);
+        LDS_DMA16(rx, d, o, 0);
     };
     // weight DMA plan: vector v = tid + 512 i -> row n = v >> 3 of the 128-row tile, physical chunk v & 7 = logical ^ ((row >> 1) & 7)
     unsigned wrow[2];
@@ -195,23 +176,21 @@ void conv3x3_stream_kernel(CsArgs a) {
         const unsigned base = (unsigned)tn * w_tile_bytes + (unsigned)((tap * a.C + cc * 64) * 2);      // rows beyond N: past the extent -> zeros
 #pragma unroll
         for (int i = 0; i < 2; ++i)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (__attribute__((address_space(3))) void*)(dst + (wave * 64 + 512 * i) * 16), 16, base + wrow[i], 0, 0, 0);
+            LDS_DMA16(rw, dst + (wave * 64 + 512 * i) * 16, base + wrow[i], 0);
     };
     auto issue_w_half = [&](int tn, int cc, int tap, int slot, int i) {           // one of the two DMA instructions of issue_w
         char* dst = wring + slot * WT_BYTES;
         const unsigned base = (unsigned)tn * w_tile_bytes + (unsigned)((tap * a.C + cc * 64) * 2);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (__attribute__((address_space(3))) void*)(dst + (wave * 64 + 512 * i) * 16), 16, base + wrow[i], 0, 0, 0);
+        LDS_DMA16(rw, dst + (wave * 64 + 512 * i) * 16, base + wrow[i], 0);
     };
     // first stage of a tile: its bias row (wave 0) and the time-embedding row of its image (wave 1) ride along — issued BEFORE the stage's
     // loads, so they have landed when the stage has.  Lanes >= 32 are out of range and write zeros into the slot's padding.
     auto issue_rows = [&](const TilePos& t, int parity) {
         char* slot = smem + ROWS_AT + parity * 2048;
         if (wave == 0 && a.bias)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rbias, (__attribute__((address_space(3))) void*)slot, 16,
-                                                     lane < 32 ? (unsigned)((t.tn * 128 + lane * 4) * 4) : OOB, 0, 0, 0);
+            LDS_DMA16(rbias, slot, lane < 32 ? (unsigned)((t.tn * 128 + lane * 4) * 4) : BUF_OOB, 0);
         if (wave == 1 && a.rowbias)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rrow, (__attribute__((address_space(3))) void*)(slot + 1024), 16,
-                                                     lane < 32 ? (unsigned)(((long long)t.img * a.rowbias_ld + t.tn * 128 + lane * 4) * 4) : OOB, 0, 0, 0);
+            LDS_DMA16(rrow, slot + 1024, lane < 32 ? (unsigned)(((long long)t.img * a.rowbias_ld + t.tn * 128 + lane * 4) * 4) : BUF_OOB, 0);
     };
 
     // this lane's pixels (columns of its two 32-pixel accumulator blocks) -> halo index of tap (0, 0)
@@ -252,7 +231,7 @@ void conv3x3_stream_kernel(CsArgs a) {
     // VALU operations: the VALU idles in this loop) instead of being kept in registers.
     // weight fragment (i, kc): row (wn * 32 NIB + 32 i + lane % 32) of the tile, 16-byte chunk (2 kc) ^ sw   -> wv[i] ^ (kc << 5) (+ slot)
     // halo fragment (j, kc) of tap (r, s): halo pixel hp0[j] + r * HWD + s, chunk ((2 kc) | hi) ^ key(j, r, s) -> (hv[j] + tap shift) | ((hi ^ key) << 4) ^ (kc << 5)
-    const unsigned lds0 = (unsigned)(size_t)smem;
+    const unsigned lds0 = lds_addr(smem);
     unsigned wv[NIB], hv[NJ];
 #pragma unroll
     for (int i = 0; i < NIB; ++i) wv[i] = lds0 + 2 * HALO_BYTES + (unsigned)((wn * (32 * NIB) + i * 32 + (lane & 31)) * 128 + (sw << 4));
@@ -501,7 +480,7 @@ void conv3x3_stream_kernel(CsArgs a) {
                     f32x4v bsum[4], brow[4];
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
-                        const unsigned ad = (unsigned)(size_t)(rows + (wn * (32 * NIB) + i * 32 + 8 * g + 4 * (lane >> 5)) * 4);
+                        const unsigned ad = lds_addr(rows + (wn * (32 * NIB) + i * 32 + 8 * g + 4 * (lane >> 5)) * 4);
                         // (unconditional: a read under `if (a.bias)` makes the result a phi, and the compiler copies an asm output into
                         // its phi register right after the asm — before the data has arrived; absent rows are zeroed after the wait)
                         asm volatile("ds_read_b128 %0, %1" : "=v"(bsum[g]) : "v"(ad) : "memory");
@@ -618,64 +597,11 @@ void conv3x3_stream_kernel(CsArgs a) {
 constexpr int PC_CNT_AT = Lds<16>::BYTES;                  // counters (below) + a junk area the idle lanes of a signal write to
 constexpr int PC_BYTES = PC_CNT_AT + 1024;
 static_assert(PC_BYTES <= 160 * 1024, "LDS");
-// ONE COUNTER PER WAVE, never a sum over waves: a loader that runs a step ahead of its siblings (it may: only `freed` holds it back)
-// would otherwise make up for a sibling's missing signal — `ready >= 4 (s + 1)` held with one loader's quarter of the tile still in
-// flight (seen as a rare wrong tile when the block's waves progress unevenly, e.g. next to another kernel).  ready[4] and freed[4] are
-// 16 contiguous bytes each: one ds_read_b128 returns all four, the poller takes the minimum.
+// ready[4] and freed[4]: one counter per signalling wave, 16 contiguous bytes each (the protocol and why never a sum: gfx950.h; a loader
+// may run a step ahead of its siblings, only `freed` holds it back).  edone is the one summed counter: the consumers' rendezvous.
 constexpr int PC_READY = 0, PC_FREED = 16, PC_EDONE = 32, PC_JUNK = 256;
 
-// the smallest of four counters is >= target (wrap-safe signed distance)
-__device__ __forceinline__ int pc_min_dist(const u32x4& v, unsigned target) {
-    const int a = (int)(v.x - target), b = (int)(v.y - target), c = (int)(v.z - target), d = (int)(v.w - target);
-    const int m = min(min(a, b), min(c, d));
-    return __builtin_amdgcn_readfirstlane(m);
-}
-// ---- what a timed-out semaphore wait leaves behind (see pc_wait_all_ge)
-__device__ unsigned g_pc_fault[4];
-constexpr unsigned long long PC_WAIT_TICKS = 500000000ull;          // 5 s of the 100 MHz s_memrealtime clock
-__device__ __forceinline__ bool pc_expired(unsigned long long& t_first) {
-    const unsigned long long now = wall_clock64();
-    if (t_first == 0) { t_first = now | 1ull; return false; }
-    return now - t_first > PC_WAIT_TICKS;
-}
-__device__ __forceinline__ void pc_fault(unsigned addr, unsigned target, unsigned kind) {
-    if ((threadIdx.x & 63) == 0) {
-        g_pc_fault[0] = blockIdx.x; g_pc_fault[1] = addr; g_pc_fault[2] = target; g_pc_fault[3] = 1u + kind;
-        __threadfence_system();
-    }
-    __builtin_trap();
-}
-__device__ __forceinline__ void pc_wait_all_ge(unsigned addr, unsigned target) {
-    // bounded: a protocol error must end the launch with an error the host sees (trap), never hang the GPU.  The bound is WALL time
-    // (s_memrealtime, 100 MHz): ~5 s, so that a profiler's thread trace, a debugger or a stalled co-tenant cannot turn a slow wait into
-    // a fault; the clock is looked at every 4096 polls only.  pc_fault() leaves {block, counter address, target, 1 + kind} in
-    // g_pc_fault before the trap (rocgdb / a core file name the wait that tripped; ddpm_conv3x3_pc_last_fault reads it where the
-    // context survives).
-    unsigned long long t_first = 0;
-    for (unsigned spins = 0;; ++spins) {
-        u32x4 v;
-        asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(v) : "v"(addr) : "memory");
-        if (pc_min_dist(v, target) >= 0) break;
-        if ((spins & 4095u) == 4095u && pc_expired(t_first)) pc_fault(addr, target, 0u);
-        __builtin_amdgcn_s_sleep(1);
-    }
-}
-__device__ __forceinline__ void pc_wait_ge(unsigned addr, unsigned target) {          // one (summed) counter: the consumers' rendezvous
-    unsigned long long t_first = 0;
-    for (unsigned spins = 0;; ++spins) {
-        unsigned v;
-        asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(v) : "v"(addr) : "memory");
-        if ((int)((unsigned)__builtin_amdgcn_readfirstlane((int)v) - target) >= 0) break;
-        if ((spins & 4095u) == 4095u && pc_expired(t_first)) pc_fault(addr, target, 1u);
-        __builtin_amdgcn_s_sleep(1);
-    }
-}
-// +1 on a counter: one ds_add_u32 of the whole wave, lane 0 on the counter, every other lane on its own word of the junk area (no exec
-// masking, no bank conflict); `lane_addr` is built once per wave
-__device__ __forceinline__ void pc_signal(unsigned lane_addr) {
-    const unsigned one = 1u;
-    asm volatile("ds_add_u32 %0, %1" :: "v"(lane_addr), "v"(one) : "memory");
-}
+__device__ unsigned g_pc_fault[4];                          // what a timed-out semaphore wait leaves behind (lds_wait_fault)
 
 #ifdef C3_TIMING
 // debug builds only (scripts/pc_timeline.py): consumer wave 0's phase stamps [block][8] as for the kernel above, then [block][64] clocks at the end of its first 64 K-steps
@@ -703,7 +629,7 @@ void conv3x3_pc_kernel(CsArgs a) {
     if (tid < 256) reinterpret_cast<unsigned*>(smem + PC_CNT_AT)[tid] = 0u;
     __syncthreads();                                        // the only barrier of the kernel
     auto tile_pos = [&](int k) {
-        const int lid = logical_tile(blockIdx.x + k * G, a.total_tiles, a.xcd);
+        const int lid = xcd_logical_id(blockIdx.x + k * G, a.total_tiles, a.xcd);
         const int tmi = (int)fdiv((unsigned)lid, a.d_tiles_n);
         const int tpi = a.tiles_y * a.tiles_x;
         const int img = (int)fdiv((unsigned)tmi, a.d_tpi), pt = tmi - img * tpi;
@@ -712,21 +638,15 @@ void conv3x3_pc_kernel(CsArgs a) {
         return t;
     };
     const int nchunks = a.C >> 6;
-    const unsigned lds0 = (unsigned)(size_t)smem;
+    const unsigned lds0 = lds_addr(smem);
     const unsigned cnt0 = lds0 + PC_CNT_AT, junk = cnt0 + PC_JUNK + (unsigned)(lane * 4);
 
     if (wave >= 4) {
         // =============================================================== loaders
         const int lw = wave - 4, lid = lw * 64 + lane;
-        auto rsrc_of = [&](const void* p, unsigned extent) {
-            const unsigned long long ad = (unsigned long long)p;
-            const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)ad), hi = __builtin_amdgcn_readfirstlane((unsigned)(ad >> 32));
-            return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0,
-                                                     __builtin_amdgcn_readfirstlane((int)extent), 0x00020000);
-        };
-        const __amdgpu_buffer_rsrc_t rx = rsrc_of(a.x, a.x_extent), rw = rsrc_of(a.w, a.w_extent);
-        const __amdgpu_buffer_rsrc_t rbias = rsrc_of(a.bias ? (const void*)a.bias : (const void*)a.w, a.bias ? (unsigned)(a.N * 4) : 0u);
-        const __amdgpu_buffer_rsrc_t rrow = rsrc_of(a.rowbias ? (const void*)a.rowbias : (const void*)a.w, a.rowbias ? a.rowbias_extent : 0u);
+        const __amdgpu_buffer_rsrc_t rx = buffer_rsrc(a.x, a.x_extent), rw = buffer_rsrc(a.w, a.w_extent);
+        const __amdgpu_buffer_rsrc_t rbias = buffer_rsrc(a.bias ? (const void*)a.bias : (const void*)a.w, a.bias ? (unsigned)(a.N * 4) : 0u);
+        const __amdgpu_buffer_rsrc_t rrow = buffer_rsrc(a.rowbias ? (const void*)a.rowbias : (const void*)a.w, a.rowbias ? a.rowbias_extent : 0u);
         // halo part p of a tile: vector v = lid + 256 p -> halo pixel v >> 3, physical 16-byte chunk v & 7 = logical ^ key(hx) (the image the
         // consumers' reads expect is the one described at halo_plan above)
         auto halo_part_off = [&](const TilePos& t, int p) {
@@ -738,14 +658,14 @@ void conv3x3_pc_kernel(CsArgs a) {
             const bool ok = hp < HP && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
             const int lc = (v & 7) ^ ((hx >> 1) & 7);
             const int sy = iy >> a.ups, sx = ix >> a.ups;
-            return ok ? ((unsigned)((t.img * (a.H >> a.ups) + sy) * (a.W >> a.ups) + sx) * (unsigned)a.x_ld + (unsigned)(lc * 8)) * 2u : OOB;
+            return ok ? ((unsigned)((t.img * (a.H >> a.ups) + sy) * (a.W >> a.ups) + sx) * (unsigned)a.x_ld + (unsigned)(lc * 8)) * 2u : BUF_OOB;
         };
         auto issue_halo_part = [&](const TilePos& t, int p, int cc, char* dst) {
             const unsigned ho = halo_part_off(t, p);
-            const unsigned o = ho == OOB ? OOB : ho + (unsigned)(cc * 128);
+            const unsigned o = ho == BUF_OOB ? BUF_OOB : ho + (unsigned)(cc * 128);
             // part 10 holds the last 32 vectors: loader 0 writes them (+ 32 zero vectors of padding), the others' lanes are all out of range
             char* d = p < 10 ? dst + (lw * 64 + 256 * p) * 16 : (lw == 0 ? dst + 2560 * 16 : smem + DUMP_AT);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (__attribute__((address_space(3))) void*)d, 16, o, 0, 0, 0);
+            LDS_DMA16(rx, d, o, 0);
         };
         // weight tile: vector v = lid + 256 i -> row v >> 3, physical chunk v & 7 = logical ^ ((row >> 1) & 7)
         unsigned wrow[4];
@@ -760,7 +680,7 @@ void conv3x3_pc_kernel(CsArgs a) {
             const unsigned base = (unsigned)tn * w_tile_bytes + (unsigned)((tap * a.C + cc * 64) * 2);      // rows beyond N: past the extent -> zeros
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (__attribute__((address_space(3))) void*)(dst + (lw * 64 + 256 * i) * 16), 16, base + wrow[i], 0, 0, 0);
+                LDS_DMA16(rw, dst + (lw * 64 + 256 * i) * 16, base + wrow[i], 0);
         };
         // the tile's bias row (loader 0) and its image's time-embedding row (loader 1) — zeros when the launch has none: the consumers start
         // their accumulators from these rows unconditionally.  EVERY loader issues exactly one request here (the others an out-of-range
@@ -768,13 +688,11 @@ void conv3x3_pc_kernel(CsArgs a) {
         auto issue_rows = [&](const TilePos& t, int parity) {
             char* slot = smem + ROWS_AT + parity * 2048;
             if (lw == 0)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rbias, (__attribute__((address_space(3))) void*)slot, 16,
-                                                         (lane < 32 && a.bias) ? (unsigned)((t.tn * 128 + lane * 4) * 4) : OOB, 0, 0, 0);
+                LDS_DMA16(rbias, slot, (lane < 32 && a.bias) ? (unsigned)((t.tn * 128 + lane * 4) * 4) : BUF_OOB, 0);
             else if (lw == 1)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rrow, (__attribute__((address_space(3))) void*)(slot + 1024), 16,
-                                                         (lane < 32 && a.rowbias) ? (unsigned)(((long long)t.img * a.rowbias_ld + t.tn * 128 + lane * 4) * 4) : OOB, 0, 0, 0);
+                LDS_DMA16(rrow, slot + 1024, (lane < 32 && a.rowbias) ? (unsigned)(((long long)t.img * a.rowbias_ld + t.tn * 128 + lane * 4) * 4) : BUF_OOB, 0);
             else
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (__attribute__((address_space(3))) void*)(smem + DUMP_AT), 16, OOB, 0, 0, 0);
+                LDS_DMA16(rw, smem + DUMP_AT, BUF_OOB, 0);
         };
         TilePos cur = tile_pos(0);
 #pragma unroll
@@ -784,7 +702,7 @@ void conv3x3_pc_kernel(CsArgs a) {
         for (int t = 0; t < RING - 1; ++t) issue_w(cur.tn, 0, t, t);
         const unsigned sig_ready = lane == 0 ? cnt0 + PC_READY + (unsigned)(lw * 4) : junk;
         wait_vm<8>();                                       // the halo, the rows and weight tile 0 are in; tiles 1 and 2 may be on their way
-        pc_signal(sig_ready);
+        lds_signal(sig_ready);
         int slot = 0, hb = 0;
         unsigned gstep = 0;                                 // flat step index
         for (int k = 0; k < my_tiles; ++k) {
@@ -803,7 +721,7 @@ void conv3x3_pc_kernel(CsArgs a) {
                 for (int tap = 0; tap < 9; ++tap) {
                     // every consumer is past step g - 1: its weight slot, the halo buffer of the chunk before this one and (when step g - 1
                     // closed a tile) the staging area of that tile's epilogue are free
-                    pc_wait_all_ge(cnt0 + PC_FREED, gstep);
+                    lds_wait_all_ge(g_pc_fault, cnt0 + PC_FREED, gstep);
                     // requests of this step, in queue order: parts of the next halo (taps 0-5: 2 2 2 2 2 1), the next tile's rows (tap 6 of a
                     // tile's last chunk), then the weight tile three steps ahead
                     if (prefetch && tap < 6) {
@@ -828,7 +746,7 @@ void conv3x3_pc_kernel(CsArgs a) {
                     } else {
                         if (tap < 6) wait_vm<8>(); else if (tap == 6) wait_vm<4>(); else wait_vm<0>();
                     }
-                    pc_signal(sig_ready);
+                    lds_signal(sig_ready);
                     ++gstep;
                 }
                 hb ^= 1;
@@ -865,7 +783,7 @@ void conv3x3_pc_kernel(CsArgs a) {
             f32x4v bsum[4], brow[4];
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const unsigned ad = (unsigned)(size_t)(rows + (wn * 64 + i * 32 + 8 * g + 4 * (lane >> 5)) * 4);
+                const unsigned ad = lds_addr(rows + (wn * 64 + i * 32 + 8 * g + 4 * (lane >> 5)) * 4);
                 asm volatile("ds_read_b128 %0, %1" : "=v"(bsum[g]) : "v"(ad) : "memory");
                 asm volatile("ds_read_b128 %0, %1 offset:1024" : "=v"(brow[g]) : "v"(ad) : "memory");
             }
@@ -898,7 +816,7 @@ void conv3x3_pc_kernel(CsArgs a) {
 #endif
     PC_STAMP(0); PC_STAMP(1);
     unsigned need = 1;                                      // `ready` value (of every loader) that opens the step about to start
-    pc_wait_all_ge(cnt0 + PC_READY, need);                 // the loaders' prologue: halo 0, rows 0 and weight tile 0 are in LDS
+    lds_wait_all_ge(g_pc_fault, cnt0 + PC_READY, need);                 // the loaders' prologue: halo 0, rows 0 and weight tile 0 are in LDS
     PC_STAMP(2);
     init_acc(0);
     int slot = 0, hb = 0;
@@ -966,7 +884,7 @@ void conv3x3_pc_kernel(CsArgs a) {
                         asm volatile("ds_read_b128 %0, %1" : "=v"(rcp) : "v"(cnt0 + PC_READY) : "memory");
                         __builtin_amdgcn_sched_barrier(0);
                     } else if (post == 2) {
-                        pc_signal(sig);                      // (behind this step's last reads in the wave's LDS queue)
+                        lds_signal(sig);                      // (behind this step's last reads in the wave's LDS queue)
                         __builtin_amdgcn_sched_barrier(0);
                     }
                     mm(1, 1);
@@ -986,7 +904,7 @@ void conv3x3_pc_kernel(CsArgs a) {
                 if (tap > 0 || pend) {
                     asm volatile("s_waitcnt lgkmcnt(5)" ::: "memory");
                     __builtin_amdgcn_sched_barrier(0);
-                    if (pc_min_dist(rcp, need) < 0) pc_wait_all_ge(cnt0 + PC_READY, need);
+                    if (lds_min_dist(rcp, need) < 0) lds_wait_all_ge(g_pc_fault, cnt0 + PC_READY, need);
                 }
                 sub_step(tap > 0 || pend, fw[1], fx[1], 0, fw[0], fx[0], 1, 0, 0u, false);
                 sub_step(true, fw[0], fx[0], 1, fw[1], fx[1], 0, 0, 0u, false);
@@ -999,7 +917,7 @@ void conv3x3_pc_kernel(CsArgs a) {
                     sub_step(true, fw[1], fx[1], -1, fw[0], fx[0], 1, 0, 0u, false);
                     pend = false;
                     if (k == 0) PC_STAMP(3); else if (k == 1) PC_STAMP(5);
-                    pc_wait_ge(cnt0 + PC_EDONE, 4u * (unsigned)(k + 1));
+                    lds_wait_ge(g_pc_fault, cnt0 + PC_EDONE, 4u * (unsigned)(k + 1));
                     break;
                 }
                 pend = true;
@@ -1066,10 +984,10 @@ void conv3x3_pc_kernel(CsArgs a) {
                     }
                 }
                 // the staging reads are done (waited for above): slot, halo buffer and staging area go back to the loaders
-                pc_signal(sig_freed);
+                lds_signal(sig_freed);
                 if (k + 1 < my_tiles) {
                     cur = tile_pos(k + 1);
-                    pc_wait_all_ge(cnt0 + PC_READY, need);     // the next tile's first weight tile, its halo and its rows are in
+                    lds_wait_all_ge(g_pc_fault, cnt0 + PC_READY, need);     // the next tile's first weight tile, its halo and its rows are in
                     init_acc((k + 1) & 1);
                     hk = halo_addr(0, hb ^ 1);
                     wk = w_addr(slot);
@@ -1113,7 +1031,7 @@ int ddpm_conv3x3_stream_launch(const void* x, long long x_ld, const void* w, voi
     if (upsample && ((H | W) & 1)) return -1;
     const long long xbytes = ((long long)B * (H >> upsample) * (W >> upsample) * x_ld - (x_ld - C)) * 2, wbytes = (long long)N * 9 * C * 2;
     const long long rbbytes = rowbias ? ((long long)(B - 1) * rowbias_ld + N) * 4 : 0;
-    if (xbytes > 0x7ffffff0ll || wbytes > 0x7ffffff0ll || rbbytes > 0x7ffffff0ll) return -1;
+    if (xbytes > BUF_OOB || wbytes > BUF_OOB || rbbytes > BUF_OOB) return -1;
     // 16 x 16 patches: the wave-specialised kernel (loaders + consumers)
     // (a residual / "+=" epilogue stays on the kernel above: its rows have to be requested a K-step ahead, into registers the
     //  wave-specialised kernel does not have — acc 128 + fragments 48 — and requested late they cost 5-12 %; the two kernels give

@@ -15,8 +15,6 @@
 
 namespace {
 
-constexpr unsigned OOB = 0x7ffffff0u;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 struct EdgeArgs {
@@ -27,19 +25,6 @@ struct EdgeArgs {
     int B, H, W, C, N;
     int tiles_y, tiles_x;
 };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_of(const void* p, unsigned extent) {
-    const unsigned long long ad = (unsigned long long)p;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)ad), hi = __builtin_amdgcn_readfirstlane((unsigned)(ad >> 32));
-    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0,
-                                             __builtin_amdgcn_readfirstlane((int)extent), 0x00020000);
-}
-__device__ __forceinline__ u32x4 lds_rd16(unsigned addr) {
-    u32x4 v;
-    asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr) : "memory");
-    return v;
-}
-__device__ __forceinline__ void lds_wait() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_sched_barrier(0); }
 
 // ------------------------------------------------------------------------------------------------ few output channels
 constexpr int FO_HALO = 324 * 128 + 1024;        // 18 x 18 pixels x 64 channels (+ the tail the sixth DMA part of wave 0 zero-fills)
@@ -54,7 +39,7 @@ void conv3x3_few_out_kernel(EdgeArgs a) {
     const int tpi = a.tiles_y * a.tiles_x;
     const int img = blockIdx.x / tpi, pt = blockIdx.x - img * tpi;
     const int py0 = (pt / a.tiles_x) * 16, px0 = (pt % a.tiles_x) * 16;
-    const __amdgpu_buffer_rsrc_t rx = rsrc_of(a.x, a.x_extent);
+    const __amdgpu_buffer_rsrc_t rx = buffer_rsrc(a.x, a.x_extent);
     const int c8 = a.C >> 3;                       // 16-byte channel groups per pixel
     // ---- weights: vector v = (tap, channel group, n) -> LDS slot v; rows n >= N are zeros
     const int nwv = 9 * c8 * 16;
@@ -72,9 +57,9 @@ void conv3x3_few_out_kernel(EdgeArgs a) {
         const int c = (v & 7) ^ ((hx >> 1) & 7);
         const int y = py0 + hy - 1, x = px0 + hx - 1;
         const bool ok = hp < 324 && y >= 0 && y < a.H && x >= 0 && x < a.W;
-        hoff[i] = ok ? (unsigned)((((long long)(img * a.H + y) * a.W + x) * a.x_ld + c * 8) * 2) : OOB;
+        hoff[i] = ok ? (unsigned)((((long long)(img * a.H + y) * a.W + x) * a.x_ld + c * 8) * 2) : BUF_OOB;
     }
-    const unsigned lds0 = (unsigned)(size_t)smem;
+    const unsigned lds0 = lds_addr(smem);
     const int px = lane & 15, g = lane >> 4;
     f32x4v acc[2] = {(f32x4v)(0.f), (f32x4v)(0.f)};
     const int nchunks = a.C >> 6;
@@ -83,9 +68,9 @@ void conv3x3_few_out_kernel(EdgeArgs a) {
 #pragma unroll
         for (int i = 0; i < 6; ++i) {
             if (i == 5 && wave != 0) break;        // part 5 = 32 vectors: wave 0 alone (its upper lanes write zeros into the tail)
-            unsigned o = hoff[i] == OOB ? OOB : hoff[i] + (unsigned)(ch * 128);
+            unsigned o = hoff[i] == BUF_OOB ? BUF_OOB : hoff[i] + (unsigned)(ch * 128);
             asm volatile("" : "+v"(o));
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (__attribute__((address_space(3))) void*)(halo + (i * 512 + wave * 64) * 16), 16, o, 0, 0, 0);
+            LDS_DMA16(rx, halo + (i * 512 + wave * 64) * 16, o, 0);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
@@ -193,7 +178,7 @@ int ddpm_edgeconv_few_out_launch(const void* x, long long x_ld, const void* w, v
                                  int dry, void* stream) {
     if (N < 1 || N > 16 || C % 64 || C > 512 || H % 16 || W % 16 || x_ld % 8 || !aligned16(x) || !aligned16(w)) return -1;
     const long long xbytes = ((long long)B * H * W * x_ld - (x_ld - C)) * 2;
-    if (xbytes > 0x7ffffff0ll) return -1;
+    if (xbytes > BUF_OOB) return -1;
     const size_t lds = (size_t)FO_HALO + (size_t)9 * (C / 8) * 256;
     if (lds > 160 * 1024) return -1;
     if (dry) return 0;

@@ -85,12 +85,6 @@ struct Epilogue {
     unsigned* splitk_cnt;     // per-tile arrival counters, zero on entry, reset to zero by the last arriver
 };
 
-template <int I> struct IC { static constexpr int v = I; };
-template <int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (N > 0) { static_for<N - 1>(f); f(IC<N - 1>{}); }
-}
-
 template <typename T> struct Mma;
 template <> struct Mma<bf16_t> {
     typedef __bf16 frag_t __attribute__((ext_vector_type(8)));
@@ -124,14 +118,13 @@ __device__ __forceinline__ int lds_off(int row, int chunk) { return row * ROW_BY
 // Per-thread loader state for one operand tile (TILE rows x BK k).  All global reads go through a raw buffer descriptor
 // (base = operand pointer of this batch, num_records = its extent): addressing is one 32-bit byte offset per vector and
 // the hardware range check returns ZEROS for any offset >= num_records — padded taps, K-tails and rows beyond the matrix
-// simply use the offset OOB (verified on gfx950 also for the direct-to-LDS form: scripts/probes/buffer_lds_oob.hip).
+// simply use the offset BUF_OOB (verified on gfx950 also for the direct-to-LDS form: scripts/probes/buffer_lds_oob.hip).
 //  !TRANS (memory is k-contiguous): `buffer_load_dwordx4 ... lds` — HBM/L2 -> LDS without touching VGPRs.  Lane l of wave w
 //          fetches, for i = 0..3, row w*8 + l/8 + 32 i, PHYSICAL chunk l%8, i.e. logical k-chunk (l%8) ^ ((row>>1)&7):
 //          the swizzle is applied on the per-lane SOURCE offset, the LDS image stays lane-linear.
 //   TRANS (k is the slow memory index): each thread owns a 4(k) x VEC(m) block — k-quad kq = tid % (BK/4) fastest over
 //          lanes, m-group ng = tid / (BK/4) — loads its 4 k-rows as 16-byte vectors, transposes in registers and writes
 //          VEC k-contiguous 4-element runs (ds_write_b64 bf16 / ds_write_b128 fp32) into the swizzled image.
-constexpr unsigned OOB = 0x7ffffff0u;
 
 // PH: the parity-phase conv form is compiled in.  CV = false: the operand is never an implicit-im2col view (the B side of the k-contiguous
 // products is always a plain weight matrix) — its gather arithmetic is left out of the block prologue.
@@ -154,19 +147,14 @@ struct Loader {
     int kv, wave, row0;           // !TRANS: logical k-chunk, wave id, first tile row
     int kvoff, kuni;              // !TRANS conv: byte offset of this lane's chunk inside a K-step; 1 when a K-step never straddles two taps (C % BK == 0)
     int kq, ng;                   // TRANS
-    int roff[NV];               // !TRANS: byte offset of the row (plain; OOB when the row is outside) or of pixel (b, y0, x0) (conv)
+    int roff[NV];               // !TRANS: byte offset of the row (plain; BUF_OOB when the row is outside) or of pixel (b, y0, x0) (conv)
     unsigned tapmask[NV];       // !TRANS conv without up/down-scaling: bit (r*S+s) set when the tap is inside the image
-    int tr, ts, tc; unsigned foff;   // TRANS: fixed tap/channel (conv) or fixed byte offset along the fast index (plain, OOB if outside)
+    int tr, ts, tc; unsigned foff;   // TRANS: fixed tap/channel (conv) or fixed byte offset along the fast index (plain, BUF_OOB if outside)
     int krow0;                    // TRANS bf16 (LDS-DMA of the m-major image): first k-row of this thread (tid>>4), +16 per vector
     int ph_py, ph_px;             // !TRANS parity-phase conv: parity of (y - pad_t), (x - pad_l) of this tile's rows; -1 otherwise
 
     __device__ __forceinline__ Loader(const MatDesc& d_, int batch, int tile0_, int tid) : d(d_) {
-        // The descriptor must be PROVABLY wave-uniform or hipcc wraps every buffer op in a waterfall loop
-        // (v_readfirstlane x4 + s_and_saveexec per load): readfirstlane its inputs once.
-        const unsigned long long baddr = (unsigned long long)(reinterpret_cast<const T*>(d.p) + (long long)batch * d.batch_stride);
-        const unsigned blo = __builtin_amdgcn_readfirstlane((unsigned)baddr), bhi = __builtin_amdgcn_readfirstlane((unsigned)(baddr >> 32));
-        rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)bhi << 32) | blo), 0,
-                                                 __builtin_amdgcn_readfirstlane((int)d.extent_bytes), 0x00020000);
+        rsrc = buffer_rsrc(reinterpret_cast<const T*>(d.p) + (long long)batch * d.batch_stride, (unsigned)d.extent_bytes);
         tile0 = tile0_;
         if (!TRANS) {
             row0 = tid >> 3;
@@ -205,7 +193,7 @@ struct Loader {
 #pragma unroll
                 for (int i = 0; i < NV; ++i) {
                     const int m = tile0 + row0 + (NT / 8) * i;
-                    roff[i] = m < d.n_slow ? (int)((long long)m * d.ld * ES) : (int)OOB;
+                    roff[i] = m < d.n_slow ? (int)((long long)m * d.ld * ES) : (int)BUF_OOB;
                     tapmask[i] = 0u;
                 }
             } else
@@ -217,7 +205,7 @@ struct Loader {
                 int b, y0, x0;
                 decode_pixel(valid ? m : 0, b, y0, x0);
                 const int conv_off = (int)((((long long)(b * d.H + y0) * d.W + x0) * d.ld) * ES);
-                const int plain_off = valid ? (int)((long long)m * d.ld * ES) : (int)OOB;
+                const int plain_off = valid ? (int)((long long)m * d.ld * ES) : (int)BUF_OOB;
                 // taps inside the image: rows r in [max(0,-y0), min(R, H-y0)), columns likewise (closed form, R,S <= 5)
                 const int rlo = min(max(-y0, 0), d.R), rhi = min(max(d.H - y0, 0), d.R);
                 const int slo = min(max(-x0, 0), d.S), shi = min(max(d.W - x0, 0), d.S);
@@ -235,7 +223,7 @@ struct Loader {
             // bf16: thread owns PHYSICAL 16-byte chunk tid&15 of k-rows krow0 + 16 i, i.e. logical chunk (tid&15) ^ ((krow&3)<<2)
             const int f = TR16 ? tile0 + (((tid & 15) ^ ((krow0 & 3) << 2)) * VEC) : tile0 + ng * VEC;
             const bool fvalid = f < d.n_fast;
-            foff = fvalid ? (unsigned)(f * ES) : OOB;
+            foff = fvalid ? (unsigned)(f * ES) : BUF_OOB;
             if (d.conv) {
                 unsigned tap = fdiv((unsigned)(fvalid ? f : 0), d.dC);
                 tc = fvalid ? f - (int)tap * d.C : -1;      // tc < 0 marks "outside"
@@ -252,14 +240,14 @@ struct Loader {
         b = (int)bb; y0 = (int)oy * d.stride - d.pad_t; x0 = (int)ox * d.stride - d.pad_l;
     }
 
-    // byte offset of the 16-byte vector at virtual pixel (y0+r, x0+s), channel c — or OOB
+    // byte offset of the 16-byte vector at virtual pixel (y0+r, x0+s), channel c — or BUF_OOB
     __device__ __forceinline__ unsigned gather_off(int b, int y0, int x0, int r, int s, int c) const {
         unsigned uy = (unsigned)(y0 + r), ux = (unsigned)(x0 + s);
         bool ok = ((uy | ux) & (unsigned)d.dmask) == 0;
         uy >>= d.sh; ux >>= d.sh;
         ok = ok && uy < (unsigned)d.H && ux < (unsigned)d.W;
         const unsigned off = (unsigned)(((b * d.H + (int)uy) * d.W + (int)ux) * (int)d.ld + c) * ES;
-        return ok ? off : OOB;
+        return ok ? off : BUF_OOB;
     }
 
     // !TRANS: enqueue the direct-to-LDS loads of the K-step starting at k0 into `tile`
@@ -279,7 +267,7 @@ struct Loader {
             const int tapoff = ((ru * d.W + su) * (int)d.ld + cu) * ES;
             const unsigned tb = k0u < k_end ? tapu : 31u;           // K is a multiple of the step here: no partial tail
 #pragma unroll
-            for (int i = 0; i < NV; ++i) off[i] = ((tapmask[i] >> tb) & 1u) ? (unsigned)(roff[i] + kvoff + tapoff) : OOB;
+            for (int i = 0; i < NV; ++i) off[i] = ((tapmask[i] >> tb) & 1u) ? (unsigned)(roff[i] + kvoff + tapoff) : BUF_OOB;
         } else if (CV && d.conv) {
             unsigned tap = fdiv((unsigned)k, d.dC);
             const int c = k - (int)tap * d.C;
@@ -288,25 +276,24 @@ struct Loader {
                 const int tapoff = ((r * d.W + s) * (int)d.ld + c) * ES;
                 tap = kok ? tap : 31u;                          // bit 31 is never set: K-tail reads zeros
 #pragma unroll
-                for (int i = 0; i < NV; ++i) off[i] = ((tapmask[i] >> tap) & 1u) ? (unsigned)(roff[i] + tapoff) : OOB;
+                for (int i = 0; i < NV; ++i) off[i] = ((tapmask[i] >> tap) & 1u) ? (unsigned)(roff[i] + tapoff) : BUF_OOB;
             } else {
 #pragma unroll
                 for (int i = 0; i < NV; ++i) {        // up/down-scaled maps (6 convs per pass): decode on the fly
                     const int m = tile0 + row0 + (NT / 8) * i;
                     int b, y0, x0;
                     decode_pixel(m < d.n_slow ? m : 0, b, y0, x0);
-                    off[i] = (kok && m < d.n_slow) ? gather_off(b, y0, x0, r, s, c) : OOB;
+                    off[i] = (kok && m < d.n_slow) ? gather_off(b, y0, x0, r, s, c) : BUF_OOB;
                 }
             }
         } else {
-            const unsigned koff = kok ? (unsigned)(k * ES) : OOB;
+            const unsigned koff = kok ? (unsigned)(k * ES) : BUF_OOB;
 #pragma unroll
-            for (int i = 0; i < NV; ++i) off[i] = (unsigned)roff[i] + koff;     // OOB + small stays out of range
+            for (int i = 0; i < NV; ++i) off[i] = (unsigned)roff[i] + koff;     // BUF_OOB + small stays out of range
         }
 #pragma unroll
         for (int i = 0; i < NV; ++i)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)(tile + (wave * 8 + (NT / 8) * i) * ROW_BYTES),
-                                                     16, off[i], 0, 0, 0);
+            LDS_DMA16(rsrc, tile + (wave * 8 + (NT / 8) * i) * ROW_BYTES, off[i], 0);
     }
 
     // TRANS bf16: LDS-DMA of the operand AS STORED (k-rows of 128 m-elements = 256 bytes, 64 rows per K-step) with the
@@ -320,15 +307,14 @@ struct Loader {
             if (d.conv) {
                 int b, y0, x0;
                 decode_pixel(k < k_end ? k : 0, b, y0, x0);
-                off[i] = (tc >= 0 && k < k_end) ? gather_off(b, y0, x0, tr, ts, tc) : OOB;
+                off[i] = (tc >= 0 && k < k_end) ? gather_off(b, y0, x0, tr, ts, tc) : BUF_OOB;
             } else {
-                off[i] = k < k_end ? (unsigned)((long long)k * d.ld * ES) + foff : OOB;
+                off[i] = k < k_end ? (unsigned)((long long)k * d.ld * ES) + foff : BUF_OOB;
             }
         }
 #pragma unroll
         for (int i = 0; i < NV; ++i)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)(tile + (wave * 64 + NT * i) * 16),
-                                                     16, off[i], 0, 0, 0);
+            LDS_DMA16(rsrc, tile + (wave * 64 + NT * i) * 16, off[i], 0);
     }
 
     // TRANS: fetch this thread's 4 k-rows of the K-step starting at k0
@@ -341,7 +327,7 @@ struct Loader {
 #pragma unroll
             for (int i = 0; i < NV; ++i) {
                 const bool ok = tc >= 0 && kb + i < k_end;
-                const unsigned o = ok ? gather_off(b, y0, x0, tr, ts, tc) : OOB;
+                const unsigned o = ok ? gather_off(b, y0, x0, tr, ts, tc) : BUF_OOB;
                 v[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, o, 0, 0));
                 x0 += d.stride;                                   // next output pixel (row-major over b, oy, ox)
                 if (x0 == xend) { x0 = -d.pad_l; y0 += d.stride; if (y0 == yend) { y0 = -d.pad_t; ++b; } }
@@ -350,7 +336,7 @@ struct Loader {
 #pragma unroll
             for (int i = 0; i < NV; ++i) {
                 const int k = kb + i;
-                const unsigned o = k < k_end ? (unsigned)((long long)k * d.ld * ES) + foff : OOB;
+                const unsigned o = k < k_end ? (unsigned)((long long)k * d.ld * ES) + foff : BUF_OOB;
                 v[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, o, 0, 0));
             }
         }
@@ -541,17 +527,14 @@ template <typename T, bool TRANS>
 __device__ __forceinline__ u32x4 read_frag(const char* tile, int rb, int kc, int lane) {
     if constexpr (TRANS && sizeof(T) == 2) {
         // m-major image (k-rows of 256 bytes): hardware transpose read, two 4-k halves
-        typedef short s16x4 __attribute__((ext_vector_type(4)));
         const int i16 = lane & 15;
         const int mcol = rb + ((lane >> 4) & 1) * 16 + (i16 & 3) * 4;
         const int krow = kc * 16 + (lane >> 5) * 8 + (i16 >> 2);
         const int pch = (mcol >> 3) ^ (((i16 >> 2) & 3) << 2);
         const char* p = tile + krow * 256 + pch * 16 + (mcol & 7) * 2;
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p + 4 * 256));
+        const uint2 lo = tr_read(p), hi = tr_read(p + 4 * 256);
         u32x4 r;
-        r.x = __builtin_bit_cast(uint2, lo).x; r.y = __builtin_bit_cast(uint2, lo).y;
-        r.z = __builtin_bit_cast(uint2, hi).x; r.w = __builtin_bit_cast(uint2, hi).y;
+        r.x = lo.x; r.y = lo.y; r.z = hi.x; r.w = hi.y;
         return r;
     } else {
         // k-contiguous image: row (lane&31), logical 16-byte chunk 2*kc + (lane>>5), swizzle key (row>>1)&7
@@ -585,17 +568,7 @@ __device__ __forceinline__ void wait_tiles_in_flight(int tiles) {
 //           ~0.65 us/step with two tiles in flight), so more tiles in flight is what shortens the step.
 // NW = 4: 4 waves as 2(M) x 2(N), 64x64 per wave.  NW = 8: 8 waves as 4(M) x 2(N), 32x64 per wave — twice the waves per CU
 //         (two 512-thread blocks) to hide LDS-DMA latency and barrier skew; needs both operands on the DMA path.
-// XCD-aware block order.  Workgroups are handed to the 8 XCDs round-robin by linear id, and each XCD has its own L2: with the
-// natural order the blocks that share operand data (the N-tiles of one pixel tile, the output tiles of one split-K slice) sit
-// on 8 different XCDs and every L2 fetches the same lines again (measured on wgrad: the LDS-DMA stream alone took as long
-// as the whole kernel).  Logical id = (id % 8) * (total / 8) + id / 8 gives each XCD a CONTIGUOUS range of logical ids, so
-// neighbours in the logical order — which share data — run on the same XCD at about the same time.  The (< 8) ids past
-// the last multiple of 8 keep their own id.  The host passes xcd = 1 (g_xcd_swizzle).
-__device__ __forceinline__ int xcd_logical_id(int id, int total, int xcd) {
-    if (!xcd) return id;
-    const int per = total >> 3;
-    return id < (per << 3) ? (id & 7) * per + (id >> 3) : id;
-}
+// Block order: xcd_logical_id (gfx950.h); the host passes xcd = 1 (g_xcd_swizzle).
 
 #ifndef DEEP_ISSUE_KC
 #define DEEP_ISSUE_KC 1
@@ -1083,13 +1056,7 @@ void conv3x3_halo_kernel(Conv3Args a, int tiles_n, int xcd) {
     const int HH = a.PH + 2, HWd = a.PW + 2, HP = a.NB * HH * HWd;
     const int ES = 2;
 
-    auto rsrc_of = [&](const void* p, unsigned extent) {
-        const unsigned long long ad = (unsigned long long)p;
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)ad), hi = __builtin_amdgcn_readfirstlane((unsigned)(ad >> 32));
-        return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0,
-                                                 __builtin_amdgcn_readfirstlane((int)extent), 0x00020000);
-    };
-    const __amdgpu_buffer_rsrc_t rx = rsrc_of(a.x, a.x_extent), rw = rsrc_of(a.w, a.w_extent);
+    const __amdgpu_buffer_rsrc_t rx = buffer_rsrc(a.x, a.x_extent), rw = buffer_rsrc(a.w, a.w_extent);
 
     // LDS swizzle of the halo rows (128 B each, bank half = hp & 1 = hx & 1 since the halo pitch is even): the 16-byte
     // chunk c of halo pixel (hy, hx) sits at physical chunk c ^ key, key = (hx >> 1) ^ ((hy & ky) << 2).  With it the 16
@@ -1105,7 +1072,7 @@ void conv3x3_halo_kernel(Conv3Args a, int tiles_n, int xcd) {
         const int iy = py0 + hy - 1, ix = px0 + hx - 1, gi = img0 + img;
         const bool ok = hp < HP && gi < a.B && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
         const int lc = (v & 7) ^ (((hx >> 1) ^ ((hy & a.ky) << 2)) & 7);
-        hoff[i] = ok ? (unsigned)((((long long)(gi * a.H + iy) * a.W + ix) * a.x_ld + lc * 8) * ES) : OOB;
+        hoff[i] = ok ? (unsigned)((((long long)(gi * a.H + iy) * a.W + ix) * a.x_ld + lc * 8) * ES) : BUF_OOB;
     }
     // weight DMA plan: vector v = tid + 512 i -> row n = v>>3 of the 128-row tile, physical chunk v&7
     unsigned woff[2];
@@ -1113,11 +1080,11 @@ void conv3x3_halo_kernel(Conv3Args a, int tiles_n, int xcd) {
     for (int i = 0; i < 2; ++i) {
         const int v = tid + 512 * i, row = v >> 3, n = tn * TILE + row;
         const int lc = (v & 7) ^ ((row >> 1) & 7);
-        woff[i] = n < a.N ? (unsigned)(((long long)n * a.K + lc * 8) * ES) : OOB;
+        woff[i] = n < a.N ? (unsigned)(((long long)n * a.K + lc * 8) * ES) : BUF_OOB;
     }
     auto issue_halo_part = [&](unsigned ho, int i, int cc, char* dst) {     // part i of the halo of channel chunk cc
-        const unsigned o = ho == OOB ? OOB : ho + (unsigned)(cc * 64 * ES);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (__attribute__((address_space(3))) void*)(dst + (wave * 64 + 512 * i) * 16), 16, o, 0, 0, 0);
+        const unsigned o = ho == BUF_OOB ? BUF_OOB : ho + (unsigned)(cc * 64 * ES);
+        LDS_DMA16(rx, dst + (wave * 64 + 512 * i) * 16, o, 0);
     };
     const int nchunks = a.C / 64;
     const int total = nchunks * 9;                        // K-steps: (channel chunk, tap)
@@ -1127,8 +1094,8 @@ void conv3x3_halo_kernel(Conv3Args a, int tiles_n, int xcd) {
         const unsigned koff = (unsigned)((tap * a.C + cc * 64) * ES);
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            const unsigned o = woff[i] == OOB ? OOB : woff[i] + koff;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (__attribute__((address_space(3))) void*)(dst + (wave * 64 + 512 * i) * 16), 16, o, 0, 0, 0);
+            const unsigned o = woff[i] == BUF_OOB ? BUF_OOB : woff[i] + koff;
+            LDS_DMA16(rw, dst + (wave * 64 + 512 * i) * 16, o, 0);
         }
     };
 
@@ -1359,17 +1326,14 @@ void attn_fwd_kernel(MatDesc Qd, MatDesc Kd, MatDesc Vd, bf16_t* __restrict__ ou
 #pragma unroll
                 for (int j = 0; j < DB; ++j) {
                     // V^T fragment of dv block j in the accumulator's key order: keys kb + 4g + {0..3}, kb + 8 + 4g + {0..3}
-                    typedef short s16x4 __attribute__((ext_vector_type(4)));
                     const int i16 = lane & 15;
                     const int mcol = (j & 3) * 32 + ((lane >> 4) & 1) * 16 + (i16 & 3) * 4;
                     const int krow = kb + g * 4 + (i16 >> 2);
                     const int pch = (mcol >> 3) ^ (((i16 >> 2) & 3) << 2);
                     const char* p = Vs + (j >> 2) * V_BYTES + krow * 256 + pch * 16 + (mcol & 7) * 2;
-                    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
-                    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p + 8 * 256));
+                    const uint2 lo = tr_read(p), hi = tr_read(p + 8 * 256);
                     u32x4 fv;
-                    fv.x = __builtin_bit_cast(uint2, lo).x; fv.y = __builtin_bit_cast(uint2, lo).y;
-                    fv.z = __builtin_bit_cast(uint2, hi).x; fv.w = __builtin_bit_cast(uint2, hi).y;
+                    fv.x = lo.x; fv.y = lo.y; fv.z = hi.x; fv.w = hi.y;
                     Mma<T>::run(fv, pb[i][t], acc_o[j]);
                 }
             }
@@ -1424,7 +1388,7 @@ static int conv3x3_halo_launch(GemmArgs& g, const void* x, long long x_ld, const
     a.x = x; a.x_ld = x_ld; a.w = w;
     a.B = B; a.H = H; a.W = W; a.C = C; a.N = N; a.K = 9 * C;
     const long long xbytes = ((long long)B * H * W * x_ld - (x_ld - C)) * 2, wbytes = (long long)N * 9 * C * 2;
-    if (xbytes > 0x7ffffff0ll || wbytes > 0x7ffffff0ll) return -1;
+    if (xbytes > BUF_OOB || wbytes > BUF_OOB) return -1;
     a.x_extent = (unsigned)xbytes; a.w_extent = (unsigned)wbytes;
     a.PH = PH; a.PW = PW; a.NB = NB; a.lPW = ilog2(PW); a.lPP = ilog2(PH * PW);
     a.ky = PW == 8 ? 1 : 0;
@@ -1459,7 +1423,7 @@ static int finish_desc(MatDesc& d, int esize) {
     const long long elems = d.conv ? (long long)d.conv_batches * d.H * d.W * d.ld - (d.ld - d.C)
                                    : (long long)(d.n_slow - 1) * d.ld + d.n_fast;
     const long long bytes = elems * esize;
-    if (bytes <= 0 || bytes > 0x7ffffff0ll) return DDPM_ERR_SHAPE;      // 32-bit buffer offsets: operands < 2 GiB
+    if (bytes <= 0 || bytes > BUF_OOB) return DDPM_ERR_SHAPE;      // 32-bit buffer offsets: operands < 2 GiB
     d.extent_bytes = (unsigned)bytes;
     if (d.conv) {
         d.dHoWo = make_fastdiv((unsigned)(d.Ho * d.Wo));

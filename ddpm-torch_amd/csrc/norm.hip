@@ -21,11 +21,6 @@ extern "C" int ddpm_colsum(const void* dy, long long ld, float* per_sample, long
 constexpr int GN_THREADS = 256;
 constexpr int GN_MAXC = 2048;
 
-template <int I> struct GnIC { static constexpr int v = I; };
-template <int N, typename F>
-__device__ __forceinline__ void static_for_gn(F&& f) {
-    if constexpr (N > 0) { static_for_gn<N - 1>(f); f(GnIC<N - 1>{}); }
-}
 // s_waitcnt vmcnt(N + extra): `extra` plain loads were issued AFTER the DMA instructions being counted (runtime 0 or NV)
 template <int N>
 __device__ __forceinline__ void gn_wait_vm(int extra) {
@@ -661,12 +656,8 @@ __device__ __forceinline__ void gn_block_channel_sum2_w(const float (&pa)[VEC], 
     gn_block_sum_w<VEC, 2, NW>(v, f, j, tid, sh_row, sh_ch);
 }
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t gn_slice_rsrc(const void* base, long long bytes) {
-    const unsigned long long ad = (unsigned long long)base;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)ad), hi = __builtin_amdgcn_readfirstlane((unsigned)(ad >> 32));
-    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0,
-                                             __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000);
-}
+// descriptor of a block's slice; the extent arrives as the 64-bit pitch arithmetic of the call sites
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t gn_slice_rsrc(const void* base, long long bytes) { return buffer_rsrc(base, (unsigned)bytes); }
 
 #ifdef GN_TIMING
 __device__ unsigned long long* g_gn_timing = nullptr;          // debug builds only (scripts/gn_timeline.sh): [block][8] stamps
@@ -731,8 +722,8 @@ void gn_lds_bwd8_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __
     for (int i = 0; i < NV; ++i) {                     // issue order x_0, dy_0, x_1, dy_1, ...: pair i is complete at vmcnt(2 (NV-1-i))
         const int p = prow + i * f.rows_per_iter;
         const bool ok = active && p < s.HW;
-        const unsigned ox = ok ? (unsigned)(((long long)p * s.x_ld + j * VEC) * ES) : 0x7ffffff0u;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (__attribute__((address_space(3))) void*)(xs + (i * 512 + wave * 64) * 16), 16, ox, 0, 0, 0);
+        const unsigned ox = ok ? (unsigned)(((long long)p * s.x_ld + j * VEC) * ES) : BUF_OOB;
+        LDS_DMA16(rx, xs + (i * 512 + wave * 64) * 16, ox, 0);
         vd[i] = ok ? ldg16(db + (long long)p * dy_ld) : zero16();
     }
     const float keep_scale = a.drop_p > 0.f ? 1.0f / (1.0f - a.drop_p) : 1.0f;
@@ -758,7 +749,7 @@ void gn_lds_bwd8_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __
 #pragma unroll
     for (int e = 0; e < VEC; ++e) a1[e] = a2[e] = 0.f;
     const u32x4* myx = reinterpret_cast<const u32x4*>(xs) + tid;
-    static_for_gn<NV>([&](auto ic) {
+    static_for<NV>([&](auto ic) {
         constexpr int i = decltype(ic)::v;
         gn_wait_vm<2 * (NV - 1 - i)>(0);
         const int p = prow + i * f.rows_per_iter;
@@ -861,7 +852,6 @@ __device__ __forceinline__ void gn_lds_rd_consts(unsigned addr, float (&o)[VEC])
 // out-of-range offset (reads return 0, writes are dropped) instead of a branch.  Branch-free matters beyond the saved address
 // arithmetic: hipcc's counted waits assume the FEWEST younger VMEM operations over all paths, so loads skipped under `if` turn every
 // later wait into vmcnt(0).
-constexpr unsigned GN_OOB = 0x7ffffff0u;
 __device__ __forceinline__ u32x4 gn_buf_ld16(__amdgpu_buffer_rsrc_t r, unsigned off) {
     return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
 }
@@ -913,7 +903,7 @@ void gn_lds_bwd_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __r
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool active = tid < f.nta;
     const int j = tid % f.seg_vecs, prow = tid / f.seg_vecs;
-    const unsigned lds0 = (unsigned)(size_t)lsm, k0 = (unsigned)(size_t)sh_k;
+    const unsigned lds0 = lds_addr(lsm), k0 = lds_addr(sh_k);
     const unsigned kcol = k0 + (unsigned)(j * VEC * 4), kstride = (unsigned)(f.seg_ch * 4);
     const __amdgpu_buffer_rsrc_t rx = gn_slice_rsrc(x + ((long long)b * s.HW) * s.x_ld + c0, ((long long)(s.HW - 1) * s.x_ld + f.seg_ch) * ES);
     // per-channel inputs first: ordinary loads issued BEFORE the DMA complete before it (in-order return), so a counted wait covers them
@@ -935,9 +925,9 @@ void gn_lds_bwd_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __r
 #pragma unroll
     for (int i = 0; i < NV; ++i) {                     // issue order x_0, dy_0, x_1, dy_1, ...: pair i is complete at vmcnt(2 (NV-1-i))
         const bool ok = row_ok(i);
-        unsigned ox = ok ? x_o + i * x_st : GN_OOB, od = ok ? dy_o + i * dy_st : GN_OOB;
+        unsigned ox = ok ? x_o + i * x_st : BUF_OOB, od = ok ? dy_o + i * dy_st : BUF_OOB;
         asm volatile("" : "+v"(ox), "+v"(od));          // one DMA + one load per row on every path (hipcc otherwise splits the select into two predicated DMA instructions)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (__attribute__((address_space(3))) void*)(xs + (i * NT + wave * 64) * 16), 16, ox, 0, 0, 0);
+        LDS_DMA16(rx, xs + (i * NT + wave * 64) * 16, ox, 0);
         vd[i] = gn_buf_ld16(rdy, od);
     }
     if (tid < f.seg_ch) {
@@ -965,7 +955,7 @@ void gn_lds_bwd_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __r
 #pragma unroll
     for (int e = 0; e < VEC; ++e) a1[e] = a2[e] = 0.f;
     const unsigned myx_ad = lds0 + (unsigned)(tid * 16);
-    static_for_gn<NV>([&](auto ic) {
+    static_for<NV>([&](auto ic) {
         constexpr int i = decltype(ic)::v;
         // (the wait takes the previous vector's last sums as operands: in straight-line code hipcc otherwise retires ALL waits and LDS
         //  reads first, unpacks every vector and spills the lot — 100 registers at NV = 8)
@@ -1051,7 +1041,7 @@ void gn_lds_bwd_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __r
     });
     GN_STAMP(2);
     // `add` (the residual gradient that joins dx) is requested now and consumed in pass 2: its latency hides behind the reduction
-    u32x4 adn = gn_buf_ld16(rad, addp && row_ok(0) ? ad_o : GN_OOB);
+    u32x4 adn = gn_buf_ld16(rad, addp && row_ok(0) ? ad_o : BUF_OOB);
     const float inv_n = 1.0f / ((float)s.HW * s.cpg);
     const bool fast = P2 || ((s.cpg & (s.cpg - 1)) == 0 && s.cpg <= 64);
     if (fast) {
@@ -1128,13 +1118,13 @@ void gn_lds_bwd_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __r
     for (int i = 0; i < NV; ++i) {
         const bool ok = row_ok2(i);
         const u32x4 adc = adn;
-        if (i + 1 < NV) adn = gn_buf_ld16(rad, addp && row_ok2(i + 1) ? ad_o2 + (i + 1) * ad_st : GN_OOB);
+        if (i + 1 < NV) adn = gn_buf_ld16(rad, addp && row_ok2(i + 1) ? ad_o2 + (i + 1) * ad_st : BUF_OOB);
         if constexpr (VEC == 8) {
             // bf16: pairs again — dx = dz*ca + x*q2 + q3 is two v_pk_fma per pair
             const u32x4 xv = myx[i * NT], dv = vd[i];
             const unsigned xw[4] = {xv.x, xv.y, xv.z, xv.w}, dw[4] = {dv.x, dv.y, dv.z, dv.w}, aw[4] = {adc.x, adc.y, adc.z, adc.w};
             u32x4 ov = zero16();
-            if (accumulate) ov = gn_buf_ld16(rdx, ok ? dx_o2 + i * dx_st : GN_OOB);
+            if (accumulate) ov = gn_buf_ld16(rdx, ok ? dx_o2 + i * dx_st : BUF_OOB);
             const unsigned ow[4] = {ov.x, ov.y, ov.z, ov.w};
             unsigned pw[4];
 #pragma unroll
@@ -1162,12 +1152,12 @@ void gn_lds_bwd_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __r
                     cs[2 * k] = c.x; cs[2 * k + 1] = c.y;
                 }
             }
-            gn_buf_st16(rdx, ok ? dx_o2 + i * dx_st : GN_OOB, packed);
+            gn_buf_st16(rdx, ok ? dx_o2 + i * dx_st : BUF_OOB, packed);
         } else {
             float fx[VEC], fd[VEC], o[VEC];
             Elem<T>::unpack(myx[i * NT], fx); Elem<T>::unpack(vd[i], fd);
             float ad[VEC];
-            if (accumulate) Elem<T>::unpack(gn_buf_ld16(rdx, ok ? dx_o2 + i * dx_st : GN_OOB), o);
+            if (accumulate) Elem<T>::unpack(gn_buf_ld16(rdx, ok ? dx_o2 + i * dx_st : BUF_OOB), o);
             if (addp) Elem<T>::unpack(adc, ad);
 #pragma unroll
             for (int e = 0; e < VEC; ++e) {
@@ -1184,7 +1174,7 @@ void gn_lds_bwd_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __r
 #pragma unroll
                 for (int e = 0; e < VEC; ++e) cs[e] += q[e];
             }
-            gn_buf_st16(rdx, ok ? dx_o2 + i * dx_st : GN_OOB, packed);
+            gn_buf_st16(rdx, ok ? dx_o2 + i * dx_st : BUF_OOB, packed);
         }
         __builtin_amdgcn_sched_barrier(0);
     }
@@ -1230,7 +1220,7 @@ void gn_lds_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, GnShape s, Gn
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool active = tid < f.nta;
     const int j = tid % f.seg_vecs, prow = tid / f.seg_vecs;
-    const unsigned lds0 = (unsigned)(size_t)lsm, k0 = (unsigned)(size_t)sh_k;
+    const unsigned lds0 = lds_addr(lsm), k0 = lds_addr(sh_k);
     const unsigned kcol = k0 + (unsigned)(j * VEC * 4), kstride = (unsigned)(f.seg_ch * 4);
     const __amdgpu_buffer_rsrc_t rx = gn_slice_rsrc(x + ((long long)b * s.HW) * s.x_ld + c0, ((long long)(s.HW - 1) * s.x_ld + f.seg_ch) * ES);
     // per-channel inputs: all threads load (channel index clamped: no branch around VMEM), the first seg_ch publish; the pivot stays
@@ -1242,9 +1232,9 @@ void gn_lds_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, GnShape s, Gn
     auto row_ok = [&](int i) { return active && prow + i * f.rows_per_iter < s.HW; };
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-        unsigned ox = row_ok(i) ? x_o + i * x_st : GN_OOB;
+        unsigned ox = row_ok(i) ? x_o + i * x_st : BUF_OOB;
         asm volatile("" : "+v"(ox));                     // exactly one DMA per row on every path (hipcc otherwise splits the select into two predicated instructions)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (__attribute__((address_space(3))) void*)(xs + (i * NT + wave * 64) * 16), 16, ox, 0, 0, 0);
+        LDS_DMA16(rx, xs + (i * NT + wave * 64) * 16, ox, 0);
     }
     if (tid < f.seg_ch) {
         const unsigned ad = k0 + (unsigned)(tid * 4);
@@ -1260,7 +1250,7 @@ void gn_lds_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, GnShape s, Gn
 #pragma unroll
     for (int e = 0; e < VEC; ++e) s1[e] = s2[e] = 0.f;
     const unsigned myx_ad = lds0 + (unsigned)(tid * 16);
-    static_for_gn<NV>([&](auto ic) {
+    static_for<NV>([&](auto ic) {
         constexpr int i = decltype(ic)::v;
         gn_wait_vm<NV - 1 - i>(0);
         const int p = prow + i * f.rows_per_iter;
@@ -1385,7 +1375,7 @@ void gn_lds_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, GnShape s, Gn
                 yw[k] = pack_bf2(z.x, z.y);
             }
             u32x4 yv; yv.x = yw[0]; yv.y = yw[1]; yv.z = yw[2]; yv.w = yw[3];
-            gn_buf_st16(ry, row_ok(i) ? y_o + i * y_st : GN_OOB, yv);
+            gn_buf_st16(ry, row_ok(i) ? y_o + i * y_st : BUF_OOB, yv);
             continue;
         }
         float fv[VEC];
@@ -1405,7 +1395,7 @@ void gn_lds_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, GnShape s, Gn
                 fv[e + 1] = (w >> 16) >= a.thresh16 ? fv[e + 1] * keep_scale : 0.f;
             }
         }
-        gn_buf_st16(ry, row_ok(i) ? y_o + i * y_st : GN_OOB, Elem<T>::pack(fv));
+        gn_buf_st16(ry, row_ok(i) ? y_o + i * y_st : BUF_OOB, Elem<T>::pack(fv));
     }
     GN_STAMP(5);
 #ifdef GN_TIMING

@@ -22,8 +22,6 @@
 
 namespace {
 
-constexpr unsigned OOB = 0x7ffffff0u;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
@@ -37,11 +35,6 @@ struct PwArgs {
     int M, N, K, tiles_m, tiles_n, ksteps;
     int spread;                                             // 1: blocks walk (pixel tile, channel tile) pairs (fewer pixel tiles than CUs)
 };
-
-template <int N> __device__ __forceinline__ void wait_vm() {
-    static_assert(N >= 0 && N < 64, "vmcnt immediate");
-    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory");
-}
 
 template <int TM, int TN>
 __global__ __launch_bounds__(512, 2)
@@ -61,14 +54,8 @@ void pw_conv_kernel(PwArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wn = wave / WM, wm = wave % WM;
 
-    auto rsrc_of = [&](const void* p, unsigned extent) {
-        const unsigned long long ad = (unsigned long long)p;
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)ad), hi = __builtin_amdgcn_readfirstlane((unsigned)(ad >> 32));
-        return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0,
-                                                 __builtin_amdgcn_readfirstlane((int)extent), 0x00020000);
-    };
-    const __amdgpu_buffer_rsrc_t rx = rsrc_of(a.x, a.x_extent), rw = rsrc_of(a.w, a.w_extent);
-    const __amdgpu_buffer_rsrc_t rb = rsrc_of(a.bias ? (const void*)a.bias : (const void*)a.w, a.bias ? (unsigned)(a.N * 4) : 0u);
+    const __amdgpu_buffer_rsrc_t rx = buffer_rsrc(a.x, a.x_extent), rw = buffer_rsrc(a.w, a.w_extent);
+    const __amdgpu_buffer_rsrc_t rb = buffer_rsrc(a.bias ? (const void*)a.bias : (const void*)a.w, a.bias ? (unsigned)(a.N * 4) : 0u);
 
     // DMA plan (LDS rows of 128 bytes = 64 k; 16-byte chunk c of row r sits at physical chunk c ^ ((r >> 1) & 7))
     unsigned xoff[4], woff[4];            // (fixed bound: hipcc's host pass rejects a lambda capturing an array of template-dependent size)
@@ -98,8 +85,7 @@ void pw_conv_kernel(PwArgs a) {
         // order — and drain the ring at every tile.  Lanes >= TN / 4 are out of range and write zeros into the slot's padding.
         if (i_ks == 0) {
             if (wave == 0 && a.bias)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (__attribute__((address_space(3))) void*)(smem + BIAS_AT + (i_tile & 3) * 1024), 16,
-                                                         lane < TN / 4 ? (unsigned)((i_nt * TN + lane * 4) * 4) : OOB, 0, 0, 0);
+                LDS_DMA16(rb, smem + BIAS_AT + (i_tile & 3) * 1024, lane < TN / 4 ? (unsigned)((i_nt * TN + lane * 4) * 4) : BUF_OOB, 0);
             ++i_tile;
         }
         const unsigned xb = (unsigned)i_mt * x_tile_bytes + (unsigned)(i_ks * 128);
@@ -107,10 +93,10 @@ void pw_conv_kernel(PwArgs a) {
         // rows beyond M / N: the offset runs past the descriptor's extent (rows are laid out in increasing order) -> zeros
 #pragma unroll
         for (int i = 0; i < XV; ++i)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (__attribute__((address_space(3))) void*)(dst + (wave * 64 + 512 * i) * 16), 16, xb + xoff[i], 0, 0, 0);
+            LDS_DMA16(rx, dst + (wave * 64 + 512 * i) * 16, xb + xoff[i], 0);
 #pragma unroll
         for (int i = 0; i < WV; ++i)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (__attribute__((address_space(3))) void*)(dst + XB + (wave * 64 + 512 * i) * 16), 16, wb + woff[i], 0, 0, 0);
+            LDS_DMA16(rw, dst + XB + (wave * 64 + 512 * i) * 16, wb + woff[i], 0);
         ++i_q;
         if (++i_ks == a.ksteps) {
             i_ks = 0;
@@ -212,7 +198,7 @@ void pw_conv_kernel(PwArgs a) {
                             // inline asm: hipcc puts `s_waitcnt vmcnt(0)` in front of a C++ LDS read it cannot prove disjoint from the
                             // pending LDS-DMA — that would drain the ring here, at every tile
                             f32x4v bv;
-                            const unsigned baddr = (unsigned)(size_t)(smem + BIAS_AT + (c_tile & 3) * 1024 + (n - c_nt * TN) * 4);
+                            const unsigned baddr = lds_addr(smem + BIAS_AT + (c_tile & 3) * 1024 + (n - c_nt * TN) * 4);
                             asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(bv) : "v"(baddr) : "memory");
                             v[0] += bv.x; v[1] += bv.y; v[2] += bv.z; v[3] += bv.w;
                         }
@@ -265,7 +251,7 @@ int ddpm_pointwise_launch(const void* x, long long x_ld, const void* w, void* y,
     constexpr int min_m = 8192;      // below: too few tiles even as (pixel, channel) pairs (the 64x64-tile kernel with its split-K serves those)
     if (M < min_m || K % 64 || N % 8 || x_ld % 8 || y_ld % 8 || (residual && res_ld % 4)) return -1;
     if (!aligned16(x) || !aligned16(w) || !aligned16(y) || (residual && (((uintptr_t)residual) & 7)) || (bias && !aligned16(bias))) return -1;
-    if ((long long)M * x_ld * 2 > 0x7ffffff0ll || (long long)N * K * 2 > 0x7ffffff0ll) return -1;
+    if ((long long)M * x_ld * 2 > BUF_OOB || (long long)N * K * 2 > BUF_OOB) return -1;
     if (dry) return DDPM_OK;
     PwArgs a; memset(&a, 0, sizeof(a));
     a.x = (const bf16_t*)x; a.x_ld = x_ld; a.x_extent = (unsigned)(((long long)(M - 1) * x_ld + K) * 2);

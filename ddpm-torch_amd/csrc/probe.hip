@@ -8,8 +8,6 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 __global__ __launch_bounds__(256) void mfma_probe_kernel(float* sink, int iters, unsigned seed, int zero) {
     const unsigned id = blockIdx.x * 256 + threadIdx.x;
     u32x4 a[4], b[4];

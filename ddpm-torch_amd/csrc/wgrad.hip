@@ -28,7 +28,6 @@
 
 namespace {
 
-constexpr unsigned OOB = 0x7ffffff0u;
 constexpr int TN = 64, TC = 32;                 // output tile: out-channels x in-channels (x 9 taps)
 constexpr int DY_ROW = TN * 2, X_ROW = TC * 2;  // LDS row bytes: one pixel of the dy tile / of the halo
 
@@ -46,13 +45,6 @@ struct Wg3Args {
     FastDiv d_tiles, d_tiles_c, d_tpi, d_tiles_x, d_halo_img, d_halo_w;
 };
 
-__device__ __forceinline__ int xcd_logical(int id, int total) {
-    const int per = total >> 3;
-    return id < (per << 3) ? (id & 7) * per + (id >> 3) : id;
-}
-
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
 #ifdef WG_TIMING
 // debug builds only (scripts/wg_timeline.py): [block][wave][16] clock64 stamps (low 32 bits, scalar registers) of ONE mid-kernel stage of
 // the 16 x 16-patch kernel — taken right behind waits that leave nothing outstanding, so reading the clock does not disturb the LGKM
@@ -63,15 +55,6 @@ __device__ unsigned long long* g_wg_timing = nullptr;
 #define WG_T(k)
 #endif
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-// hardware transpose read: the 16-lane group's lanes 4r..4r+3 address 4 k-rows x (4 x 8 bytes); lane c receives, for its
-// column c of the 16 columns, the 4 k values (see read_frag<T, true> in gemm.hip)
-__device__ __forceinline__ uint2 tr_read(const char* p) {
-    const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
-    return __builtin_bit_cast(uint2, v);
-}
 
 // STAGE_PX: pixels per stage (256: one 16x16 patch; 128: 2 images of 8x8 / 8 images of 4x4).  PW: patch width (16 / 8 / 4).
 // RING: LDS stages in flight + 1.  NI_DY / NI_X: DMA instructions per thread per stage for the dy tile / the halo.
@@ -100,20 +83,14 @@ void wgrad3x3_kernel(Wg3Args a) {
     const int wn = wave & 1, wk = wave >> 1;
 
     const int ntiles = a.tiles_n * a.tiles_c;
-    const int lid = xcd_logical(blockIdx.x, gridDim.x);
+    const int lid = xcd_logical_id(blockIdx.x, gridDim.x, 1);
     const int split = (int)fdiv((unsigned)lid, a.d_tiles), tile = lid - split * ntiles;
     const int tn = (int)fdiv((unsigned)tile, a.d_tiles_c), tc = tile - tn * a.tiles_c;
     const int st_begin = split * a.stages_per_split, st_end = min(a.stages, st_begin + a.stages_per_split);
     const int nst = max(st_end - st_begin, 0);
     const int PP = 1 << a.lPP, HH = a.PH + 2, HP = a.NB * HH * HW, tpi = a.tiles_y * a.tiles_x;
 
-    auto rsrc_of = [&](const void* p, unsigned extent) {
-        const unsigned long long ad = (unsigned long long)p;
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)ad), hi = __builtin_amdgcn_readfirstlane((unsigned)(ad >> 32));
-        return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0,
-                                                 __builtin_amdgcn_readfirstlane((int)extent), 0x00020000);
-    };
-    const __amdgpu_buffer_rsrc_t rdy = rsrc_of(a.dy, a.dy_extent), rx = rsrc_of(a.x, a.x_extent);
+    const __amdgpu_buffer_rsrc_t rdy = buffer_rsrc(a.dy, a.dy_extent), rx = buffer_rsrc(a.x, a.x_extent);
 
     // ---- DMA plans.  dy tile: vector v = tid + 512 i -> stage pixel p = v >> 3, PHYSICAL chunk v & 7 of its 128-byte row; the
     // logical chunk is XOR-swizzled by ((p >> 1) & 1) << 2 on the source side so that the four k-rows one transpose read touches
@@ -155,18 +132,18 @@ void wgrad3x3_kernel(Wg3Args a) {
         const unsigned base_x = (unsigned)((((long long)(img0 * (a.H >> a.ups) + (py0 >> a.ups)) * (a.W >> a.ups) + (px0 >> a.ups)) * a.x_ld) * 2);   // wave-uniform
 #pragma unroll
         for (int i = 0; i < NI_DY; ++i) {
-            const unsigned o = (img0 + dy_il0 + i * dy_il_delta < a.B) ? base + dy_rel0 + i * dy_delta : OOB;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rdy, (__attribute__((address_space(3))) void*)(dst + (wave * 64 + 512 * i) * 16), 16, o, 0, 0, 0);
+            const unsigned o = (img0 + dy_il0 + i * dy_il_delta < a.B) ? base + dy_rel0 + i * dy_delta : BUF_OOB;
+            LDS_DMA16(rdy, dst + (wave * 64 + 512 * i) * 16, o, 0);
         }
 #pragma unroll
         for (int i = 0; i < NI_X; ++i) {
             const unsigned xp = x_pos[i];
             const int gi = img0 + (int)(xp & 0xff), iy = py0 + (int)(xp >> 16) - 1, ix = px0 + (int)((xp >> 8) & 0xff) - 1;
             const bool ok = xp != 0xffffffffu && gi < a.B && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-            const unsigned o = ok ? base_x + x_rel[i] : OOB;
+            const unsigned o = ok ? base_x + x_rel[i] : BUF_OOB;
             const int rel = (wave * 64 + 512 * i) * 16;
             char* to = (rel + 1024 <= X_BYTES) ? dst + DY_BYTES + rel : smem + DUMP_OFF;       // wave-uniform
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (__attribute__((address_space(3))) void*)to, 16, o, 0, 0, 0);
+            LDS_DMA16(rx, to, o, 0);
         }
     };
     auto wait_inflight = [&](int stages_newer) {      // stages issued after the one that must have landed may stay in flight
@@ -461,7 +438,7 @@ void wgrad3x3_kernel(Wg3Args a) {
 //   * waves 4-7 are LOADERS: they own the whole DMA schedule (dy tile 32 KiB + two 21-KiB channel-half planes of the halo per stage,
 //     ring of two stages) and their own vmcnt queue;
 //   * no s_barrier in the loop: ready[4] (one per loader: stages completely landed) and freed[4] (one per consumer: stages completely
-//     read) are monotone counters in LDS, each with a single writer; a check is one ds_read_b128.
+//     read) are monotone counters in LDS, each with a single writer; a check is one ds_read_b128 (the protocol: gfx950.h).
 // A 64-wide in-channel tile halves the L2 -> LDS bytes per FLOP (74 KiB per 4608 clk of MFMA against 53 KiB per 2304).
 // Covers C % 64 == 0 and N % 64 == 0 on images with 16-divisible sides (every 3 x 3 conv of the 32 x 32 / 16 x 16 levels but in_conv / out_conv).
 constexpr int WS_TC = 64;
@@ -471,9 +448,9 @@ constexpr int WS_STAGE = WS_DY_BYTES + 2 * WS_XP_BYTES;    // 75776
 constexpr int WS_CNT_AT = 2 * WS_STAGE;                    // ready[4] | freed[4] | junk words for the signalling waves' idle lanes
 constexpr int WS_BYTES = WS_CNT_AT + 1024;
 static_assert(WS_BYTES <= 160 * 1024 && TN * 9 * WS_TC * 4 + 1024 <= WS_CNT_AT, "LDS");
-constexpr unsigned long long WS_WAIT_TICKS = 500000000ull; // 5 s of the 100 MHz clock: a protocol error traps, it never hangs the GPU
-__device__ unsigned g_ws_fault[4];
-
+__device__ unsigned g_ws_fault[4];                          // what a timed-out semaphore wait leaves behind
+// lds_wait_all_ge (gfx950.h) in this kernel's own spelling: the shared one changes the register allocation around the wait loops here,
+// and this spelling changes conv3x3_pc_kernel's (profiles/device_primitives.txt)
 __device__ __forceinline__ void ws_wait_all_ge(unsigned addr, unsigned target) {
     unsigned long long t_first = 0;
     for (unsigned spins = 0;; ++spins) {
@@ -484,17 +461,13 @@ __device__ __forceinline__ void ws_wait_all_ge(unsigned addr, unsigned target) {
         if ((spins & 4095u) == 4095u) {
             const unsigned long long now = wall_clock64();
             if (t_first == 0) t_first = now | 1ull;
-            else if (now - t_first > WS_WAIT_TICKS) {
+            else if (now - t_first > LDS_WAIT_TICKS) {
                 if ((threadIdx.x & 63) == 0) { g_ws_fault[0] = blockIdx.x; g_ws_fault[1] = addr; g_ws_fault[2] = target; g_ws_fault[3] = 1; __threadfence_system(); }
                 __builtin_trap();
             }
         }
         __builtin_amdgcn_s_sleep(1);
     }
-}
-// a wave publishes its counter: lane 0 writes the counter, every other lane its own junk word (no exec masking)
-__device__ __forceinline__ void ws_publish(unsigned lane_addr, unsigned value) {
-    asm volatile("ds_write_b32 %0, %1" :: "v"(lane_addr), "v"(value) : "memory");
 }
 
 __global__ __launch_bounds__(512, 2)
@@ -504,7 +477,7 @@ void wgrad3x3_ws_kernel(Wg3Args a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int ntiles = a.tiles_n * a.tiles_c;
-    const int lid = xcd_logical(blockIdx.x, gridDim.x);
+    const int lid = xcd_logical_id(blockIdx.x, gridDim.x, 1);
     const int split = (int)fdiv((unsigned)lid, a.d_tiles), tile = lid - split * ntiles;
     const int tn = (int)fdiv((unsigned)tile, a.d_tiles_c), tc = tile - tn * a.tiles_c;
     const int st_begin = split * a.stages_per_split, st_end = min(a.stages, st_begin + a.stages_per_split);
@@ -533,13 +506,7 @@ void wgrad3x3_ws_kernel(Wg3Args a) {
     const bool want_bias = a.dbias != nullptr && tc == 0;
 
     // ---- DMA plan (every wave builds it: the first two stages are fetched by all eight waves, see below)
-    auto rsrc_of = [&](const void* p, unsigned extent) {
-        const unsigned long long ad = (unsigned long long)p;
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)ad), hi = __builtin_amdgcn_readfirstlane((unsigned)(ad >> 32));
-        return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0,
-                                                 __builtin_amdgcn_readfirstlane((int)extent), 0x00020000);
-    };
-    const __amdgpu_buffer_rsrc_t rdy = rsrc_of(a.dy, a.dy_extent), rx = rsrc_of(a.x, a.x_extent);
+    const __amdgpu_buffer_rsrc_t rdy = buffer_rsrc(a.dy, a.dy_extent), rx = buffer_rsrc(a.x, a.x_extent);
     // dy tile: instruction d (0..31) fills the 1 KiB at d * 1024 = stage pixels d * 8 + lane / 8 (patch row d / 2, columns (d & 1) * 8 ...), physical
     // chunk lane % 8; the logical chunk is XOR-swizzled by bit 1 of the pixel (= bit 4 of the lane), as in the kernel above.
     // halo: instruction g (0..41) -> channel-half plane g / 21, rows (g % 21) * 16 + lane / 4 of the 18 x 18 halo.
@@ -554,7 +521,7 @@ void wgrad3x3_ws_kernel(Wg3Args a) {
         const unsigned base = (unsigned)((((long long)(img * a.H + py0) * a.W + px0) * a.dy_ld) * 2);
         for (int d = d0; d < d0 + dn; ++d) {
             const unsigned so = base + (unsigned)((((d >> 1) * a.W + (d & 1) * 8) * (int)a.dy_ld) * 2);      // wave-uniform
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rdy, (__attribute__((address_space(3))) void*)(dst + d * 1024), 16, dy_lane, so, 0, 0);
+            LDS_DMA16(rdy, dst + d * 1024, dy_lane, so);
         }
         const unsigned base_x = (unsigned)((((long long)(img * (a.H >> a.ups) + (py0 >> a.ups)) * (a.W >> a.ups) + (px0 >> a.ups)) * a.x_ld) * 2);
         for (int g = g0; g < 42; g += gstep) {
@@ -564,9 +531,9 @@ void wgrad3x3_ws_kernel(Wg3Args a) {
             const int iy = py0 + hy - 1, ix = px0 + hx - 1;
             const bool ok = hp < 324 && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
             const int dyi = (hy - 1) >> a.ups, dxi = (hx - 1) >> a.ups;
-            unsigned o = ok ? base_x + (unsigned)((dyi * (a.W >> a.ups) + dxi) * (int)a.x_ld * 2) + x_c2 + (unsigned)(pl * 64) : OOB;
+            unsigned o = ok ? base_x + (unsigned)((dyi * (a.W >> a.ups) + dxi) * (int)a.x_ld * 2) + x_c2 + (unsigned)(pl * 64) : BUF_OOB;
             asm volatile("" : "+v"(o));
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (__attribute__((address_space(3))) void*)(dst + WS_DY_BYTES + pl * WS_XP_BYTES + q * 1024), 16, o, 0, 0, 0);
+            LDS_DMA16(rx, dst + WS_DY_BYTES + pl * WS_XP_BYTES + q * 1024, o, 0);
         }
     };
     // ---- the first two stages are fetched by ALL eight waves (the consumers have nothing to multiply yet; an LDS-DMA instruction holds its
@@ -581,13 +548,13 @@ void wgrad3x3_ws_kernel(Wg3Args a) {
         const unsigned sig_ready = lane == 0 ? cnt0 + (unsigned)(lw * 4) : cnt0 + 64u + (unsigned)(lane * 4);
         for (int s = 2; s < nst; ++s) {
             WS_T0();
-            ws_wait_all_ge(cnt0 + 16u, (unsigned)(s - 1));                      // every consumer is through stage s - 2: its slot is free
+            ws_wait_all_ge(cnt0 + 16u, (unsigned)(s - 1));         // every consumer is through stage s - 2: its slot is free
             WS_T1(wclk);
             issue(s, lw * 8, 8, lw, 4);
             WS_T0();
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             WS_T1(vclk);
-            ws_publish(sig_ready, (unsigned)(s + 1));
+            lds_publish(sig_ready, (unsigned)(s + 1));
         }
     } else {
         // ---------------------------------------------------------------- consumers
@@ -614,7 +581,7 @@ void wgrad3x3_ws_kernel(Wg3Args a) {
             const unsigned stage0 = lds0 + (unsigned)((s & 1) * WS_STAGE);
             const unsigned abase = stage0 + (unsigned)a_off, blo0 = stage0 + (unsigned)(WS_DY_BYTES + b_lo), bhi0 = stage0 + (unsigned)(WS_DY_BYTES + b_hi);
             WS_T0();
-            if (s >= 2) ws_wait_all_ge(cnt0, (unsigned)(s + 1));                // every loader's share of this stage has landed (stages 0, 1: the barrier above)
+            if (s >= 2) ws_wait_all_ge(cnt0, (unsigned)(s + 1));   // every loader's share of this stage has landed (stages 0, 1: the barrier above)
             WS_T1(wclk);
             Frag fa[2], fh[4][3];
             WS_READ_A(fa[0], 0); WS_READ_H(fh[0], 0);
@@ -634,7 +601,7 @@ void wgrad3x3_ws_kernel(Wg3Args a) {
                 if (j + 3 < 18) { if (j + 1 < 16) WS_WAIT_AH(fa[(j + 1) & 1], fh[(j + 3) & 3]); else WS_WAIT_H(fh[(j + 3) & 3]); }
                 else if (j + 1 < 16) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fa[(j + 1) & 1].lo), "+v"(fa[(j + 1) & 1].hi) :: "memory");
             }
-            ws_publish(sig_freed, (unsigned)(s + 1));                            // (behind this stage's last reads, all of them retired above)
+            lds_publish(sig_freed, (unsigned)(s + 1));                           // (behind this stage's last reads, all of them retired above)
         }
 #undef TR_READ
 #undef WS_READ_A
@@ -759,7 +726,7 @@ static int wgrad3x3_launch(const void* dy, long long dy_ld, const void* x, long 
     if (slab_stride < 0 || (slab_stride > 0 && slab_stride < (long long)Nreal * 9 * C)) return DDPM_ERR_SHAPE;
     if (slab_stride > 0 && dbias && bias_stride < Nreal) return DDPM_ERR_SHAPE;
     const long long dyb = ((long long)B * H * W * dy_ld - (dy_ld - N)) * 2, xb = ((long long)B * (H >> ups) * (W >> ups) * x_ld - (x_ld - C)) * 2;
-    if (dyb > 0x7ffffff0ll || xb > 0x7ffffff0ll) return DDPM_ERR_SHAPE;
+    if (dyb > BUF_OOB || xb > BUF_OOB) return DDPM_ERR_SHAPE;
     Wg3Args a; memset(&a, 0, sizeof(a));
     a.dy = dy; a.dy_ld = dy_ld; a.dy_extent = (unsigned)dyb; a.x = x; a.x_ld = x_ld; a.x_extent = (unsigned)xb;
     a.dw = dw; a.slab_stride = slab_stride; a.dbias = dbias; a.bias_stride = bias_stride;

@@ -17,7 +17,6 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 struct Wg1Args {
@@ -31,11 +30,6 @@ struct Wg1Args {
 constexpr int RING = 4, OP_BYTES = 64 * 256, STAGE = 2 * OP_BYTES;     // stage = x tile [64 px][128 c] | dy tile [64 px][128 n]
 constexpr int PER = 4;                                                  // LDS-DMA instructions per thread per stage
 
-template <int N> __device__ __forceinline__ void wait_vm() {
-    static_assert(N >= 0 && N < 64, "vmcnt immediate");
-    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory");
-}
-
 __global__ __launch_bounds__(512, 2)
 void wgrad1x1_kernel(Wg1Args a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -47,13 +41,7 @@ void wgrad1x1_kernel(Wg1Args a) {
     const int tn = tile / a.tiles_c, tc = tile - tn * a.tiles_c;
     const int ks0 = split * a.ksteps_per_split, nst = max(min(a.ksteps, ks0 + a.ksteps_per_split) - ks0, 0);
 
-    auto rsrc_of = [&](const void* p, unsigned extent) {
-        const unsigned long long ad = (unsigned long long)p;
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)ad), hi = __builtin_amdgcn_readfirstlane((unsigned)(ad >> 32));
-        return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0,
-                                                 __builtin_amdgcn_readfirstlane((int)extent), 0x00020000);
-    };
-    const __amdgpu_buffer_rsrc_t rdy = rsrc_of(a.dy, a.dy_extent), rx = rsrc_of(a.x, a.x_extent);
+    const __amdgpu_buffer_rsrc_t rdy = buffer_rsrc(a.dy, a.dy_extent), rx = buffer_rsrc(a.x, a.x_extent);
 
     // DMA plan: vector v = tid + 512 i -> k-row (pixel) v >> 4 of the stage, PHYSICAL 16-byte chunk v & 15 of its 256-byte row; the logical
     // chunk is XOR-swizzled by (row & 3) << 2 on the source side so that the four k-rows one transpose read touches fall on four
@@ -63,8 +51,8 @@ void wgrad1x1_kernel(Wg1Args a) {
     for (int i = 0; i < 2; ++i) {
         const int v = tid + 512 * i, row = v >> 4, lc = (v & 15) ^ ((row & 3) << 2);
         const int c = tc * 128 + lc * 8, n = tn * 128 + lc * 8;
-        xoff[i] = c < a.C ? (unsigned)(((long long)row * a.x_ld + c) * 2) : 0x7ffffff0u;
-        yoff[i] = n < a.N ? (unsigned)(((long long)row * a.dy_ld + n) * 2) : 0x7ffffff0u;
+        xoff[i] = c < a.C ? (unsigned)(((long long)row * a.x_ld + c) * 2) : BUF_OOB;
+        yoff[i] = n < a.N ? (unsigned)(((long long)row * a.dy_ld + n) * 2) : BUF_OOB;
     }
     const unsigned x_step = (unsigned)(64 * a.x_ld * 2), y_step = (unsigned)(64 * a.dy_ld * 2);
     auto issue = [&](int st) {                                  // stage st of this block's slice into ring slot st % RING
@@ -72,12 +60,10 @@ void wgrad1x1_kernel(Wg1Args a) {
         const unsigned kx = (unsigned)(ks0 + st) * x_step, ky = (unsigned)(ks0 + st) * y_step;
 #pragma unroll
         for (int i = 0; i < 2; ++i)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (__attribute__((address_space(3))) void*)(dst + (wave * 64 + 512 * i) * 16), 16,
-                                                     xoff[i] == 0x7ffffff0u ? xoff[i] : xoff[i] + kx, 0, 0, 0);
+            LDS_DMA16(rx, dst + (wave * 64 + 512 * i) * 16, xoff[i] == BUF_OOB ? xoff[i] : xoff[i] + kx, 0);
 #pragma unroll
         for (int i = 0; i < 2; ++i)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rdy, (__attribute__((address_space(3))) void*)(dst + OP_BYTES + (wave * 64 + 512 * i) * 16), 16,
-                                                     yoff[i] == 0x7ffffff0u ? yoff[i] : yoff[i] + ky, 0, 0, 0);
+            LDS_DMA16(rdy, dst + OP_BYTES + (wave * 64 + 512 * i) * 16, yoff[i] == BUF_OOB ? yoff[i] : yoff[i] + ky, 0);
     };
 
     // fragment addressing (m-major image, k-rows of 256 bytes): this lane's transpose read of the 32-wide channel block at `rb`, K sub-step kc
@@ -91,7 +77,7 @@ void wgrad1x1_kernel(Wg1Args a) {
     unsigned offA[2], offB;                                     // kc = 0; kc adds 16 rows = 4096 bytes (the swizzle key (krow & 3) is unchanged)
     offA[0] = frag_off(wc * 64, 0); offA[1] = frag_off(wc * 64 + 32, 0);
     offB = frag_off(wn * 32, 0) + OP_BYTES;
-    const unsigned lds0 = (unsigned)(size_t)smem;
+    const unsigned lds0 = lds_addr(smem);
 
     f32x16 acc[2] = {(f32x16)(0.f), (f32x16)(0.f)};
     float bsum = 0.f;
@@ -200,7 +186,7 @@ extern "C" int ddpm_conv1x1_wgrad_nhwc(const void* dy, long long dy_ld, const vo
     if (!make_plan(P, C, N, p) || splits != p.splits || slab_stride < (long long)N * C || (dbias && bias_stride < N) || dy_ld < N || x_ld < C) return DDPM_ERR_SHAPE;
     if (!aligned16(dy) || !aligned16(x) || !aligned16(dw) || dy_ld % 8 || x_ld % 8 || slab_stride % 4 || C % 4) return DDPM_ERR_ALIGN;
     const long long dyb = ((long long)(P - 1) * dy_ld + N) * 2, xb = ((long long)(P - 1) * x_ld + C) * 2;
-    if (dyb > 0x7ffffff0ll || xb > 0x7ffffff0ll) return DDPM_ERR_SHAPE;
+    if (dyb > BUF_OOB || xb > BUF_OOB) return DDPM_ERR_SHAPE;
     Wg1Args a; memset(&a, 0, sizeof(a));
     a.dy = (const bf16_t*)dy; a.dy_ld = dy_ld; a.dy_extent = (unsigned)dyb;
     a.x = (const bf16_t*)x; a.x_ld = x_ld; a.x_extent = (unsigned)xb;

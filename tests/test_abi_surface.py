@@ -135,3 +135,26 @@ def test_every_environment_switch_is_in_the_integration_table_and_no_ablation_ma
     for path in _sources(os.path.join(PKG, "csrc"), (".hip", ".h")):
         src = open(path).read()
         assert not [m for m in RETIRED_MACROS if m in src], path
+
+
+PRIMITIVES = ("BUF_OOB", "buffer_rsrc", "lds_addr", "LDS_DMA16", "wait_vm", "lds_rd16", "lds_rd_tr", "lds_wait", "lds_wait_n", "static_for",
+              "xcd_logical_id", "lds_wait_all_ge", "lds_wait_ge", "lds_signal", "lds_publish")
+
+
+def test_gfx950_device_primitives_live_in_the_shared_header_only():
+    """The low-level building blocks of the LDS-DMA kernels are written once, in csrc/gfx950.h: outside it no .hip file spells the
+    LDS-DMA builtin or the out-of-range offset, the buffer-descriptor builtin appears exactly once (gemm.hip's slab_rs, built without
+    readfirstlane on purpose), and no file defines a second copy of a primitive the header defines (once)."""
+    csrc = os.path.join(PKG, "csrc")
+    hips = {os.path.basename(p): open(p).read() for p in _sources(csrc, (".hip",))}
+    assert len(hips) >= 14
+    assert not [f for f, src in hips.items() if "__builtin_amdgcn_raw_ptr_buffer_load_lds" in src]
+    assert not [f for f, src in hips.items() if "0x7ffffff0" in src.lower()]
+    rsrc = [(f, line.strip()) for f, src in hips.items() for line in src.splitlines() if "__builtin_amdgcn_make_buffer_rsrc" in line]
+    assert len(rsrc) == 1 and rsrc[0][0] == "gemm.hip" and "slab_rs" in rsrc[0][1], rsrc
+    header = open(os.path.join(csrc, "gfx950.h")).read()
+    assert '#include "gfx950.h"' in open(os.path.join(csrc, "common.h")).read()
+    for name in PRIMITIVES:
+        definition = re.compile(r"(?:__device__ __forceinline__ \w+|#define|constexpr unsigned) %s\b" % name)
+        assert len(definition.findall(header)) == 1, name
+        assert not [f for f, src in hips.items() if definition.search(src)], name
