@@ -75,7 +75,7 @@ const EntryPoint kEntryPoints[] = {
     EP(ddpm_add_rows), EP(ddpm_softmax_fwd), EP(ddpm_softmax_bwd), EP(ddpm_sumsq_accumulate), EP(ddpm_adam_ema_step), EP(ddpm_mt_grad_sumsq),
     EP(ddpm_mt_adam_ema), EP(ddpm_mt_gather_f32), EP(ddpm_mfma_probe), EP(ddpm_copy_probe), EP(ddpm_dropout_mask), EP_AS(ddpm_stream_order, EP_EDGE), EP_AS(ddpm_fill_zero, EP_ENQUEUES),
     EP(ddpm_toy_time_table), EP(ddpm_toy_decoder_fwd), EP(ddpm_toy_decoder_bwd), EP(ddpm_toy_time_table_bwd),
-    EP(ddpm_manifold_kth_f16), EP(ddpm_manifold_cover_f16), EP(ddpm_bpd_terms), EP(ddpm_bpd_finish),
+    EP(ddpm_manifold_kth_f16), EP(ddpm_manifold_cover_f16), EP(ddpm_bpd_terms), EP(ddpm_bpd_finish), EP(ddpm_batch_gather),
 };
 constexpr int kNumEntryPoints = (int)(sizeof(kEntryPoints) / sizeof(kEntryPoints[0]));
 

@@ -92,6 +92,8 @@ PROTOTYPES = {
     # precision / recall manifolds (csrc/manifold.hip; driven by metrics/precision_recall.py)
     "ddpm_manifold_kth_f16": [P, L, I, P, L, I, I, I, P, P, L, P],
     "ddpm_manifold_cover_f16": [P, L, I, P, L, I, I, P, P, P, L, P],
+    # device-resident training data (csrc/batch.hip; driven by datasets.DeviceLoader)
+    "ddpm_batch_gather": [P, I, P, P, P, I, L, I, I, I, I, U, P],
     # launch plans (csrc/plan.hip; driven by _plan.LaunchPlan)
     "ddpm_stream_order": [P, P],
     "ddpm_fill_zero": [P, L, P],

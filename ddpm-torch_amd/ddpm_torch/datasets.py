@@ -21,7 +21,10 @@ feed a 10 ms training step) and, when ``DDPM_TORCH_AMD_SYNTHETIC_DATA=N`` is set
 
 ``get_dataloader(dataset, batch_size, split, ...) -> (loader, sampler)`` keeps the reference's contract (:225-266): per-rank batch =
 ``batch_size // WORLD_SIZE`` when ``distributed``, ``DistributedSampler`` with per-epoch reshuffling, no shuffling for raw / test reads.
+With ``device=`` it returns a ``DeviceLoader`` instead: the whole data set is put on the GPU once and every batch is assembled there by
+one kernel (``ddpm_batch_gather``, csrc/batch.hip) in the order a host ``DataLoader`` would have drawn.
 """
+import copy
 import gzip
 import io
 import os
@@ -30,10 +33,12 @@ import struct
 
 import numpy as np
 import torch
-from torch.utils.data import DataLoader, Dataset
+from torch.utils.data import DataLoader, Dataset, Subset
 from torch.utils.data.distributed import DistributedSampler
 
-__all__ = ["DATASET_INFO", "DATASET_DICT", "get_dataloader", "TensorImages", "MNIST", "CIFAR10", "CelebA", "CelebA_HQ", "ImageFolder"]
+from . import _hip
+
+__all__ = ["DATASET_INFO", "DATASET_DICT", "get_dataloader", "DeviceLoader", "TensorImages", "MNIST", "CIFAR10", "CelebA", "CelebA_HQ", "ImageFolder"]
 
 ROOT = os.path.expanduser("~/datasets")
 DATASET_DICT, DATASET_INFO = {}, {}
@@ -268,6 +273,117 @@ class TensorImages(Dataset):
         return x
 
 
+class _OwnIndex(Dataset):
+    """item i is i: a ``DataLoader`` over it yields the batches of indices a ``DataLoader`` over the images would have fetched."""
+
+    def __init__(self, n):
+        self.n = n
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, i):
+        return i
+
+
+def _resident(data, num_workers):
+    """(images [N, C, H, W] uint8 or float32 on the host, positions in them or None, table of the 256 byte values' floats or None)
+    of a data set this module can hold on the device."""
+    if isinstance(data, Subset):
+        images, inner, lut = _resident(data.dataset, num_workers)
+        picked = torch.as_tensor(data.indices, dtype=torch.int64)
+        return images, picked if inner is None else inner[picked], lut
+    every_byte = torch.arange(256, dtype=torch.uint8)
+    if isinstance(data, TensorImages) and not data.raw and data.data.dtype in (torch.uint8, torch.float32):
+        if data.data.dtype == torch.float32:
+            return data.data, None, None
+        return data.data, None, TensorImages(every_byte.view(1, 1, 1, 256))[0].reshape(256)       # its own rounding chain, whatever it is
+    if isinstance(data, _Images) and data.transform == "train":
+        if isinstance(data, CIFAR10):
+            images = torch.from_numpy(data.data)
+        else:                                                    # decode (and resize) every image once, in the caller's worker processes
+            raw = copy.copy(data)
+            raw.transform = None
+            images, at = None, 0                                 # filled chunk by chunk: the data set is held once (CelebA-HQ is 5.9 GB)
+            for chunk in DataLoader(raw, batch_size=256, num_workers=num_workers):
+                if images is None:
+                    images = torch.empty((len(raw),) + tuple(chunk.shape[1:]), dtype=torch.uint8)
+                images[at:at + len(chunk)] = chunk
+                at += len(chunk)
+        return images, None, _to_unit(every_byte)
+    raise TypeError(f"{type(data).__name__}: not a data set DeviceLoader can hold on the device (TensorImages of uint8 / float32 in its "
+                    f"training form, the dataset classes of this module in theirs, or a Subset of one)")
+
+
+class _Epoch:
+    """Iterator over one epoch of a ``DeviceLoader``: the epoch's indices on the device and where each batch ends."""
+
+    def __init__(self, loader, index, ends, seed):
+        self.loader, self.index, self.ends, self.seed, self.at = loader, index, ends, seed, 0
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        if self.at >= len(self.ends):
+            raise StopIteration
+        lo, hi = self.ends[self.at - 1] if self.at else 0, self.ends[self.at]
+        self.at += 1
+        data, lut = self.loader.data, self.loader.lut
+        n, c, h, w = data.shape
+        out = torch.empty((hi - lo, c, h, w), dtype=torch.float32, device=data.device)
+        _hip.call("ddpm_batch_gather", data.data_ptr(), 0 if data.dtype == torch.uint8 else 1, self.index.data_ptr() + 8 * lo, _hip.ptr(lut),
+                  out.data_ptr(), hi - lo, n, c, h, w, int(self.loader.flip), self.seed, _hip.stream())
+        return out
+
+
+class DeviceLoader:
+    """The training batches of ``DataLoader(data, batch_size, shuffle / sampler, drop_last)`` with the images resident on ``device``.
+
+    Construction copies the data set to the device once (uint8 stays uint8: CIFAR-10 is 150 MB, CelebA-HQ 5.9 GB).  ``iter()`` draws the
+    epoch's index batches exactly as the host loader would — a ``DataLoader`` over a data set that returns its own index, so the same
+    ``RandomSampler`` / ``DistributedSampler`` / ``Subset`` composition and the same draws from the global generator — and uploads them
+    as one int64 tensor; ``next()`` on the iterator it returns then allocates the batch and enqueues one ``ddpm_batch_gather`` on the
+    current stream: no copy from the host, no synchronisation.  (The upload is ordered on the stream that is current at ``iter()``;
+    consume the batches on it.)  Each ``iter()`` is an epoch of its own, as with a ``DataLoader``: iterators do not disturb each other.
+
+    Flips do not consume the global generator: image i is mirrored iff the top bit of the library's counter hash of
+    ``((random_seed or 0) << 32 | epoch, i)`` is set, ``epoch`` = ``sampler.epoch`` where the sampler has one, else the number of
+    earlier ``iter()`` calls — the same for any batch size and any number of ranks."""
+
+    def __init__(self, data, batch_size, device, shuffle=False, sampler=None, drop_last=False, flip=None, random_seed=None, num_workers=0):
+        images, self._positions, lut = _resident(data, num_workers)
+        if flip is None:
+            base = data
+            while isinstance(base, Subset):
+                base = base.dataset
+            flip = base.flip
+        self.device = torch.device(device)
+        self.data = images.contiguous().to(self.device)
+        self.lut = None if lut is None else lut.to(self.device)
+        _hip.require_cuda(self.data)
+        self.flip, self.sampler, self.random_seed = bool(flip), sampler, random_seed or 0
+        self.batch_size = batch_size
+        self._order = DataLoader(_OwnIndex(len(data)), batch_size=batch_size, shuffle=shuffle, sampler=sampler, drop_last=drop_last)
+        self._epochs = 0
+
+    def __len__(self):
+        return len(self._order)
+
+    def __iter__(self):
+        epoch = self.sampler.epoch if hasattr(self.sampler, "epoch") else self._epochs
+        self._epochs += 1
+        seed = ((self.random_seed << 32) | (epoch & 0xFFFFFFFF)) & 0xFFFFFFFFFFFFFFFF
+        batches = list(self._order)
+        index = torch.cat(batches) if batches else torch.zeros(0, dtype=torch.int64)
+        if self._positions is not None:
+            index = self._positions[index]
+        if self.device.type == "cuda":
+            index = index.pin_memory()
+        ends = torch.tensor([len(b) for b in batches], dtype=torch.int64).cumsum(0).tolist()
+        return _Epoch(self, index.to(self.device, non_blocking=True), ends, seed)
+
+
 def _open(name, root, split, raw=False):
     """Tensor file, then the dataset's own files, then (if asked for) synthetic images."""
     info = DATASET_INFO[name]
@@ -293,9 +409,14 @@ def _open(name, root, split, raw=False):
 
 
 def get_dataloader(dataset, batch_size, split, val_size=0., random_seed=None, root=ROOT, pin_memory=False, drop_last=False,
-                   num_workers=0, distributed=False, raw=False, **kwargs):
-    """(DataLoader, sampler) with the reference's batch / shard semantics (datasets.py:225-266)."""
+                   num_workers=0, distributed=False, raw=False, device=None, **kwargs):
+    """(DataLoader, sampler) with the reference's batch / shard semantics (datasets.py:225-266).  ``device``: the same batches, in the same
+    order, from a ``DeviceLoader`` that holds the data set on that GPU (training form only; ``num_workers`` then only serves the one-off
+    decode of a dataset read from image files)."""
+    if device is not None and raw:
+        raise ValueError("device= serves the training form only: the evaluation readers (raw=True) stay on the host path")
     data = _open(dataset, root, split, raw=raw)
+    flip = data.flip and split != "test"
     if distributed:
         batch_size = batch_size // int(os.environ.get("WORLD_SIZE", "1"))
     if split != "test" and val_size > 0.:
@@ -307,6 +428,9 @@ def get_dataloader(dataset, batch_size, split, val_size=0., random_seed=None, ro
         data = torch.utils.data.Subset(data, idx.tolist())
     sampler = DistributedSampler(data, shuffle=True, seed=random_seed or 0, drop_last=drop_last) if distributed else None
     shuffle = sampler is None and split in ("train", "all") and not raw
+    if device is not None:
+        return DeviceLoader(data, batch_size, device, shuffle=shuffle, sampler=sampler, drop_last=drop_last, flip=flip, random_seed=random_seed,
+                            num_workers=num_workers), sampler
     loader = DataLoader(data, batch_size=batch_size, shuffle=shuffle, sampler=sampler, drop_last=drop_last,
                         pin_memory=pin_memory and torch.cuda.is_available(), num_workers=num_workers)
     return loader, sampler

@@ -8,7 +8,7 @@ Differences that follow from the platform, not from taste: there is no CPU path 
 ``--distributed`` uses the engine's own data parallelism (``UNet.set_process_group``: gradient all-reduce over RCCL issued
 from inside the hand-written backward) unless ``--ddp-wrapper`` asks for ``DistributedDataParallel``; ``--compute``
 chooses the arithmetic (bf16 throughput mode or exact-fp32 MFMA); images come from a tensor file or synthetic data
-(``ddpm_torch/datasets.py``); ``--eval`` scores FID through ``ddpm_torch.metrics`` when a feature network is provisioned (``DDPM_TORCH_AMD_INCEPTION`` = TorchScript file, ``precomputed/fid_stats_<dataset>.npz``) and is refused otherwise.
+(``ddpm_torch/datasets.py``), with ``--device-data`` from a copy of the data set on the training GPU; ``--eval`` scores FID through ``ddpm_torch.metrics`` when a feature network is provisioned (``DDPM_TORCH_AMD_INCEPTION`` = TorchScript file, ``precomputed/fid_stats_<dataset>.npz``) and is refused otherwise.
 """
 import argparse
 import json
@@ -81,6 +81,8 @@ def parse_args(argv=None):
     add("--dry-run", action="store_true", help="stop after the first parameter update; checkpoint and sample once")
     add("--compute", choices=["bf16", "fp32"], default="bf16", help="arithmetic of the UNet kernels (not in the reference)")
     add("--ddp-wrapper", action="store_true", help="wrap the model in DistributedDataParallel instead of the native reducer")
+    add("--device-data", action="store_true", help="hold the data set on the training GPU and assemble every batch there (not in the "
+                                                   "reference); --num-workers then only serves a one-off decode of image files")
     return p.parse_args(argv)
 
 
@@ -159,7 +161,8 @@ def run(rank=0, args=None, temp_dir=""):
     sched = torch.optim.lr_scheduler.LambdaLR(opt, lr_lambda=lambda t: min((t + 1) / tcfg.warmup, 1.0)) if tcfg.warmup > 0 else None
     loader, sampler = ddpm_torch.get_dataloader(dataset, batch_size=tcfg.batch_size, split="all" if dataset == "celeba" else "train", val_size=0.,
                                                 random_seed=seed, root=os.path.expanduser(args.root), drop_last=True, pin_memory=True,
-                                                num_workers=args.num_workers, distributed=args.distributed)
+                                                num_workers=args.num_workers, distributed=args.distributed,
+                                                device=device if args.device_data else None)
     if args.dry_run:
         say("This is a dry run.")
         args.chkpt_intv = tcfg.image_intv = 1

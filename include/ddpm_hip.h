@@ -221,6 +221,16 @@ int ddpm_add_i64(long long* t, int B, long long delta, void* stream);
  * ResidualBlock's time bias fc(act(t_emb)) (unet.py:86, with UNet.embed :122-126,207 in front of it) depends on t alone, so the sampler
  * precomputes the [T][sum Cout] table once per weight version and each step gathers its rows instead of running the embedding MLP. */
 int ddpm_gather_rows_f32(const float* table, const long long* idx, float* out, int rows, int row_len, int table_rows, void* stream);
+/* One training batch out of a data set that lives on the device — what the reference does per image on the host: the dataset's
+ * `transforms` (ToTensor + Normalize(0.5, 0.5), RandomHorizontalFlip; ddpm_torch/datasets.py:28-198) and the DataLoader's collate.
+ *   out[b] = T(data[index[b]]), out [B][C][H][W] fp32; data [n_images][C][H][W] contiguous, src_dtype 0 = uint8, 1 = fp32 (else status 2).
+ * uint8: T(x) = lut[x], lut = the host transform evaluated on the 256 byte values (bit-identical to it by construction); fp32: a copy
+ * (lut may be null).  flip != 0 mirrors sample b along W iff the top bit of the library's counter hash of (seed, index[b]) is set
+ * (csrc/common.h dropout_word): a pure function of the seed and the DATASET index, not of the position in the batch.
+ * An index outside [0, n_images) fills that sample with NaN and touches no other.  C*H*W < 2^31 (else status 1); the data set itself
+ * may be any size: image bases are 64-bit offsets from a plain pointer.  No workspace, no atomics. */
+int ddpm_batch_gather(const void* data, int src_dtype, const long long* index, const float* lut, float* out,
+                      int B, long long n_images, int C, int H, int W, int flip, unsigned long long seed, void* stream);
 
 /* nn.SiLU on the time-embedding path (unet.py:86,124) */
 int ddpm_silu_fwd(const float* x, float* y, long long n, void* stream);
