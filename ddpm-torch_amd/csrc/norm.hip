@@ -38,12 +38,17 @@ struct GnShape {
     int pix_per_slab;
 };
 
-// Pivot of group g of sample b: the group's first stored element.  The streaming kernels accumulate sum(x - k) and
-// sum((x - k)^2) instead of raw moments: with k within a few standard deviations of the mean the single-pass variance keeps
-// its accuracy when |mean| >> std (raw fp32 moments lose (mean/std)^2 * 1e-7 of relative precision).
+// Pivot of group g of sample b: the MEDIAN of three stored elements of the group's first channel, at the first, the middle and the
+// last pixel.  The kernels accumulate sum(x - k) and sum((x - k)^2) instead of raw moments: with k within a few standard deviations of
+// the mean the single-pass variance keeps its accuracy when |mean| >> std (raw fp32 moments lose (mean/std)^2 * 1e-7 of relative
+// precision).  One element alone is no safe pivot: the first one is the image corner, where zero padding makes activations atypical,
+// and a pivot k sigma from the mean costs a factor 1 + k^2 (k = 64: rstd off by 25 bars of tests/launch_replay.py); the median of
+// three is as close to the mean as the second-closest of them.
+__device__ __forceinline__ float gn_median3(float a, float b, float c) { return __builtin_amdgcn_fmed3f(a, b, c); }
 template <typename T>
 __device__ __forceinline__ float gn_pivot(const T* __restrict__ x, long long x_ld, int HW, int b, int g, int cpg) {
-    return Elem<T>::ld(x + (long long)b * HW * x_ld + g * cpg);
+    const T* p = x + (long long)b * HW * x_ld + g * cpg;
+    return gn_median3(Elem<T>::ld(p), Elem<T>::ld(p + (long long)(HW / 2) * x_ld), Elem<T>::ld(p + (long long)(HW - 1) * x_ld));
 }
 
 // thread (cx, py): channel-vector cx fixed, pixels py, py+PY, ...  (blockDim = (CV, PY))
@@ -934,7 +939,7 @@ void gn_lds_bwd_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __r
         const float rs = in_st.y, mean = in_st.x, ca = rs * in_g;
         const unsigned ad = k0 + (unsigned)(tid * 4);
         gn_lds_wr4(ad + K_RS * kstride, rs); gn_lds_wr4(ad + K_MS * kstride, -mean * rs); gn_lds_wr4(ad + K_MEAN * kstride, mean);
-        gn_lds_wr4(ad + K_CA * kstride, ca); gn_lds_wr4(ad + K_CB * kstride, in_b - mean * ca); gn_lds_wr4(ad + K_GAM * kstride, in_g);
+        gn_lds_wr4(ad + K_CA * kstride, ca); gn_lds_wr4(ad + K_CB * kstride, in_b); gn_lds_wr4(ad + K_GAM * kstride, in_g);
     }
     gn_lds_barrier();
     constexpr int NM = P2 ? 2 : VEC;                   // distinct means / pass-2 coefficients of a vector column
@@ -980,7 +985,9 @@ void gn_lds_bwd_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __r
                 mn2.x = mean[(2 * k) / MS]; mn2.y = mean[(2 * k + 1) / MS];
                 g2.x = g2.y = keep_scale;
                 if (do_silu) {
-                    const gn_f32x2 z = x2 * ca2 + cb2, nz = z * (-1.4426950408889634f);
+                    // z = (x - mean) ca + beta, not x ca + (beta - mean ca): the latter's two terms are rstd |x| gamma each and cancel —
+                    // with rstd = eps^-1/2 = 1000 (a constant group) z was off by 1e-4 and dx by 22 bars of tests/launch_replay.py
+                    const gn_f32x2 z = (x2 - mn2) * ca2 + cb2, nz = z * (-1.4426950408889634f);
                     gn_f32x2 t;
                     t.x = __builtin_amdgcn_exp2f(nz.x); t.y = __builtin_amdgcn_exp2f(nz.y);
                     t = t + 1.0f;
@@ -1023,7 +1030,7 @@ void gn_lds_bwd_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __r
                 }
                 if (do_silu) {
 #pragma unroll
-                    for (int e = h; e < h + 4; ++e) fd[e] *= silu_grad_fast_(fx[e] * ca[e] + cb[e]);
+                    for (int e = h; e < h + 4; ++e) fd[e] *= silu_grad_fast_((fx[e] - mean[e / MS]) * ca[e] + cb[e]);     // (see the bf16 branch)
                 }
 #pragma unroll
                 for (int e = h; e < h + 4; ++e) { a1[e] += fd[e] * (fx[e] - mean[e / MS]); a2[e] += fd[e]; }
@@ -1227,7 +1234,8 @@ void gn_lds_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, GnShape s, Gn
     // raw until after the DMA is out — its conversion would otherwise wait for the load right here
     const int kc = c0 + min(tid, f.seg_ch - 1);
     const float in_g = a.gamma[kc], in_b = a.beta[kc];
-    T in_praw = x[(long long)b * s.HW * s.x_ld + gn_gidx(kc, s.cpg) * s.cpg];
+    const T* pivp = x + (long long)b * s.HW * s.x_ld + gn_gidx(kc, s.cpg) * s.cpg;          // the three elements of gn_pivot
+    T in_praw = pivp[0], in_praw1 = pivp[(long long)(s.HW / 2) * s.x_ld], in_praw2 = pivp[(long long)(s.HW - 1) * s.x_ld];
     const unsigned x_o = (unsigned)((prow * s.x_ld + j * VEC) * ES), x_st = (unsigned)(f.rows_per_iter * s.x_ld * ES);
     auto row_ok = [&](int i) { return active && prow + i * f.rows_per_iter < s.HW; };
 #pragma unroll
@@ -1238,13 +1246,13 @@ void gn_lds_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, GnShape s, Gn
     }
     if (tid < f.seg_ch) {
         const unsigned ad = k0 + (unsigned)(tid * 4);
-        gn_lds_wr4(ad + K_GAM * kstride, in_g); gn_lds_wr4(ad + K_BET * kstride, in_b); gn_lds_wr4(ad + K_PIV * kstride, Elem<T>::ld(&in_praw));
+        gn_lds_wr4(ad + K_GAM * kstride, in_g); gn_lds_wr4(ad + K_BET * kstride, in_b); gn_lds_wr4(ad + K_PIV * kstride, gn_median3(Elem<T>::ld(&in_praw), Elem<T>::ld(&in_praw1), Elem<T>::ld(&in_praw2)));
     }
     gn_lds_barrier();
     float piv[VEC];
     gn_lds_rd_consts<VEC>(kcol + K_PIV * kstride, piv);
     const float n = (float)s.HW * (float)s.cpg;
-    // single pass over the slice while it lands: moments of (x - pivot), pivot = the group's first element (gn_pivot) — accurate
+    // single pass over the slice while it lands: moments of (x - pivot), pivot = gn_pivot's median of three — accurate
     // when |mean| >> std, and the statistics cost nothing beyond the load phase
     float s1[VEC], s2[VEC];
 #pragma unroll
@@ -1289,7 +1297,7 @@ void gn_lds_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, GnShape s, Gn
             acc = gn_group_lanes_sum(acc, s.cpg); sq = gn_group_lanes_sum(sq, s.cpg);
             // fp32 is enough here: the moments are of (x - pivot) with the pivot inside the data, so E[d^2] - E[d]^2 does not cancel
             const float inv_n = 1.0f / n, dmean = acc * inv_n;
-            const float var = fmaxf(sq * inv_n - dmean * dmean, 0.f);
+            const float vraw = sq * inv_n - dmean * dmean, var = vraw < 0.f ? 0.f : vraw;      // (a select, not fmaxf: a NaN stays a NaN)
             const float mean_g = sh_k[K_PIV * f.seg_ch + tid] + dmean;
             float rstd = __builtin_amdgcn_rsqf(var + a.eps);
             rstd = rstd * (1.5f - 0.5f * (var + a.eps) * rstd * rstd);          // one Newton step on the hardware estimate
@@ -1316,7 +1324,7 @@ void gn_lds_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, GnShape s, Gn
         for (int c = tid * s.cpg; c < (tid + 1) * s.cpg; ++c) { acc += sh_ch[c]; sq += sh_ch[f.seg_ch + c]; }
         // fp32 is enough here: the moments are of (x - pivot) with the pivot inside the data, so E[d^2] - E[d]^2 does not cancel
         const float inv_n = 1.0f / n, dmean = acc * inv_n;
-        const float var = fmaxf(sq * inv_n - dmean * dmean, 0.f);
+        const float vraw = sq * inv_n - dmean * dmean, var = vraw < 0.f ? 0.f : vraw;          // (a select, not fmaxf: a NaN stays a NaN)
         const float mean_g = sh_k[K_PIV * f.seg_ch + tid * s.cpg] + dmean;
         float rstd = __builtin_amdgcn_rsqf(var + a.eps);
         rstd = rstd * (1.5f - 0.5f * (var + a.eps) * rstd * rstd);          // one Newton step on the hardware estimate

@@ -43,7 +43,7 @@ __global__ void adam_ema_kernel(float* __restrict__ p, const float* __restrict__
     float clip = 1.f;
     if (total_sq && max_norm > 0.f) {
         const float c = max_norm / (sqrtf(total_sq[0]) + 1e-6f);
-        clip = c < 1.f ? c : 1.f;
+        clip = c >= 1.f ? 1.f : c;                  // a NaN norm gives a NaN coefficient, as clip_grad_norm_ does
     }
     const float step = lr / bc1;
     const float sqrt_bc2 = sqrtf(bc2);
@@ -134,7 +134,7 @@ __global__ void mt_adam_ema_kernel(const long long* __restrict__ table, const fl
         float tot = 0.f;
         for (int i = 0; i < MT_SUMSQ_LANES; ++i) tot += total_sq[i];           // fixed order: every block gets the same value
         const float c = max_norm / (sqrtf(tot) + 1e-6f);
-        clip = c < 1.f ? c : 1.f;
+        clip = c >= 1.f ? 1.f : c;                  // a NaN norm gives a NaN coefficient, as clip_grad_norm_ does
     }
     const float step = lr / bc1;
     const float sqrt_bc2 = sqrtf(bc2);

@@ -138,7 +138,10 @@ int ddpm_attention_bwd(const void* qkv, long long ld, const void* o, long long o
  * stats (optional) receives [B][G][2] = (mean, rstd) for the backward.  workspace: ddpm_gn_workspace_floats().
  * Dropout keep-mask = hash(seed, linear NHWC index) (see ddpm_dropout_mask); scale 1/(1-p).  seed_dev (optional device
  * word): the effective seed is seed + *seed_dev — a captured hipGraph then draws a fresh mask on every replay.
- * Statistics are accumulated about a per-group pivot (the group's first element), so |mean| >> std keeps full accuracy. */
+ * A dropped element is exactly 0 whatever its value (a select, not a product); a NaN or inf in a group makes every kept element of
+ * that (sample, group) and its statistics non-finite, and nothing else.
+ * Statistics are accumulated about a per-group pivot (the median of three elements of the group), so |mean| >> std keeps full
+ * accuracy. */
 int ddpm_groupnorm_silu_fwd(const void* x, long long x_ld, void* y, long long y_ld, const float* gamma, const float* beta,
                             float* stats, float* workspace, int B, int HW, int C, int G, float eps, int silu,
                             float drop_p, unsigned long long seed, const unsigned long long* seed_dev, int dtype, void* stream);

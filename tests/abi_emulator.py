@@ -244,15 +244,17 @@ class Emulator:
 
     # ------------------------------------------------------------------ group norm
     def _gn(self, x, gamma, beta, G, eps, silu, drop_p, seed, B, HW, C):
-        t = x.reshape(B, HW, C).permute(0, 2, 1).reshape(B, C, HW, 1)
-        y = F.group_norm(t, G, gamma, beta, eps)
+        # float64: torch's fp32 CPU group norm takes E[x^2] - E[x]^2, which cancels where |mean| >> std (the far_mean profile of
+        # tests/launch_replay.py); the result is rounded to fp32 where it is stored
+        t = x.reshape(B, HW, C).permute(0, 2, 1).reshape(B, C, HW, 1).double()
+        y = F.group_norm(t, G, gamma.double(), beta.double(), eps)
         if silu:
             y = F.silu(y)
         if drop_p > 0:
             idx = np.arange(B * HW * C, dtype=np.uint64)
             keep = torch.from_numpy(_keep_mask(seed, idx, _thresh(drop_p)).astype(np.float32)).reshape(B, HW, C).permute(0, 2, 1).reshape(B, C, HW, 1)
-            y = y * keep / (1.0 - drop_p)
-        return y.reshape(B, C, HW).permute(0, 2, 1).reshape(B * HW, C)
+            y = torch.where(keep > 0, y / (1.0 - drop_p), torch.zeros_like(y))      # a select: a dropped element is 0 whatever its value
+        return y.reshape(B, C, HW).permute(0, 2, 1).reshape(B * HW, C).float()
 
     def ddpm_groupnorm_silu_fwd(self, x, x_ld, y, y_ld, gamma, beta, stats, ws, B, HW, C, G, eps, silu, drop_p, seed, seed_dev, dt, st):
         if seed_dev and drop_p > 0:
@@ -271,14 +273,26 @@ class Emulator:
                                 seed, seed_dev, acc, dx_colsum, colsum_ld, add, add_ld, dt, st):
         if seed_dev and drop_p > 0:
             seed = (seed + int(_np(seed_dev, 1, ctypes.c_uint64, np.uint64)[0])) & ((1 << 64) - 1)
-        xin = torch.from_numpy(Mat(x, B * HW, C, x_ld, dt).get()).requires_grad_(True)
-        g = torch.from_numpy(f32(gamma, C).copy()).requires_grad_(True)
-        b = torch.from_numpy(f32(beta, C).copy()).requires_grad_(True)
-        gy = torch.from_numpy(Mat(dy, B * HW, C, dy_ld, dt).get())
-        with torch.enable_grad():                  # we are called from inside an autograd.Function.backward
-            self._gn(xin, g, b, G, 1e-6, silu, drop_p, seed, B, HW, C).backward(gy)
+        # the contract's formula on the statistics the caller passes (the kernel recomputes neither), in float64
+        xin = Mat(x, B * HW, C, x_ld, dt).get().astype(np.float64).reshape(B, HW, G, C // G)
+        gy = Mat(dy, B * HW, C, dy_ld, dt).get().astype(np.float64).reshape(B, HW, G, C // G)
+        gm, bt = (f32(v, C).astype(np.float64).reshape(1, 1, G, C // G) for v in (gamma, beta))
+        stv = f32(stats, B * G * 2).astype(np.float64).reshape(B, G, 2)
+        mean, rstd = stv[:, None, :, :1], stv[:, None, :, 1:]
+        xh = (xin - mean) * rstd
+        tt = gm * xh + bt
+        dz = gy
+        if silu:
+            sg = 1.0 / (1.0 + np.exp(-tt))
+            dz = dz * sg * (1.0 + tt * (1.0 - sg))
+        if drop_p > 0:
+            keep = _keep_mask(seed, np.arange(B * HW * C, dtype=np.uint64), _thresh(drop_p)).reshape(B, HW, G, C // G)
+            dz = dz * keep / (1.0 - drop_p)
+        a = dz * gm
+        c1, c2 = (a * xh).mean((1, 3), keepdims=True), a.mean((1, 3), keepdims=True)
+        val = (rstd * (a - xh * c1 - c2)).reshape(B * HW, C).astype(np.float32)
+        g_grad, b_grad = ((dz * xh).sum((0, 1)).reshape(C).astype(np.float32), dz.sum((0, 1)).reshape(C).astype(np.float32))
         dst = Mat(dx, B * HW, C, dx_ld, dt)
-        val = xin.grad.numpy()
         if add:
             val = val + Mat(add, B * HW, C, add_ld, dt).get()
         dst.set(dst.get() + val if acc else val)
@@ -286,9 +300,9 @@ class Emulator:
             cs = Mat(dx_colsum, B, C, colsum_ld, F32)
             cs.set(cs.get() + dst.get().reshape(B, HW, C).sum(1))
         if dgamma:
-            f32(dgamma, C)[...] += g.grad.numpy()
+            f32(dgamma, C)[...] += g_grad
         if dbeta:
-            f32(dbeta, C)[...] += b.grad.numpy()
+            f32(dbeta, C)[...] += b_grad
 
     # ------------------------------------------------------------------ elementwise
     def ddpm_timestep_embedding(self, t, freqs, out, B, dim, st):
@@ -431,7 +445,8 @@ class Emulator:
             lr, bc1, bc2, ema_w = (float(v) for v in f32(hyper, 4))
         clip = 1.0
         if total and max_norm > 0:
-            clip = min(1.0, max_norm / (float(np.sqrt(f32(total, 64).astype(np.float64).sum())) + 1e-6))
+            c = max_norm / (float(np.sqrt(f32(total, 64).astype(np.float64).sum())) + 1e-6)
+            clip = 1.0 if c >= 1.0 else c                       # a NaN norm gives a NaN coefficient (csrc/optim.hip, clip_grad_norm_)
         for row in i64(table, 6 * n).reshape(n, 6):
             p_, g_, m_, v_, sh_, numel = (int(v) for v in row)
             p, g, m, v = f32(p_, numel), f32(g_, numel) * np.float32(clip), f32(m_, numel), f32(v_, numel)
@@ -496,8 +511,10 @@ class Emulator:
         dst.set(dst.get() + v if acc else v)
 
     def ddpm_softmax_fwd(self, s, p, rows, L, dt, st):
-        v = torch.softmax(torch.from_numpy(f32(s, rows * L).reshape(rows, L).copy()), -1)
-        Mat(p, rows, L, L, dt).set(v.numpy())
+        v = f32(s, rows * L).reshape(rows, L).astype(np.float64)          # numpy: max and sum propagate a NaN, as the contract's row does
+        with np.errstate(invalid="ignore"):                                # inf - inf of a row that holds an inf
+            e = np.exp(v - v.max(-1, keepdims=True))
+        Mat(p, rows, L, L, dt).set((e / e.sum(-1, keepdims=True)).astype(np.float32))
 
     def ddpm_attention_fwd(self, qkv, ld, out, out_ld, B, L, C, scale, dt, st):
         x = Mat(qkv, B * L, 3 * C, ld, dt).get().reshape(B, L, 3 * C).astype(np.float64)

@@ -13,6 +13,11 @@ Memory safety: every buffer's extent is computed from the contract (a pitched [r
 elements), and sits between two 64 KiB guard bands filled with a sentinel byte.  After each launch the guards, and every element of the
 buffer the contract does not let the call write (pitch gaps, read-only operands), must hold what they held before.
 
+Hostile inputs (opt-in keywords of replay(); tests/test_hostile_inputs_gpu.py and _host.py): poison=True overwrites, before the launch,
+everything the contract does not let the call read — both guard bands, pitch gaps and channel-slice neighbours of inputs, the prior
+content of overwritten outputs, unspecified workspaces — with 0xFF bytes (NaN); profile= transforms the data operands after the draw
+(PROFILES); yardstick=True also puts a plain fp32 torch composition through the same bars.  Without keywords the draws are unchanged.
+
 Error model: each output element i gets its own bar
     |got_i - ref_i| <= c * (u_out * M_i + u_acc * sqrt(K) * S_i)
 M_i is the sum of the magnitudes of the terms added into element i (the product sum, bias, row bias, residual, prior content), S_i is
@@ -34,6 +39,7 @@ U_BF16, U_F32 = 2.0 ** -8, 2.0 ** -24
 U_ACC = 2.0 ** -24
 GUARD = 64 * 1024                   # bytes of sentinel on each side of every buffer
 SENTINEL = 0xA5
+POISON = 0xFF                       # poison mode: NaN in fp32 and bf16, -1 in int64
 C_GEMM = 4                          # c of the GEMM-shaped families (conv, dgrad, wgrad, gemm, atb, colsum, upsample backward)
 C_NORM = 4                          # GroupNorm forward / backward
 C_ATTN = 4                          # attention forward / backward
@@ -91,10 +97,13 @@ _INT = {torch.float32: torch.int32, torch.bfloat16: torch.int16, torch.int64: to
 class Arena:
     """All buffers of one replay, each between sentinel guard bands, allocated on `device`."""
 
-    def __init__(self, device, seed):
+    def __init__(self, device, seed, poison=False, profile=None, yardstick=False):
         self.device = device
         self.gen = torch.Generator().manual_seed(seed)                   # host draws (time steps)
         self.dgen = torch.Generator(device=device).manual_seed(seed)    # buffer contents, drawn where they live
+        self.pgen = torch.Generator(device=device).manual_seed(seed + 7919)   # draws of a profile (masks): never the buffers' stream
+        self.poison, self.profile, self.yardstick = poison, profile, yardstick
+        assert profile is None or profile in PROFILES, profile
         self.bufs = []
 
     def buf(self, name, n, dtype, mod=0):
@@ -105,7 +114,23 @@ class Arena:
     def randn(self, n, mean=0.0, scale=1.0):
         return torch.randn(n, generator=self.dgen, device=self.device) * scale + mean
 
+    def shape(self, role, view, **kw):
+        """Apply the active profile's transform for `role` (PROFILES) to a strided view of a buffer, in place; the values are formed
+        in fp32 and stored in the buffer's type, and the references read the stored values.  No profile, or a profile without that
+        role: nothing happens and nothing is drawn."""
+        fn = PROFILES[self.profile][1].get(role) if self.profile else None
+        if fn is not None and view.numel():
+            view.copy_(fn(self, view.to(torch.float32), **kw))
+
+    def shaped(self, role, values, **kw):
+        """shape() for values that are not in a buffer yet."""
+        fn = PROFILES[self.profile][1].get(role) if self.profile else None
+        return values if fn is None else fn(self, values, **kw)
+
     def snapshot(self):
+        if self.poison:
+            for b in self.bufs:
+                b.poison()
         for b in self.bufs:
             b.before = b.raw.clone()
 
@@ -131,6 +156,30 @@ class Buf:
         self.t = self.raw[self.start:self.start + self.nbytes].view(dtype)
         self.written = torch.zeros(self.n, dtype=torch.bool, device=device)
         self.ptr = self.raw.data_ptr() + self.start
+        # poison mode: the elements the contract lets the call READ (inp / all_in); every other element, and both guard bands, are
+        # overwritten with POISON before the first snapshot.  A buffer that declares nothing is poisoned whole.
+        self.readable = torch.zeros(self.n, dtype=torch.bool, device=device)
+        self.poisoned = False
+        self.atomic = False             # an fp32-atomic accumulation target: its bits depend on the order of arrival
+        self.scratch = False            # a workspace whose final content the contract does not state
+
+    def inp(self, rows, cols, ld, off=0):
+        """The call may read the [rows][cols] elements with pitch ld starting `off` elements in."""
+        if rows > 0 and cols > 0:
+            self.readable.as_strided((rows, cols), (ld, 1), off).fill_(True)
+        return self
+
+    def all_in(self):
+        self.readable.fill_(True)
+        return self
+
+    def poison(self):
+        if self.poisoned:
+            return
+        self.poisoned = True
+        self.raw[:self.start] = POISON
+        self.raw[self.start + self.nbytes:] = POISON
+        self.t.view(_INT[self.t.dtype])[~self.readable] = -1
 
     def fill(self, values):
         self.t.copy_(values.to(self.t.dtype).reshape(-1)[:self.n])
@@ -168,13 +217,40 @@ def image_slices(B, per_image):
 
 
 class Result:
-    def __init__(self, sig):
+    def __init__(self, sig, nonfinite=False):
         self.sig, self.worst, self.where, self.max_bytes = sig, 0.0, "", 0
+        self.nonfinite = nonfinite          # the `nonfinite_*` profiles: cmp_nonfinite stands in for cmp
+        self.yard, self.yard_where = None, ""
+        self.planted = {}                   # what -> number of elements the float64 reference makes non-finite
+        self.outputs = {}                   # buffer name -> the stored output elements (replay() fills it)
 
-    def cmp(self, what, got, ref, bar):
+    def cmp(self, what, got, ref, bar, yard=None):
+        """yard (optional): the yardstick's value of the same output, put through the same bar; it never decides a replay."""
+        if self.nonfinite:
+            return self.cmp_nonfinite(what, got, ref, bar)
         got, ref, bar = _d(got), ref.to(got.device), bar.to(got.device)
         assert bool(torch.isfinite(got).all()), f"{what}: non-finite output"
         r = float(((got - ref).abs() / (bar + TINY)).max()) if got.numel() else 0.0
+        if r >= self.worst:
+            self.worst, self.where = r, what
+        if yard is not None and got.numel():
+            ry = float(((_d(yard).to(got.device) - ref).abs() / (bar + TINY)).max())
+            if self.yard is None or ry >= self.yard:
+                self.yard, self.yard_where = ry, what
+        return r
+
+    def cmp_nonfinite(self, what, got, ref, bar):
+        """cmp for inputs that hold a NaN or an inf: wherever the float64 reference is non-finite the output must be non-finite, and
+        everywhere else it must be finite and within its bar."""
+        got, ref, bar = _d(got), ref.to(got.device), bar.to(got.device)
+        nf = ~torch.isfinite(ref)
+        self.planted[what] = self.planted.get(what, 0) + int(nf.sum())
+        swallowed = nf & torch.isfinite(got)
+        assert not bool(swallowed.any()), f"{what}: {int(swallowed.sum())} of {int(nf.sum())} element(s) finite where the reference is not"
+        ok = ~nf
+        assert bool(torch.isfinite(got[ok]).all()), f"{what}: {int((~torch.isfinite(got) & ok).sum())} non-finite element(s) where the reference is finite"
+        assert bool(torch.isfinite(bar[ok]).all()), f"{what}: the bar is non-finite where the reference is finite"
+        r = float(((got[ok] - ref[ok]).abs() / (bar[ok] + TINY)).max()) if bool(ok.any()) else 0.0
         if r >= self.worst:
             self.worst, self.where = r, what
         return r
@@ -277,6 +353,18 @@ def rep_conv2d(A, sig, res):
     for b in (bias, rb, r_):
         if b is not None:
             b.fill(A.randn(b.n))
+    x.inp(B * H * W, C, x_ld)
+    w.all_in()
+    A.shape("data", x.mat(B * H * W, C, x_ld))
+    for b, v in ((bias, (1, N, N)), (rb, (B, N, rb_ld)), (r_, (M, N, res_ld))):
+        if b is not None:
+            A.shape("additive", b.inp(*v).mat(*v))
+    if acc:                                                 # the prior content is an operand; otherwise it is overwritten
+        A.shape("additive", y.all_in().t if mode == 3 else y.inp(M, N, y_ld).mat(M, N, y_ld))
+    if ws is not None:
+        ws.scratch = True
+    if cnt is not None:
+        cnt.all_in()                                        # zero on entry (contract)
     prior = _d(y.t).clone()
     if mode == 3:
         y.all_out()
@@ -383,6 +471,8 @@ def rep_conv3x3_wgrad(A, sig, res, up=False):
     assert copies > 0
     dy = A.buf("dy", pitched(B * H * W, N, dy_ld), dt, _mod(pdy)).fill(A.randn(pitched(B * H * W, N, dy_ld)))
     x = A.buf("x", pitched(B * Hs * Ws, C, x_ld), dt, _mod(px)).fill(A.randn(pitched(B * Hs * Ws, C, x_ld)))
+    A.shape("data", dy.inp(B * H * W, N, dy_ld).mat(B * H * W, N, dy_ld))
+    x.inp(B * Hs * Ws, C, x_ld)
     n_one = Nreal * 9 * C
     if slab_stride:
         dw = _slab_setup(A, "dw", n_one, copies, slab_stride, _mod(pdw))
@@ -391,10 +481,14 @@ def rep_conv3x3_wgrad(A, sig, res, up=False):
     else:
         dw = A.buf("dw", n_one, F32, _mod(pdw)).fill(A.randn(n_one))
         dw.all_out()
+        A.shape("additive", dw.all_in().t)
+        dw.atomic = True
         prior = _d(dw.t).clone()
         db = A.buf("dbias", Nreal, F32, _mod(pdb)).fill(A.randn(Nreal)) if _opt(pdb) else None
         if db is not None:
             db.all_out()
+            A.shape("additive", db.all_in().t)
+            db.atomic = True
         bprior = None if db is None else _d(db.t).clone()
     _wgrad_launch(A, "ddpm_conv3x3_wgrad_up_nhwc" if up else "ddpm_conv3x3_wgrad_nhwc",
                   [dy.ptr, dy_ld, x.ptr, x_ld, dw.ptr, slab_stride, _ptr(db), bias_stride, B, H, W, C, N, Nreal, splits, dt])
@@ -415,6 +509,8 @@ def rep_conv1x1_wgrad(A, sig, res):
     assert slab_stride > 0 and splits >= 1
     dy = A.buf("dy", pitched(P, N, dy_ld), dt, _mod(pdy)).fill(A.randn(pitched(P, N, dy_ld)))
     x = A.buf("x", pitched(P, C, x_ld), dt, _mod(px)).fill(A.randn(pitched(P, C, x_ld)))
+    A.shape("data", dy.inp(P, N, dy_ld).mat(P, N, dy_ld))
+    x.inp(P, C, x_ld)
     dw = _slab_setup(A, "dw", N * C, splits, slab_stride, _mod(pdw))
     db = _slab_setup(A, "dbias", N, splits, bias_stride, _mod(pdb)) if _opt(pdb) else None
     _wgrad_launch(A, "ddpm_conv1x1_wgrad_nhwc", [dy.ptr, dy_ld, x.ptr, x_ld, dw.ptr, slab_stride, _ptr(db), bias_stride, P, C, N, splits, dt])
@@ -427,6 +523,8 @@ def rep_conv2d_wgrad(A, sig, res):
     (pdy, dy_ld, px, x_ld, pdw, slab_stride, B, H, W, C, Creal, Ho, Wo, N, Nreal, R, S, stride, pad_t, pad_l, ups, splits, dt) = sig
     dy = A.buf("dy", pitched(B * Ho * Wo, N, dy_ld), dt, _mod(pdy)).fill(A.randn(pitched(B * Ho * Wo, N, dy_ld)))
     x = A.buf("x", pitched(B * H * W, C, x_ld), dt, _mod(px)).fill(A.randn(pitched(B * H * W, C, x_ld)))
+    A.shape("data", dy.inp(B * Ho * Wo, N, dy_ld).mat(B * Ho * Wo, N, dy_ld))
+    x.inp(B * H * W, C, x_ld)
     n_one = Nreal * R * S * Creal
     if slab_stride:
         copies = splits
@@ -436,6 +534,8 @@ def rep_conv2d_wgrad(A, sig, res):
         copies = 1
         dw = A.buf("dw", n_one, F32, _mod(pdw)).fill(A.randn(n_one))
         dw.all_out()
+        A.shape("additive", dw.all_in().t)
+        dw.atomic = True
         prior = _d(dw.t).clone()
     _wgrad_launch(A, "ddpm_conv2d_wgrad_nhwc", [dy.ptr, dy_ld, x.ptr, x_ld, dw.ptr, slab_stride, B, H, W, C, Creal, Ho, Wo, N, Nreal,
                                                R, S, stride, pad_t, pad_l, ups, splits, dt])
@@ -446,9 +546,12 @@ def rep_conv2d_wgrad(A, sig, res):
 
 
 def rep_wgrad_reduce(A, sig, res):
-    """Stand-alone check of the fixed-order slab sum (the slab replays above also run it): copies of random partials."""
-    n_one, copies, stride = 1000, 3, 1024
+    """Stand-alone check of the fixed-order slab sum (the slab replays above also run it): copies of random partials.  A hand-written
+    signature may name (floats, copies, stride) behind the two recorded words."""
+    n_one, copies, stride = sig[2:5] if len(sig) >= 5 else (1000, 3, 1024)
     slab = A.buf("slabs", (copies - 1) * stride + n_one, F32).fill(A.randn((copies - 1) * stride + n_one))
+    for c in range(copies):
+        A.shape("data", slab.inp(1, n_one, n_one, c * stride).mat(1, n_one, n_one, c * stride))
     got = _reduce_slabs(A, slab, n_one, copies, stride)
     parts = torch.stack([_d(slab.t[s * stride:s * stride + n_one]) for s in range(copies)])
     # a short fixed-order fp32 sum: the worst-case bound u * sum |partials| (M of every added term)
@@ -470,6 +573,17 @@ def rep_gemm(A, sig, res):
     if _opt(pres):
         nr = (batch - 1) * res_bs + pitched(M, N, res_ld)
         r_ = A.buf("residual", nr, dt, _mod(pres)).fill(A.randn(nr))
+    for i in range(batch):
+        av = (K, M, a_ld, i * a_bs) if a_tr else (M, K, a_ld, i * a_bs)
+        A.shape("data", a.inp(*av).mat(*av), k_axis=0 if a_tr else 1)
+        b.inp(*((K, N, b_ld, i * b_bs) if b_tr else (N, K, b_ld, i * b_bs)))
+        if r_ is not None:
+            A.shape("additive", r_.inp(M, N, res_ld, i * res_bs).mat(M, N, res_ld, i * res_bs))
+        if acc or mode == 2:
+            A.shape("additive", c.inp(M, N, c_ld, i * c_bs).mat(M, N, c_ld, i * c_bs))
+    if bias is not None:
+        A.shape("additive", bias.all_in().t)
+    c.atomic = mode == 2
     prior = _d(c.t).clone()
     A.snapshot()
     _launch("ddpm_gemm", [a.ptr, a_ld, a_bs, a_tr, b.ptr, b_ld, b_bs, b_tr, c.ptr, c_ld, c_bs, _ptr(bias), _ptr(r_), res_ld, res_bs,
@@ -502,6 +616,8 @@ def rep_atb(A, sig, res):
     a = A.buf("a", pitched(K, M, lda), F32, _mod(pa)).fill(A.randn(pitched(K, M, lda)))
     b = A.buf("b", pitched(K, N, ldb), F32, _mod(pb)).fill(A.randn(pitched(K, N, ldb)))
     c = A.buf("c", pitched(M, N, ldc), F32, _mod(pc)).fill(A.randn(pitched(M, N, ldc)))
+    A.shape("data", a.inp(K, M, lda).mat(K, M, lda))
+    b.inp(K, N, ldb)
     A.snapshot()
     _launch("ddpm_atb_f32", [a.ptr, lda, b.ptr, ldb, c.ptr, ldc, M, N, K])
     sync()
@@ -569,6 +685,7 @@ def _seed(A, pseed, seed, drop_p):
     word = A.buf("seed_dev", 1, "u64", _mod(pseed))
     w = 0x5DEECE66D
     word.t.fill_(w)
+    word.all_in()
     return word, (seed + w) & ((1 << 64) - 1)
 
 
@@ -590,8 +707,12 @@ def rep_gn_fwd(A, sig, res):
     nws = int(_hip.lib().ddpm_gn_workspace_floats(B, HW, C, G, dt))
     ws = A.buf("workspace", nws, F32, _mod(pws)).fill(torch.zeros(nws))
     ws.all_out()
+    ws.scratch = True                                     # the header does not state its initial content: poisoned
     if st is not None:
         st.all_out()
+    A.shape("gn_x", x.inp(B * HW, C, x_ld).mat(B * HW, C, x_ld), B=B, HW=HW, C=C, G=G)
+    A.shape("gn_gamma", g.all_in().t, silu=silu)
+    b.all_in()
     word, eff = _seed(A, pseed, seed, drop_p)
     A.snapshot()
     _launch("ddpm_groupnorm_silu_fwd", [x.ptr, x_ld, y.ptr, y_ld, g.ptr, b.ptr, _ptr(st), ws.ptr, B, HW, C, G, eps, silu, drop_p, seed,
@@ -612,14 +733,27 @@ def rep_gn_fwd(A, sig, res):
         sg = torch.sigmoid(t)
         yv, dyv = (t * sg, sg * (1 + t * (1 - sg))) if silu else (t, torch.ones_like(t))
         del xh, sg
+        dropped = None
         if drop_p > 0:
             k = _keep(A, nb, HW, C, drop_p, eff, b0) / (1.0 - drop_p)
-            yv, dyv = yv * k, dyv * k
+            dropped = k == 0
+            # a dropped element is exactly zero whatever its value (the contract's dropout is a select: a NaN group stays NaN only
+            # where it is kept); for finite values this is the product it always was
+            yv, dyv = torch.where(k > 0, yv * k, torch.zeros_like(yv)), torch.where(k > 0, dyv * k, torch.zeros_like(dyv))
             del k
         bar = C_NORM * (u * yv.abs() + U_ACC * math.sqrt(n) * (gm.abs() * (xs.abs() + mu.abs()) * rs + bt.abs()) * dyv.abs())
         if dt == F32:
             bar = bar + C_NORM * U_ACC * ((_sigmoid_err(t) + 3) if silu else 1.0) * yv.abs()
-        res.cmp("y", got[b0 * HW:b1 * HW].reshape(nb, HW, C), yv, bar)
+        if dropped is not None:
+            bar = torch.where(dropped, torch.zeros_like(bar), bar)       # exactly zero (it was: every term of the bar carries y or y')
+        yard = None
+        if A.yardstick:                                   # F.group_norm -> F.silu -> the same mask, in fp32, rounded to the stored type
+            yard = F.group_norm(x.mat(B * HW, C, x_ld)[b0 * HW:b1 * HW].float().reshape(nb, HW, C).permute(0, 2, 1), G, g.t, b.t, eps)
+            yard = (F.silu(yard) if silu else yard).permute(0, 2, 1)
+            if drop_p > 0:
+                yard = yard * (_keep(A, nb, HW, C, drop_p, eff, b0) / (1.0 - drop_p)).float()
+            yard = yard.to(_TD[dt])
+        res.cmp("y", got[b0 * HW:b1 * HW].reshape(nb, HW, C), yv, bar, yard)
         del xs, t, yv, dyv, bar
         if st is not None:
             s_ = _d(st.t).reshape(B, G, 2)[b0:b1]
@@ -645,22 +779,33 @@ def rep_gn_bwd(A, sig, res):
     dx = A.buf("dx", pitched(rows, C, dx_ld), dt, _mod(pdx)).fill(A.randn(pitched(rows, C, dx_ld)))
     g = A.buf("gamma", C, F32, _mod(pg)).fill(1.0 + 0.3 * A.randn(C))
     b = A.buf("beta", C, F32, _mod(pb)).fill(0.5 * A.randn(C))
+    A.shape("gn_x", x.inp(rows, C, x_ld).mat(rows, C, x_ld), B=B, HW=HW, C=C, G=G)
+    A.shape("gn_dy", dy.inp(rows, C, dy_ld).mat(rows, C, dy_ld))
+    A.shape("gn_gamma", g.all_in().t, silu=silu)
+    b.all_in()
     xs = _d(x.mat(rows, C, x_ld)).reshape(B, HW, C)
     mean, rstd = _gn_stats(xs, G, 1e-6)
-    st = A.buf("stats", B * G * 2, F32, _mod(pst)).fill(torch.stack([mean, rstd], -1))
+    st = A.buf("stats", B * G * 2, F32, _mod(pst)).fill(torch.stack([mean, rstd], -1)).all_in()
     dg = A.buf("dgamma", C, F32, _mod(pdg)).fill(A.randn(C)) if _opt(pdg) else None
     db = A.buf("dbeta", C, F32, _mod(pdb)).fill(A.randn(C)) if _opt(pdb) else None
     nws = int(_hip.lib().ddpm_gn_workspace_floats(B, HW, C, G, dt))
     ws = A.buf("workspace", nws, F32, _mod(pws)).fill(torch.zeros(nws))
     ws.all_out()
+    ws.scratch = True
     cs = None
     if _opt(pcs):
         cs = A.buf("dx_colsum", pitched(B, C, cs_ld), F32, _mod(pcs)).fill(A.randn(pitched(B, C, cs_ld)))
         cs.mat(B, C, cs_ld).zero_()                        # zero on entry (contract)
+        cs.inp(B, C, cs_ld).atomic = True
     ad = A.buf("add", pitched(rows, C, add_ld), dt, _mod(padd)).fill(A.randn(pitched(rows, C, add_ld))) if _opt(padd) else None
+    if ad is not None:
+        ad.inp(rows, C, add_ld)
+    if acc:
+        dx.inp(rows, C, dx_ld)
     for o in (dg, db):
         if o is not None:
             o.all_out()
+            o.all_in().atomic = True
     word, eff = _seed(A, pseed, seed, drop_p)
     prior = _d(dx.mat(rows, C, dx_ld)).reshape(B, HW, C).clone()
     pdg_v = None if dg is None else _d(dg.t).clone()
@@ -702,7 +847,27 @@ def rep_gn_bwd(A, sig, res):
     n = (C // G) * HW
     u = U_BF16 if dt == BF16 else U_F32
     fp32_part = U_ACC * math.sqrt(n) * (inner + rs * c1.abs() * (xs.abs() + mu.abs()) * rs + rs * gm.abs() * dt_err)
-    res.cmp("dx", got.reshape(B, HW, C), ref, C_NORM * (u * mag + fp32_part))
+    yard = None
+    if A.yardstick:                                       # the same formula on the given statistics, every step in fp32
+        x32, st32 = x.mat(rows, C, x_ld).float().reshape(B, HW, C), st.t.reshape(B, G, 2)
+        mu32, rs32 = _per_c(st32[..., 0], B, HW, C, G), _per_c(st32[..., 1], B, HW, C, G)
+        xh32 = (x32 - mu32) * rs32
+        dz32 = dy.mat(rows, C, dy_ld).float().reshape(B, HW, C)
+        if silu:
+            t32 = g.t * xh32 + b.t
+            sg32 = torch.sigmoid(t32)
+            dz32 = dz32 * (sg32 * (1 + t32 * (1 - sg32)))
+        if drop_p > 0:
+            dz32 = dz32 * (_keep(A, B, HW, C, drop_p, eff) / (1.0 - drop_p)).float()
+        a32 = dz32 * g.t
+        grp32 = lambda v: _per_c(v.reshape(B, HW, G, C // G).mean((1, 3)), B, HW, C, G)
+        yard = rs32 * (a32 - xh32 * grp32(a32 * xh32) - grp32(a32))
+        if ad is not None:
+            yard = yard + ad.mat(rows, C, add_ld).float().reshape(B, HW, C)
+        if acc:
+            yard = yard + prior.float()
+        yard = yard.to(_TD[dt])
+    res.cmp("dx", got.reshape(B, HW, C), ref, C_NORM * (u * mag + fp32_part), yard)
     if cs is not None:
         # the colsum adds the dx values the kernel forms (before or after the store): their per-element error is part of M
         dxm = mag * u + fp32_part
@@ -723,6 +888,7 @@ def rep_gn_bwd(A, sig, res):
 # attention ----------------------------------------------------------------------------------------------------------------------------
 def _qkv(A, sig_p, ld, B, L, C, dt):
     qkv = A.buf("qkv", pitched(B * L, 3 * C, ld), dt, _mod(sig_p)).fill(A.randn(pitched(B * L, 3 * C, ld), scale=1.5))
+    A.shape("qkv", qkv.inp(B * L, 3 * C, ld).mat(B * L, 3 * C, ld), B=B, L=L, C=C)
     v = _d(qkv.mat(B * L, 3 * C, ld)).reshape(B, L, 3 * C)
     return qkv, v[..., :C], v[..., C:2 * C], v[..., 2 * C:]
 
@@ -763,9 +929,13 @@ def rep_attn_fwd(A, sig, res, lse_entry=False):
     e = _logit_err(q, k, scale).amax(-1, keepdim=True)
     sq = ((P * P) @ (v * v)).sqrt()
     bar = C_ATTN * (U_BF16 * (ref.abs() + pv) + 2 * e * pv + U_ACC * math.sqrt(L) * sq)
-    res.cmp("out", got.reshape(B, L, C), ref, bar)
+    yard = ylse = None
+    if A.yardstick:                                       # matmul -> softmax -> matmul in fp32
+        s32 = q.float() @ k.float().transpose(1, 2) * scale
+        yard, ylse = (torch.softmax(s32, -1) @ v.float()).to(_TD[dt]), torch.logsumexp(s32, -1)
+    res.cmp("out", got.reshape(B, L, C), ref, bar, yard)
     if lse is not None:
-        res.cmp("lse", lse.t.reshape(B, L), ls, C_ATTN * (U_ACC * (ls.abs() + math.log(L)) + e[..., 0]))
+        res.cmp("lse", lse.t.reshape(B, L), ls, C_ATTN * (U_ACC * (ls.abs() + math.log(L)) + e[..., 0]), ylse)
 
 
 def rep_attn_fwd_lse(A, sig, res):
@@ -783,9 +953,10 @@ def rep_attn_bwd(A, sig, res):
     s = q @ k.transpose(1, 2) * scale
     ls = torch.logsumexp(s, -1)
     o = A.buf("o", pitched(B * L, C, o_ld), dt, _mod(po)).fill(A.randn(pitched(B * L, C, o_ld)))
-    o.mat(B * L, C, o_ld).copy_((torch.exp(s - ls[..., None]) @ v).reshape(B * L, C))
+    o.inp(B * L, C, o_ld).mat(B * L, C, o_ld).copy_((torch.exp(s - ls[..., None]) @ v).reshape(B * L, C))
     d_o = A.buf("d_o", pitched(B * L, C, do_ld), dt, _mod(pdo)).fill(A.randn(pitched(B * L, C, do_ld)))
-    lse = A.buf("lse", B * L, F32, _mod(plse)).fill(ls)
+    A.shape("attn_do", d_o.inp(B * L, C, do_ld).mat(B * L, C, do_ld))
+    lse = A.buf("lse", B * L, F32, _mod(plse)).fill(ls).all_in()
     dvec = A.buf("dvec", B * L, F32, _mod(pdv)).fill(torch.full((B * L,), float("nan")))
     dvec.all_out()
     dq = A.buf("dqkv", pitched(B * L, 3 * C, dq_ld), dt, _mod(pdq)).fill(A.randn(pitched(B * L, 3 * C, dq_ld)))
@@ -810,11 +981,17 @@ def rep_attn_bwd(A, sig, res):
         ("dk", kT(dS) @ q * scale, kT(dS * dS) @ (q * q), kT(dS_err) @ q.abs() * scale, C),
         ("dv", kT(P) @ dO, kT(P * P) @ (dO * dO), kT(e_s * P) @ dO.abs(), 2 * C),
     )
+    yard = {}
+    if A.yardstick:                                       # the same products on the given o and lse, every step in fp32, stores in bf16
+        q32, k32, v32, O32, dO32 = (t.float() for t in (q, k, v, O, dO))
+        P32 = torch.exp(q32 @ kT(k32) * scale - lse.t.reshape(B, L, 1))
+        dS32 = P32 * (dO32 @ kT(v32) - (dO32 * O32).sum(-1, keepdim=True))
+        yard = {"dq": (dS32 @ k32 * scale).to(_TD[dt]), "dk": (kT(dS32) @ q32 * scale).to(_TD[dt]), "dv": (kT(P32) @ dO32).to(_TD[dt])}
     for nm, ref, sq, prop, c0 in outs:
         sq = sq.sqrt() * (scale if nm != "dv" else 1.0)
         rounding = (U_BF16 * (kT(P) @ dO.abs())) if nm == "dv" else U_BF16 * sq
         bar = C_ATTN * (U_BF16 * ref.abs() + rounding + prop + U_ACC * math.sqrt(L) * sq)
-        res.cmp(nm, got[..., c0:c0 + C], ref, bar)
+        res.cmp(nm, got[..., c0:c0 + C], ref, bar, yard.get(nm))
 
 
 # elementwise, reductions and diffusion -----------------------------------------------------------------------------------------------
@@ -823,6 +1000,13 @@ def rep_colsum(A, sig, res):
     dy = A.buf("dy", pitched(B * HW, C, ld), dt, _mod(pdy)).fill(A.randn(pitched(B * HW, C, ld)))
     ps = A.buf("per_sample", pitched(B, C, ps_ld), F32, _mod(pps)).fill(A.randn(pitched(B, C, ps_ld))) if _opt(pps) else None
     tot = A.buf("total", C, F32, _mod(ptot)).fill(A.randn(C)) if _opt(ptot) else None
+    A.shape("data", dy.inp(B * HW, C, ld).mat(B * HW, C, ld))
+    if ps is not None:
+        A.shape("additive", ps.inp(B, C, ps_ld).mat(B, C, ps_ld))
+        ps.atomic = True
+    if tot is not None:
+        A.shape("additive", tot.all_in().t)
+        tot.atomic = True
     p_ps = None if ps is None else _d(ps.mat(B, C, ps_ld)).clone()
     p_tot = None if tot is None else _d(tot.t).clone()
     A.snapshot()
@@ -847,6 +1031,9 @@ def rep_upsample2x_bwd(A, sig, res):
     pdy, pdx, dx_ld, B, H, W, C, acc, dt = sig
     dyu = A.buf("dy_up", B * 4 * H * W * C, dt, _mod(pdy)).fill(A.randn(B * 4 * H * W * C))
     dx = A.buf("dx", pitched(B * H * W, C, dx_ld), dt, _mod(pdx)).fill(A.randn(pitched(B * H * W, C, dx_ld)))
+    A.shape("data", dyu.all_in().t)
+    if acc:
+        A.shape("additive", dx.inp(B * H * W, C, dx_ld).mat(B * H * W, C, dx_ld))
     prior = _d(dx.mat(B * H * W, C, dx_ld)).clone()
     A.snapshot()
     _launch("ddpm_upsample2x_bwd", [dyu.ptr, dx.ptr, dx_ld, B, H, W, C, acc, dt])
@@ -872,6 +1059,7 @@ def _t(A, B, T, p):
     tv = torch.randint(0, T, (B,), generator=A.gen)
     tv[0], tv[-1] = 0, T - 1
     tb.t.copy_(tv)
+    tb.all_in()
     return tb, tv
 
 
@@ -883,6 +1071,9 @@ def rep_q_sample(A, sig, res):
     ta = A.buf("sqrt_ab", T, F32, _mod(pa)).fill(A.randn(T).abs())
     tbb = A.buf("sqrt_1mab", T, F32, _mod(pb)).fill(A.randn(T).abs())
     xt = A.buf("xt", B * n, F32, _mod(pxt)).fill(A.randn(B * n))
+    for b in (x0, nz, ta, tbb):
+        b.all_in()
+    A.shape("elem", x0.t.view(B, n))
     A.snapshot()
     _launch("ddpm_q_sample", [x0.ptr, nz.ptr, tb.ptr, ta.ptr, tbb.ptr, xt.ptr, B, n, T])
     sync()
@@ -899,6 +1090,8 @@ def rep_mse_fwd(A, sig, res):
     p = A.buf("pred", B * n, F32, _mod(pp)).fill(A.randn(B * n))
     tg = A.buf("target", B * n, F32, _mod(pt)).fill(A.randn(B * n))
     loss = A.buf("loss", B, F32, _mod(pl)).fill(A.randn(B))
+    A.shape("elem", p.all_in().t.view(B, n))
+    tg.all_in()
     A.snapshot()
     _launch("ddpm_mse_fwd", [p.ptr, tg.ptr, loss.ptr, B, n])
     sync()
@@ -916,6 +1109,8 @@ def rep_mse_bwd(A, sig, res):
     tg = A.buf("target", B * n, F32, _mod(pt)).fill(A.randn(B * n))
     gl = A.buf("gloss", B, F32, _mod(pg)).fill(A.randn(B))
     gp = A.buf("gpred", B * n, F32, _mod(pgp)).fill(A.randn(B * n))
+    for b in (p, tg, gl):
+        b.all_in()
     A.snapshot()
     _launch("ddpm_mse_bwd", [p.ptr, tg.ptr, gl.ptr, gp.ptr, B, n])
     sync()
@@ -938,6 +1133,8 @@ def rep_p_sample_step(A, sig, res):
             (("recip", pr, 1.0), ("recip_m1", prm1, 0.5), ("coef1", pc1, 0.3), ("coef2", pc2, 0.7), ("logvar", plv, -2.0))]
     xp = A.buf("x_prev", B * n, F32, _mod(pxp)).fill(A.randn(B * n))
     pred = A.buf("pred_x0", B * n, F32, _mod(ppred)).fill(A.randn(B * n)) if _opt(ppred) else None
+    for b in [xt, out, z] + tabs:
+        b.all_in()
     A.snapshot()
     _launch("ddpm_p_sample_step", [xt.ptr, out.ptr, z.ptr, tb.ptr] + [tb_.ptr for tb_ in tabs] + [xp.ptr, _ptr(pred), B, n, mean_type,
                                                                                                   clip, T])
@@ -974,6 +1171,7 @@ def rep_softmax_fwd(A, sig, res):
     ps, pp, rows, L, dt = sig
     s_ = A.buf("s", rows * L, F32, _mod(ps)).fill(A.randn(rows * L, scale=3.0))
     p = A.buf("p", rows * L, dt, _mod(pp)).fill(A.randn(rows * L))
+    A.shape("logits", s_.all_in().t.view(rows, L))
     A.snapshot()
     _launch("ddpm_softmax_fwd", [s_.ptr, p.ptr, rows, L, dt])
     sync()
@@ -985,7 +1183,8 @@ def rep_softmax_fwd(A, sig, res):
     r = U_ACC * (2 * d.abs() + 4)
     zr = (P * r).sum(-1, keepdim=True) + U_ACC * (math.sqrt(L) * (P * P).sum(-1, keepdim=True).sqrt() + 2)
     u = U_BF16 if dt == BF16 else U_F32
-    res.cmp("p", got.reshape(rows, L), P, C_ATTN * P * (u + r + zr))
+    yard = torch.softmax(s_.t.view(rows, L), -1).to(_TD[dt]) if A.yardstick else None
+    res.cmp("p", got.reshape(rows, L), P, C_ATTN * P * (u + r + zr), yard)
 
 
 def rep_softmax_bwd(A, sig, res):
@@ -994,9 +1193,11 @@ def rep_softmax_bwd(A, sig, res):
     sum_j |p_j dp_j|), and both scale with p_i through the product; the product and the store add u_acc |dS_i| and u_out |dS_i|:
         |got_i - dS_i| <= c * ((u_out + u_acc) |dS_i| + u_acc p_i (|dp_i| + 2 sum_j |p_j dp_j| + sqrt(L) sqrt(sum_j (p_j dp_j)^2)))."""
     pp, pdp, pds, rows, L, dt = sig
-    p = A.buf("p", rows * L, dt, _mod(pp)).fill(torch.softmax(A.randn(rows * L, scale=3.0).reshape(rows, L), -1))
+    p = A.buf("p", rows * L, dt, _mod(pp)).fill(torch.softmax(A.shaped("logits", A.randn(rows * L, scale=3.0).reshape(rows, L)), -1))
     dp = A.buf("dp", rows * L, F32, _mod(pdp)).fill(A.randn(rows * L))
     ds = A.buf("ds", rows * L, dt, _mod(pds)).fill(A.randn(rows * L))
+    p.all_in()
+    dp.all_in()
     A.snapshot()
     _launch("ddpm_softmax_bwd", [p.ptr, dp.ptr, ds.ptr, rows, L, dt])
     sync()
@@ -1007,7 +1208,11 @@ def rep_softmax_bwd(A, sig, res):
     ref = P * (G - pg.sum(-1, keepdim=True))
     dot_err = 2 * pg.abs().sum(-1, keepdim=True) + math.sqrt(L) * (pg * pg).sum(-1, keepdim=True).sqrt()
     u = U_BF16 if dt == BF16 else U_F32
-    res.cmp("ds", got.reshape(rows, L), ref, C_ATTN * ((u + U_ACC) * ref.abs() + U_ACC * P * (G.abs() + dot_err)))
+    yard = None
+    if A.yardstick:
+        p32, g32 = p.t.float().view(rows, L), dp.t.view(rows, L)
+        yard = (p32 * (g32 - (p32 * g32).sum(-1, keepdim=True))).to(_TD[dt])
+    res.cmp("ds", got.reshape(rows, L), ref, C_ATTN * ((u + U_ACC) * ref.abs() + U_ACC * P * (G.abs() + dot_err)), yard)
 
 
 def _sigmoid_err(x):
@@ -1021,6 +1226,7 @@ def rep_silu_fwd(A, sig, res):
     px, py, n = sig
     x = A.buf("x", n, F32, _mod(px)).fill(A.randn(n, scale=4.0))
     y = A.buf("y", n, F32, _mod(py)).fill(A.randn(n))
+    A.shape("silu_x", x.all_in().t)
     A.snapshot()
     _launch("ddpm_silu_fwd", [x.ptr, y.ptr, n])
     sync()
@@ -1028,7 +1234,7 @@ def rep_silu_fwd(A, sig, res):
     A.check()
     X = _d(x.t)
     ref = X * torch.sigmoid(X)
-    res.cmp("y", got, ref, C_ELEM * U_F32 * (1 + _sigmoid_err(X)) * ref.abs())
+    res.cmp("y", got, ref, C_ELEM * U_F32 * (1 + _sigmoid_err(X)) * ref.abs(), F.silu(x.t) if A.yardstick else None)
 
 
 def rep_silu_bwd(A, sig, res):
@@ -1041,6 +1247,10 @@ def rep_silu_bwd(A, sig, res):
     x = A.buf("x", n, F32, _mod(px)).fill(A.randn(n, scale=4.0))
     dy = A.buf("dy", n, F32, _mod(pdy)).fill(A.randn(n))
     dx = A.buf("dx", n, F32, _mod(pdx)).fill(A.randn(n))
+    A.shape("silu_x", x.all_in().t)
+    dy.all_in()
+    if acc:
+        dx.all_in()
     prior = _d(dx.t).clone()
     A.snapshot()
     _launch("ddpm_silu_bwd", [x.ptr, dy.ptr, dx.ptr, n, acc])
@@ -1056,7 +1266,13 @@ def rep_silu_bwd(A, sig, res):
     mag = G.abs() * e1 + 2 * ref.abs()
     if acc:
         ref, mag = ref + prior, mag + prior.abs() + ref.abs()
-    res.cmp("dx", got, ref, C_ELEM * U_F32 * mag)
+    yard = None
+    if A.yardstick:
+        with torch.enable_grad():
+            x32 = x.t.clone().requires_grad_(True)
+            F.silu(x32).backward(dy.t.clone())
+        yard = x32.grad + prior.float() if acc else x32.grad
+    res.cmp("dx", got, ref, C_ELEM * U_F32 * mag, yard)
 
 
 def rep_add_rows(A, sig, res):
@@ -1065,6 +1281,9 @@ def rep_add_rows(A, sig, res):
     px, x_ld, py, y_ld, rows, C, acc, dt = sig
     x = A.buf("x", pitched(rows, C, x_ld), dt, _mod(px)).fill(A.randn(pitched(rows, C, x_ld)))
     y = A.buf("y", pitched(rows, C, y_ld), dt, _mod(py)).fill(A.randn(pitched(rows, C, y_ld)))
+    A.shape("data", x.inp(rows, C, x_ld).mat(rows, C, x_ld))
+    if acc:
+        A.shape("additive", y.inp(rows, C, y_ld).mat(rows, C, y_ld))
     prior = _d(y.mat(rows, C, y_ld)).clone()
     A.snapshot()
     _launch("ddpm_add_rows", [x.ptr, x_ld, y.ptr, y_ld, rows, C, acc, dt])
@@ -1092,7 +1311,8 @@ def rep_timestep_embedding(A, sig, res):
     tv[-1] = 999
     tb.t.copy_(tv)
     f = torch.exp(-torch.arange(half, dtype=torch.float64) * math.log(1e4) / (half - 1)).to(torch.float32)
-    fr = A.buf("freqs", half, F32, _mod(pf)).fill(f)
+    fr = A.buf("freqs", half, F32, _mod(pf)).fill(f).all_in()
+    tb.all_in()
     out = A.buf("out", B * dim, F32, _mod(po)).fill(A.randn(B * dim))
     A.snapshot()
     _launch("ddpm_timestep_embedding", [tb.ptr, fr.ptr, out.ptr, B, dim])
@@ -1109,8 +1329,8 @@ def rep_gather_rows(A, sig, res):
     """out[r] = table[idx[r]], bit-exact (bar 0); an index outside [0, table_rows) must give a NaN row.  Two launches: every index
     valid (first and last table row included), then every even row's index out of range (-1, table_rows, 2^40 in turn)."""
     ptab, pidx, pout, rows, row_len, table_rows = sig
-    tab = A.buf("table", table_rows * row_len, F32, _mod(ptab)).fill(A.randn(table_rows * row_len))
-    ib = A.buf("idx", rows, "i64", _mod(pidx))
+    tab = A.buf("table", table_rows * row_len, F32, _mod(ptab)).fill(A.randn(table_rows * row_len)).all_in()
+    ib = A.buf("idx", rows, "i64", _mod(pidx)).all_in()
     out = A.buf("out", rows * row_len, F32, _mod(pout))
     T = _d(tab.t).reshape(table_rows, row_len)
     for bad in (False, True):
@@ -1123,6 +1343,7 @@ def rep_gather_rows(A, sig, res):
             iv[::2] = oob[torch.arange(0, rows, 2) // 2 % 3]
         ib.t.copy_(iv)
         out.fill(A.randn(out.n))
+        out.poisoned = False                              # overwritten by each launch: poisoned before each
         A.snapshot()
         _launch("ddpm_gather_rows_f32", [tab.ptr, ib.ptr, out.ptr, rows, row_len, table_rows])
         sync()
@@ -1142,6 +1363,8 @@ def rep_weighted_sum(A, sig, res):
     x = A.buf("x", n, F32, _mod(px)).fill(A.randn(n))
     w = A.buf("w", n, F32, _mod(pw)).fill(A.randn(n))
     out = A.buf("out", 1, F32, _mod(po)).fill(A.randn(1))
+    x.all_in()
+    w.all_in()
     A.snapshot()
     _launch("ddpm_weighted_sum_f32", [x.ptr, w.ptr, out.ptr, n])
     sync()
@@ -1323,12 +1546,204 @@ for _B, _L, _C in ((2, 96, 128), (2, 144, 256), (1, 192, 512), (2, 240, 64), (3,
     ODD_GEOMETRY += _attn_sigs(_B, _L, _C)
 
 
+# ----------------------------------------------------------------------------------------------------------------- small extras
+# Replayed entries that neither list above holds, at the smallest shapes that still take every path: ragged GEMM tiles, the batched
+# form, the four transposes, every epilogue and output mode, the in-launch split-K reductions of the conv, the fused attention forward
+# and the diffusion elementwise kernels at a batch and a row length that are no power of two.
+def _up(n, m):
+    return -(-n // m) * m
+
+
+def _gemm_sig(M, N, K, batch, a_tr=0, b_tr=0, bias=0, res=0, acc=0, mode=0, alpha=1.0, dt=BF16):
+    ar, ac = (K, M) if a_tr else (M, K)
+    br, bc = (K, N) if b_tr else (N, K)
+    a_ld, b_ld, c_ld, r_ld = _up(ac, 8) + 16, _up(bc, 8) + 16, _up(N, 8) + 32, _up(N, 8) + 8
+    return ("ddpm_gemm", (_p(), a_ld, ar * a_ld + 32, a_tr, _p(), b_ld, br * b_ld + 64, b_tr, _p(), c_ld, M * c_ld + 16, _p(null=not bias),
+                          _p(null=not res), r_ld if res else 0, M * r_ld + 8 if res else 0, M, N, K, batch, alpha, acc, mode, 1, dt))
+
+
+EXTRA_SMALL = []
+for _dt in (BF16, F32):
+    # the contract wants the contiguous extent of an operand in whole 16-byte vectors: a transposed A of bf16 cannot have M = 300
+    _Mt = 300 if _dt == F32 else 296
+    EXTRA_SMALL += [
+        _gemm_sig(300, 136, 200, 1, bias=1, res=1, acc=1, alpha=0.5, dt=_dt),
+        _gemm_sig(_Mt, 136, 200, 1, a_tr=1, mode=1, dt=_dt),
+        _gemm_sig(300, 136, 200, 1, b_tr=1, mode=2, dt=_dt),
+        _gemm_sig(_Mt, 136, 200, 1, a_tr=1, b_tr=1, dt=_dt),
+        _gemm_sig(16, 16, 16, 3, bias=1, res=1, acc=1, dt=_dt),
+        _gemm_sig(16, 16, 16, 3, a_tr=1, b_tr=1, mode=2, dt=_dt),
+        _gemm_sig(16, 16, 16, 3, a_tr=1, mode=1, alpha=0.25, dt=_dt),
+        _conv_sig(2, 8, 8, 512, 512, splits=2, dt=_dt),
+    ]
+EXTRA_SMALL += [
+    _conv_sig(16, 4, 4, 256, 256, splits=5),
+    ("ddpm_atb_f32", (_p(), 136, _p(), 76, _p(), 80, 130, 70, 37)),
+    ("ddpm_atb_f32", (_p(), 100, _p(), 72, _p(), 72, 100, 72, 96)),
+    ("ddpm_attention_fwd", (_p(), 3 * 128 + 16, _p(), 128 + 8, 2, 128, 128, 128.0 ** -0.5, BF16)),
+    ("ddpm_attention_fwd", (_p(), 3 * 256 + 16, _p(), 256 + 8, 2, 384, 256, 256.0 ** -0.5, BF16)),
+    ("ddpm_q_sample", (_p(), _p(), _p(), _p(), _p(), _p(), 5, 192, 1000)),
+    ("ddpm_mse_fwd", (_p(), _p(), _p(), 5, 192)),
+    ("ddpm_mse_bwd", (_p(), _p(), _p(), _p(), 5, 192)),
+    ("ddpm_p_sample_step", (_p(), _p(), _p(), _p(), _p(), _p(), _p(), _p(), _p(), _p(), _p(), 5, 192, 0, 1, 1000)),
+    ("ddpm_p_sample_step", (_p(), _p(), _p(), _p(), _p(), _p(), _p(), _p(), _p(), _p(), _p(null=True), 5, 192, 0, 0, 1000)),
+    ("ddpm_wgrad_reduce", (_p(), 1, 4100, 3, 4104)),
+]
+
+
+# ----------------------------------------------------------------------------------------------------------------- value profiles
+# A profile transforms the data operands after the draw (Arena.shape); the float64 references read the stored values, so they follow.
+# Each transform takes (arena, fp32 values of a [rows][cols] view, geometry keywords) and returns the new values.
+def _scale(f):
+    return lambda A, v, **kw: v * f
+
+
+def _sparse(A, v, **kw):
+    """90 % exact zeros: four rows (pixels) in five are zero whole, half of the rest element by element — so that 1x1 convs and GEMMs
+    have outputs whose every term is zero, which must come out exactly zero (TINY)."""
+    rows = torch.rand(v.shape[0], generator=A.pgen, device=v.device) < 0.2
+    keep = torch.rand(v.shape, generator=A.pgen, device=v.device) < 0.5
+    return v * (keep & rows.reshape(-1, *([1] * (v.dim() - 1))))
+
+
+def _groups(v, B, HW, C, G):
+    return v.reshape(B, HW, G, C // G)
+
+
+def _corner_outlier(sigmas):
+    def f(A, v, B, HW, C, G, **kw):
+        g = _groups(v.clone(), B, HW, C, G)
+        g[:, 0, :, 0] = g.mean((1, 3)) + sigmas * g.std((1, 3), unbiased=False)
+        return g.reshape(v.shape)
+    return f
+
+
+def _constant_group(A, v, B, HW, C, G, **kw):
+    return _groups(v, B, HW, C, G)[:, :1, :, :1].expand(B, HW, G, C // G).reshape(v.shape)
+
+
+def _flat_keys(A, v, B, L, C, **kw):
+    t = v.reshape(B, L, 3 * C).clone()
+    t[..., C:2 * C] = t[:, :1, C:2 * C]
+    return t.reshape(v.shape)
+
+
+def _q_times(f):
+    def g(A, v, C, **kw):
+        v = v.clone()
+        v[:, :C] *= f
+        return v
+    return g
+
+
+def _plant(value):
+    """one non-finite value at a fixed in-range position of the view: row rows/2 + 1 (an interior pixel, a middle sample), column 3"""
+    def f(A, v, **kw):
+        v = v.clone()
+        v[v.shape[0] // 2 + 1 if v.shape[0] > 2 else v.shape[0] - 1, min(3, v.shape[-1] - 1)] = value
+        return v
+    return f
+
+
+_LINEAR = ("ddpm_conv2d_nhwc", "ddpm_gemm", "ddpm_atb_f32", "ddpm_conv3x3_wgrad_nhwc", "ddpm_conv3x3_wgrad_up_nhwc", "ddpm_conv1x1_wgrad_nhwc",
+           "ddpm_conv2d_wgrad_nhwc", "ddpm_wgrad_reduce", "ddpm_colsum", "ddpm_upsample2x_bwd", "ddpm_add_rows")
+_GN = ("ddpm_groupnorm_silu_fwd", "ddpm_groupnorm_silu_bwd")
+_SOFT = ("ddpm_softmax_fwd", "ddpm_softmax_bwd", "ddpm_attention_fwd", "ddpm_attention_fwd_lse", "ddpm_attention_bwd")
+_NONFINITE = ("ddpm_conv2d_nhwc", "ddpm_gemm", "ddpm_groupnorm_silu_fwd", "ddpm_softmax_fwd", "ddpm_attention_fwd", "ddpm_attention_fwd_lse",
+              "ddpm_mse_fwd", "ddpm_q_sample")
+_NF_ROLES = ("data", "gn_x", "logits", "qkv", "elem")
+# name -> (what it is for, {role: transform}, the entries it applies to).  Roles: data / additive (the linear families: the operand
+# the sum runs over, and bias, row bias, residual and prior content), gn_x / gn_dy / gn_gamma, logits (softmax), qkv, attn_do, silu_x,
+# elem (q_sample's x0, mse's prediction).  Yardstick figures: the worst err/bar of the plain fp32 torch composition over every row
+# the profile applies to (tests/test_hostile_inputs_host.py holds them to 0.5); intensities are final.
+PROFILES = {
+    # linear in the data: every output is exactly 2^+-30 times the plain run's (power-of-two scaling commutes with rounding away from
+    # the denormal and overflow ranges).  GroupNorm: x * 2^-30 is the eps-dominated regime (var = 2^-60 << eps), x * 2^30 the opposite.
+    "scaled_up": ("operands 2^30 larger than unity", {"data": _scale(2.0 ** 30), "additive": _scale(2.0 ** 30), "gn_x": _scale(2.0 ** 30)},
+                  _LINEAR + _GN),
+    "scaled_down": ("operands 2^-30 of unity; GroupNorm: eps dominates", {"data": _scale(2.0 ** -30), "additive": _scale(2.0 ** -30),
+                                                                          "gn_x": _scale(2.0 ** -30)}, _LINEAR + _GN),
+    "sparse": ("90 % exact zeros: an element whose every term is zero must be exactly zero", {"data": _sparse, "gn_dy": _sparse, "attn_do": _sparse},
+               ("ddpm_conv2d_nhwc", "ddpm_gemm", "ddpm_conv3x3_wgrad_nhwc", "ddpm_conv3x3_wgrad_up_nhwc", "ddpm_conv1x1_wgrad_nhwc",
+                "ddpm_conv2d_wgrad_nhwc", "ddpm_groupnorm_silu_bwd", "ddpm_attention_bwd")),
+    # csrc/norm.hip accumulates moments about the group's first element: pixel 0 of the group's first channel at mean + 64 sigma
+    "corner_outlier": ("the pivot of the GroupNorm statistics is an outlier", {"gn_x": _corner_outlier(64.0)}, _GN),
+    "far_mean": ("GroupNorm input 50 +- 0.1: |mean| >> std", {"gn_x": lambda A, v, **kw: 50.0 + 0.1 * (v - 1.5)}, _GN),
+    "constant_group": ("every GroupNorm group constant: variance 0, rstd = eps^-1/2", {"gn_x": _constant_group}, _GN),
+    # gamma x 40 puts z = gamma xh + beta beyond +-120; x of the SiLU entries is drawn at std 4, x 10 gives std 40: exp overflows
+    "saturating": ("SiLU arguments beyond +-88.7, where exp overflows", {"gn_gamma": lambda A, v, silu=1, **kw: v * 40.0 if silu else v,
+                                                                       "silu_x": _scale(10.0)}, _GN + ("ddpm_silu_fwd", "ddpm_silu_bwd")),
+    # softmax logits are drawn at std 3, attention logits at std 1.5^2 = 2.25
+    "wide_logits": ("logit std 40: one-hot rows, large lse", {"logits": _scale(40.0 / 3.0), "qkv": _q_times(40.0 / 2.25)}, _SOFT),
+    "flat_logits": ("all keys identical: uniform rows", {"logits": lambda A, v, **kw: v[:, :1].expand_as(v).clone(), "qkv": _flat_keys}, _SOFT),
+    "offset_logits": ("a common +1e4 on softmax logits; q x 8 for attention", {"logits": lambda A, v, **kw: v + 1.0e4, "qkv": _q_times(8.0)}, _SOFT),
+    "nonfinite_nan": ("one NaN in a data operand: exactly what the reference makes non-finite is non-finite",
+                      {r: _plant(float("nan")) for r in _NF_ROLES}, _NONFINITE),
+    "nonfinite_inf": ("one +inf in a data operand", {r: _plant(float("inf")) for r in _NF_ROLES}, _NONFINITE),
+}
+YARDSTICK = _GN + _SOFT + ("ddpm_silu_fwd", "ddpm_silu_bwd")          # the non-linear families: Result.yard is filled
+# what Result.outputs of a deterministic entry must satisfy bit for bit against the plain run of the same seed
+EXACT_SCALE = {"scaled_up": 2.0 ** 30, "scaled_down": 2.0 ** -30}
+
+
+HOSTILE_FAMILIES = {
+    "conv": ("ddpm_conv2d_nhwc",),
+    "wgrad": ("ddpm_conv3x3_wgrad_nhwc", "ddpm_conv3x3_wgrad_up_nhwc", "ddpm_conv2d_wgrad_nhwc", "ddpm_conv1x1_wgrad_nhwc", "ddpm_wgrad_reduce"),
+    "gemm": ("ddpm_gemm", "ddpm_atb_f32"),
+    "reduce": ("ddpm_colsum", "ddpm_upsample2x_bwd", "ddpm_add_rows"),
+    "groupnorm_fwd": ("ddpm_groupnorm_silu_fwd",),
+    "groupnorm_bwd": ("ddpm_groupnorm_silu_bwd",),
+    "attention": ("ddpm_attention_fwd", "ddpm_attention_fwd_lse", "ddpm_attention_bwd"),
+    "softmax": ("ddpm_softmax_fwd", "ddpm_softmax_bwd"),
+    "silu": ("ddpm_silu_fwd", "ddpm_silu_bwd"),
+    "diffusion": ("ddpm_q_sample", "ddpm_mse_fwd", "ddpm_mse_bwd", "ddpm_p_sample_step"),
+    "misc": ("ddpm_timestep_embedding", "ddpm_gather_rows_f32", "ddpm_weighted_sum_f32"),
+}
+
+
+def hostile_cases():
+    """[(family, mode)]: poison for every family, then each profile that names one of the family's entries."""
+    return [(fam, mode) for fam, names in HOSTILE_FAMILIES.items()
+            for mode in ["poison"] + [p for p, (_, _, entries) in PROFILES.items() if set(entries) & set(names)]]
+
+
+def hostile_replay(sig, device, seed, mode, plain):
+    """One replay of `sig` in `mode` ("poison" or a profile).  plain: a dict that caches the plain replays by seed.  Besides what
+    replay() checks, every output of a deterministic entry must equal the plain run of the same seed bit for bit (poison), or be
+    exactly 2^+-30 times it (scaled_up / scaled_down on the linear families); fp32-atomic targets are held to their bars alone."""
+    if mode == "poison":
+        r = replay(sig, device, seed, poison=True)
+    else:
+        r = replay(sig, device, seed, profile=mode, yardstick=sig[0] in YARDSTICK)
+    if mode == "poison" or (mode in EXACT_SCALE and sig[0] in _LINEAR):
+        if seed not in plain:
+            plain[seed] = replay(sig, device, seed).outputs
+        f = EXACT_SCALE.get(mode)
+        assert set(r.outputs) == set(plain[seed])
+        for name, (t, atomic) in r.outputs.items():
+            if atomic:
+                continue
+            want = plain[seed][name][0]
+            want = want if f is None else want * f
+            assert same_bits(t, want), (f"{short(sig)}: {name} differs from the plain run" + ("" if f is None else f" times {f:g}")
+                                        + f" in {int((t.view(_INT[t.dtype]) != want.view(_INT[t.dtype])).sum())} of {t.numel()} element(s)")
+    return r
+
+
+def hostile_rows():
+    """Every hand-written signature: ODD_GEOMETRY, SYNTHETIC and EXTRA_SMALL, with the index that seeds its replay."""
+    sigs = [s for s, _ in ODD_GEOMETRY] + SYNTHETIC + EXTRA_SMALL
+    return list(enumerate(sigs))
+
+
 # Entries a step launches that are not replayed here, the existing test that covers each (tests/test_kernels_gpu.py unless named) and
 # what that test holds it to: [torch] a plain torch reference (Adam + clip_grad_norm_, or a float64 restatement), [exact] a bit-exact
 # copy or integer comparison.
 COVERED_ELSEWHERE = {
-    "ddpm_mt_adam_ema": "test_fused_adam_ema_matches_torch_adam, test_multi_tensor_update_with_scalars_from_device_memory [torch]",
-    "ddpm_mt_grad_sumsq": "test_multi_tensor_update_with_scalars_from_device_memory [torch]",
+    "ddpm_mt_adam_ema": "test_fused_adam_ema_matches_torch_adam, test_multi_tensor_update_with_scalars_from_device_memory, "
+                        "test_optimizer_on_nonfinite_overflowing_zero_and_tiny_gradients [torch]",
+    "ddpm_mt_grad_sumsq": "test_multi_tensor_update_with_scalars_from_device_memory, "
+                          "test_optimizer_on_nonfinite_overflowing_zero_and_tiny_gradients [torch]",
     "ddpm_mt_gather_f32": "test_multi_tensor_gather [exact]",
     "ddpm_wgrad_unpack": "test_wgrad_unpack_and_fused_norm [exact]",
     "ddpm_wgrad_unpack_sumsq": "test_wgrad_unpack_and_fused_norm [exact, torch]",
@@ -1347,15 +1762,24 @@ def sync():
         torch.cuda.synchronize()
 
 
-def replay(sig, device, seed=0):
-    """Replay one signature on `device`; returns a Result (worst err/bar and where)."""
+def replay(sig, device, seed=0, poison=False, profile=None, yardstick=False):
+    """Replay one signature on `device`; returns a Result (worst err/bar and where).  Without keywords: the draws and checks the
+    recorded and odd-geometry tests have always had.  poison: everything the contract does not let the call read holds POISON bytes
+    (Buf.poison).  profile: a key of PROFILES.  yardstick: the non-linear families also put a plain fp32 torch composition through cmp."""
     _DEVICE[0] = device
     name, words = sig
-    res = Result(sig)
-    A = Arena(device, seed)
+    res = Result(sig, nonfinite=bool(profile) and profile.startswith("nonfinite"))
+    A = Arena(device, seed, poison=poison, profile=profile, yardstick=yardstick)
     REPLAY[name](A, words, res)
     res.max_bytes = max((b.nbytes for b in A.bufs), default=0)
+    for b in A.bufs:
+        if bool(b.written.any()) and not b.scratch:
+            res.outputs[b.name] = (b.t[b.written].clone(), b.atomic)
     return res
+
+
+def same_bits(a, b):
+    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.view(_INT[a.dtype]), b.view(_INT[b.dtype]))
 
 
 def geometry(sig, offsets=True):

@@ -771,6 +771,75 @@ def test_multi_tensor_update_with_scalars_from_device_memory():
             assert float((s_.cpu() - sr).abs().max()) < 3e-6, hyper_mode
 
 
+def _hostile_grads(case, sizes):
+    gs = [r(n, seed=300 + i, scale=0.5) for i, n in enumerate(sizes)]
+    if case == "nan":                      # (a) one NaN element in one tensor
+        gs[2][17] = float("nan")
+    elif case == "overflow":               # (b) finite gradients whose squared norm overflows fp32: 4096 + ... elements of ~1e18
+        gs = [g * 1e18 for g in gs]
+    elif case == "zero":                   # (c) one tensor whose gradient is exactly zero
+        gs[1] = torch.zeros_like(gs[1])
+    elif case == "tiny":                   # (d) g^2 is far below the fp32 normal range
+        gs = [g * 1e-20 for g in gs]
+    return gs
+
+
+@pytest.mark.parametrize("entry", ["single", "multi_tensor"])
+@pytest.mark.parametrize("case", ["nan", "overflow", "zero", "tiny"])
+def test_optimizer_on_nonfinite_overflowing_zero_and_tiny_gradients(case, entry):
+    """ddpm_sumsq_accumulate + ddpm_adam_ema_step and ddpm_mt_grad_sumsq + ddpm_mt_adam_ema at step 1 against clip_grad_norm_(1.0) +
+    torch.optim.Adam + the EMA recurrence on the same device (fp32 norm, as the kernels take it):
+      nan       a NaN norm gives a NaN clip coefficient: every p, m, v and shadow of EVERY tensor is NaN, as torch makes them — a
+                diverged model stays visible (the coefficient used to fall back to 1 and the other tensors stepped normally);
+      overflow  the squared norm is inf, the coefficient 0: nothing moves, within the 3e-6 of the tests above;
+      zero      the tensor without gradient keeps p and shadow bit for bit;
+      tiny      gradients of 1e-20: finite, p and shadow within 3e-6, m within 1e-5 relative."""
+    sizes = [4096, 37, 1000, 1536, 3]
+    ps = [r(n, seed=10 + i) for i, n in enumerate(sizes)]
+    gs = _hostile_grads(case, sizes)
+    lr, d = 3e-3, min(0.9999, 1 / (9 + 1))
+    refs = [p.clone().to(DEV).requires_grad_(True) for p in ps]
+    opt = torch.optim.Adam(refs, lr=lr, betas=(0.9, 0.999), eps=1e-8)
+    for q, g_ in zip(refs, gs):
+        q.grad = g_.clone().to(DEV)
+    norm = float(torch.nn.utils.clip_grad_norm_(refs, 1.0))
+    assert {"nan": math.isnan, "overflow": math.isinf}.get(case, math.isfinite)(norm), norm          # what the case is about
+    opt.step()
+    shadow_ref = [p.to(DEV) + (1 - d) * (q.detach() - p.to(DEV)) for p, q in zip(ps, refs)]
+    state = [opt.state[q] for q in refs]
+    P = [p.clone().to(DEV) for p in ps]
+    M, V, S = [torch.zeros_like(p) for p in P], [torch.zeros_like(p) for p in P], [p.clone() for p in P]
+    G = [g_.clone().to(DEV) for g_ in gs]
+    sc = (lr, 0.9, 0.999, 1e-8, 1 - 0.9, 1 - 0.999, 1 - d)
+    if entry == "single":
+        tot, ws = torch.zeros(1, device=DEV), torch.zeros(1024, device=DEV)
+        for g_ in G:
+            _hip.call("ddpm_sumsq_accumulate", g_.data_ptr(), g_.numel(), tot.data_ptr(), ws.data_ptr(), _hip.stream())
+        for p, g_, m, v, s_ in zip(P, G, M, V, S):
+            _hip.call("ddpm_adam_ema_step", p.data_ptr(), g_.data_ptr(), m.data_ptr(), v.data_ptr(), s_.data_ptr(), p.numel(), tot.data_ptr(), 1.0,
+                      *sc, _hip.stream())
+    else:
+        table = torch.tensor([[p.data_ptr(), g_.data_ptr(), m.data_ptr(), v.data_ptr(), s_.data_ptr(), p.numel()]
+                              for p, g_, m, v, s_ in zip(P, G, M, V, S)], dtype=torch.int64).to(DEV)
+        total = torch.zeros(_hip.lib().ddpm_mt_sumsq_slots(len(sizes)), device=DEV)
+        _hip.call("ddpm_mt_grad_sumsq", table.data_ptr(), len(P), total.data_ptr(), total.numel(), _hip.stream())
+        _hip.call("ddpm_mt_adam_ema", table.data_ptr(), len(P), total.data_ptr(), 1.0, *sc, 0, _hip.stream())
+    torch.cuda.synchronize()
+    for i, (p, m, v, s_, q, st, sr) in enumerate(zip(P, M, V, S, refs, state, shadow_ref)):
+        if case == "nan":
+            for nm, t, ref in (("p", p, q.detach()), ("m", m, st["exp_avg"]), ("v", v, st["exp_avg_sq"]), ("shadow", s_, sr)):
+                assert bool(torch.isnan(ref).all()), (nm, i)                       # as torch makes them
+                assert bool(torch.isnan(t).all()), f"{nm} of tensor {i}: {int((~torch.isnan(t)).sum())} of {t.numel()} element(s) are not NaN"
+            continue
+        assert all(bool(torch.isfinite(t).all()) for t in (p, m, v, s_)), i
+        assert float((p - q.detach()).abs().max()) < 3e-6, (case, i)
+        assert float((s_ - sr).abs().max()) < 3e-6, (case, i)
+        if case == "zero" and i == 1:
+            assert torch.equal(p.cpu(), ps[i]) and torch.equal(s_.cpu(), ps[i])
+        if case == "tiny":
+            assert float((m - st["exp_avg"]).abs().max()) <= 1e-5 * float(st["exp_avg"].abs().max()), i
+
+
 def test_multi_tensor_gather():
     a = [r(n, seed=i) for i, n in enumerate((512 * 128, 128, 7, 4096))]
     b = [r(n, seed=10 + i) for i, n in enumerate((512 * 128, 128, 7, 4096))]
