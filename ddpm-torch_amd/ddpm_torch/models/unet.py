@@ -889,8 +889,9 @@ class _Engine:
             return cats[len(enc) - 1 - e][1][1]
 
         # ---- encoder
-        xin = self._new(B, H, W, self.vec)                      # channel-padded NHWC copy of x
-        _hip.call("ddpm_nchw_to_nhwc", x.data_ptr(), xin.ptr, B, m.in_channels, H * W, self.vec, self.dcode, _hip.stream())
+        cin = self.convs[id(m.in_conv)].Cp                      # in_conv's packed width: one vector for RGB, more from 9 (bf16) / 5 (fp32) channels on
+        xin = self._new(B, H, W, cin)                           # channel-padded NHWC copy of x
+        _hip.call("ddpm_nchw_to_nhwc", x.data_ptr(), xin.ptr, B, m.in_channels, H * W, cin, self.dcode, _hip.stream())
         e = 0
         cur = skip_slot(e)
         self._conv(st, m.in_conv, xin, cur, 3)

@@ -302,6 +302,43 @@ def g9_train_lr():
     save("g9_train_lr.pt", out)
 
 
+# ----------------------------------------------------------------------------- G19 gradient accumulation and the pixel-shuffle wrapper
+def g19_accum_wrapper():
+    """What ``train.py --num-accum 2`` and ``train.py --block-size 2`` make of the reference Trainer: (accum2) ``num_accum=2`` for six
+    calls on the tiny net — gradients accumulate over two micro-batches, three updates; (wrapped12) the tiny net at 12 channels inside
+    the reference's ModelWrapper(PixelUnshuffle(2), PixelShuffle(2)) for three calls on 3 x 16 x 16 images.  Inputs, losses, final
+    parameters and EMA shadow (keys of the UNet itself: the wrapper's ``_model.`` prefix is stripped).  Tensors above 1024 elements
+    are kept as digests, which holds the file below G9's size."""
+    def small(d):
+        return {k.replace("_model.", "", 1) if k.startswith("_model.") else k: (v.detach().clone() if v.numel() <= 1024 else digest(v))
+                for k, v in d.items()}
+
+    lr, out = 3e-3, dict(init_seed=1234, rand_seed=31, lr=3e-3, gen_seed=8191)
+    for part, cfg, block, num_accum, calls, hw in (("accum2", TINY, 1, 2, 6, 8),
+                                                   ("wrapped12", dict(TINY, in_channels=12, out_channels=12), 2, 1, 3, 16)):
+        betas = ref.get_beta_schedule("linear", 1e-4, 0.02, 1000)
+        dif = ref.GaussianDiffusion(betas, "eps", "fixed-large", "mse")
+        torch.manual_seed(1234)
+        unet = ref.UNet(**cfg)
+        randomized(unet, 31)
+        net = unet if block == 1 else ref.train.ModelWrapper(unet, torch.nn.PixelUnshuffle(block), torch.nn.PixelShuffle(block))
+        opt = torch.optim.Adam(net.parameters(), lr=lr, betas=(0.9, 0.999))
+        sched = torch.optim.lr_scheduler.LambdaLR(opt, lr_lambda=lambda t: 1.0 if t < 2 else 0.5)
+        tr = ref.Trainer(net, opt, dif, epochs=1, trainloader=None, scheduler=sched, num_accum=num_accum, use_ema=True, grad_norm=1.0,
+                         shape=(3, hw, hw), device=torch.device("cpu"), ema_decay=0.9999)
+        net.train()
+        xs = [(torch.rand(4, 3, hw, hw, generator=torch.Generator().manual_seed(190 + i)) * 2 - 1) for i in range(calls)]
+        losses = []
+        for i, x in enumerate(xs):
+            tr.stats.reset()
+            tr.step(x, global_steps=i + 1)
+            losses.append(tr.current_stats["loss"])
+        out[part] = dict(cfg=cfg, block=block, num_accum=num_accum, lr_change=2, xs=xs, losses=torch.tensor(losses, dtype=torch.float64),
+                         params=small(net.state_dict()), shadow=small(tr.ema.shadow), num_updates=tr.ema.num_updates,
+                         last_lr=sched.get_last_lr()[0])
+    save("g19_accum_wrapper.pt", out)
+
+
 # ----------------------------------------------------------------------------- G8 toy plumbing
 def g8_toy():
     torch.manual_seed(1234)
@@ -640,6 +677,6 @@ if __name__ == "__main__":
     import sys
     ALL = dict(g1=g1_ops, g2=g2_blocks, g3=g3_model, g4=g4_tables, g5=g5_steps, g6=g6_loops, g7=g7_train, g8=g8_toy, g9=g9_train_lr, g10=g10_config2,
                g11=g11_config2_bench_batch, g12=g12_config2_train_steps, g13=g13_config5_and_4_at_their_batches,
-               g14=g14_config4_ddim50_at_its_batch, g15=g15_metrics, g16=g16_oracle_checks)
+               g14=g14_config4_ddim50_at_its_batch, g15=g15_metrics, g16=g16_oracle_checks, g19=g19_accum_wrapper)
     for name in (sys.argv[1:] or list(ALL)):          # `make_golden.py g9` regenerates one fixture, no argument = all
         ALL[name]()

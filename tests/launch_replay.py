@@ -1591,6 +1591,58 @@ EXTRA_SMALL += [
 ]
 
 
+# ----------------------------------------------------------------------------------------------------------------- edge channel counts
+# Hand-written signatures of what in_conv and out_conv launch when the network's edge channel counts are not 3 (W18-W24 record the same
+# geometries live): 1 and 4 channels stored as 8 (bf16) or 4 (fp32), 12 stored as 16 (bf16) or 12 (fp32), at the images those networks
+# see (B = 64 at 16 x 16, B = 16 at 32 x 32: 16384 pixels, the floor of the edge kernels).  Operands are pitched the way the engine
+# pitches them (the staged image and the output gradient are dense).  Each row is (signature, kernel id variant_of must name).
+def _wg3_edge_sig(B, H, W, C, N, Nreal, splits=16):
+    return ("ddpm_conv3x3_wgrad_nhwc", (_p(), N, _p(), C, _p(), _up(Nreal * 9 * C, 4), _p(null=True), _up(Nreal, 4), B, H, W, C, N, Nreal, splits, BF16))
+
+
+def _wg_edge_sig(B, H, W, C, Creal, N, Nreal, splits, dt):
+    return ("ddpm_conv2d_wgrad_nhwc", (_p(), N if N <= 16 else N + 64, _p(), C if C <= 16 else C + 64, _p(), 0, B, H, W, C, Creal, H, W, N, Nreal, 3, 3,
+                                       1, 1, 1, 0, splits, dt))
+
+
+EDGE_CHANNELS = [
+    # ---- bf16 forward: in_conv from the staged image, out_conv into NCHW fp32
+    (_conv_sig(64, 16, 16, 8, 64, bias=1, x_ld=8), 12),                      # 1 or 4 channels in 8 lanes: the few-input-channel kernel
+    (_conv_sig(64, 16, 16, 16, 64, bias=1, x_ld=16), 3),                     # 12 channels in 16 lanes: the tile GEMM, K = 144
+    (_conv_sig(16, 32, 32, 64, 1, bias=1, mode=3), 11),
+    (_conv_sig(64, 16, 16, 64, 4, bias=1, mode=3), 11),
+    (_conv_sig(64, 16, 16, 64, 12, bias=1, mode=3), 11),
+    (_conv_sig(64, 16, 16, 64, 24, bias=1, mode=3), 3),                      # past the edge kernel's 16: the tile GEMM writes NCHW
+    # ---- bf16 backward: out_conv's data gradient (K = 9 Np), in_conv's data gradient when the input asks for it (want_dx)
+    (_conv_sig(64, 16, 16, 8, 64, x_ld=8), 12),
+    (_conv_sig(64, 16, 16, 16, 64, x_ld=16), 3),
+    (_conv_sig(16, 32, 32, 64, 1, mode=3), 11),
+    (_conv_sig(64, 16, 16, 64, 12, mode=3), 11),
+    # ---- bf16 weight gradients: out_conv (Nreal / N) through the patch kernel, in_conv (Creal / C) through the generic GEMM
+    (_wg3_edge_sig(16, 32, 32, 64, 8, 1), 6),
+    (_wg3_edge_sig(64, 16, 16, 64, 8, 4), 6),
+    (_wg3_edge_sig(64, 16, 16, 64, 16, 12), 6),
+    (_wg_edge_sig(16, 32, 32, 8, 1, 64, 64, 12, BF16), 2),
+    (_wg_edge_sig(64, 16, 16, 8, 4, 64, 64, 12, BF16), 2),
+    (_wg_edge_sig(64, 16, 16, 16, 12, 64, 64, 12, BF16), 2),
+    # ---- fp32 (vectors of 4): everything on the templated tile GEMMs
+    (_conv_sig(64, 16, 16, 4, 64, bias=1, x_ld=4, dt=F32), 2),
+    (_conv_sig(64, 16, 16, 12, 64, bias=1, x_ld=12, dt=F32), 3),
+    (_conv_sig(16, 32, 32, 64, 1, bias=1, mode=3, dt=F32), 3),
+    (_conv_sig(64, 16, 16, 64, 12, bias=1, mode=3, dt=F32), 3),
+    (_conv_sig(64, 16, 16, 4, 64, x_ld=4, dt=F32), 2),
+    (_wg_edge_sig(16, 32, 32, 64, 64, 4, 1, 25, F32), 1),
+    (_wg_edge_sig(64, 16, 16, 64, 64, 12, 12, 25, F32), 1),
+    (_wg_edge_sig(16, 32, 32, 4, 1, 64, 64, 25, F32), 1),
+    (_wg_edge_sig(64, 16, 16, 12, 12, 64, 64, 25, F32), 1),
+    # ---- bias gradients over the padded output gradient
+    (("ddpm_colsum", (_p(), 8, _p(null=True), 0, _p(), 64, 256, 8, BF16)), None),
+    (("ddpm_colsum", (_p(), 16, _p(null=True), 0, _p(), 64, 256, 16, BF16)), None),
+    (("ddpm_colsum", (_p(), 4, _p(null=True), 0, _p(), 16, 1024, 4, F32)), None),
+    (("ddpm_colsum", (_p(), 12, _p(null=True), 0, _p(), 64, 256, 12, F32)), None),
+]
+
+
 # ----------------------------------------------------------------------------------------------------------------- value profiles
 # A profile transforms the data operands after the draw (Arena.shape); the float64 references read the stored values, so they follow.
 # Each transform takes (arena, fp32 values of a [rows][cols] view, geometry keywords) and returns the new values.
@@ -1731,8 +1783,8 @@ def hostile_replay(sig, device, seed, mode, plain):
 
 
 def hostile_rows():
-    """Every hand-written signature: ODD_GEOMETRY, SYNTHETIC and EXTRA_SMALL, with the index that seeds its replay."""
-    sigs = [s for s, _ in ODD_GEOMETRY] + SYNTHETIC + EXTRA_SMALL
+    """Every hand-written signature: ODD_GEOMETRY, SYNTHETIC, EXTRA_SMALL and EDGE_CHANNELS, with the index that seeds its replay."""
+    sigs = [s for s, _ in ODD_GEOMETRY] + SYNTHETIC + EXTRA_SMALL + [s for s, _ in EDGE_CHANNELS]
     return list(enumerate(sigs))
 
 
@@ -1810,7 +1862,8 @@ def _net(cfg, device, seed=0, dtype=torch.bfloat16):
     import ddpm_torch
     torch.manual_seed(seed)
     kw = {k: v for k, v in cfg["model"].items() if k != "block_size"}
-    return ddpm_torch.UNet(out_channels=kw["in_channels"], **kw).to(device).set_compute_dtype(dtype)
+    kw.setdefault("out_channels", kw["in_channels"])
+    return ddpm_torch.UNet(**kw).to(device).set_compute_dtype(dtype)
 
 
 def _diffusion(cfg):
@@ -1834,9 +1887,9 @@ def _train_step(cfg, device, B, size, drop=None, dtype=torch.bfloat16):
     tc = cfg["train"]
     opt = torch.optim.Adam(m.parameters(), lr=tc["lr"], betas=(0.9, 0.999))
     tr = ddpm_torch.Trainer(m, opt, _diffusion(cfg), epochs=1, trainloader=None, use_ema=tc["use_ema"], grad_norm=tc["grad_norm"],
-                            shape=(3, H, W), device=torch.device(device), ema_decay=tc["ema_decay"])
+                            shape=(m.in_channels, H, W), device=torch.device(device), ema_decay=tc["ema_decay"])
     m.train()
-    x = torch.rand(B, 3, H, W, generator=torch.Generator().manual_seed(1)) * 2 - 1
+    x = torch.rand(B, m.in_channels, H, W, generator=torch.Generator().manual_seed(1)) * 2 - 1
     return lambda: tr.step(x.to(device), global_steps=1)
 
 
@@ -1850,7 +1903,7 @@ def _sample_step(cfg, device, B, size, ddim_steps=None, dtype=torch.bfloat16):
         dif = ddim.DDIM(dif.betas if torch.is_tensor(dif.betas) else torch.as_tensor(dif.betas), d["model_mean_type"], "fixed-small",
                         d["loss_type"], eta=0.0, subsequence=ddim.get_selection_schedule("linear", ddim_steps, d["timesteps"]))
     g = torch.Generator().manual_seed(2)
-    x = torch.randn(B, 3, H, W, generator=g).to(device)
+    x = torch.randn(B, m.in_channels, H, W, generator=g).to(device)
     t = torch.full((B,), 500, dtype=torch.int64, device=device)
     if ddim_steps:
         t = torch.full((B,), ddim_steps // 2, dtype=torch.int64, device=device)
@@ -1861,12 +1914,14 @@ def _sample_step(cfg, device, B, size, ddim_steps=None, dtype=torch.bfloat16):
     return run
 
 
-def _reduced(mult=(1, 2, 2), drop=0.0):
+def _reduced(mult=(1, 2, 2), drop=0.0, ch=None):
     """cifar10.json with a reduced network (hid 64, one res block per level, attention at level 1 and in the middle block): the
-    non-square workloads W14-W17 keep the levels, the kernels and the dispatch of a real configuration at a few seconds a test."""
+    non-square workloads W14-W17 keep the levels, the kernels and the dispatch of a real configuration at a few seconds a test.
+    ch = (in, out): the edge channel counts of W18-W24 instead of the configuration's 3 -> 3."""
     cfg = _config("cifar10.json")
+    edge = {} if ch is None else dict(in_channels=ch[0], out_channels=ch[1])
     return dict(cfg, model=dict(cfg["model"], hid_channels=64, ch_multipliers=list(mult), num_res_blocks=1,
-                                apply_attn=[i == 1 for i in range(len(mult))], drop_rate=drop))
+                                apply_attn=[i == 1 for i in range(len(mult))], drop_rate=drop, **edge))
 
 
 # key -> (what it runs, builder(device, B, size), B, size); full size: the geometry the benchmark, the configs and the CLIs run; size is
@@ -1902,6 +1957,17 @@ WORKLOADS = {
     "W17": ("reduced net [1, 2] train step, B=2, 24x20, dropout 0.1",
             lambda dev, B=2, s=(24, 20): _train_step(_reduced(mult=(1, 2), drop=0.1), dev, B, s), 2, (24, 20)),
 }
+# edge channel counts other than 3 (EDGE_CHANNEL_WORKLOADS), on the reduced [1, 2] network at the smallest images that still reach the
+# edge convs (H, W multiples of 16, >= 16384 pixels): 1 -> 1 is `--dataset mnist` (B = 16 at 32 x 32), 4 -> 4 and 12 -> 12 are what
+# `train.py --block-size 2` makes of MNIST and of the RGB data sets (B = 64 at 16 x 16); each in bf16 and fp32, then one sampling step
+for _i, (_ch, _B, _s, _dt) in enumerate([((1, 1), 16, 32, torch.bfloat16), ((1, 1), 16, 32, _F32), ((4, 4), 64, 16, torch.bfloat16),
+                                         ((4, 4), 64, 16, _F32), ((12, 12), 64, 16, torch.bfloat16), ((12, 12), 64, 16, _F32)]):
+    WORKLOADS[f"W{18 + _i}"] = (
+        f"reduced net [1, 2] {_ch[0]} -> {_ch[1]} channels train step, {'bf16' if _dt == torch.bfloat16 else 'fp32'}, B={_B}, {_s}x{_s}, dropout 0.1",
+        lambda dev, B=_B, s=_s, ch=_ch, dt=_dt: _train_step(_reduced(mult=(1, 2), drop=0.1, ch=ch), dev, B, s, dtype=dt), _B, _s)
+WORKLOADS["W24"] = ("reduced net [1, 2] 12 -> 12 channels ancestral sampling step, B=64, 16x16",
+                    lambda dev, B=64, s=16: _sample_step(_reduced(mult=(1, 2), ch=(12, 12)), dev, B, s), 64, 16)
+EDGE_CHANNEL_WORKLOADS = tuple(f"W{i}" for i in range(18, 25))
 
 
 def record(monkeypatch, key, device, B=None, size=None):

@@ -80,6 +80,40 @@ def test_train_then_generate_round_trip(emu, workdir):
     assert len(glob.glob(os.path.join(out2, "*.png"))) == 1
 
 
+def test_block_size_and_accumulation_round_trip(emu, workdir):
+    """``train.py --block-size 2 --num-accum 2 --dry-run`` -> resume -> ``generate.py``: a 12 -> 12 UNet between PixelUnshuffle(2) and
+    PixelShuffle(2), two micro-batches of batch_size // 2 per update, through the generic step (a ModelWrapper is not a UNet)."""
+    tmp, cfg = workdir
+    train = _import_cli("train")
+    common = ["--config-path", cfg, "--train-device", "cpu", "--dry-run", "--block-size", "2", "--num-accum", "2", "--num-workers", "0",
+              "--compute", "fp32"]
+    tr = train.main(common + ["--num-samples", "2", "--use-ddim", "--chkpt-dir", str(tmp / "chk"), "--image-dir", str(tmp / "img")])
+    unet = tr.model._model
+    assert type(tr.model).__name__ == "ModelWrapper" and unet.in_channels == 12 and unet.out_channels == 12
+    assert tr.num_accum == 2 and not tr._direct and "ddpm_mt_adam_ema" in emu.log
+    assert tr.ema.num_updates == 0 and int(next(iter(tr.optimizer.state.values()))["step"]) == 1      # two calls, exactly one update
+    assert tr.trainloader.batch_size == TINY_CFG["train"]["batch_size"] // 2
+    rec = json.load(open(glob.glob(str(tmp / "chk" / "tiny" / "exp_*.info"))[0]))
+    assert rec["model"]["block_size"] == 2 and rec["model"]["in_channels"] == 12 and rec["model"]["out_channels"] == 12
+    chk = tmp / "chk" / "tiny" / "tiny_1.pt"
+    assert chk.exists() and (tmp / "img" / "train" / "tiny" / "1.jpg").exists()
+    saved = torch.load(chk, weights_only=False)
+    assert all(k.startswith("_model.") for k in saved["model"]) and saved["model"]["_model.in_conv.weight"].shape == (32, 12, 3, 3)
+    tr2 = train.main(common + ["--num-samples", "0", "--resume", "--chkpt-path", str(chk), "--chkpt-dir", str(tmp / "chk2"),
+                               "--image-dir", str(tmp / "img2")])
+    assert tr2.ema.num_updates == 1 and int(next(iter(tr2.optimizer.state.values()))["step"]) == 2
+    # generate.py takes the block size from the configuration (the flag exists for train.py only)
+    gcfg = tmp / "tiny_block2.json"
+    gcfg.write_text(json.dumps(dict(TINY_CFG, model=dict(TINY_CFG["model"], block_size=2))))
+    gen = _import_cli("generate")
+    out = gen.main(["--config-path", str(gcfg), "--device", "cpu", "--chkpt-path", str(chk), "--use-ddim", "--subseq-size", "4", "--total-size", "3",
+                    "--batch-size", "2", "--save-dir", str(tmp / "gen"), "--compute", "fp32", "--seed", "7"])
+    files = glob.glob(os.path.join(out, "*.png"))
+    assert len(files) == 3
+    from PIL import Image
+    assert Image.open(files[0]).size == (32, 32)
+
+
 def test_eval_flag_without_a_feature_network_is_refused_loudly(emu, workdir, monkeypatch):
     tmp, cfg = workdir
     train = _import_cli("train")

@@ -1,8 +1,8 @@
 """-m gpu: the HIP kernels on poisoned memory and on hostile value distributions.
 
 Every other replay draws N(0, 1)-like operands into buffers whose unreadable parts (guard bands, pitch gaps, overwritten outputs,
-workspaces) hold finite, harmless values.  Here every hand-written signature of tests/launch_replay.py (ODD_GEOMETRY, SYNTHETIC and
-EXTRA_SMALL — the smallest shapes at which each kernel is dispatched) is replayed against the same float64 references under the same,
+workspaces) hold finite, harmless values.  Here every hand-written signature of tests/launch_replay.py (ODD_GEOMETRY, SYNTHETIC,
+EXTRA_SMALL — the smallest shapes at which each kernel is dispatched — and EDGE_CHANNELS, the edge convs at 1, 4 and 12 channels) is replayed against the same float64 references under the same,
 unchanged per-element bars, one test per family x mode:
 
   poison          everything include/ddpm_hip.h does not let the call read holds 0xFF bytes (NaN in fp32 and bf16): both guard bands,

@@ -1,5 +1,5 @@
 """Host check (CPU) of the hostile-input replays of tests/test_hostile_inputs_gpu.py: the same rows (launch_replay.ODD_GEOMETRY,
-SYNTHETIC and EXTRA_SMALL) in the same modes (poison, then every value profile of launch_replay.PROFILES), through the host-emulated
+SYNTHETIC, EXTRA_SMALL and EDGE_CHANNELS) in the same modes (poison, then every value profile of launch_replay.PROFILES), through the host-emulated
 ABI (tests/abi_emulator.py), the way tests/test_step_launches_host.py drives replay().
 
 What it shows before any GPU time:

@@ -285,16 +285,33 @@ def test_conv_out3_channels_nchw(dt):
          B, H, H, C, H, H, N, 3, 3, 1, 1, 1, 0, 0, 0, 3, 1, None, None, dt, tol=TOL[0] if dt == 0 else 4e-3)
 
 
-@pytest.mark.parametrize("B,H,W,C,N", [(16, 32, 32, 128, 3), (5, 64, 64, 64, 3), (17, 32, 32, 128, 8), (64, 16, 16, 256, 3)])
+EDGE_GUARD = 4096                      # floats behind an output of exactly B * N * H * W elements
+
+
+@pytest.mark.parametrize("B,H,W,C,N", [(16, 32, 32, 128, 3), (5, 64, 64, 64, 3), (17, 32, 32, 128, 8), (64, 16, 16, 256, 3)]
+                         + [(64, 16, 16, C, N) for C in (64, 128) for N in (1, 2, 4, 12, 16)])
 def test_conv_edge_few_output_channels(B, H, W, C, N):
-    """out_conv on full-size images (>= 16384 pixels, bf16): the few-output-channel kernel — NCHW fp32 result, pitched input, bias or none."""
+    """out_conv on full-size images (>= 16384 pixels, bf16): the few-output-channel kernel — NCHW fp32 result, pitched input, bias or none.
+    N = 1, 4 and 12 are the out_conv of the 1-channel (MNIST) and the pixel-unshuffled networks, 2 and 16 the neighbours up to the
+    kernel's limit.  The output is exactly B * N * H * W floats followed by a guard band: nothing may land past channel N - 1."""
     ld = C + 16
+    n = B * N * H * W
     x, w = r(B * H * W, ld, seed=1, dt=1), r(N, 9 * C, seed=2, dt=1, scale=0.03)
-    for bias in (A(r(N, seed=3)), None):
-        y = torch.zeros(B, N, H, W)
-        both("ddpm_conv2d_nhwc", A(x), ld, A(w), A(y, out=True, name="y"), 0, bias, None, 0, None, 0,
-             B, H, W, C, H, W, N, 3, 3, 1, 1, 1, 0, 0, 0, 3, 1, None, None, 1, tol=4e-3)
     assert _hip.lib().ddpm_conv2d_variant(ld, 0, B, H, W, C, H, W, N, 3, 3, 1, 1, 1, 0, 0, 3, 1, 1, 0) == 11
+    for bias in (A(r(N, seed=3)), None):
+        y = torch.cat([torch.zeros(n), torch.full((EDGE_GUARD,), 0.5)])
+        worst = both("ddpm_conv2d_nhwc", A(x), ld, A(w), A(y, out=True, name="y"), 0, bias, None, 0, None, 0,
+                     B, H, W, C, H, W, N, 3, 3, 1, 1, 1, 0, 0, 0, 3, 1, None, None, 1, tol=4e-3)
+        assert torch.equal(y[n:], torch.full((EDGE_GUARD,), 0.5))                 # (the emulator's copy: its own writes end at n)
+    # the guard band on the device, bit for bit, behind a NaN-filled output
+    yd = torch.cat([torch.full((n,), float("nan")), torch.full((EDGE_GUARD,), 0.5)]).cuda()
+    xd, wdv, bd = x.cuda(), w.cuda(), r(N, seed=3).cuda()
+    _hip.call("ddpm_conv2d_nhwc", xd.data_ptr(), ld, wdv.data_ptr(), yd.data_ptr(), 0, bd.data_ptr(), 0, 0, 0, 0,
+              B, H, W, C, H, W, N, 3, 3, 1, 1, 1, 0, 0, 0, 3, 1, 0, 0, 1, _hip.stream())
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(yd[:n]).all()), "an element of the NCHW output was not written"
+    assert torch.equal(yd[n:].cpu(), torch.full((EDGE_GUARD,), 0.5)), "the kernel wrote past channel N - 1"
+    print(f"few_out C={C} N={N}: variant 11, worst err {worst:.2e} of the largest output (bar 4e-3)")
 
 
 @pytest.mark.parametrize("B,H,W,N", [(16, 32, 32, 128), (5, 64, 64, 64), (17, 32, 32, 96), (64, 16, 16, 128)])
@@ -308,6 +325,152 @@ def test_conv_edge_few_input_channels(B, H, W, N):
         both("ddpm_conv2d_nhwc", A(x), ld, A(w), A(y, out=True, name="y"), yld, bias, None, 0, None, 0,
              B, H, W, C, H, W, N, 3, 3, 1, 1, 1, 0, 0, 0, 0, 1, None, None, 1, tol=TOL[1])
     assert _hip.lib().ddpm_conv2d_variant(ld, yld, B, H, W, C, H, W, N, 3, 3, 1, 1, 1, 0, 0, 0, 1, 1, 0) == 12
+
+
+def _staged(img, Cp, dt):
+    """The engine's staging of an NCHW fp32 image: ddpm_nchw_to_nhwc on the device over a NaN-filled [B * HW][Cp] buffer followed by a
+    NaN guard band.  Returns the staged rows on the host."""
+    B, C, H, W = img.shape
+    n = B * H * W * Cp
+    yd = torch.full((n + EDGE_GUARD,), float("nan"), dtype=DT[dt]).cuda()
+    xd = img.contiguous().cuda()
+    _hip.call("ddpm_nchw_to_nhwc", xd.data_ptr(), yd.data_ptr(), B, C, H * W, Cp, dt, _hip.stream())
+    torch.cuda.synchronize()
+    out = yd.cpu()
+    assert bool(torch.isnan(out[n:]).all()), "ddpm_nchw_to_nhwc wrote past its output"
+    return out[:n].reshape(B * H * W, Cp)
+
+
+@pytest.mark.parametrize("dt", [0, 1])
+@pytest.mark.parametrize("C,Cp", [(1, 8), (4, 8), (12, 16), (1, 4), (4, 4), (5, 8), (12, 12)])
+def test_nchw_to_nhwc_channel_padding(C, Cp, dt):
+    """The image staging at every (channels, packed width) pair the engine forms for 1, 4, 5 and 12 channels in both modes: exact (the
+    rounding of the stored type aside, which is torch's own), every pad lane zero, nothing written past the output."""
+    B, H, W = 3, 5, 7
+    img = r(B, C, H, W, seed=C * 16 + Cp)
+    y = _staged(img, Cp, dt).reshape(B, H * W, Cp)
+    want = img.reshape(B, C, H * W).permute(0, 2, 1).to(DT[dt])
+    assert torch.equal(y[..., :C], want)
+    assert bool((y[..., C:] == 0).all()) and not bool(torch.isnan(y).any())
+    emu = torch.full((B * H * W, Cp), float("nan"), dtype=DT[dt])
+    Emulator().call("ddpm_nchw_to_nhwc", img.data_ptr(), emu.data_ptr(), B, C, H * W, Cp, dt, 0)
+    assert torch.equal(emu.reshape(B, H * W, Cp), y)
+
+
+@pytest.mark.parametrize("creal", [1, 3, 4])
+@pytest.mark.parametrize("B,H,W,N", [(16, 32, 32, 128), (64, 16, 16, 64)])
+def test_conv_edge_few_input_channels_from_the_staged_image(B, H, W, N, creal):
+    """in_conv as the engine runs it: x comes out of ddpm_nchw_to_nhwc with 1, 3 or 4 real channels written over a NaN-filled buffer.
+    The few-input-channel kernel reads every pixel as one 16-byte vector of 8 lanes, so the zeroed pad lanes are part of the operand:
+    a lane the staging kernel left alone would make every output NaN.  Results finite and within TOL[1] of the emulator."""
+    C, yld = 8, N + 32
+    x = _staged(r(B, creal, H, W, seed=11), C, 1)
+    assert bool((x[:, creal:] == 0).all())
+    w = r(N, 9 * C, seed=2, dt=1, scale=0.2)
+    w.reshape(N, 9, C)[:, :, creal:] = 0                             # ddpm_pack_weight's channel pad
+    assert _hip.lib().ddpm_conv2d_variant(C, yld, B, H, W, C, H, W, N, 3, 3, 1, 1, 1, 0, 0, 0, 1, 1, 0) == 12
+    y = r(B * H * W, yld, seed=6, dt=1)
+    worst = both("ddpm_conv2d_nhwc", A(x), C, A(w), A(y, out=True, name="y"), yld, A(r(N, seed=3)), None, 0, None, 0,
+                 B, H, W, C, H, W, N, 3, 3, 1, 1, 1, 0, 0, 0, 0, 1, None, None, 1, tol=TOL[1])
+    print(f"few_in creal={creal} N={N}: variant 12, worst err {worst:.2e} of the largest output (bar {TOL[1]:.1e})")
+
+
+# in_conv and out_conv of a 12-channel network (train.py --block-size 2 on an RGB data set): C = 12 is stored as 16 lanes in bf16 and
+# as 12 in fp32, N = 12 as 16 / 12.  (name, dt, C, N, output mode, bias, kernel id the dispatch must name)
+CONV12_CASES = [
+    ("in_conv_bf16", 1, 16, 64, 0, 1, 3),                    # not the edge kernel (C != 8): the tile GEMM with K = 144
+    ("out_conv_bf16", 1, 64, 12, 3, 1, 11),
+    ("out_conv_24_bf16", 1, 64, 24, 3, 1, 3),                # past the edge kernel's limit of 16: the tile GEMM writing NCHW
+    ("out_dgrad_bf16", 1, 16, 64, 0, 0, 3),                  # out_conv's data gradient, K = 9 Np
+    ("in_dgrad_bf16", 1, 64, 12, 3, 0, 11),                  # in_conv's data gradient when the input asks for it (want_dx)
+    ("in_conv_fp32", 0, 12, 64, 0, 1, 3),
+    ("out_conv_fp32", 0, 64, 12, 3, 1, 3),
+    ("out_conv_24_fp32", 0, 64, 24, 3, 1, 3),
+]
+
+
+@pytest.mark.parametrize("case", CONV12_CASES, ids=[c[0] for c in CONV12_CASES])
+def test_conv_rows_of_a_12_channel_network(case):
+    """B = 64 at 16 x 16 (what --block-size 2 makes of CIFAR-10): bars of test_conv_fwd (TOL[dt] for stored NHWC, 4e-3 / TOL[0] for the
+    fp32 NCHW result of bf16 / fp32 operands)."""
+    _, dt, C, N, mode, has_bias, variant = case
+    B, H, W = 64, 16, 16
+    ld = C if C <= 16 else C + 16                                  # the staged image and the padded output gradient are dense
+    yld = 0 if mode == 3 else N + 32
+    assert _hip.lib().ddpm_conv2d_variant(ld, yld, B, H, W, C, H, W, N, 3, 3, 1, 1, 1, 0, 0, mode, 1, dt, 0) == variant
+    x, w = r(B * H * W, ld, seed=1, dt=dt), r(N, 9 * C, seed=2, dt=dt, scale=1.0 / math.sqrt(9 * C))
+    bias = A(r(N, seed=3)) if has_bias else None
+    n = B * N * H * W
+    if mode == 3:
+        y = torch.cat([torch.zeros(n), torch.full((EDGE_GUARD,), 0.5)])
+        tol = TOL[0] if dt == 0 else 4e-3
+    else:
+        y = r(B * H * W, yld, seed=6, dt=dt)
+        tol = TOL[dt]
+    worst = both("ddpm_conv2d_nhwc", A(x), ld, A(w), A(y, out=True, name="y"), yld, bias, None, 0, None, 0,
+                 B, H, W, C, H, W, N, 3, 3, 1, 1, 1, 0, 0, 0, mode, 1, None, None, dt, tol=tol)
+    print(f"{case[0]}: variant {variant}, worst err {worst:.2e} of the largest output (bar {tol:.1e})")
+
+
+# weight gradients of the edge convs: Creal / C of in_conv, Nreal / N of out_conv.  bf16: out_conv goes to the patch-stationary kernel
+# (ddpm_conv3x3_wgrad_nhwc, variant 6), in_conv to the generic GEMM (ddpm_conv2d_wgrad_nhwc, variant 2: Creal != C); fp32: both to the
+# generic GEMM (variant 1), with the splits the engine asks for.  (name, dt, B, H, C, Creal, N, Nreal, splits, variant)
+WGRAD_EDGE_CASES = [
+    ("in_1of8_bf16", 1, 16, 32, 8, 1, 64, 64, 12, 2),
+    ("in_4of8_bf16", 1, 64, 16, 8, 4, 64, 64, 12, 2),
+    ("in_12of16_bf16", 1, 64, 16, 16, 12, 64, 64, 12, 2),
+    ("in_1of4_fp32", 0, 16, 32, 4, 1, 64, 64, 25, 1),
+    ("in_4of4_fp32", 0, 64, 16, 4, 4, 64, 64, 25, 1),
+    ("in_12of12_fp32", 0, 64, 16, 12, 12, 64, 64, 25, 1),
+    ("out_1of4_fp32", 0, 16, 32, 64, 64, 4, 1, 25, 1),
+    ("out_4of4_fp32", 0, 64, 16, 64, 64, 4, 4, 25, 1),
+    ("out_12of12_fp32", 0, 64, 16, 64, 64, 12, 12, 25, 1),
+]
+
+
+@pytest.mark.parametrize("case", WGRAD_EDGE_CASES, ids=[c[0] for c in WGRAD_EDGE_CASES])
+def test_conv_wgrad_edge_channel_pads(case):
+    """Bars of test_conv_wgrad (1e-4 fp32, 3e-3 bf16 of the largest gradient), atomics on top of existing content.  The pad lanes of
+    the operands hold random values: lanes >= Creal / Nreal must not reach the compact [Nreal][3][3][Creal] gradient."""
+    _, dt, B, H, C, Creal, N, Nreal, splits, variant = case
+    W = H
+    xld, yld = C, N
+    eff = int(_hip.lib().ddpm_wgrad_effective_splits(B * H * W, splits, dt))
+    assert _hip.lib().ddpm_conv2d_wgrad_variant(yld, xld, B, H, W, C, Creal, H, W, N, Nreal, 3, 3, 1, 1, 1, 0, eff, dt) == variant
+    x, dy = r(B * H * W, xld, seed=1, dt=dt), r(B * H * W, yld, seed=2, dt=dt)
+    dw = torch.cat([r(Nreal * 9 * Creal, seed=3), torch.full((EDGE_GUARD,), 0.5)])
+    worst = both("ddpm_conv2d_wgrad_nhwc", A(dy), yld, A(x), xld, A(dw, out=True, name="dw"), 0, B, H, W, C, Creal, H, W, N, Nreal, 3, 3,
+                 1, 1, 1, 0, eff, dt, tol=1e-4 if dt == 0 else 3e-3)
+    print(f"{case[0]}: variant {variant}, splits {eff}, worst err {worst:.2e} of the largest gradient (bar {1e-4 if dt == 0 else 3e-3:.0e})")
+
+
+@pytest.mark.parametrize("B,H,N,Nreal", [(16, 32, 8, 1), (64, 16, 8, 4), (64, 16, 16, 12)])
+def test_conv3x3_wgrad_patch_kernel_few_output_channels(B, H, N, Nreal):
+    """out_conv's weight gradient in bf16 as the engine calls it: the patch-stationary kernel (variant 6) with N = Np = 8 or 16 lanes of
+    which Nreal = 1, 4, 12 are real, dense dy, slab copies summed by ddpm_wgrad_reduce, no bias pointer.  Bar of
+    test_conv3x3_wgrad_patch_kernel (4e-3 of the largest gradient); the slab copies sit in front of a guard band."""
+    C, W, dt = 64, H, 1
+    assert _hip.lib().ddpm_conv3x3_wgrad_variant(B, H, W, C, N) == 6
+    copies = int(_hip.lib().ddpm_conv3x3_wgrad_splits(B, H, W, C, N, 0))
+    assert copies >= 1
+    x, dy = r(B * H * W, C, seed=1, dt=dt), r(B * H * W, N, seed=2, dt=dt)
+    n = Nreal * 9 * C
+    ref = torch.zeros(n)
+    Emulator(_hip.lib()).call("ddpm_conv3x3_wgrad_nhwc", dy.data_ptr(), N, x.data_ptr(), C, ref.data_ptr(), 0, 0, 0, B, H, W, C, N, Nreal, 0, dt, 0)
+    stride = (n + 3) // 4 * 4
+    slabs = torch.cat([torch.full((copies * stride,), float("nan")), torch.full((EDGE_GUARD,), 0.5)]).cuda()
+    xd, dyd = x.cuda(), dy.cuda()
+    _hip.call("ddpm_conv3x3_wgrad_nhwc", dyd.data_ptr(), N, xd.data_ptr(), C, slabs.data_ptr(), stride, 0, 0, B, H, W, C, N, Nreal, 0, dt, _hip.stream())
+    out = torch.zeros(n).cuda()
+    table = torch.tensor([[slabs.data_ptr(), out.data_ptr(), n, copies, stride]], dtype=torch.int64).cuda()
+    _hip.call("ddpm_wgrad_reduce", table.data_ptr(), 1, _hip.stream())
+    torch.cuda.synchronize()
+    assert torch.equal(slabs[copies * stride:].cpu(), torch.full((EDGE_GUARD,), 0.5)), "a slab copy was written past Nreal rows"
+    got = out.cpu()
+    assert bool(torch.isfinite(got).all())
+    err = float((got - ref).abs().max()) / float(ref.abs().max())
+    print(f"out_conv wgrad Nreal/N = {Nreal}/{N}: variant 6, {copies} slab copies, worst err {err:.2e} of the largest gradient (bar 4e-3)")
+    assert err <= 4e-3
 
 
 def test_gather_rows_time_table():
@@ -962,9 +1125,34 @@ def test_pack_weight_multi(dt):
     """All derived weight layouts in one launch: forward pack [N][tap][Cp], dgrad pack [C][flipped tap][Np], the 4x4 / stride-2 effective
     dgrad kernel of the Upsample convs, channel padding, ragged 32-tiles — bit-exact against the numpy restatement (the 4x4 kernel, a sum
     of up to four fp32 taps, to fp32 / bf16 rounding)."""
+    _pack_multi([(64, 64, 3, 0), (40, 24, 3, 0), (3, 128, 3, 0), (128, 3, 3, 0), (96, 72, 1, 0), (64, 64, 3, 0x100), (40, 72, 3, 0x100)], dt)
+
+
+@pytest.mark.parametrize("dt", [0, 1])
+def test_pack_weight_multi_at_edge_channel_pads(dt):
+    """in_conv (N = 64, C = 1, 4, 5, 12) and out_conv (N = 1, 4, 12, 24, C = 64) of the 1-channel and the pixel-unshuffled networks: the
+    zeroed pad lanes of both packs are what the edge kernels multiply the pad lanes of their operands with."""
+    _pack_multi([(64, 1, 3, 0), (64, 4, 3, 0), (64, 5, 3, 0), (64, 12, 3, 0), (1, 64, 3, 0), (4, 64, 3, 0), (12, 64, 3, 0), (24, 64, 3, 0)], dt)
+
+
+def test_wgrad_unpack_at_edge_channel_pads():
+    """ddpm_wgrad_unpack on the compact gradients of the edge convs ([N][9][Creal] -> [N][Creal][9] with Creal = 1, 4, 12; Nreal = 1, 4,
+    12 rows) and on a bias slot of 1, 4 and 12 floats: exact."""
+    g = torch.Generator().manual_seed(6)
+    shapes = [(64, 1, 9), (64, 4, 9), (64, 12, 9), (1, 64, 9), (4, 64, 9), (12, 64, 9), (1, 1, 1), (1, 4, 1), (1, 12, 1)]
+    src_off, dst_off, rows = 0, 0, []
+    for N, C, RS in shapes:
+        rows.append([src_off, dst_off, N, C, RS])
+        src_off += (N * C * RS + 3) // 4 * 4 + 4
+        dst_off += (N * C * RS + 3) // 4 * 4
+    gpack = torch.randn(src_off, generator=g)
+    gflat = torch.full((dst_off,), 3.0)
+    both("ddpm_wgrad_unpack", A(gpack), A(gflat, out=True, name="gflat"), A(torch.tensor(rows, dtype=torch.int64)), len(rows), 0.5, tol=0.0)
+
+
+def _pack_multi(cases, dt):
     vec = 4 if dt == 0 else 8
     pad = lambda n: -(-n // vec) * vec
-    cases = [(64, 64, 3, 0), (40, 24, 3, 0), (3, 128, 3, 0), (128, 3, 3, 0), (96, 72, 1, 0), (64, 64, 3, 0x100), (40, 72, 3, 0x100)]
     ws, wfs, wds, rows, keep = [], [], [], [], []
     for i, (N, C, R, flag) in enumerate(cases):
         w = r(N, C, R, R, seed=10 + i)

@@ -3,7 +3,8 @@ float64 reference at the geometry the step uses.
 
 The workloads (tests/launch_replay.py WORKLOADS: W1-W4 the benchmarked bf16 steps, W5-W8 the same configurations in the fp32 compute
 mode, W9-W13 bf16 steps at the batch sizes train.py --num-accum and generate.py run, up to operands >= 1 GiB, W14-W17 a reduced network
-on non-square 16 x 48, 48 x 16 and 24 x 20 images) are recorded live through
+on non-square 16 x 48, 48 x 16 and 24 x 20 images, W18-W24 the reduced network with 1, 4 and 12 image channels — what --dataset mnist
+and train.py --block-size 2 build — in both compute modes) are recorded live through
 ddpm_torch._hip._invoke — the geometry list is taken from the step every time the test runs, not from a committed snapshot.  Each
 distinct signature of a replayed entry is (dropout seeds aside) re-issued once on fresh random inputs (same pitches, pointer offsets
 modulo 256, optional operands, modes, splits and workspaces) and every output element is held to its own error-model bar; the float64
@@ -24,7 +25,7 @@ DEV = "cuda:0"
 # kernels the benchmark line is made of (include/ddpm_hip_debug.h): 13 conv3x3_pc, 10 / 8 conv3x3_stream<8> / <16>, 7 pw_conv,
 # 4 gemm64, 11 / 12 edge convs, 14 wgrad3x3_ws, 6 wgrad3x3 (patch-stationary)
 W1_VARIANTS = {13, 10, 8, 7, 4, 11, 12, 14, 6}
-FP32 = ("W5", "W6", "W7", "W8")
+FP32 = ("W5", "W6", "W7", "W8", "W19", "W21", "W23")
 # recorded launches of the fp32 workloads that may pass a dtype other than fp32 (none: every operand of the fp32 mode is fp32)
 FP32_DTYPE_EXEMPT = {}
 
@@ -43,7 +44,7 @@ def _check_fp32_mode(key, rec, variants):
     bf16_only = sorted(set(variants) & LR.BF16_ONLY)
     assert not bf16_only, f"{key}: fp32 signatures dispatched to bf16-only kernels {bf16_only}"
     assert "ddpm_softmax_fwd" in rec.names, f"{key}: fp32 attention ran no ddpm_softmax_fwd"
-    if key in ("W5", "W7"):
+    if key in ("W5", "W7", "W19", "W21", "W23"):
         assert "ddpm_softmax_bwd" in rec.names, f"{key}: fp32 attention backward ran no ddpm_softmax_bwd"
 
 
@@ -98,6 +99,29 @@ def _check_w12(rec):
     print(f"W12: {len(gn)} GroupNorm backward signature(s) at HW = 4096, {len(wg)} 3x3 weight gradient(s) over 128*64*64 pixels")
 
 
+# (in, out) channels of the edge-channel workloads, and the kernels their bf16 edge convs must reach: 11 few-output-channel kernel at
+# N = 1, 4, 12; 12 few-input-channel kernel while the image fits one 8-lane vector (also out_conv's data gradient at Np = 8); at 12
+# channels (16 lanes) in_conv and out_conv's data gradient are the tile GEMM 3.  6: out_conv's weight gradient (Nreal < N) on the patch
+# kernel; 2: in_conv's (Creal < C) on the generic one.
+EDGE_CHANNELS_OF = {"W18": (1, 1), "W19": (1, 1), "W20": (4, 4), "W21": (4, 4), "W22": (12, 12), "W23": (12, 12), "W24": (12, 12)}
+
+
+def _check_edge_channels(key, rec, variants):
+    cin, cout = EDGE_CHANNELS_OF[key]
+    convs = [s for s in rec.sigs if s[0] == "ddpm_conv2d_nhwc" and s[1][17] == 3]
+    staged = sorted({(s[1][3], s[1][5]) for s in rec.sigs if s[0] == "ddpm_nchw_to_nhwc"})               # (C, Cp) of every NCHW -> NHWC staging
+    print(f"{key}: staged (C, Cp) {staged}; edge convs " + ", ".join(f"C{s[1][13]}->N{s[1][16]} mode {s[1][25]} v{LR.variant_of(s)}"
+                                                                     for s in convs if s[1][13] <= 16 or s[1][16] <= 16))
+    assert any(s[1][13] == -(-cin // (4 if key in FP32 else 8)) * (4 if key in FP32 else 8) and s[1][16] == 64 for s in convs), f"{key}: no in_conv"
+    assert any(s[1][16] == cout and s[1][25] == 3 for s in convs), f"{key}: no out_conv into NCHW"
+    if key in FP32:
+        return
+    want = {11, 12} if cin <= 8 else {11, 3}
+    if key != "W24":
+        want |= {6, 2}
+    assert want <= set(variants), f"{key} did not reach variants {sorted(want - set(variants))}"
+
+
 @pytest.mark.parametrize("key", list(LR.WORKLOADS))
 def test_every_launch_of_the_step_matches_float64(key, monkeypatch):
     t0 = time.perf_counter()
@@ -126,6 +150,8 @@ def test_every_launch_of_the_step_matches_float64(key, monkeypatch):
         _check_w14(rec, variants)
     if key == "W17":
         _check_w17(rec)
+    if key in LR.EDGE_CHANNEL_WORKLOADS:
+        _check_edge_channels(key, rec, variants)
     rows, bad, seen = [], [], set()
     for i, s in enumerate(rec.sigs):
         if s[0] not in LR.REPLAY or LR.geometry(s) in seen:
@@ -145,6 +171,23 @@ def test_every_launch_of_the_step_matches_float64(key, monkeypatch):
     if key == "W13":
         assert biggest[2].max_bytes >= 2 ** 30, f"W13: largest replayed operand {biggest[2].max_bytes} bytes < 1 GiB"
     assert not bad, f"{key}: {len(bad)} signature(s) beyond their bar:\n" + "\n".join(bad)
+
+
+def test_edge_channel_signatures_match_float64():
+    """launch_replay.EDGE_CHANNELS: what in_conv and out_conv launch at 1, 4 and 12 channels, hand-written (the workloads W18-W24 record
+    the same geometries live), each on the kernel the table names."""
+    rows, bad = [], []
+    for i, (sig, variant) in enumerate(LR.EDGE_CHANNELS):
+        got = LR.variant_of(sig)
+        assert got == variant, f"{LR.short(sig)}: dispatched to {got}, the table names {variant}"
+        r = LR.replay(sig, DEV, seed=i)
+        rows.append((sig, variant, r))
+        if r.worst > 1.0:
+            bad.append(f"{LR.short(sig)}: {r.where} err/bar {r.worst:.3g}")
+    print(f"\n== edge channel counts: {len(rows)} replayed signatures")
+    for sig, var, r in rows:
+        print(f"  {LR.short(sig):<130s} v{'' if var is None else var:<3} {r.where:<10s} err/bar {r.worst:.3f}")
+    assert not bad, "\n".join(bad)
 
 
 def test_synthetic_signatures_match_float64():

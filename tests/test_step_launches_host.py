@@ -1,6 +1,7 @@
 """Host check (CPU) of tests/launch_replay.py, the replay-against-float64 machinery of tests/test_step_launches_gpu.py.
 
-The benchmarked workloads of the GPU test, their fp32 twins and the non-square workloads W14-W17 run through the host-emulated engine
+The benchmarked workloads of the GPU test, their fp32 twins, the non-square workloads W14-W17 and the edge-channel workloads W18-W24
+(1, 4 and 12 image channels) run through the host-emulated engine
 (tests/abi_emulator.py) at batch 2 (CelebA-HQ at 128x128 instead of 256x256: its geometry does not change how the contract is read),
 their launches are recorded, and every recorded signature of a
 replayed entry is replayed against the emulator.  This shows, before any GPU time, that the replay builders size their buffers, read
@@ -26,7 +27,10 @@ pytestmark = pytest.mark.skipif(not os.path.exists(_hip.LIB_PATH), reason="libdd
 # epilogue term is off by the size of the value itself, 10^3..10^7 bars.
 HOST_SLACK = 4.0
 HOST_SIZE = {"W1": (2, 32), "W2": (2, 32), "W3": (2, 128), "W4": (2, 64), "W5": (2, 32), "W6": (2, 32), "W7": (2, 128), "W8": (2, 64),
-             "W14": (2, (16, 48)), "W15": (2, (16, 48)), "W16": (2, (48, 16)), "W17": (2, (24, 20))}      # the non-square workloads
+             "W14": (2, (16, 48)), "W15": (2, (16, 48)), "W16": (2, (48, 16)), "W17": (2, (24, 20)),      # the non-square workloads
+             # edge channel counts 1, 4 and 12 (train.py --dataset mnist / --block-size 2), bf16 and fp32, and the 12-channel sampling step
+             "W18": (2, 32), "W19": (2, 32), "W20": (2, 16), "W21": (2, 16), "W22": (2, 16), "W23": (2, 16), "W24": (2, 16)}
+assert set(LR.EDGE_CHANNEL_WORKLOADS) <= set(HOST_SIZE)
 
 
 def test_replay_builders_agree_with_the_emulator_on_every_recorded_signature(monkeypatch):
@@ -70,6 +74,18 @@ def test_odd_geometry_signatures_agree_with_the_emulator_and_name_their_kernel(r
     """launch_replay.ODD_GEOMETRY (non-square images, pixel and token counts that are no power of two) before any GPU time: the float64
     replayers meet the emulator at these shapes, and the dispatch queries (pure host functions) send each row to the kernel the table
     names, so that the GPU test of the same rows runs the kernels it means to."""
+    sig, variant = row
+    abi_emulator.install(monkeypatch, _hip)
+    assert sig[0] in LR.REPLAY
+    assert LR.variant_of(sig) == variant, f"{LR.short(sig)}: dispatched to {LR.variant_of(sig)}, the table names {variant}"
+    r = LR.replay(sig, "cpu")
+    assert r.worst <= HOST_SLACK, f"{LR.short(sig)}: {r.where} err/bar {r.worst:.3g}"
+
+
+@pytest.mark.parametrize("row", LR.EDGE_CHANNELS, ids=lambda row: LR.short(row[0]))
+def test_edge_channel_signatures_agree_with_the_emulator_and_name_their_kernel(row, monkeypatch):
+    """launch_replay.EDGE_CHANNELS (what in_conv and out_conv launch at 1, 4 and 12 channels) before any GPU time, like the odd-geometry
+    rows above: the replayers meet the emulator with Creal < C and Nreal < N, and the dispatch queries name the kernel the table names."""
     sig, variant = row
     abi_emulator.install(monkeypatch, _hip)
     assert sig[0] in LR.REPLAY
