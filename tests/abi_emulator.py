@@ -440,7 +440,23 @@ class Emulator:
         bank[...] = 0
         bank[0] = np.float32(tot)
 
+    def ddpm_sumsq_accumulate(self, g, n, total, ws, st):
+        if n > 0:
+            v = f32(g, n).astype(np.float64)
+            f32(total, 1)[0] = np.float32(float(f32(total, 1)[0]) + float((v * v).sum()))
+
+    def ddpm_adam_ema_step(self, p, g, m, v, shadow, n, total, max_norm, lr, b1, b2, eps, bc1, bc2, ema_w, st):
+        if n <= 0:
+            return
+        row = np.array([p, g, m, v, shadow or 0, n], dtype=np.int64)
+        bank = np.zeros(64, dtype=np.float32)
+        if total:
+            bank[0] = f32(total, 1)[0]
+        self.ddpm_mt_adam_ema(row.ctypes.data, 1, bank.ctypes.data if total else 0, max_norm, lr, b1, b2, eps, bc1, bc2, ema_w, 0, st)
+
     def ddpm_mt_adam_ema(self, table, n, total, max_norm, lr, b1, b2, eps, bc1, bc2, ema_w, hyper, st):
+        # the ABI takes these as C floats: the kernel sees 0.999f, not 0.999
+        max_norm, lr, b1, b2, eps, bc1, bc2, ema_w = (float(np.float32(x)) for x in (max_norm, lr, b1, b2, eps, bc1, bc2, ema_w))
         if hyper:
             lr, bc1, bc2, ema_w = (float(v) for v in f32(hyper, 4))
         clip = 1.0

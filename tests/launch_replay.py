@@ -18,6 +18,12 @@ everything the contract does not let the call read — both guard bands, pitch g
 content of overwritten outputs, unspecified workspaces — with 0xFF bytes (NaN); profile= transforms the data operands after the draw
 (PROFILES); yardstick=True also puts a plain fp32 torch composition through the same bars.  Without keywords the draws are unchanged.
 
+Table-driven entries (the optimizer tail: ddpm_wgrad_unpack(_sumsq), ddpm_mt_grad_sumsq, ddpm_mt_adam_ema, ddpm_pack_weight_multi,
+ddpm_mt_gather_f32) read their geometry from a table in device memory.  record() keeps the table's address and, once the workload has
+ended, replaces the pointer word of the signature by the normalised table (resolve_tables / normalise_table: per row the element counts,
+for every pointer column null / address modulo 16 / byte gap to the next row's tensor); the replay rebuilds that packing out of guarded
+buffers.  Their references and bars are stated where they are defined ("the optimizer tail").
+
 Error model: each output element i gets its own bar
     |got_i - ref_i| <= c * (u_out * M_i + u_acc * sqrt(K) * S_i)
 M_i is the sum of the magnitudes of the terms added into element i (the product sum, bias, row bias, residual, prior content), S_i is
@@ -79,9 +85,13 @@ class Recorder:
     def __init__(self, inner):
         self.inner = inner
         self.sigs = {}
+        self.tables = {}                    # signature of a table-driven launch -> the address of the table it read (resolve_tables)
 
     def __call__(self, name, args):
-        self.sigs.setdefault(signature(name, args), None)
+        sig = signature(name, args)
+        self.sigs.setdefault(sig, None)
+        if name in TABLE_ARG:
+            self.tables.setdefault(sig, int(args[TABLE_ARG[name][0]] or 0))
         return self.inner(name, args)
 
     @property
@@ -162,6 +172,7 @@ class Buf:
         self.poisoned = False
         self.atomic = False             # an fp32-atomic accumulation target: its bits depend on the order of arrival
         self.scratch = False            # a workspace whose final content the contract does not state
+        self.result = None              # mask of the written elements whose content the contract states (None: all of them)
 
     def inp(self, rows, cols, ld, off=0):
         """The call may read the [rows][cols] elements with pitch ld starting `off` elements in."""
@@ -223,6 +234,8 @@ class Result:
         self.yard, self.yard_where = None, ""
         self.planted = {}                   # what -> number of elements the float64 reference makes non-finite
         self.outputs = {}                   # buffer name -> the stored output elements (replay() fills it)
+        self.tensors = {}                   # table-driven entries: (row, column name) -> that row's output, whatever the packing
+        self.depth, self.clip = None, None  # reductions: the chain length of the bound; the update: the float64 clip coefficient
 
     def cmp(self, what, got, ref, bar, yard=None):
         """yard (optional): the yardstick's value of the same output, put through the same bar; it never decides a replay."""
@@ -1374,7 +1387,646 @@ def rep_weighted_sum(A, sig, res):
     res.cmp("out", got, pr.sum().reshape(1), (C_GEMM * (U_F32 * pr.abs().sum() + U_ACC * math.sqrt(n) * (pr * pr).sum().sqrt())).reshape(1))
 
 
+# ----------------------------------------------------------------------------------------------------------------- the optimizer tail
+# What a step runs after its last weight gradient: ddpm_wgrad_unpack(_sumsq) -> ddpm_mt_adam_ema -> ddpm_pack_weight_multi ->
+# ddpm_mt_gather_f32 (and ddpm_mt_grad_sumsq / the single-tensor pair on the autograd path).  All but the single-tensor pair read their
+# geometry from a TABLE in device memory, so the signature of such a launch carries, in place of the table pointer, a table word
+#     ("t", rows, opts)
+# rows: the normalised table (normalise_table: per row the element counts / descriptor fields and, for every pointer column, whether it
+# is null, its address modulo 16 and the byte gap to the next row's tensor when the two share a buffer); opts: ((key, value), ...) that
+# only hand-written rows set (the draw of the gradient, the optimizer step, the scalars behind hyper_dev).  The replay rebuilds that
+# packing out of guarded buffers (_carve): every float between two tensors of a buffer is outside the contract's output.
+TABLE_ARG = {            # entry -> (index of the table argument, index of n_tensors, int64 words per row)
+    "ddpm_mt_adam_ema": (0, 1, 6), "ddpm_mt_grad_sumsq": (0, 1, 6), "ddpm_mt_gather_f32": (0, 1, 4),
+    "ddpm_pack_weight_multi": (0, 1, 8), "ddpm_wgrad_unpack": (2, 3, 5), "ddpm_wgrad_unpack_sumsq": (2, 3, 5),
+}
+SEPARATE = -1                       # gap of a tensor whose successor in the column lives in another buffer (or is null / the last row)
+GAP_SHARED = 4096                   # recorded addresses: a successor that starts within this many bytes of a tensor's end shares its buffer
+GAP_CAP = 256                       # ... and gaps beyond this are shortened to it (keeping the successor's address modulo 16)
+DENORM = 2.0 ** -149                # absolute rounding step below the fp32 normal range
+BETA1, BETA2, ADAM_EPS = 0.9, 0.999, 1e-8
+SUMSQ_SLOT_BLOCKS = 64              # ddpm_mt_sumsq_slots(n) = 64 + 64 n
+
+
+def _f(x):
+    """the value a C float argument takes"""
+    return float(np.float32(x))
+
+
+def is_table(w):
+    return isinstance(w, tuple) and len(w) == 3 and w[0] == "t"
+
+
+def _columns(ptrs, nbytes):
+    """ptrs[r][c] (addresses), nbytes[r][c] -> per row a tuple of (null, address % 16, gap) per pointer column."""
+    out = []
+    for r, row in enumerate(ptrs):
+        cols = []
+        for c, a in enumerate(row):
+            if not a:
+                cols.append((True, 0, SEPARATE))
+                continue
+            gap = SEPARATE
+            if r + 1 < len(ptrs) and ptrs[r + 1][c]:
+                g = ptrs[r + 1][c] - (a + nbytes[r][c])
+                if 0 <= g < GAP_SHARED:
+                    gap = g if g <= GAP_CAP else GAP_CAP + g % 16
+            cols.append((False, a % 16, gap))
+        out.append(tuple(cols))
+    return out
+
+
+def _pack_extents(N, C, Rf, Cp, Np, es):
+    R, up = Rf & 0xff, bool(Rf & 0x100)
+    return 4 * N * C * R * R, es * N * R * R * Cp, es * C * (16 if up else R * R) * Np
+
+
+def normalise_table(name, rows, dtype=None):
+    """rows: the int64 table a launch of `name` read, as lists of ints -> the table word of its signature (no pointer values)."""
+    if name in ("ddpm_wgrad_unpack", "ddpm_wgrad_unpack_sumsq"):       # offsets into gpack / gflat, not addresses: kept as they are
+        return ("t", tuple(tuple(int(v) for v in r) for r in rows), ())
+    if name == "ddpm_pack_weight_multi":
+        es = 2 if dtype == BF16 else 4
+        cols = _columns([r[:3] for r in rows], [_pack_extents(*r[3:8], es) for r in rows])
+        return ("t", tuple((tuple(int(v) for v in r[3:8]), c) for r, c in zip(rows, cols)), ())
+    k = TABLE_ARG[name][2] - 1                                           # pointer columns; the last word is numel
+    cols = _columns([r[:k] for r in rows], [[4 * r[k]] * k for r in rows])
+    return ("t", tuple((int(r[k]), c) for r, c in zip(rows, cols)), ())
+
+
+def _carve(A, name, col, sizes, dtype):
+    """One pointer column of a table out of guarded buffers.  col[r] = (null, address % 16, gap), sizes[r] in elements.  Consecutive
+    rows with a gap share a Buf, `gap` bytes apart; returns per row None (null) or (Buf, offset in elements)."""
+    es = 2 if dtype == BF16 else 4
+    out, run = [None] * len(col), []
+
+    def flush():
+        if not run:
+            return
+        offs, o = [], 0
+        for r in run:
+            offs.append(o)
+            o += sizes[r] + (col[r][2] // es if r != run[-1] else 0)
+        b = A.buf(f"{name}[{run[0]}]", o, dtype, col[run[0]][1])
+        for r, off in zip(run, offs):
+            assert (b.ptr + off * es) % 16 == col[r][1], f"{name}[{r}]: the packing does not give the recorded address modulo 16"
+            out[r] = (b, off)
+        run.clear()
+
+    for r, (null, _, gap) in enumerate(col):
+        if null:
+            flush()
+            continue
+        assert gap == SEPARATE or gap % es == 0
+        run.append(r)
+        if gap == SEPARATE:
+            flush()
+    flush()
+    return out
+
+
+def _sl(slot, n):
+    b, off = slot
+    return b.t[off:off + n]
+
+
+def _addr(slot, es=4):
+    return 0 if slot is None else slot[0].ptr + slot[1] * es
+
+
+def _mark(slot, n, read=False, write=False):
+    b, off = slot
+    if read:
+        b.readable[off:off + n] = True
+    if write:
+        b.written[off:off + n] = True
+
+
+def _table_buf(A, rows):
+    t = A.buf("table", max(len(rows) * len(rows[0]) if rows else 1, 1), "i64")
+    if rows:
+        t.t.copy_(torch.tensor(rows, dtype=torch.int64).reshape(-1))
+    return t.all_in()
+
+
+def bias_corrections(k):
+    """(bias_corr1, bias_corr2) of optimizer step k as torch.optim.Adam forms them from the betas the kernel is handed (0.9f, 0.999f)"""
+    return 1.0 - _f(BETA1) ** k, 1.0 - _f(BETA2) ** k
+
+
+def _step_of(bc2):
+    """optimizer step behind a recorded bias_corr2"""
+    if not 0.0 < bc2 < 1.0:
+        return 10 ** 6
+    return max(1, min(10 ** 6, round(math.log1p(-bc2) / math.log(BETA2))))
+
+
+def _planted(numels, sweep, store):
+    """The exact coverage draw: zero everywhere except up to 12 positions of the first and the last non-empty row, which hold distinct
+    powers of two 2^0 .. 2^11 — index 0, n - 2, n - 1, the first scalar-tail index 4 (n >> 2) and either side of one grid sweep
+    (sweep(row) elements).  Every partial sum of squares is then exact in fp32: a missed position clears its bit of the total, a
+    doubled one sets an odd bit.  store(row, i, value) plants element i of the row.  Returns the sum of the squares planted."""
+    live = [r for r, n in enumerate(numels) if n > 0]
+    k, total = 0, 0.0
+    for r in dict.fromkeys(live[:1] + live[-1:]):
+        n = numels[r]
+        for i in sorted({0, n - 2, n - 1, 4 * (n >> 2), sweep(r) - 1, sweep(r)} & set(range(n))):
+            store(r, i, 2.0 ** k)
+            total += 4.0 ** k
+            k += 1
+    assert 0 < k <= 12
+    return total
+
+
+def _mt_setup(A, rows, opts):
+    """Buffers and draws of a {p, g, m, v, shadow, numel} table.  The values of a row do not depend on how the table is packed (the same
+    seed gives the same numbers at every alignment): p = N(0, 1) 10^U(-4, 0), shadow = p (1 + 0.01 N), g by opts["g"] — "normal" N(0, 0.5),
+    "loguniform" +-10^U(-9, 0) so that eps matters on part of the tensor, "planted" (_planted) — times opts["gscale"]; m = |g| N(0, 1)
+    and v = g^2 U(0.5, 2): non-zero state of the gradient's own magnitude."""
+    numels = [n for n, _ in rows]
+    names = ("p", "g", "m", "v", "shadow")
+    slots = [_carve(A, nm, [c[i] for _, c in rows], numels, F32) for i, nm in enumerate(names)]
+    kind, gscale = opts.get("g", "normal"), opts.get("gscale", 1.0)
+    for r, n in enumerate(numels):
+        if n == 0:
+            continue
+        p = A.randn(n) * 10.0 ** (-4.0 * torch.rand(n, generator=A.dgen, device=A.device))
+        s = p * (1.0 + 0.01 * A.randn(n))
+        if kind == "loguniform":
+            g = torch.sign(A.randn(n)) * 10.0 ** (-9.0 * torch.rand(n, generator=A.dgen, device=A.device))
+        else:
+            g = A.randn(n, scale=0.5)
+        g = g * gscale
+        m = g.abs() * A.randn(n)
+        v = g * g * (0.5 + 1.5 * torch.rand(n, generator=A.dgen, device=A.device))
+        if kind == "planted":
+            g = torch.zeros_like(g)
+        else:
+            g = A.shaped("grad", g.reshape(-1, 1)).reshape(-1)
+        for slot, val in zip((slots[0][r], slots[1][r], slots[2][r], slots[3][r], slots[4][r]), (p, g, m, v, s)):
+            if slot is not None:
+                _sl(slot, n).copy_(val)
+    return numels, slots
+
+
+def _mt_rows_table(rows, slots):
+    return [[_addr(slots[c][r]) for c in range(5)] + [n] for r, (n, _) in enumerate(rows)]
+
+
+def _sumsq_depth(numel_its, n_slots):
+    """Longest chain of fp32 additions (and the product) one squared term passes through: the thread's own chain (numel_its, from the
+    launch geometry), 6 levels of the wave reduction, 2 of the 4-way block sum, the finish kernel's per-thread chain over n_slots slots
+    in 1024 threads and its 10-level tree."""
+    return numel_its + 6 + 2 + -(-n_slots // 1024) + 10
+
+
+def _check_bank(res, what, bank, ref, bar, planted_sum=None):
+    """bank: the 64 floats at total_sq after a producing launch.  Lane 0 against the float64 sum, lanes 1..63 exactly zero; after a
+    planted draw lane 0 must hold the planted sum bit for bit."""
+    assert not bool(bank[1:].view(torch.int32).any()), f"{what}: lanes 1..63 of the bank are not zero"
+    if planted_sum is not None:
+        assert float(bank[0]) == planted_sum, f"{what}: planted sum of squares {float(bank[0]):.1f}, exactly {planted_sum:.1f} expected " \
+                                              f"(difference {float(bank[0]) - planted_sum:+.1f})"
+    res.cmp(what, bank[:1], ref.reshape(1), bar.reshape(1))
+
+
+def rep_mt_grad_sumsq(A, sig, res):
+    """total_sq[0] = sum_i ||g_i||^2 in a fixed order, lanes 1..63 zero.  Bound (first order): d u sum g^2 with d the longest chain
+    of operations a term passes through (_sumsq_depth) — csrc/optim.hip mt_sumsq_kernel: 16 blocks of 256 threads a row, a float4
+    body (two in-vector levels and the thread's running sum) when g is 16-byte aligned, then the scalar tail — plus one denormal step
+    a term for squares below the normal range."""
+    table, n, ptot, total_floats = sig
+    rows, opts = table[1], dict(table[2])
+    assert n == len(rows) and total_floats >= 64 + SUMSQ_SLOT_BLOCKS * n
+    numels, slots = _mt_setup(A, rows, opts)
+    tot = A.buf("total_sq", total_floats, F32, _mod(ptot)).fill(A.randn(total_floats))
+    tot.written[:64 + SUMSQ_SLOT_BLOCKS * n] = True
+    tot.result = torch.zeros_like(tot.written)
+    tot.result[:64] = True
+    planted = None
+    if opts.get("g") == "planted":
+        def store(r, i, value):
+            _sl(slots[1][r], numels[r])[i] = value
+        planted = _planted(numels, lambda r: 16 * 256 * 4, store)
+    for r, nn in enumerate(numels):
+        _mark(slots[1][r], nn, read=True)
+    tb = _table_buf(A, _mt_rows_table(rows, slots))
+    A.snapshot()
+    _launch("ddpm_mt_grad_sumsq", [tb.ptr, n, tot.ptr, total_floats])
+    sync()
+    A.check()
+    S = sum((_d(_sl(slots[1][r], nn)) ** 2).sum() for r, nn in enumerate(numels) if nn) + torch.zeros((), dtype=torch.float64, device=A.device)
+    its = 0
+    for (nn, cols) in rows:
+        nv = nn >> 2 if cols[1][1] == 0 else 0
+        its = max(its, 1 + (2 + -(-nv // 4096) if nv else 0) + -(-(nn - 4 * nv) // 4096))
+    d = _sumsq_depth(its, 16 * n)
+    res.depth = d
+    _check_bank(res, "total_sq", tot.t[:64], S, d * U_F32 * S + sum(numels) * DENORM, planted)
+
+
+def _adam_bars(P, G, M, V, S, ref, clip_on, lr, bc1, bc2, eps, w):
+    """Per-element bars of one row (float64 tensors; ref = (p', m', v', shadow') of the float64 chain) — the first-order propagation of
+    the operation list of `upd` in csrc/optim.hip, one u per fp32 operation weighted by the magnitude of its result (u = U_F32; an
+    operation on values below the normal range adds DENORM instead), the whole multiplied by C_ELEM:
+        clip   c = max_norm / (sqrtf(tot) + 1e-6):  sqrtf, +, /  ->  3 u relative (0 when nothing clips: the bank's sum is exact by the draw)
+        g'     g c                                   e_g = |g'| (e_c + u)
+        m'     b1 m + (1 - b1) g'                    e_m = u |b1 m| + (1 - b1) (e_g + 2 u |g'|) + u |m'|          (1 - b1 and the product round)
+        v'     b2 v + (1 - b2) g' g'                 e_v = u |b2 v| + (1 - b2) (2 |g'| e_g + 3 u g'^2) + u |v'|
+        s      sqrtf(v')                             e_s = e_v / (2 s) + u s
+        q      s / sqrtf(bc2)                        e_q = e_s / sqrt(bc2) + 2.5 u q       (bc2 is handed in fp32: u / 2; sqrtf; the division)
+        d      q + eps                               e_d = e_q + u d
+        r      m' / d                                e_r = e_m / d + |r| e_d / d + u |r|
+        t      (lr / bc1) r                          e_t = step e_r + 3 u |t|              (bc1 handed in fp32, the division, the product)
+        p'     p - t                                 e_p = e_t + u |p'|
+        sh'    sh + w (p' - sh)                      e_sh = w (e_p + u |p' - sh|) + u |w (p' - sh)| + u |sh'|
+    Returns (bar_p, bar_m, bar_v, bar_shadow)."""
+    b1, b2 = _f(BETA1), _f(BETA2)
+    p1, m1, v1, s1 = ref
+    u = U_F32
+    g = G.abs()
+    e_g = g * ((3 * u if clip_on else 0.0) + u) + DENORM
+    e_m = u * (b1 * M).abs() + (1 - b1) * (e_g + 2 * u * g) + u * m1.abs() + DENORM
+    e_v = u * (b2 * V).abs() + (1 - b2) * (2 * g * e_g + 3 * u * g * g) + u * v1.abs() + 4 * DENORM
+    s = v1.sqrt()
+    e_s = torch.minimum(e_v / (2 * s).clamp_min(1e-300), e_v.sqrt()) + u * s            # (sqrt(0 + e) = sqrt(e))
+    q = s / math.sqrt(bc2)
+    e_q = e_s / math.sqrt(bc2) + 2.5 * u * q
+    d = q + eps
+    e_d = e_q + u * d
+    r = m1 / d
+    e_r = e_m / d + r.abs() * e_d / d + u * r.abs()
+    step = lr / bc1
+    e_t = step * e_r + 3 * u * (step * r).abs()
+    e_p = e_t + u * p1.abs()
+    bars = [C_ELEM * e_p, C_ELEM * e_m, C_ELEM * e_v]
+    if S is not None:
+        diff = (p1 - S).abs()
+        bars.append(C_ELEM * (w * (e_p + u * diff) + u * w * diff + u * s1.abs()))
+    else:
+        bars.append(None)
+    return bars
+
+
+ADAM_CHUNK = 32 << 20               # elements of a table that go through one torch.optim.Adam in float64 (the CIFAR table: two passes)
+
+
+def _adam_chunks(numels):
+    out, cur, tot = [], [], 0
+    for r, n in enumerate(numels):
+        if n == 0:
+            continue
+        if cur and tot + n > ADAM_CHUNK:
+            out.append(cur)
+            cur, tot = [], 0
+        cur.append(r)
+        tot += n
+    return out + ([cur] if cur else [])
+
+
+def adam_reference(P, G, M, V, S, clip, k, lr, bc1, bc2, eps, w):
+    """One optimizer step of torch.optim.Adam in float64 on lists of float64 tensors (state handed in), on gradients scaled by `clip`
+    the way clip_grad_norm_ scales them, then the EMA recurrence shadow += w (p - shadow).  Returns [(p', m', v', shadow')].
+    The kernel is HANDED its bias corrections (bc1, bc2: C floats); torch.optim.Adam forms its own, t1 = 1 - b1^k and t2 = 1 - b2^k.
+    Its update (lr' / t1) m / (sqrt(v) / sqrt(t2) + eps') is the handed one, (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps), exactly when
+    eps' = rho eps and lr' = lr rho t1 / bc1 with rho = sqrt(bc2 / t2): torch runs with those (any step k serves)."""
+    t1, t2 = bias_corrections(k)
+    rho = math.sqrt(bc2 / t2)
+    params = [torch.nn.Parameter(p.clone()) for p in P]
+    for q, g in zip(params, G):
+        q.grad = g * clip
+    opt = torch.optim.Adam(params, lr=lr * rho * t1 / bc1, betas=(_f(BETA1), _f(BETA2)), eps=eps * rho)
+    for q, m, v in zip(params, M, V):
+        opt.state[q] = {"step": torch.tensor(float(k - 1)), "exp_avg": m.clone(), "exp_avg_sq": v.clone()}
+    opt.step()
+    out = []
+    for q, s in zip(params, S):
+        p1 = q.detach()
+        out.append((p1, opt.state[q]["exp_avg"], opt.state[q]["exp_avg_sq"], None if s is None else s + w * (p1 - s)))
+    return out
+
+
+def clip_coefficient(bank, max_norm):
+    """min(1, max_norm / (norm + 1e-6)) in float64 from the bank the update is handed (clip_grad_norm_'s coefficient; a NaN norm gives
+    NaN).  Returns (coefficient, whether it clips)."""
+    c = max_norm / (math.sqrt(float(_d(bank).sum())) + 1e-6) if float(_d(bank).sum()) >= 0 else float("nan")
+    return (1.0, False) if c >= 1.0 else (c, True)
+
+
+def _adam_yardstick(p, g, m, v, s, bank, max_norm, lr, bc1, bc2, eps, w):
+    """the same update as a plain fp32 torch composition (torch.optim.Adam's own operation order)"""
+    f = lambda x: torch.tensor(x, dtype=torch.float32, device=p.device)
+    b1, b2 = f(BETA1), f(BETA2)
+    bc1, bc2 = f(bc1), f(bc2)
+    if bank is not None:
+        c = f(max_norm) / (bank.sum().sqrt() + f(1e-6))
+        g = g * torch.where(c >= 1, torch.ones_like(c), c)
+    m1 = b1 * m + (1 - b1) * g
+    v1 = b2 * v + (1 - b2) * g * g
+    p1 = p - (f(lr) / bc1) * (m1 / (v1.sqrt() / bc2.sqrt() + f(eps)))
+    return p1, m1, v1, None if s is None else s + f(w) * (p1 - s)
+
+
+def _adam_check(A, res, before, after, bank, max_norm, lr, bc1, bc2, eps, w):
+    """before[r] = (p, g, m, v, shadow or None) as stored before the launch (fp32 clones; None for an empty row), after[r] = (p, m, v,
+    shadow or None) as they are now.  bank: the 64 floats the update read (None: no clipping).  Scalars: what the kernel was handed."""
+    lr, bc1, bc2, eps, w, max_norm = (_f(x) for x in (lr, bc1, bc2, eps, w, max_norm))
+    k = _step_of(bc2)
+    if max_norm <= 0:
+        bank = None
+    clip, clip_on = (1.0, False) if bank is None else clip_coefficient(bank, max_norm)
+    res.clip = clip
+    if clip_on and math.isfinite(clip) and clip > 0 and not res.nonfinite:
+        # the coefficient torch's own clip_grad_norm_ derives from these gradients: the bank the update is handed must agree with it
+        gs = [torch.nn.Parameter(torch.zeros(1, dtype=torch.float64, device=A.device)) for b in before if b is not None]
+        for q, b in zip(gs, [b for b in before if b is not None]):
+            q.grad = (_d(b[1]) ** 2).sum().sqrt().reshape(1)
+        norm = float(torch.nn.utils.clip_grad_norm_(gs, max_norm))
+        assert abs(max_norm / (norm + 1e-6) / clip - 1) < 2.0 ** -16, "the bank handed to the update is not the gradients' squared norm"
+    for chunk in _adam_chunks([0 if b is None else b[0].numel() for b in before]):
+        B = [before[r] for r in chunk]
+        D = [[_d(t) if t is not None else None for t in b] for b in B]
+        refs = adam_reference([d[0] for d in D], [d[1] for d in D], [d[2] for d in D], [d[3] for d in D], [d[4] for d in D], clip, k, lr, bc1, bc2, eps, w)
+        for r, b, d, ref in zip(chunk, B, D, refs):
+            bars = _adam_bars(d[0], d[1] * clip, d[2], d[3], d[4], ref, clip_on, lr, bc1, bc2, eps, w)
+            yard = _adam_yardstick(*b, bank, max_norm, lr, bc1, bc2, eps, w) if A.yardstick else (None,) * 4
+            for j, nm in enumerate(("p", "m", "v", "shadow")):
+                if after[r][j] is not None:
+                    res.tensors[(r, nm)] = after[r][j].clone()
+                    res.cmp(f"{nm}[{r}]", after[r][j], ref[j], bars[j], yard[j])
+
+
+def _after(numels, slots):
+    return [tuple(None if slots[c][r] is None or n == 0 else _sl(slots[c][r], n) for c in (0, 2, 3, 4)) for r, n in enumerate(numels)]
+
+
+def _before(numels, slots):
+    return [None if n == 0 else tuple(None if slots[c][r] is None else _sl(slots[c][r], n).clone() for c in range(5)) for r, n in enumerate(numels)]
+
+
+def _bank_for(A, numels, slots, tot, spread=True):
+    """Fill the 64-float bank with the squared norm of the drawn gradients: 64 equal lanes whose low six mantissa bits are zero, so
+    that the kernel's fp32 sum of the lanes is exact whatever its order (a kernel that reads lane 0 alone is off by sqrt(64) in the
+    coefficient).  The reference reads the bank back."""
+    S = sum(float((_d(_sl(slots[1][r], n)) ** 2).sum()) for r, n in enumerate(numels) if n)
+    lane = np.float32(S / 64 if spread else S)
+    if spread and np.isfinite(lane):
+        lane = (lane.view(np.uint32) & np.uint32(0xFFFFFFC0)).view(np.float32)
+    tot.t[:64] = float(lane) if spread else 0.0
+    if not spread:
+        tot.t[0] = float(lane)
+
+
+def rep_mt_adam_ema(A, sig, res):
+    """clip_grad_norm_ -> torch.optim.Adam -> EMA over every row of the table, in place.  Reference: adam_reference (torch's own Adam in
+    float64 on the stored values, the betas, lr and eps as the C floats the kernel is handed), with the clip coefficient taken in
+    float64 from the bank the kernel reads; bars: _adam_bars.  The scalars of a signature recorded with hyper_dev are not in it: the
+    replay hands over those of step 1000 (lr 2e-4, ema_w 1e-4, where training spends its life) unless opts say otherwise."""
+    table, n, ptot, max_norm, lr, b1, b2, eps, bc1, bc2, ema_w, phyper = sig
+    rows, opts = table[1], dict(table[2])
+    assert n == len(rows) and _f(b1) == _f(BETA1) and _f(b2) == _f(BETA2)
+    numels, slots = _mt_setup(A, rows, opts)
+    by_value = [lr, b1, b2, eps, bc1, bc2, ema_w]
+    hyper = None
+    if _opt(phyper):
+        bcs = bias_corrections(opts.get("step", 1000))
+        hyper = A.buf("hyper", 4, F32, _mod(phyper)).fill(torch.tensor([opts.get("lr", 2e-4), bcs[0], bcs[1], opts.get("ema_w", 1e-4)],
+                                                                       dtype=torch.float64)).all_in()
+        lr, bc1, bc2, ema_w = (float(x) for x in hyper.t)              # what the kernel reads
+    tot = None
+    if _opt(ptot):
+        tot = A.buf("total_sq", 64, F32, _mod(ptot)).all_in()
+        _bank_for(A, numels, slots, tot)
+    for r, nn in enumerate(numels):
+        for c in range(5):
+            if slots[c][r] is not None:
+                _mark(slots[c][r], nn, read=True, write=c != 1)
+    before = _before(numels, slots)
+    tb = _table_buf(A, _mt_rows_table(rows, slots))
+    A.snapshot()
+    _launch("ddpm_mt_adam_ema", [tb.ptr, n, _ptr(tot), max_norm] + by_value + [_ptr(hyper)])
+    sync()
+    A.check()
+    _adam_check(A, res, before, _after(numels, slots), None if tot is None else tot.t.clone(), max_norm, lr, bc1, bc2, eps, ema_w)
+
+
+def rep_adam_ema_step(A, sig, res):
+    """The single-tensor form of the same update (total_sq[0] is the squared norm): the same reference and bars."""
+    pp, pg, pm, pv, psh, n, ptot, max_norm, lr, b1, b2, eps, bc1, bc2, ema_w = sig
+    cols = tuple((not _opt(p), _mod(p) % 16, SEPARATE) for p in (pp, pg, pm, pv, psh))
+    rows = ((n, cols),)
+    numels, slots = _mt_setup(A, rows, {"g": "loguniform"})
+    tot = None
+    if _opt(ptot):
+        tot = A.buf("total_sq", 1, F32, _mod(ptot)).all_in()
+        tot.t[0] = float((_d(_sl(slots[1][0], n)) ** 2).sum())
+    for c in range(5):
+        if slots[c][0] is not None:
+            _mark(slots[c][0], n, read=True, write=c != 1)
+    before = _before(numels, slots)
+    A.snapshot()
+    _launch("ddpm_adam_ema_step", [_addr(slots[c][0]) for c in range(5)] + [n, _ptr(tot), max_norm, lr, b1, b2, eps, bc1, bc2, ema_w])
+    sync()
+    A.check()
+    bank = None
+    if tot is not None:
+        bank = torch.zeros(64, dtype=torch.float32, device=A.device)
+        bank[0] = tot.t[0]
+    _adam_check(A, res, before, _after(numels, slots), bank, max_norm, lr, bc1, bc2, eps, ema_w)
+
+
+def rep_sumsq_accumulate(A, sig, res):
+    """total_sq[0] += ||g||^2 (csrc/optim.hip sumsq_kernel + sum_partials_kernel: min(1024, ceil(n / 256)) blocks of 256 threads, one
+    running sum a thread, 6 wave levels, a 3-step block sum; then one block over the partials and the add into the prior content).
+    Bound: d u (sum g^2 + |prior|)."""
+    pg, n, ptot, pws = sig
+    g = A.buf("g", n, F32, _mod(pg)).fill(A.randn(n, scale=0.5)).all_in()
+    A.shape("grad", g.t.view(-1, 1))
+    tot = A.buf("total_sq", 1, F32, _mod(ptot)).fill(A.randn(1).abs()).all_in()
+    ws = A.buf("workspace", 1024, F32, _mod(pws))
+    ws.all_out()
+    ws.scratch = True
+    tot.all_out()
+    prior = _d(tot.t).clone()
+    A.snapshot()
+    _launch("ddpm_sumsq_accumulate", [g.ptr, n, tot.ptr, ws.ptr])
+    sync()
+    A.check()
+    nblk = min(1024, -(-n // 256))
+    d = (1 + -(-n // (nblk * 256)) + 6 + 3) + (-(-nblk // 256) + 6 + 3 + 1)
+    S = (_d(g.t) ** 2).sum().reshape(1)
+    res.cmp("total_sq", tot.t, S + prior, d * U_F32 * (S + prior.abs()) + n * DENORM)
+
+
+# ---- layout entries: bit-exact against an indexing reference rounded once to the stored type (bar 0)
+def _unpack_common(A, sig, res, fused):
+    pgp, pgf, table, n, scale = sig[:5]
+    rows, opts = table[1], dict(table[2])
+    assert n == len(rows)
+    cnt = [N * C * RS for _, _, N, C, RS in rows]
+    gp = A.buf("gpack", max(r[0] + c for r, c in zip(rows, cnt)), F32, _mod(pgp))
+    gf = A.buf("gflat", max(r[1] + c for r, c in zip(rows, cnt)), F32, _mod(pgf))
+    gp.fill(A.randn(gp.n))
+    gf.fill(A.randn(gf.n))
+    planted = None
+    if opts.get("g") == "planted":
+        gp.t.zero_()
+
+        def store(r, i, value):                       # element i of the row's destination comes from (n, tap, c) of its source
+            src, _, N, C, RS = rows[r]
+            nc, tap = divmod(i, RS)
+            nn, c = divmod(nc, C)
+            gp.t[src + (nn * RS + tap) * C + c] = value
+        # one sweep of the 64 blocks: 64 * 256 elements, or 64 * 4 wave items of 64 channels x 9 taps in the slab form
+        planted = _planted(cnt, lambda r: 64 * 4 * 64 * 9 if rows[r][4] == 9 and rows[r][3] % 64 == 0 else 64 * 256, store)
+        planted *= _f(scale) ** 2
+    else:
+        for src, c in dict.fromkeys((r[0], c) for r, c in zip(rows, cnt) if c):       # (rows may share a source: transformed once)
+            A.shape("data", gp.t[src:src + c].view(-1, 1))
+    for (src, dst, _, _, _), c in zip(rows, cnt):
+        gp.readable[src:src + c] = True
+        gf.written[dst:dst + c] = True
+    tot = None
+    if fused:
+        ptot, total_floats = sig[5:7]
+        assert total_floats >= 64 + SUMSQ_SLOT_BLOCKS * n
+        tot = A.buf("total_sq", total_floats, F32, _mod(ptot)).fill(A.randn(total_floats))
+        tot.written[:64 + SUMSQ_SLOT_BLOCKS * n] = True
+        tot.result = torch.zeros_like(tot.written)
+        tot.result[:64] = True
+    tb = _table_buf(A, [list(r) for r in rows])
+    A.snapshot()
+    if fused:
+        _launch("ddpm_wgrad_unpack_sumsq", [gp.ptr, gf.ptr, tb.ptr, n, scale, tot.ptr, total_floats])
+    else:
+        _launch("ddpm_wgrad_unpack", [gp.ptr, gf.ptr, tb.ptr, n, scale])
+    sync()
+    A.check()
+    S = torch.zeros((), dtype=torch.float64, device=A.device)
+    its = 0
+    for r, ((src, dst, N, C, RS), c) in enumerate(zip(rows, cnt)):
+        if c == 0:
+            continue
+        ref = (_d(gp.t[src:src + c]).reshape(N, RS, C).transpose(1, 2) * _f(scale)).to(torch.float32).reshape(-1)
+        got = gf.t[dst:dst + c]
+        res.tensors[(r, "gflat")] = got.clone()
+        res.cmp(f"gflat[{r}]", got, _d(ref), torch.zeros(c, dtype=torch.float64, device=A.device))
+        S = S + (_d(got) ** 2).sum()
+        if RS == 9 and C % 64 == 0:
+            its = max(its, 1 + 9 * -(-(N * (C // 64)) // 256))
+        else:
+            its = max(its, 1 + -(-c // (64 * 256)))
+    if fused:
+        d = _sumsq_depth(its, 64 * n)
+        res.depth = d
+        _check_bank(res, "total_sq", tot.t[:64], S, d * U_F32 * S + sum(cnt) * DENORM, planted)
+
+
+def rep_wgrad_unpack(A, sig, res):
+    """gflat[dst + (n C + c) RS + tap] = fl32(scale gpack[src + (n RS + tap) C + c]) for every row {src, dst, N, C, RS} of the table:
+    one fp32 product an element, bit-exact against the float64 product rounded once; nothing outside the rows' destinations changes."""
+    _unpack_common(A, sig, res, False)
+
+
+def rep_wgrad_unpack_sumsq(A, sig, res):
+    """The same pass, and total_sq[0] = the sum of squares of what it wrote (csrc/elementwise.hip wgrad_unpack_kernel: 64 blocks a row;
+    a thread's running sum over ceil(count / (64 * 256)) elements, or in the wave-slab form of the 3x3 rows with C % 64 == 0 nine taps
+    an item over ceil(N (C / 64) / 256) items).  Bound: d u sum g^2 against the float64 sum of the values read back from gflat."""
+    _unpack_common(A, sig, res, True)
+
+
+def rep_pack_weight_multi(A, sig, res):
+    """Both derived layouts of every row {w, w_fwd, w_dgrad, N, C, R | flags, Cp, Np}: w_fwd[n][tap][c] and w_dgrad[c][flipped tap][n],
+    channel pads zero — copies rounded once to the stored type, bit-exact.  Flag 0x100: w_dgrad is the 4 x 4 effective kernel of the
+    Upsample convs, E[P][Q] = sum of up to four flipped taps in fp32, held to c (u_f32 sum |taps| + u_out |E|)."""
+    table, n, dt = sig
+    rows = table[1]
+    assert n == len(rows)
+    es, T = (2 if dt == BF16 else 4), _TD[dt]
+    ext = [_pack_extents(*g, es) for g, _ in rows]
+    ws = _carve(A, "w", [c[0] for _, c in rows], [e[0] // 4 for e in ext], F32)
+    wf = _carve(A, "w_fwd", [c[1] for _, c in rows], [e[1] // es for e in ext], dt)
+    wd = _carve(A, "w_dgrad", [c[2] for _, c in rows], [e[2] // es for e in ext], dt)
+    tab = []
+    for r, ((N, C, Rf, Cp, Np), _) in enumerate(rows):
+        R = Rf & 0xff
+        _sl(ws[r], ext[r][0] // 4).copy_(A.randn(ext[r][0] // 4, scale=1.0 / math.sqrt(C * R * R)))
+        _mark(ws[r], ext[r][0] // 4, read=True)
+        for slot, e in ((wf[r], ext[r][1] // es), (wd[r], ext[r][2] // es)):
+            if slot is not None:
+                _sl(slot, e).copy_(A.randn(e).to(T))
+                _mark(slot, e, write=True)
+        tab.append([_addr(ws[r]), _addr(wf[r], es), _addr(wd[r], es), N, C, Rf, Cp, Np])
+    tb = _table_buf(A, tab)
+    A.snapshot()
+    _launch("ddpm_pack_weight_multi", [tb.ptr, n, dt])
+    sync()
+    A.check()
+    u = U_BF16 if dt == BF16 else U_F32
+    for r, ((N, C, Rf, Cp, Np), _) in enumerate(rows):
+        R, up = Rf & 0xff, bool(Rf & 0x100)
+        w = _d(_sl(ws[r], N * C * R * R)).reshape(N, C, R, R)
+        if wf[r] is not None:
+            ref = w.new_zeros(N, R, R, Cp)
+            ref[..., :C] = w.permute(0, 2, 3, 1)
+            got = _sl(wf[r], ext[r][1] // es)
+            res.tensors[(r, "w_fwd")] = got.clone()
+            res.cmp(f"w_fwd[{r}]", got, _d(ref.reshape(-1).to(T)), torch.zeros(got.numel(), dtype=torch.float64, device=A.device))
+        if wd[r] is None:
+            continue
+        got = _sl(wd[r], ext[r][2] // es)
+        res.tensors[(r, "w_dgrad")] = got.clone()
+        D = w.flip(2, 3)
+        if up:
+            E, mag = w.new_zeros(N, C, 4, 4), w.new_zeros(N, C, 4, 4)
+            for a in range(2):
+                for b in range(2):
+                    E[:, :, a:a + 3, b:b + 3] += D
+                    mag[:, :, a:a + 3, b:b + 3] += D.abs()
+            ref, bar = w.new_zeros(C, 4, 4, Np), w.new_zeros(C, 4, 4, Np)
+            ref[..., :N], bar[..., :N] = E.permute(1, 2, 3, 0), C_GEMM * (U_F32 * mag + u * E.abs()).permute(1, 2, 3, 0)
+            res.cmp(f"w_dgrad4x4[{r}]", got, ref.reshape(-1), bar.reshape(-1))
+        else:
+            ref = w.new_zeros(C, R, R, Np)
+            ref[..., :N] = D.permute(1, 2, 3, 0)
+            res.cmp(f"w_dgrad[{r}]", got, _d(ref.reshape(-1).to(T)), torch.zeros(got.numel(), dtype=torch.float64, device=A.device))
+
+
+def rep_mt_gather(A, sig, res):
+    """dst_i = a_i (+ b_i) for every row {a, b (0 = none), dst, numel}: a copy, or one fp32 addition — the float64 sum rounded once."""
+    table, n = sig
+    rows = table[1]
+    assert n == len(rows)
+    numels = [nn for nn, _ in rows]
+    slots = [_carve(A, nm, [c[i] for _, c in rows], numels, F32) for i, nm in enumerate(("a", "b", "dst"))]
+    for r, nn in enumerate(numels):
+        for c in range(3):
+            if slots[c][r] is not None:
+                _sl(slots[c][r], nn).copy_(A.randn(nn))
+                _mark(slots[c][r], nn, read=c < 2, write=c == 2)
+    tb = _table_buf(A, [[_addr(slots[c][r]) for c in range(3)] + [nn] for r, nn in enumerate(numels)])
+    A.snapshot()
+    _launch("ddpm_mt_gather_f32", [tb.ptr, n])
+    sync()
+    A.check()
+    for r, nn in enumerate(numels):
+        ref = _d(_sl(slots[0][r], nn))
+        if slots[1][r] is not None:
+            ref = ref + _d(_sl(slots[1][r], nn))
+        got = _sl(slots[2][r], nn)
+        res.tensors[(r, "dst")] = got.clone()
+        res.cmp(f"dst[{r}]", got, _d(ref.to(torch.float32)), torch.zeros(nn, dtype=torch.float64, device=A.device))
+
+
 REPLAY = {
+    "ddpm_mt_grad_sumsq": rep_mt_grad_sumsq,
+    "ddpm_mt_adam_ema": rep_mt_adam_ema,
+    "ddpm_sumsq_accumulate": rep_sumsq_accumulate,
+    "ddpm_adam_ema_step": rep_adam_ema_step,
+    "ddpm_wgrad_unpack": rep_wgrad_unpack,
+    "ddpm_wgrad_unpack_sumsq": rep_wgrad_unpack_sumsq,
+    "ddpm_pack_weight_multi": rep_pack_weight_multi,
+    "ddpm_mt_gather_f32": rep_mt_gather,
     "ddpm_conv2d_nhwc": rep_conv2d,
     "ddpm_conv3x3_wgrad_nhwc": rep_conv3x3_wgrad,
     "ddpm_conv3x3_wgrad_up_nhwc": rep_conv3x3_wgrad_up,
@@ -1643,6 +2295,199 @@ EDGE_CHANNELS = [
 ]
 
 
+# ----------------------------------------------------------------------------------------------------------------- the optimizer tail, by hand
+# Hand-written tables of a few tensors each: the smallest shapes at which the tail's kernels can go wrong.  numel 0 (nothing may be
+# written), 1, 3, 4, 5 and 1023 .. 1025 around the float4 body and its scalar tail; one grid sweep of mt_adam_ema_kernel (32 blocks x 256
+# threads x 4) and of mt_sumsq_kernel (16 x 256 x 4) and one element either side; 512 x 512 x 9, the largest tensor of any shipped
+# configuration.  Packings: every tensor its own 16-byte aligned buffer ("sep"); back to back with the trainer's rounding to 4 floats
+# ("r4", what the flat gradient is); 1-float gaps ("g1": most rows misaligned, the scalar path next to the vector one); exactly one of
+# p, g, m, v, shadow at 4, 8 or 12 bytes modulo 16 (misaligned).
+SMALL_NUMELS = (0, 1, 3, 4, 5, 1023, 1024, 1025)
+SWEEP_NUMELS = (32 * 256 * 4 - 1, 32 * 256 * 4, 32 * 256 * 4 + 1, 16 * 256 * 4 - 1, 16 * 256 * 4, 16 * 256 * 4 + 1)
+MIS_NUMELS = (5, 1025, 16 * 256 * 4 + 1)
+LARGEST = 512 * 512 * 9
+_MT_COLS = ("p", "g", "m", "v", "shadow")
+
+
+def _packed_cols(numels, k, pack="sep", mis=None, null=()):
+    """[(numel, k columns)] of a table whose k pointer columns are packed as `pack`; mis = (column, bytes modulo 16); null = {(row,
+    column)} pointers that are null."""
+    rows = []
+    mods = [0] * k
+    for r, n in enumerate(numels):
+        cols = []
+        for c in range(k):
+            if (r, c) in null:
+                cols.append((True, 0, SEPARATE))
+                mods[c] = 0
+                continue
+            last = r + 1 == len(numels) or (r + 1, c) in null
+            if pack == "sep" or last:
+                m = mis[1] if mis and mis[0] == c and pack == "sep" else mods[c]
+                cols.append((False, m, SEPARATE))
+                mods[c] = 0
+            else:
+                gap = 4 if pack == "g1" else 4 * (-n % 4)
+                cols.append((False, mods[c], gap))
+                mods[c] = (mods[c] + 4 * n + gap) % 16
+        rows.append((n, tuple(cols)))
+    return tuple(rows)
+
+
+def _mt_table(numels, pack="sep", mis=None, no_shadow=(), **opts):
+    mis = None if mis is None else (_MT_COLS.index(mis[0]), mis[1])
+    return ("t", _packed_cols(numels, 5, pack, mis, {(r, 4) for r in no_shadow}), tuple(sorted(opts.items())))
+
+
+def _adam_sig(table, k, max_norm=1.0, lr=2e-4, ema_w=1e-4, hyper=False, total=True):
+    """ddpm_mt_adam_ema at optimizer step k; hyper: lr, the bias corrections and ema_w through hyper_dev instead of by value"""
+    bc1, bc2 = bias_corrections(k)
+    table = (table[0], table[1], tuple(sorted(dict(table[2], step=k, **({"lr": lr, "ema_w": ema_w} if hyper else {})).items())))
+    scal = (0.0, BETA1, BETA2, ADAM_EPS, 1.0, 1.0, 0.0) if hyper else (lr, BETA1, BETA2, ADAM_EPS, bc1, bc2, ema_w)
+    return ("ddpm_mt_adam_ema", (table, len(table[1]), _p(null=not total), max_norm) + scal + (_p(null=not hyper),))
+
+
+def _sumsq_sig(table):
+    n = len(table[1])
+    return ("ddpm_mt_grad_sumsq", (table, n, _p(), 64 + SUMSQ_SLOT_BLOCKS * n))
+
+
+def _unpack_table(shapes, **opts):
+    """rows {src, dst, N, C, R*S}: sources 4 floats apart beyond the rounding to 4 (pad floats between segments), destinations rounded
+    to 4 floats like the flat gradient; a shape with a 4th field shares the source of the row before it (fc.bias and conv1.bias)."""
+    rows, so, do = [], 0, 0
+    for sh in shapes:
+        N, C, RS = sh[:3]
+        c = N * C * RS
+        if len(sh) > 3:
+            rows.append((rows[-1][0], do, N, C, RS))
+        else:
+            rows.append((so, do, N, C, RS))
+            so += (c + 3) // 4 * 4 + 4
+        do += (c + 3) // 4 * 4
+    return ("t", tuple(rows), tuple(sorted(opts.items())))
+
+
+def _unpack_sig(table, scale, fused):
+    n = len(table[1])
+    if fused:
+        return ("ddpm_wgrad_unpack_sumsq", (_p(), _p(), table, n, scale, _p(), 64 + SUMSQ_SLOT_BLOCKS * n))
+    return ("ddpm_wgrad_unpack", (_p(), _p(), table, n, scale))
+
+
+# R*S in {1, 9, 16}; C % 64 == 0 (the wave-slab form; 130 x 128 is more than one sweep of its 256 items) and C % 64 != 0 (the gather
+# form; 64 x 96 x 9 is more than one sweep of 16384 elements); the edge-channel shapes Creal / Nreal in {1, 4, 12}; plain segments
+UNPACK_SHAPES = [(130, 128, 9), (5, 64, 9), (64, 96, 9), (8, 40, 16), (1, 20000, 1), (1, 64, 1), (1, 64, 1, "shared"), (64, 1, 9), (64, 4, 9),
+                 (64, 12, 9), (1, 64, 9), (4, 64, 9), (12, 64, 9), (1, 1, 1), (1, 4, 1), (1, 12, 1), (96, 72, 1), (3, 192, 9)]
+UNPACK_SCALES = (1.0, 0.5, 0.125, 1.0 / 3.0)
+
+
+def _pack_sig(shapes, dt, pack="sep"):
+    """rows (N, C, R, up, with w_dgrad); Cp / Np: the channel counts rounded up to the 16-byte vector of dt"""
+    vec = 8 if dt == BF16 else 4
+    geo = [(N, C, R | (0x100 if up else 0), _up(C, vec), _up(N, vec)) for N, C, R, up, _ in shapes]
+    es = 2 if dt == BF16 else 4
+    ptrs, nbytes, mod = [], [], 0
+    for g, sh in zip(geo, shapes):                 # w packed as `pack`; the derived layouts each in a buffer of their own
+        e = _pack_extents(*g, es)
+        nbytes.append(e)
+        ptrs.append((mod, sh[4]))
+        mod = (mod + e[0] + 4) % 16 if pack == "g1" else 0
+    rows = []
+    for r, (g, (m, wd)) in enumerate(zip(geo, ptrs)):
+        wcol = (False, m, 4 if pack == "g1" and r + 1 < len(geo) else SEPARATE)
+        rows.append((g, (wcol, (False, 0, SEPARATE), (not wd, 0, SEPARATE))))
+    return ("ddpm_pack_weight_multi", (("t", tuple(rows), ()), len(rows), dt))
+
+
+# both packs of 3x3, 1x1 and 2x2 kernels; ragged 32-tiles (40 x 72); the edge convs' pads (C or N in {1, 3, 4, 12}); the Upsample convs'
+# 4 x 4 effective dgrad kernel; rows without a dgrad pack
+PACK_SHAPES = [(64, 64, 3, 0, 1), (40, 72, 3, 0, 1), (64, 3, 3, 0, 1), (64, 1, 3, 0, 0), (64, 12, 3, 0, 1), (1, 64, 3, 0, 1), (4, 64, 3, 0, 1),
+               (12, 64, 3, 0, 1), (96, 72, 1, 0, 1), (128, 64, 1, 0, 0), (8, 16, 2, 0, 1), (64, 64, 3, 1, 1), (40, 72, 3, 1, 1)]
+
+
+def _gather_sig(numels, pack="sep", mis=None):
+    """rows {a, b (null on odd rows), dst, numel}: the destinations packed like the rows of the concatenated projection"""
+    null = {(r, 1) for r in range(len(numels)) if r % 2}
+    rows = [(n, (ca, cb, cd)) for (n, (ca, cb)), (_, (cd,)) in zip(_packed_cols(numels, 2, "sep", mis, null), _packed_cols(numels, 1, pack))]
+    return ("ddpm_mt_gather_f32", (("t", tuple(rows), ()), len(rows)))
+
+
+def _single_adam(n, k, mods=(0, 0, 0, 0, 0), shadow=True, total=True, max_norm=1.0, ema_w=1e-4):
+    bc1, bc2 = bias_corrections(k)
+    return ("ddpm_adam_ema_step", tuple(_p(m) for m in mods[:4]) + (_p(mods[4], null=not shadow), n, _p(null=not total), max_norm, 2e-4, BETA1, BETA2,
+                                                                   ADAM_EPS, bc1, bc2, ema_w))
+
+
+TAIL_ALIGNED = _mt_table(MIS_NUMELS, g="loguniform")
+TAIL_MISALIGNED = [_mt_table(MIS_NUMELS, mis=(c, b), g="loguniform") for c in _MT_COLS for b in (4, 8, 12)]
+_QUIET = dict(g="normal", gscale=1e-4)         # a norm of 3e-3, below max_norm = 1: the coefficient is exactly 1
+TAIL = [
+    # ---- the update: steps 1, 2, 1000 and 10^6; ema_w 0.9 and 1e-4; scalars by value and through hyper_dev; both draws of the gradient
+    _adam_sig(_mt_table(SMALL_NUMELS, g="loguniform"), 1, ema_w=0.9),
+    _adam_sig(_mt_table(SMALL_NUMELS, g="loguniform"), 1, ema_w=0.9, hyper=True),
+    _adam_sig(_mt_table(SWEEP_NUMELS, "r4"), 2),
+    _adam_sig(_mt_table(SWEEP_NUMELS, "g1", g="loguniform"), 1000, hyper=True),
+    _adam_sig(_mt_table(SMALL_NUMELS, "r4", no_shadow=(1, 3, 4, 6), g="loguniform"), 10 ** 6, ema_w=0.9),
+    _adam_sig(_mt_table(SMALL_NUMELS, "g1", no_shadow=range(8)), 2),
+    _adam_sig(_mt_table(SMALL_NUMELS, **_QUIET), 1000),
+    _adam_sig(_mt_table(SMALL_NUMELS, **_QUIET), 1000, max_norm=0.0),
+    _adam_sig(_mt_table(SMALL_NUMELS, **_QUIET), 1000, total=False),
+    _adam_sig(_mt_table((LARGEST, 64), "r4"), 1000),
+    _adam_sig(TAIL_ALIGNED, 1, ema_w=0.9),
+] + [_adam_sig(t, 1, ema_w=0.9) for t in TAIL_MISALIGNED] + [
+    # ---- the norm
+    _sumsq_sig(_mt_table(SMALL_NUMELS)),
+    _sumsq_sig(_mt_table(SWEEP_NUMELS, "r4")),
+    _sumsq_sig(_mt_table(SWEEP_NUMELS + SMALL_NUMELS, "g1", g="loguniform")),
+    _sumsq_sig(_mt_table((LARGEST, 64), "r4")),
+] + [_sumsq_sig(_mt_table(MIS_NUMELS, mis=("g", b))) for b in (4, 8, 12)] + [
+    # ---- the single-tensor pair: past the caps of their grids (1024 and 4096 blocks of 256), odd lengths, misaligned, no EMA, no clip
+    ("ddpm_sumsq_accumulate", (_p(), 1, _p(), _p())),
+    ("ddpm_sumsq_accumulate", (_p(4), 1025, _p(8), _p())),
+    ("ddpm_sumsq_accumulate", (_p(), 1024 * 256 + 1, _p(), _p())),
+    _single_adam(5, 1, ema_w=0.9),
+    _single_adam(1025, 2, mods=(4, 8, 12, 0, 4)),
+    _single_adam(1025, 1000, shadow=False),
+    _single_adam(1025, 1000, total=False),
+    _single_adam(1025, 10 ** 6, max_norm=0.0),
+    _single_adam(4096 * 256 + 1, 1000),
+] + [_unpack_sig(_unpack_table(UNPACK_SHAPES), sc, f) for sc in UNPACK_SCALES for f in (False, True)] + [
+    _pack_sig(PACK_SHAPES, BF16), _pack_sig(PACK_SHAPES, F32), _pack_sig(PACK_SHAPES, F32, "g1"), _pack_sig(PACK_SHAPES, BF16, "g1"),
+    _gather_sig((64 * 128, 64, 5, 1, 1025, 32 * 256 * 4 + 1, 0, 3)),
+    _gather_sig((64 * 128, 64, 5, 1, 1025, 32 * 256 * 4 + 1, 0, 3), "g1"),
+    _gather_sig((1025, 1025, 5, 5), mis=(0, 4)),
+    _gather_sig((1025, 1025, 5, 5), mis=(1, 8)),
+]
+# The exact coverage check of the reductions (_planted): not part of hostile_rows(), a profile would undo the draw.
+TAIL_PLANTED = [_sumsq_sig(_mt_table(nm, pk, g="planted")) for nm, pk in ((SMALL_NUMELS, "sep"), (SWEEP_NUMELS, "r4"), (SWEEP_NUMELS, "g1"), ((LARGEST, 64), "r4"),
+                                                                         ((5,), "sep"), ((16 * 256 * 4 + 1, 1025), "sep"))] + \
+               [_sumsq_sig(_mt_table(MIS_NUMELS, mis=("g", b), g="planted")) for b in (4, 8, 12)] + \
+               [_unpack_sig(_unpack_table(sh, g="planted"), sc, True) for sc in (0.5, 2.0) for sh in (UNPACK_SHAPES, UNPACK_SHAPES[2:4], UNPACK_SHAPES[4:9] + UNPACK_SHAPES[:1])]
+
+
+def tail_identities():
+    """[(what, signature a, signature b, columns)]: replays of a and b with the same seed must give the same bits in every row of the
+    named columns.  The scalar path against the aligned run; hyper_dev against by-value scalars; a norm below max_norm (coefficient
+    exactly 1) against no clipping at all; the fused unpack against the plain one."""
+    out = [(f"{_MT_COLS[i // 3]} at {4 * (i % 3 + 1)} bytes modulo 16", _adam_sig(TAIL_ALIGNED, 1, ema_w=0.9), _adam_sig(t, 1, ema_w=0.9), ("p", "m", "v", "shadow"))
+           for i, t in enumerate(TAIL_MISALIGNED)]
+    out.append(("hyper_dev", TAIL[0], TAIL[1], ("p", "m", "v", "shadow")))
+    out.append(("norm below max_norm / max_norm = 0", TAIL[6], TAIL[7], ("p", "m", "v", "shadow")))
+    out.append(("norm below max_norm / total_sq null", TAIL[6], TAIL[8], ("p", "m", "v", "shadow")))
+    for sc in UNPACK_SCALES:
+        out.append((f"fused / plain unpack, scale {sc:g}", _unpack_sig(_unpack_table(UNPACK_SHAPES), sc, False), _unpack_sig(_unpack_table(UNPACK_SHAPES), sc, True), ("gflat",)))
+    return out
+
+
+def assert_same_tensors(a, b, cols, what):
+    keys = [k for k in a.tensors if k[1] in cols]
+    assert keys and set(keys) == {k for k in b.tensors if k[1] in cols}, what
+    for k in keys:
+        assert same_bits(a.tensors[k], b.tensors[k]), f"{what}: {k[1]}[{k[0]}] differs in " \
+            f"{int((a.tensors[k].view(_INT[a.tensors[k].dtype]) != b.tensors[k].view(_INT[b.tensors[k].dtype])).sum())} of {a.tensors[k].numel()} element(s)"
+
+
 # ----------------------------------------------------------------------------------------------------------------- value profiles
 # A profile transforms the data operands after the draw (Arena.shape); the float64 references read the stored values, so they follow.
 # Each transform takes (arena, fp32 values of a [rows][cols] view, geometry keywords) and returns the new values.
@@ -1698,12 +2543,16 @@ def _plant(value):
 
 
 _LINEAR = ("ddpm_conv2d_nhwc", "ddpm_gemm", "ddpm_atb_f32", "ddpm_conv3x3_wgrad_nhwc", "ddpm_conv3x3_wgrad_up_nhwc", "ddpm_conv1x1_wgrad_nhwc",
-           "ddpm_conv2d_wgrad_nhwc", "ddpm_wgrad_reduce", "ddpm_colsum", "ddpm_upsample2x_bwd", "ddpm_add_rows")
+           "ddpm_conv2d_wgrad_nhwc", "ddpm_wgrad_reduce", "ddpm_colsum", "ddpm_upsample2x_bwd", "ddpm_add_rows", "ddpm_wgrad_unpack")
 _GN = ("ddpm_groupnorm_silu_fwd", "ddpm_groupnorm_silu_bwd")
 _SOFT = ("ddpm_softmax_fwd", "ddpm_softmax_bwd", "ddpm_attention_fwd", "ddpm_attention_fwd_lse", "ddpm_attention_bwd")
 _NONFINITE = ("ddpm_conv2d_nhwc", "ddpm_gemm", "ddpm_groupnorm_silu_fwd", "ddpm_softmax_fwd", "ddpm_attention_fwd", "ddpm_attention_fwd_lse",
               "ddpm_mse_fwd", "ddpm_q_sample")
-_NF_ROLES = ("data", "gn_x", "logits", "qkv", "elem")
+_NF_ROLES = ("data", "gn_x", "logits", "qkv", "elem", "grad")
+# the optimizer tail: `grad` is the gradient operand of the norm and of the update (with a NaN gradient and clipping on, the norm and
+# with it every p, m, v and shadow of every row is NaN, as clip_grad_norm_ + Adam make them); the unpack's gpack is `data`
+_OPT = ("ddpm_mt_grad_sumsq", "ddpm_mt_adam_ema", "ddpm_sumsq_accumulate", "ddpm_adam_ema_step")
+_UNPACK = ("ddpm_wgrad_unpack", "ddpm_wgrad_unpack_sumsq")
 # name -> (what it is for, {role: transform}, the entries it applies to).  Roles: data / additive (the linear families: the operand
 # the sum runs over, and bias, row bias, residual and prior content), gn_x / gn_dy / gn_gamma, logits (softmax), qkv, attn_do, silu_x,
 # elem (q_sample's x0, mse's prediction).  Yardstick figures: the worst err/bar of the plain fp32 torch composition over every row
@@ -1711,13 +2560,15 @@ _NF_ROLES = ("data", "gn_x", "logits", "qkv", "elem")
 PROFILES = {
     # linear in the data: every output is exactly 2^+-30 times the plain run's (power-of-two scaling commutes with rounding away from
     # the denormal and overflow ranges).  GroupNorm: x * 2^-30 is the eps-dominated regime (var = 2^-60 << eps), x * 2^30 the opposite.
-    "scaled_up": ("operands 2^30 larger than unity", {"data": _scale(2.0 ** 30), "additive": _scale(2.0 ** 30), "gn_x": _scale(2.0 ** 30)},
-                  _LINEAR + _GN),
+    "scaled_up": ("operands 2^30 larger than unity", {"data": _scale(2.0 ** 30), "additive": _scale(2.0 ** 30), "gn_x": _scale(2.0 ** 30),
+                                                      "grad": _scale(2.0 ** 30)}, _LINEAR + _GN + _OPT + _UNPACK),
     "scaled_down": ("operands 2^-30 of unity; GroupNorm: eps dominates", {"data": _scale(2.0 ** -30), "additive": _scale(2.0 ** -30),
-                                                                          "gn_x": _scale(2.0 ** -30)}, _LINEAR + _GN),
-    "sparse": ("90 % exact zeros: an element whose every term is zero must be exactly zero", {"data": _sparse, "gn_dy": _sparse, "attn_do": _sparse},
+                                                                          "gn_x": _scale(2.0 ** -30), "grad": _scale(2.0 ** -30)},
+                    _LINEAR + _GN + _OPT + _UNPACK),
+    "sparse": ("90 % exact zeros: an element whose every term is zero must be exactly zero",
+               {"data": _sparse, "gn_dy": _sparse, "attn_do": _sparse, "grad": _sparse},
                ("ddpm_conv2d_nhwc", "ddpm_gemm", "ddpm_conv3x3_wgrad_nhwc", "ddpm_conv3x3_wgrad_up_nhwc", "ddpm_conv1x1_wgrad_nhwc",
-                "ddpm_conv2d_wgrad_nhwc", "ddpm_groupnorm_silu_bwd", "ddpm_attention_bwd")),
+                "ddpm_conv2d_wgrad_nhwc", "ddpm_groupnorm_silu_bwd", "ddpm_attention_bwd") + _OPT + _UNPACK),
     # csrc/norm.hip accumulates moments about the group's first element: pixel 0 of the group's first channel at mean + 64 sigma
     "corner_outlier": ("the pivot of the GroupNorm statistics is an outlier", {"gn_x": _corner_outlier(64.0)}, _GN),
     "far_mean": ("GroupNorm input 50 +- 0.1: |mean| >> std", {"gn_x": lambda A, v, **kw: 50.0 + 0.1 * (v - 1.5)}, _GN),
@@ -1730,10 +2581,10 @@ PROFILES = {
     "flat_logits": ("all keys identical: uniform rows", {"logits": lambda A, v, **kw: v[:, :1].expand_as(v).clone(), "qkv": _flat_keys}, _SOFT),
     "offset_logits": ("a common +1e4 on softmax logits; q x 8 for attention", {"logits": lambda A, v, **kw: v + 1.0e4, "qkv": _q_times(8.0)}, _SOFT),
     "nonfinite_nan": ("one NaN in a data operand: exactly what the reference makes non-finite is non-finite",
-                      {r: _plant(float("nan")) for r in _NF_ROLES}, _NONFINITE),
-    "nonfinite_inf": ("one +inf in a data operand", {r: _plant(float("inf")) for r in _NF_ROLES}, _NONFINITE),
+                      {r: _plant(float("nan")) for r in _NF_ROLES}, _NONFINITE + _OPT + _UNPACK),
+    "nonfinite_inf": ("one +inf in a data operand", {r: _plant(float("inf")) for r in _NF_ROLES}, _NONFINITE + _OPT + _UNPACK),
 }
-YARDSTICK = _GN + _SOFT + ("ddpm_silu_fwd", "ddpm_silu_bwd")          # the non-linear families: Result.yard is filled
+YARDSTICK = _GN + _SOFT + ("ddpm_silu_fwd", "ddpm_silu_bwd", "ddpm_mt_adam_ema", "ddpm_adam_ema_step")   # the non-linear families: Result.yard is filled
 # what Result.outputs of a deterministic entry must satisfy bit for bit against the plain run of the same seed
 EXACT_SCALE = {"scaled_up": 2.0 ** 30, "scaled_down": 2.0 ** -30}
 
@@ -1750,6 +2601,8 @@ HOSTILE_FAMILIES = {
     "silu": ("ddpm_silu_fwd", "ddpm_silu_bwd"),
     "diffusion": ("ddpm_q_sample", "ddpm_mse_fwd", "ddpm_mse_bwd", "ddpm_p_sample_step"),
     "misc": ("ddpm_timestep_embedding", "ddpm_gather_rows_f32", "ddpm_weighted_sum_f32"),
+    "optimizer": _OPT,
+    "layout": _UNPACK + ("ddpm_pack_weight_multi", "ddpm_mt_gather_f32"),
 }
 
 
@@ -1783,24 +2636,15 @@ def hostile_replay(sig, device, seed, mode, plain):
 
 
 def hostile_rows():
-    """Every hand-written signature: ODD_GEOMETRY, SYNTHETIC, EXTRA_SMALL and EDGE_CHANNELS, with the index that seeds its replay."""
-    sigs = [s for s, _ in ODD_GEOMETRY] + SYNTHETIC + EXTRA_SMALL + [s for s, _ in EDGE_CHANNELS]
+    """Every hand-written signature: ODD_GEOMETRY, SYNTHETIC, EXTRA_SMALL, EDGE_CHANNELS and TAIL, with the index that seeds its replay."""
+    sigs = [s for s, _ in ODD_GEOMETRY] + SYNTHETIC + EXTRA_SMALL + [s for s, _ in EDGE_CHANNELS] + TAIL      # (appended: the seeds of the rows before stay)
     return list(enumerate(sigs))
 
 
-# Entries a step launches that are not replayed here, the existing test that covers each (tests/test_kernels_gpu.py unless named) and
-# what that test holds it to: [torch] a plain torch reference (Adam + clip_grad_norm_, or a float64 restatement), [exact] a bit-exact
-# copy or integer comparison.
+# Entries a step launches that are not replayed here, the existing test that covers each (tests/test_kernels_gpu.py) and what that test
+# holds it to: [exact] a bit-exact copy or integer comparison.
 COVERED_ELSEWHERE = {
-    "ddpm_mt_adam_ema": "test_fused_adam_ema_matches_torch_adam, test_multi_tensor_update_with_scalars_from_device_memory, "
-                        "test_optimizer_on_nonfinite_overflowing_zero_and_tiny_gradients [torch]",
-    "ddpm_mt_grad_sumsq": "test_multi_tensor_update_with_scalars_from_device_memory, "
-                          "test_optimizer_on_nonfinite_overflowing_zero_and_tiny_gradients [torch]",
-    "ddpm_mt_gather_f32": "test_multi_tensor_gather [exact]",
-    "ddpm_wgrad_unpack": "test_wgrad_unpack_and_fused_norm [exact]",
-    "ddpm_wgrad_unpack_sumsq": "test_wgrad_unpack_and_fused_norm [exact, torch]",
     "ddpm_pack_weight": "test_timestep_embedding_and_layout_kernels [exact]",
-    "ddpm_pack_weight_multi": "test_pack_weight_multi [exact]",
     "ddpm_nchw_to_nhwc": "test_timestep_embedding_and_layout_kernels [exact]",
     "ddpm_gather_i64": "test_diffusion_algebra_kernels [exact]",
     "ddpm_add_i64": "test_diffusion_algebra_kernels [exact]",
@@ -1826,7 +2670,7 @@ def replay(sig, device, seed=0, poison=False, profile=None, yardstick=False):
     res.max_bytes = max((b.nbytes for b in A.bufs), default=0)
     for b in A.bufs:
         if bool(b.written.any()) and not b.scratch:
-            res.outputs[b.name] = (b.t[b.written].clone(), b.atomic)
+            res.outputs[b.name] = (b.t[b.written if b.result is None else b.result].clone(), b.atomic)
     return res
 
 
@@ -1836,17 +2680,30 @@ def same_bits(a, b):
 
 def geometry(sig, offsets=True):
     """The signature without its dropout seed (every dropout layer draws its own seed; the replay draws masks from the recorded one), and
-    with offsets=False also without the pointer offsets (the host check replays each geometry once)."""
+    with offsets=False also without the pointer offsets, those inside a table word included (the host check replays each geometry
+    once; the packings are on the host through the hand-written tables)."""
     name, words = sig
     types = _hip.PROTOTYPES[name]
-    return (name, tuple(0 if t is ctypes.c_ulonglong else (w[0], w[1], w[2] if offsets else 0) if isinstance(w, tuple) else w
-                        for w, t in zip(words, types)))
+    return (name, tuple(0 if t is ctypes.c_ulonglong else (w if offsets else _unplaced(name, w)) if is_table(w) else
+                        (w[0], w[1], w[2] if offsets else 0) if isinstance(w, tuple) else w for w, t in zip(words, types)))
+
+
+def _unplaced(name, table):
+    """the table word without its pointer offsets: every tensor 16-byte aligned in a buffer of its own (descriptor tables hold none)"""
+    if name in ("ddpm_wgrad_unpack", "ddpm_wgrad_unpack_sumsq"):
+        return table
+    return ("t", tuple((head, tuple((null, 0, SEPARATE) for null, _, _ in cols)) for head, cols in table[1]), table[2])
 
 
 def short(sig):
     name, words = sig
-    ws = ",".join(("-" if w[1] else f"@{w[2]}") if isinstance(w, tuple) else (f"{w:g}" if isinstance(w, float) else str(w)) for w in words)
-    return f"{name[5:]}({ws})"
+
+    def word(w):
+        if is_table(w):                    # rows and a checksum of the normalised table (and the options of a hand-written row)
+            import zlib
+            return f"T{len(w[1])}#{zlib.crc32(repr(w[1:]).encode()) & 0xffff:04x}" + "".join(f";{k}={v}" for k, v in w[2] if k != "step")
+        return ("-" if w[1] else f"@{w[2]}") if isinstance(w, tuple) else (f"{w:g}" if isinstance(w, float) else str(w))
+    return f"{name[5:]}({','.join(word(w) for w in words)})"
 
 
 # ----------------------------------------------------------------------------------------------------------------- workloads
@@ -1890,7 +2747,10 @@ def _train_step(cfg, device, B, size, drop=None, dtype=torch.bfloat16):
                             shape=(m.in_channels, H, W), device=torch.device(device), ema_decay=tc["ema_decay"])
     m.train()
     x = torch.rand(B, m.in_channels, H, W, generator=torch.Generator().manual_seed(1)) * 2 - 1
-    return lambda: tr.step(x.to(device), global_steps=1)
+    def run():
+        tr.step(x.to(device), global_steps=1)
+    run.owners = (tr, m)
+    return run
 
 
 def _sample_step(cfg, device, B, size, ddim_steps=None, dtype=torch.bfloat16):
@@ -1911,6 +2771,7 @@ def _sample_step(cfg, device, B, size, ddim_steps=None, dtype=torch.bfloat16):
     def run():
         with torch.no_grad():
             dif.p_sample_step(m, x, t)
+    run.owners = (None, m)
     return run
 
 
@@ -1981,7 +2842,141 @@ def record(monkeypatch, key, device, B=None, size=None):
         sync_dev(device)
     finally:
         monkeypatch.setattr(_hip, "_invoke", rec.inner)
+    resolve_tables(rec, *run.owners)
     return rec
+
+
+def resolve_tables(rec, trainer, unet):
+    """After the workload has ended and the device is synchronised: every table-driven signature gets, in place of its table pointer,
+    the normalised form (normalise_table) of the persistent table that lives at the recorded address — the trainer's fused-update
+    table, the engine's wdesc, pack_table or fc_table.  An address that is none of them fails."""
+    owned = {}
+    fused = getattr(trainer, "_fused", None)
+    eng = getattr(unet, "_eng", None)
+    for owner, attr in ((fused, "table"), (eng, "wdesc"), (eng, "pack_table"), (eng, "fc_table")):
+        t = getattr(owner, attr, None)
+        if t is not None:
+            owned[t.data_ptr()] = (attr, t)
+    sigs = {}
+    for sig in rec.sigs:
+        name, words = sig
+        if name in TABLE_ARG:
+            ti, ni, width = TABLE_ARG[name]
+            addr, n = rec.tables[sig], words[ni]
+            assert addr in owned, f"{name}: the table at the recorded address is none of {[a for a, _ in owned.values()]}"
+            attr, t = owned[addr]
+            assert t.dim() == 2 and t.shape[1] == width and t.shape[0] >= n, f"{name}: {attr} is {tuple(t.shape)}, the launch read {n} rows of {width}"
+            rows = t[:n].cpu().tolist()
+            tw = normalise_table(name, rows, words[2] if name == "ddpm_pack_weight_multi" else None)
+            sig = (name, words[:ti] + (tw,) + words[ti + 1:])
+        sigs.setdefault(sig, None)
+    rec.sigs = sigs
+
+
+def _unpack_depth(rows):
+    """chain length of ddpm_wgrad_unpack_sumsq's bound over a descriptor table (rep_wgrad_unpack_sumsq)"""
+    its = 0
+    for _, _, N, C, RS in rows:
+        if N * C * RS:
+            its = max(its, 1 + 9 * -(-(N * (C // 64)) // 256) if RS == 9 and C % 64 == 0 else 1 + -(-(N * C * RS) // (64 * 256)))
+    return _sumsq_depth(its, 64 * len(rows))
+
+
+def chained_tail(device, dtype, steps=3, seed=0):
+    """Three optimizer steps of the tail on the tables Trainer and UNet build for the reduced network (_reduced: hid 64, multipliers
+    (1, 2, 2), attention on), issued as Trainer.step issues them — ddpm_wgrad_unpack_sumsq over the engine's wdesc into the flat
+    gradient, ddpm_mt_adam_ema over the trainer's table with the scalars in hyper_dev (warm-up LR, clip 1.0, EMA on), ddpm_pack_weight_multi
+    over pack_table, ddpm_mt_gather_f32 over fc_table — on a drawn gpack.  After every step, against float64 (each step's reference starts
+    from the state the kernels left): the flat gradient bit for bit, the norm within its bound, p / m / v / shadow within their bars
+    (_adam_check), both packs of every conv equal to the pack of the fp32 parameters the update left — bit for bit, the 4 x 4 kernels of
+    the Upsample convs within their rounding bar — and the time-bias projection.  Returns [(step, Result)]."""
+    import ddpm_torch
+    _DEVICE[0] = device
+    cfg = _reduced()
+    m = _net(cfg, device, seed=seed, dtype=dtype).train()
+    tc = cfg["train"]
+    opt = torch.optim.Adam(m.parameters(), lr=tc["lr"], betas=(BETA1, BETA2))
+    sched = torch.optim.lr_scheduler.LambdaLR(opt, lr_lambda=lambda t: min((t + 1) / 5000, 1.0))
+    tr = ddpm_torch.Trainer(m, opt, _diffusion(cfg), epochs=1, trainloader=None, scheduler=sched, use_ema=True, grad_norm=1.0,
+                            shape=(m.in_channels, 16, 16), device=torch.device(device), ema_decay=tc["ema_decay"])
+    eng, fused = m.engine(), tr._fused
+    wdesc = eng._wgrad_table()
+    rows = [tuple(r) for r in wdesc.cpu().tolist()]
+    gen = torch.Generator(device=device).manual_seed(seed + 1)
+    gpack = torch.empty(eng.ptotal, dtype=torch.float32, device=device)
+    gflat = torch.full((eng.gtotal,), float("nan"), dtype=torch.float32, device=device)
+    order = tr._fused_param_order()
+    fused.prepare(grad_ptrs=[gflat.data_ptr() + 4 * eng.goff[id(p)] for p in order], stable_grads=True)
+    table = fused.table.cpu().tolist()
+    assert [r[5] for r in table] == [p.numel() for p in order]
+    hyper_dev = torch.zeros(4, dtype=torch.int64, device=device)
+    shadow_of = {id(prm): sh for sh, prm in tr.ema._pairs()}
+    eng._refresh_packs(True)
+    eng._fc_all()
+    out = []
+    for step in range(1, steps + 1):
+        res = Result(("chained_tail", (step,)))
+        A = Arena(device, seed + step)
+        # gradients of very different sizes from tensor to tensor, as a network has them
+        gpack.copy_(torch.randn(eng.ptotal, generator=gen, device=device) * 10.0 ** (-3.0 * torch.rand(eng.ptotal, generator=gen, device=device)))
+        scal = fused.scalars(tr.ema.weight_of_next_update())
+        hyper_dev.view(torch.float32)[:4] = torch.tensor(scal, dtype=torch.float64).to(torch.float32).to(device)
+        lr, bc1, bc2, w = (float(x) for x in hyper_dev.view(torch.float32)[:4])
+        state = [(p.data, opt.state[p]["exp_avg"], opt.state[p]["exp_avg_sq"], shadow_of.get(id(p))) for p in order]
+        state = [tuple(None if t is None else t.reshape(-1) for t in st) for st in state]
+        before = [(p.clone(), None, a.clone(), b.clone(), None if sh is None else sh.clone()) for p, a, b, sh in state]
+        _hip.call("ddpm_wgrad_unpack_sumsq", gpack.data_ptr(), gflat.data_ptr(), wdesc.data_ptr(), wdesc.shape[0], 1.0, fused.total.data_ptr(),
+                  _hip.SUMSQ_FLOATS, _hip.stream() if torch.device(device).type == "cuda" else 0)
+        fused.launch(tr.grad_norm, hyper_dev=hyper_dev.data_ptr(), have_sumsq=True)
+        fused.committed()
+        tr.ema.num_updates += 1
+        sched.step()
+        eng._launch_pack()
+        eng._launch_fc()
+        sync()
+        # ---- the flat gradient and its norm
+        S = torch.zeros((), dtype=torch.float64, device=device)
+        for r, (src, dst, N, C, RS) in enumerate(rows):
+            c = N * C * RS
+            ref = _d(gpack[src:src + c]).reshape(N, RS, C).transpose(1, 2).reshape(-1)
+            res.cmp(f"gflat[{r}]", gflat[dst:dst + c], ref, torch.zeros(c, dtype=torch.float64, device=device))
+            S = S + (ref * ref).sum()
+        d = _unpack_depth(rows)
+        _check_bank(res, "total_sq", fused.total[:64], S, d * U_F32 * S + eng.ptotal * DENORM)
+        # ---- the update
+        before = [(b[0], gflat[eng.goff[id(p)]:eng.goff[id(p)] + p.numel()].clone(), b[2], b[3], b[4]) for b, p in zip(before, order)]
+        _adam_check(A, res, before, state, fused.total[:64].clone(), tr.grad_norm, lr, bc1, bc2, opt.param_groups[0]["eps"], w)
+        # ---- the derived copies: the pack of the fp32 parameters the update left
+        T = _TD[eng.dcode]
+        u = U_BF16 if eng.dcode == BF16 else U_F32
+        for i, cw in enumerate(eng.convs.values()):
+            W = _d(cw.mod.weight.data)
+            N, C, R = cw.N, cw.C, cw.R
+            ref = W.new_zeros(N, R, R, cw.Cp)
+            ref[..., :C] = W.permute(0, 2, 3, 1)
+            res.cmp(f"w_fwd[{i}]", cw.wf, _d(ref.reshape(-1).to(T)), torch.zeros(cw.wf.numel(), dtype=torch.float64, device=device))
+            D = W.flip(2, 3)
+            if cw.up:
+                E, mag = W.new_zeros(N, C, 4, 4), W.new_zeros(N, C, 4, 4)
+                for a in range(2):
+                    for b in range(2):
+                        E[:, :, a:a + 3, b:b + 3] += D
+                        mag[:, :, a:a + 3, b:b + 3] += D.abs()
+                ref, bar = W.new_zeros(C, 4, 4, cw.Np), W.new_zeros(C, 4, 4, cw.Np)
+                ref[..., :N], bar[..., :N] = E.permute(1, 2, 3, 0), C_GEMM * (U_F32 * mag + u * E.abs()).permute(1, 2, 3, 0)
+                res.cmp(f"w_dgrad4x4[{i}]", cw.wd, ref.reshape(-1), bar.reshape(-1))
+            else:
+                ref = W.new_zeros(C, R, R, cw.Np)
+                ref[..., :N] = D.permute(1, 2, 3, 0)
+                res.cmp(f"w_dgrad[{i}]", cw.wd, _d(ref.reshape(-1).to(T)), torch.zeros(cw.wd.numel(), dtype=torch.float64, device=device))
+        # ---- the concatenated time-bias projection
+        for rb in eng.res_blocks:
+            o, c = eng.tb_off[id(rb)], rb.out_channels
+            res.cmp("fc_w", eng.fc_w[o:o + c].reshape(-1), _d(rb.fc.weight.data).reshape(-1), torch.zeros(c * eng.E, dtype=torch.float64, device=device))
+            ref = (_d(rb.fc.bias.data) + _d(rb.conv1.bias.data)).to(torch.float32)
+            res.cmp("fc_b", eng.fc_b[o:o + c], _d(ref), torch.zeros(c, dtype=torch.float64, device=device))
+        out.append((step, res))
+    return out
 
 
 def sync_dev(device):

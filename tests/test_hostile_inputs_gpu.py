@@ -17,7 +17,9 @@ unchanged per-element bars, one test per family x mode:
                   non-finite (the receptive field of a conv over all N channels, the GEMM row, the (sample, group) of a GroupNorm and
                   its statistics, the softmax / attention row, the sample's loss, the element of q_sample), everything else is finite
                   and within its bar.
-tests/test_kernels_gpu.py holds the optimizer kernels to torch on NaN, overflowing, zero and tiny gradients.
+tests/test_kernels_gpu.py holds the optimizer kernels to torch on NaN, overflowing, zero and tiny gradients; the rows of
+launch_replay.TAIL put them, the gradient unpack, the weight packs and the time-bias gather through the same modes here (`grad` is the
+role of the gradient operand: with a NaN gradient and clipping on, every p, m, v and shadow of every row is NaN).
 
 Measured on the MI355X (worst kernel err/bar | the yardstick's, per family x mode; the whole module runs in 6 s, the GPU suite in 4 min):
   conv            poison, scaled_up, scaled_down, sparse, nonfinite_nan, nonfinite_inf: 0.249 each (bit relations hold on every row)
@@ -33,6 +35,9 @@ Measured on the MI355X (worst kernel err/bar | the yardstick's, per family x mod
   softmax         poison 0.249   wide_logits 0.242 | 0.242   flat_logits 0.246 | 0.246   offset_logits 0.249 | 0.249   nonfinite_nan / _inf 0.248
   silu            poison 0.117   saturating 0.137 | 0.114
   diffusion       poison 0.299   nonfinite_nan / _inf 0.228        misc  poison 0.248
+  optimizer       poison 0.125   scaled_up / scaled_down / sparse 0.125 | 0.125   nonfinite_nan 0.124   nonfinite_inf 0.125 (the store of shadow)
+  layout          poison 0.265 (the 4 x 4 dgrad pack, fp32; everything else bit-exact)   scaled_up / scaled_down / sparse 0.023 (the unpack's
+                  norm)   nonfinite_nan / _inf: the planted element and the norm, nothing else
 Profile intensities are the ones launch_replay.PROFILES states (none had to be halved: the yardstick's worst figure on the CPU is 0.373).
 What the rows found when they first ran, and what was done ("Hostile inputs"):
   * GroupNorm forward, corner_outlier: rstd beyond its bar in all eight forms and both dtypes, 2.3 .. 25 bars (y up to 18.7; yardstick

@@ -9,7 +9,20 @@ ddpm_torch._hip._invoke — the geometry list is taken from the step every time 
 distinct signature of a replayed entry is (dropout seeds aside) re-issued once on fresh random inputs (same pitches, pointer offsets
 modulo 256, optional operands, modes, splits and workspaces) and every output element is held to its own error-model bar; the float64
 references run in torch on the GPU, over every image (in slices of images where one pass would need tens of GB).
-Every recorded entry must be either replayed or mapped to the existing test that covers it (launch_replay.COVERED_ELSEWHERE)."""
+Every recorded entry must be either replayed or mapped to the existing test that covers it (launch_replay.COVERED_ELSEWHERE).
+
+The optimizer tail of a training step — ddpm_wgrad_unpack_sumsq, ddpm_mt_adam_ema, ddpm_pack_weight_multi, ddpm_mt_gather_f32 — is
+replayed with the rest on the geometry of the tables the step built (W1: the CIFAR trainer's 304 rows), and at the end of this module
+on hand-written tables (launch_replay.TAIL), planted sums of squares, bit identities and a three-step chain on the real tables.
+Measured on the MI355X, worst |got - ref| / bar per entry over the hand-written rows, the hostile modes and W1 / W14 / W15:
+  ddpm_mt_adam_ema       0.125 (shadow; the yardstick — the same update as a plain fp32 torch composition — 0.125: the final store)
+  ddpm_adam_ema_step     0.125 (yardstick 0.125)
+  ddpm_mt_grad_sumsq     0.044 of d u sum g^2 (d = 24 .. 166)      ddpm_sumsq_accumulate    0.055
+  ddpm_wgrad_unpack      bit-exact at scale 1, 0.5, 0.125, 1/3     ddpm_wgrad_unpack_sumsq  gflat bit-exact, norm 0.023 (d = 39 .. 110)
+  ddpm_pack_weight_multi bit-exact; the 4 x 4 kernels of the Upsample convs 0.249 (bf16) / 0.304 (fp32) of their rounding bar
+  ddpm_mt_gather_f32     bit-exact                                 chained tail: 0.296 (fp32), 0.249 (bf16), both the 4 x 4 kernels
+Every planted sum exact, every identity bit for bit, every second launch bit-equal to the first.  W1's update replays in 0.61 s (1216
+guarded buffers; its float64 reference already runs in two passes, ADAM_CHUNK), the slowest other replay of W1 in 0.30 s."""
 import collections
 import time
 
@@ -122,6 +135,26 @@ def _check_edge_channels(key, rec, variants):
     assert want <= set(variants), f"{key} did not reach variants {sorted(want - set(variants))}"
 
 
+def _check_tail(key, rec, rows, took):
+    """The table-driven launches of the optimizer tail: a training step must have replayed its update, its fused unpack, its weight
+    packs and its time-bias gather on the geometry of the tables it built; W1's update is the CIFAR trainer's own table."""
+    tail = [(s, r) for s, _, r in rows if s[0] in LR.TABLE_ARG]
+    assert all(LR.is_table(s[1][LR.TABLE_ARG[s[0]][0]]) for s, _ in tail)
+    names = {s[0] for s, _ in tail}
+    if "ddpm_mt_adam_ema" in rec.names:
+        assert {"ddpm_mt_adam_ema", "ddpm_wgrad_unpack_sumsq", "ddpm_pack_weight_multi", "ddpm_mt_gather_f32"} <= names, f"{key}: replayed of the tail only {sorted(names)}"
+    for s, r in tail:
+        n_rows = len(s[1][LR.TABLE_ARG[s[0]][0]][1])
+        print(f"{key}: tail {s[0][5:]:<20s} {n_rows:4d} rows  {r.where:<14s} err/bar {r.worst:.3f}  replayed in {took[s]:.2f} s"
+              + ("" if r.depth is None else f"  (chain length {r.depth})"))
+    others = [t for s, t in took.items() if s[0] not in LR.TABLE_ARG]
+    if tail and others:
+        print(f"{key}: slowest tail replay {max(took[s] for s, _ in tail):.2f} s, slowest other replay {max(others):.2f} s")
+    if key == "W1":
+        adam = next(s for s, _ in tail if s[0] == "ddpm_mt_adam_ema")
+        assert len(adam[1][0][1]) >= 300, f"W1: the update's table has {len(adam[1][0][1])} rows"
+
+
 @pytest.mark.parametrize("key", list(LR.WORKLOADS))
 def test_every_launch_of_the_step_matches_float64(key, monkeypatch):
     t0 = time.perf_counter()
@@ -152,13 +185,15 @@ def test_every_launch_of_the_step_matches_float64(key, monkeypatch):
         _check_w17(rec)
     if key in LR.EDGE_CHANNEL_WORKLOADS:
         _check_edge_channels(key, rec, variants)
-    rows, bad, seen = [], [], set()
+    rows, bad, seen, took = [], [], set(), {}
     for i, s in enumerate(rec.sigs):
         if s[0] not in LR.REPLAY or LR.geometry(s) in seen:
             continue
         seen.add(LR.geometry(s))
+        t1 = time.perf_counter()
         r = LR.replay(s, DEV, seed=i)
         torch.cuda.empty_cache()
+        took[s] = time.perf_counter() - t1
         rows.append((s, LR.variant_of(s), r))
         if r.worst > 1.0:
             bad.append(f"{LR.short(s)}: {r.where} err/bar {r.worst:.3g}")
@@ -168,6 +203,7 @@ def test_every_launch_of_the_step_matches_float64(key, monkeypatch):
     print(f"{key}: {len(rec.sigs)} recorded / {len(rows)} replayed signatures, worst err/bar {worst[2].worst:.3f} ({LR.short(worst[0])[:60]}, "
           f"{worst[2].where}), largest operand {biggest[2].max_bytes / 2 ** 30:.2f} GiB ({LR.short(biggest[0])[:60]}), "
           f"peak device memory {torch.cuda.max_memory_allocated() / 1e9:.1f} GB, record + replay {time.perf_counter() - t0:.1f} s")
+    _check_tail(key, rec, rows, took)
     if key == "W13":
         assert biggest[2].max_bytes >= 2 ** 30, f"W13: largest replayed operand {biggest[2].max_bytes} bytes < 1 GiB"
     assert not bad, f"{key}: {len(bad)} signature(s) beyond their bar:\n" + "\n".join(bad)
@@ -200,3 +236,59 @@ def test_synthetic_signatures_match_float64():
         if r.worst > 1.0:
             bad.append(f"{LR.short(s)}: {r.where} err/bar {r.worst:.3g}")
     assert not bad, "\n".join(bad)
+
+
+# ------------------------------------------------------------------------------------------------------------------ the optimizer tail
+TAIL_ENTRIES = sorted({s[0] for s in LR.TAIL})
+
+
+@pytest.mark.parametrize("name", TAIL_ENTRIES)
+def test_tail_rows_match_float64_and_repeat_bit_for_bit(name):
+    """launch_replay.TAIL: hand-written tables of the optimizer tail (numel 0 .. 512 x 512 x 9, every packing and alignment, EMA and
+    clipping on and off, steps 1 .. 10^6, scalars by value and through hyper_dev).  Every output within its bar (the layout entries: bit
+    for bit), nothing outside the rows' tensors touched, and a second launch on the same inputs gives the same bits (no atomics)."""
+    bad = []
+    for i, s in [(i, s) for i, s in enumerate(LR.TAIL) if s[0] == name]:
+        r = LR.replay(s, DEV, seed=i)
+        again = LR.replay(s, DEV, seed=i)
+        print(f"  {LR.short(s)[:120]:<120s} {r.where:<14s} err/bar {r.worst:.3f}" + ("" if r.depth is None else f"  chain {r.depth}"))
+        if r.worst > 1.0:
+            bad.append(f"{LR.short(s)}: {r.where} err/bar {r.worst:.3g}")
+        assert set(r.outputs) == set(again.outputs)
+        for k, (t, _) in r.outputs.items():
+            assert LR.same_bits(t, again.outputs[k][0]), f"{LR.short(s)}: {k} differs between two launches on the same inputs"
+    assert not bad, "\n".join(bad)
+
+
+def test_tail_planted_sums_of_squares_are_exact():
+    """launch_replay.TAIL_PLANTED: gradients that are zero except for distinct powers of two at the first, last and tail elements, either
+    side of one grid sweep, in the first and the last row — total_sq[0] must be the planted sum bit for bit (one element dropped or
+    counted twice changes it), lanes 1..63 zero.  ddpm_mt_grad_sumsq and ddpm_wgrad_unpack_sumsq (power-of-two scale)."""
+    for i, s in enumerate(LR.TAIL_PLANTED):
+        r = LR.replay(s, DEV, seed=i)
+        assert r.worst == 0.0, f"{LR.short(s)}: {r.where} err/bar {r.worst:.3g}"
+
+
+def test_tail_identities_hold_bit_for_bit():
+    """launch_replay.tail_identities: the scalar path (one of p, g, m, v, shadow at 4, 8, 12 bytes modulo 16) against the aligned run,
+    hyper_dev against scalars by value, a norm below max_norm against no clipping, the fused unpack against the plain one."""
+    cache = {}
+
+    def run(sig):
+        if sig not in cache:
+            cache[sig] = LR.replay(sig, DEV, seed=11)
+        return cache[sig]
+    for what, a, b, cols in LR.tail_identities():
+        LR.assert_same_tensors(run(a), run(b), cols, what)
+        if what.startswith("norm below"):
+            assert run(a).clip == 1.0 and a[1][3] == 1.0, "the coefficient of a norm below max_norm is exactly 1"
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+def test_chained_tail_on_the_real_tables_matches_float64(dtype):
+    """launch_replay.chained_tail: three steps of unpack + norm -> Adam / EMA -> re-pack -> time-bias gather on the tables Trainer and
+    UNet build for the reduced network, as Trainer.step issues them."""
+    for step, r in LR.chained_tail(DEV, dtype):
+        print(f"  chained tail, step {step}: worst err/bar {r.worst:.3f} ({r.where}), clip coefficient {r.clip:.4g}")
+        assert r.worst <= 1.0, f"step {step}: {r.where} err/bar {r.worst:.3g}"
+        assert r.clip < 1.0
