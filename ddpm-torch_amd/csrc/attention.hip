@@ -15,7 +15,9 @@
 // softmax normalisation comes from the saved log-sum-exp and whose row-sum term is D[q] = sum_c dO[q,c] O[q,c]).
 // 512 threads = 8 waves as 2 (row halves of 64) x 4 (column tiles, round robin); operand chunks are register-staged one chunk
 // ahead into a double-buffered LDS stage (one barrier per chunk).  Every L <= 256 and C <= 512 with C % 32 == 0, L % 16 == 0
-// goes through here (rows / keys beyond L are masked, loads beyond the tensors return zeros through the buffer descriptor).
+// goes through here (rows / keys beyond L are masked, loads beyond the tensors return zeros through the buffer descriptor);
+// every other token count — more than 256, or no multiple of 8 — goes through attention_stream.hip, which streams the other
+// side of the score matrix in tiles instead of holding a whole row block of it.
 #include "common.h"
 #include <string.h>
 

@@ -1038,23 +1038,29 @@ class _Engine:
         prob = lse = None
         scale = 1.0 / math.sqrt(C)
         flash = self.T == torch.bfloat16 and Lk <= 256 and Lk % 16 == 0 and C <= 512 and C % 32 == 0
-        if not save and not flash and self.T == torch.bfloat16 and Lk % 128 == 0 and C in (128, 256):
+        fused = not save and not flash and self.T == torch.bfloat16 and Lk % 128 == 0 and C in (128, 256)
+        # any other token count in the bf16 mode — more than 256, or no multiple of 8 — streams the keys through LDS with an online softmax
+        # (csrc/attention_stream.hip): no L x L tensor, no L as a memory row.  (L <= 256 with L % 8 == 0 keeps the kernels it had.)
+        stream = (self.T == torch.bfloat16 and not flash and not fused and (Lk > 256 or Lk % 8) and C <= 512 and C % 32 == 0
+                  and Lk * qkv.ld * 2 <= 0x7ffffff0)
+        if fused:
             # inference over more tokens than the kernel below serves: one kernel, the L x L logits / probabilities stay in LDS and
             # registers (unet.py:41-52).  (Up to 256 tokens the training forward — DMA rings, one-butterfly softmax — is the faster
             # one, 27 vs 32 us at B=128, L=256, C=256, and serves inference too.)
             _hip.call("ddpm_attention_fwd", qkv.ptr, qkv.ld, o.ptr, o.ld, B, Lk, C, scale, self.dcode, _hip.stream())
-        elif flash:
+        elif flash or stream:
             # training (and the geometries the kernel above does not serve): same, plus the row log-sum-exp the backward
             # kernels rebuild the probabilities from — no L x L tensor exists in memory
             lse = self._f32(B, Lk) if save else None
-            _hip.call("ddpm_attention_fwd_lse", qkv.ptr, qkv.ld, o.ptr, o.ld, lse.data_ptr() if save else 0, B, Lk, C, scale,
-                      self.dcode, _hip.stream())
+            _hip.call("ddpm_attention_fwd_lse" if flash else "ddpm_attention_stream_fwd", qkv.ptr, qkv.ld, o.ptr, o.ld,
+                      lse.data_ptr() if save else 0, B, Lk, C, scale, self.dcode, _hip.stream())
         else:
             if Lk % self.vec:
-                # (the probability matrix [B][L][L] is an operand of the second product: its rows must be 16-byte multiples.  No shipped
-                #  configuration attends over fewer than 16 tokens; the reference itself has no such limit)
-                raise NotImplementedError(f"attention over {Lk} tokens in the {'bf16' if self.T == torch.bfloat16 else 'fp32'} mode: the token "
-                                          f"count must be a multiple of {self.vec} (use a larger image, or the fp32 mode for multiples of 4)")
+                # (the probability matrix [B][L][L] is an operand of the second product: its rows must be 16-byte multiples.  The bf16
+                #  mode never gets here with C <= 512, C % 32 == 0: its streaming kernels serve any token count)
+                raise NotImplementedError(f"attention over {Lk} tokens in the {'bf16' if self.T == torch.bfloat16 else 'fp32'} mode: this path "
+                                          f"needs a token count that is a multiple of {self.vec} (the bf16 mode attends over any token count "
+                                          f"when the channel count is a multiple of 32 up to 512)")
             q, kk, v = qkv.ptr, qkv.ptr + C * es, qkv.ptr + 2 * C * es
             logits = self._f32(B, Lk, Lk)                       # S = Q K^T / sqrt(C)   (unet.py:46-48)
             ops.gemm(q, 3 * C, bs, 0, kk, 3 * C, bs, 0, logits.data_ptr(), Lk, Lk * Lk, Lk, Lk, C, self.dcode, batch=B,
@@ -1295,8 +1301,9 @@ class _Engine:
         if lse is not None:
             # flash-style: P is rebuilt from q, k and the saved log-sum-exp inside the kernels (dQ; then dK and dV)
             dvec = self._f32(B, Lk)
-            _hip.call("ddpm_attention_bwd", qkv.ptr, qkv.ld, o.ptr, o.ld, do.ptr, do.ld, lse.data_ptr(), dvec.data_ptr(),
-                      dqkv.ptr, dqkv.ld, B, Lk, C, scale, self.dcode, _hip.stream())
+            # (up to 256 tokens in multiples of 16 the forward was ddpm_attention_fwd_lse; every other record with an lse was streamed)
+            _hip.call("ddpm_attention_bwd" if Lk <= 256 and Lk % 16 == 0 else "ddpm_attention_stream_bwd", qkv.ptr, qkv.ld, o.ptr, o.ld,
+                      do.ptr, do.ld, lse.data_ptr(), dvec.data_ptr(), dqkv.ptr, dqkv.ld, B, Lk, C, scale, self.dcode, _hip.stream())
         else:
             dp = self._f32(B, Lk, Lk)                            # dP = dO V^T
             ops.gemm(do.ptr, C, Lk * C, 0, v, 3 * C, bs, 0, dp.data_ptr(), Lk, Lk * Lk, Lk, Lk, C, self.dcode, batch=B, out_mode=1)

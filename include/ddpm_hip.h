@@ -133,6 +133,18 @@ int ddpm_attention_bwd(const void* qkv, long long ld, const void* o, long long o
                        const float* lse, float* dvec, void* dqkv, long long dqkv_ld, int B, int L, int C, float scale,
                        int dtype, void* stream);
 
+/* The same pair at ANY token count (csrc/attention_stream.hip): the other side of the score matrix is streamed through LDS in tiles
+ * with an online softmax, so no L x L object exists and no L is a memory row.  Parameter lists, layouts, null / alignment / pitch rules
+ * and status codes are those of the pair above; lse may be NULL in the forward.  bf16 only (DDPM_ERR_DTYPE); any L >= 1 with
+ * L * ld * 2 bytes within the buffer descriptors' range (0x7ffffff0), C <= 512 with C % 32 == 0 (else DDPM_ERR_SHAPE).  No allocation,
+ * synchronisation or attribute call: safe as the first call inside a stream capture.  The backward uses no atomics and no split
+ * accumulation: a repeated call is bit-identical.  Reads only [B][L][C] of each operand, writes only [B][L][C] of each output. */
+int ddpm_attention_stream_fwd(const void* qkv, long long ld, void* out, long long out_ld, float* lse, int B, int L, int C, float scale,
+                              int dtype, void* stream);
+int ddpm_attention_stream_bwd(const void* qkv, long long ld, const void* o, long long o_ld, const void* d_o, long long do_ld,
+                              const float* lse, float* dvec, void* dqkv, long long dqkv_ld, int B, int L, int C, float scale,
+                              int dtype, void* stream);
+
 /* nn.GroupNorm(32, C, eps=1e-6) -> SiLU -> Dropout(p) (unet.py:18-20,15,81,85-87,139-140; :57 without SiLU):
  *   y = drop(silu((x - mean_g) * rstd_g * gamma_c + beta_c)),  biased variance over (C/G)*HW elements.
  * stats (optional) receives [B][G][2] = (mean, rstd) for the backward.  workspace: ddpm_gn_workspace_floats().
