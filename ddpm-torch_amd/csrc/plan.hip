@@ -40,12 +40,14 @@ typedef int (*thunk_t)(const word_t*);
 template <class... A, size_t... I> inline int invoke(int (*fn)(A...), const word_t* w, std::index_sequence<I...>) {
     return fn(from_word<A>(w[I])...);
 }
-template <class... A> constexpr int arity(int (*)(A...)) { return (int)sizeof...(A); }
+template <class R, class... A> constexpr int arity(R (*)(A...)) { return (int)sizeof...(A); }
 template <class... A> inline int invoke_all(int (*fn)(A...), const word_t* w) { return invoke(fn, w, std::index_sequence_for<A...>{}); }
 
 // what an entry point puts on its stream (always its LAST argument): kernels through the launch wrapper of common.h, something else
-// the wrapper never sees (a memset), or nothing at all (ddpm_stream_order, whose two arguments are both streams)
-enum EntryKind { EP_KERNELS, EP_ENQUEUES, EP_EDGE };
+// the wrapper never sees (a memset), or nothing at all (ddpm_stream_order, whose two arguments are both streams).  EP_SIZING: a
+// workspace-size query that belongs to a launching entry of this table — listed so that ddpm_plan_entry_arity can tell a recorder the
+// argument count it was declared with, never appended to a plan (it enqueues nothing and its value is not a status)
+enum EntryKind { EP_KERNELS, EP_ENQUEUES, EP_EDGE, EP_SIZING };
 
 struct EntryPoint {
     const char* name;
@@ -56,6 +58,7 @@ struct EntryPoint {
 
 #define EP(fn) {#fn, [](const word_t* w) -> int { return invoke_all(&fn, w); }, arity(&fn), EP_KERNELS}
 #define EP_AS(fn, kind) {#fn, [](const word_t* w) -> int { return invoke_all(&fn, w); }, arity(&fn), kind}
+#define EP_SIZE_OF(fn) {#fn, nullptr, arity(&fn), EP_SIZING}
 
 }  // namespace
 
@@ -77,6 +80,7 @@ const EntryPoint kEntryPoints[] = {
     EP(ddpm_mt_adam_ema), EP(ddpm_mt_gather_f32), EP(ddpm_mfma_probe), EP(ddpm_copy_probe), EP(ddpm_dropout_mask), EP_AS(ddpm_stream_order, EP_EDGE), EP_AS(ddpm_fill_zero, EP_ENQUEUES),
     EP(ddpm_toy_time_table), EP(ddpm_toy_decoder_fwd), EP(ddpm_toy_decoder_bwd), EP(ddpm_toy_time_table_bwd),
     EP(ddpm_manifold_kth_f16), EP(ddpm_manifold_cover_f16), EP(ddpm_bpd_terms), EP(ddpm_bpd_finish), EP(ddpm_batch_gather),
+    EP(ddpm_ddim_encode_step), EP(ddpm_slerp), EP_SIZE_OF(ddpm_slerp_workspace_floats),
 };
 constexpr int kNumEntryPoints = (int)(sizeof(kEntryPoints) / sizeof(kEntryPoints[0]));
 
@@ -214,7 +218,7 @@ int ddpm_plan_append(void* plan, const char* entry, const unsigned long long* wo
     Plan* p = static_cast<Plan*>(plan);
     for (int i = 0; i < kNumEntryPoints; ++i) {
         if (std::strcmp(kEntryPoints[i].name, entry) != 0) continue;
-        if (kEntryPoints[i].nargs != n_words) return -DDPM_ERR_SHAPE;
+        if (kEntryPoints[i].nargs != n_words || kEntryPoints[i].kind == EP_SIZING) return -DDPM_ERR_SHAPE;
         Entry e;
         e.thunk = kEntryPoints[i].thunk;
         e.first_word = (int)p->words.size();

@@ -21,7 +21,7 @@ _ERR = {1: "bad shape / divisibility", 2: "unsupported dtype", 3: "misaligned po
 
 P, I, L, F, U = c_void_p, c_int, c_longlong, c_float, c_ulonglong
 
-# name -> argtypes; every function returns int status (0 = OK) except ddpm_gn_workspace_floats and
+# name -> argtypes; every function returns int status (0 = OK) except ddpm_gn_workspace_floats, ddpm_slerp_workspace_floats and
 # the ddpm_*_variant queries / ddpm_wgrad_effective_splits / ddpm_conv3x3_wgrad_splits (plain values).
 PROTOTYPES = {
     "ddpm_conv2d_nhwc": [P, L, P, P, L, P, P, L, P, L] + [I] * 14 + [I, I, I, P, P, I, P],
@@ -96,6 +96,10 @@ PROTOTYPES = {
     "ddpm_manifold_cover_f16": [P, L, I, P, L, I, I, P, P, P, L, P],
     # device-resident training data (csrc/batch.hip; driven by datasets.DeviceLoader)
     "ddpm_batch_gather": [P, I, P, P, P, I, L, I, I, I, I, U, P],
+    # DDIM inversion and latent interpolation (csrc/ddim.hip; driven by ddim.DDIM.encode / ddim.slerp)
+    "ddpm_ddim_encode_step": [P] * 9 + [I, I, I, P],
+    "ddpm_slerp": [P, P, P, P, P, I, I, I, P],
+    "ddpm_slerp_workspace_floats": [I, I],
     # launch plans (csrc/plan.hip; driven by _plan.LaunchPlan)
     "ddpm_stream_order": [P, P],
     "ddpm_fill_zero": [P, L, P],
@@ -109,7 +113,7 @@ PROTOTYPES = {
     "ddpm_plan_failed_entry": [P, P],
     "ddpm_plan_entry_arity": [ctypes.c_char_p],
 }
-RESTYPES = {"ddpm_gn_workspace_floats": c_longlong, "ddpm_plan_create": c_void_p, "ddpm_plan_failed_entry": ctypes.c_char_p}
+RESTYPES = {"ddpm_gn_workspace_floats": c_longlong, "ddpm_slerp_workspace_floats": c_longlong, "ddpm_plan_create": c_void_p, "ddpm_plan_failed_entry": ctypes.c_char_p}
 
 _lib = None
 

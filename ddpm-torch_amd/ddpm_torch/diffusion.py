@@ -340,16 +340,18 @@ class GaussianDiffusion:
             return None
         return [m.engine() for m in denoise_fn.modules() if isinstance(m, UNet)]
 
-    def _graph_entry(self, denoise_fn, shape, device, default_rng, external_z=False, bpd=None):
+    def _graph_entry(self, denoise_fn, shape, device, default_rng, external_z=False, bpd=None, kind=None):
         """Cached captured step for (denoiser, shape), capturing it on first use; None when capture is not possible.
         ``external_z`` (parity tests): the step does not draw its noise, the caller fills the captured ``z`` buffer before every replay.
-        ``bpd``: None for the sampling step, ``(clip_denoised,)`` for the bits/dim evaluation step of ``calc_all_bpd``."""
+        ``bpd``: None for the sampling step, ``(clip_denoised,)`` for the bits/dim evaluation step of ``calc_all_bpd``.
+        ``kind``: None for those two; a tuple naming another step a subclass captures itself (``_capture_kind_step``; ddim.py: the encode and
+        decode steps) — it extends the key, so such a step and a sampling step of the same denoiser and shape never serve each other."""
         cache = self.__dict__.setdefault("_sample_graphs", {})
         engines = self._engines_of(denoise_fn)
         # engine serials: model.to() / .float() / set_compute_dtype() re-create the engine (packed weights, workspaces) — a step
         # captured against the previous one points at freed memory and must never be replayed
         # ... and so is the time-bias table the step gathers from: a sampler with a longer schedule re-allocates it
-        key = (id(denoise_fn), shape, str(device), (default_rng, external_z, bpd), getattr(denoise_fn, "training", None),
+        key = (id(denoise_fn), shape, str(device), (default_rng, external_z, bpd) + ((kind,) if kind is not None else ()), getattr(denoise_fn, "training", None),
                tuple((e.serial, e.T, e.tt.data_ptr() if e.tt_on and e.tt is not None else 0) for e in engines) if engines else None)
         ent = cache.get(key)
         if ent is not None and ent["ref"]() is not denoise_fn:
@@ -359,7 +361,9 @@ class GaussianDiffusion:
             for k in [k for k, v in cache.items() if v["ref"]() is denoise_fn and k[5] and {q[0] for q in k[5]} != live]:
                 cache.pop(k)                                      # entries of this denoiser's earlier engines: dead weight (and dead pointers)
         if ent is None:
-            if bpd is None:
+            if kind is not None:
+                ent = self._capture_kind_step(denoise_fn, shape, device, default_rng, external_z, kind)
+            elif bpd is None:
                 ent = self._capture_sample_step(denoise_fn, shape, device, default_rng, external_z)
             else:
                 ent = self._capture_bpd_step(denoise_fn, shape, device, default_rng, external_z, *bpd)

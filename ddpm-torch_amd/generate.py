@@ -4,6 +4,13 @@ is accepted too), freezes the model and writes ``--total-size`` samples as PNG f
 (ancestral DDPM or ``--use-ddim``).  One process per GPU when ``--num-gpus`` > 1 (independent chains, no exchange).
 
     python generate.py --dataset cifar10 --chkpt-path chkpts/cifar10/cifar10_2040.pt --use-ddim --total-size 50000
+
+Not in the reference (the deterministic sampler run both ways, ddim.py): ``--interpolate K`` writes one K-column grid per pair of latents
+(drawn, or encoded from ``--source``), ``--reconstruct`` writes every ``--source`` image next to its encode -> decode reconstruction and
+prints the error.  Both need ``--use-ddim --eta 0``.
+
+    python generate.py --dataset celeba --use-ddim --interpolate 9 --total-size 16 --seed 0
+    python generate.py --dataset celeba --use-ddim --reconstruct --source faces.pt
 """
 import argparse
 import json
@@ -45,7 +52,28 @@ def parse_args(argv=None):
     add("--num-gpus", default=1, type=int)
     add("--compute", choices=["bf16", "fp32"], default="bf16")
     add("--seed", default=None, type=int, help="seeds x_T AND the per-step noise of every chain (default: nondeterministic, like the reference)")
-    return p.parse_args(argv)
+    add("--interpolate", default=0, type=int, metavar="K", help="write K-step spherical interpolations between pairs of latents (--total-size "
+        "pairs of drawn latents, or the consecutive pairs of --source), one grid picture per pair; needs --use-ddim --eta 0")
+    add("--reconstruct", action="store_true", help="encode every --source image and decode it again; writes input | reconstruction and prints "
+        "the mean squared error per dimension on the [0, 1] scale (Song et al. 2020, Table 2)")
+    add("--source", default="", type=str, help="images for --interpolate / --reconstruct: a tensor file ([N, C, H, W], uint8 or float in [-1, 1]) "
+        "or a folder of pictures at the dataset's resolution")
+    args = p.parse_args(argv)
+    if args.interpolate or args.reconstruct:
+        what = "--interpolate" if args.interpolate else "--reconstruct"
+        if not args.use_ddim or args.eta != 0:
+            p.error(f"{what} runs the deterministic sampler both ways: it requires --use-ddim --eta 0")
+        if args.interpolate and args.reconstruct:
+            p.error("--interpolate and --reconstruct are separate runs")
+        if args.interpolate < 0 or args.interpolate == 1:
+            p.error("--interpolate K needs K >= 2 columns")
+        if args.reconstruct and not args.source:
+            p.error("--reconstruct requires --source")
+        if args.num_gpus > 1:
+            p.error(f"{what} runs on one GPU")
+    elif args.source:
+        p.error("--source is read by --interpolate and --reconstruct only")
+    return args
 
 
 def weights_from(chkpt, prefer_ema):
@@ -127,8 +155,79 @@ def generate(rank, args):
     return out_dir
 
 
+def load_source(path, shape):
+    """``--source`` as float32 [N, C, H, W] in [-1, 1]: a tensor file (uint8 is mapped like the data sets', x / 127.5 - 1; float is taken as
+    it is) or a folder of pictures of exactly the dataset's resolution, in name order."""
+    if os.path.isdir(path):
+        import numpy as np
+        from PIL import Image
+        names = sorted(f for f in os.listdir(path) if f.lower().endswith((".png", ".jpg", ".jpeg", ".bmp")))
+        if not names:
+            raise ValueError(f"--source {path}: no pictures in this folder")
+        imgs = []
+        for f in names:
+            im = Image.open(os.path.join(path, f)).convert("L" if shape[0] == 1 else "RGB")
+            if im.size != (shape[2], shape[1]):
+                raise ValueError(f"--source {os.path.join(path, f)}: {im.size[0]} x {im.size[1]}, the dataset is {shape[2]} x {shape[1]}")
+            arr = torch.from_numpy(np.asarray(im).copy())
+            imgs.append(arr[None] if arr.ndim == 2 else arr.permute(2, 0, 1))
+        x = torch.stack(imgs)
+    else:
+        x = torch.load(path, map_location="cpu")
+        if not torch.is_tensor(x):
+            raise ValueError(f"--source {path}: expected a tensor, got {type(x).__name__}")
+    if x.ndim != 4 or tuple(x.shape[1:]) != tuple(shape):
+        raise ValueError(f"--source {path}: shape {tuple(x.shape)}, expected [N, {shape[0]}, {shape[1]}, {shape[2]}]")
+    return x.float() / 127.5 - 1.0 if x.dtype == torch.uint8 else x.float()
+
+
+def invert(args):
+    """--interpolate / --reconstruct: deterministic file names (interp_00000.png, recon_00000.png, ...), so a seeded run repeats byte for byte."""
+    from ddpm_torch.utils import save_image_grid
+    process, model, device, shape, out_dir = build(args)
+    os.makedirs(out_dir, exist_ok=True)
+    src = load_source(args.source, shape) if args.source else None
+    if args.reconstruct:
+        sq = done = 0
+        for i in range(0, len(src), args.batch_size):
+            x = src[i:i + args.batch_size].to(device)
+            x_rec, _ = process.reconstruct(model, x)
+            sq += float((((x_rec - x) / 2) ** 2).double().sum())
+            for j in range(len(x)):
+                save_image_grid(torch.stack([x[j], x_rec[j]]), os.path.join(out_dir, f"recon_{done + j:05d}.png"), nrow=2)
+            done += len(x)
+        print(f"reconstruction error of {done} images (mean squared error per dimension, [0, 1] scale): {sq / (done * src[0].numel()):.6f}")
+        return out_dir
+    K = args.interpolate
+    pairs = len(src) // 2 if src is not None else args.total_size
+    per_chain = max(1, args.batch_size // K)                   # a chain decodes per_chain * K <= --batch-size rows (one pair at the least)
+    done = chain = 0
+    while done < pairs:
+        p = min(per_chain, pairs - done)
+        if src is not None:
+            ends = src[2 * done:2 * (done + p)].to(device)
+            x = process.interpolate(model, ends[0::2], ends[1::2], num=K, batch_size=args.batch_size)
+        else:
+            rng = torch.Generator(device)
+            if args.seed is not None:
+                rng.manual_seed(args.seed + chain)
+            else:
+                rng.seed()
+            z = torch.randn((2 * p,) + shape, device=device, generator=rng)
+            x = process.interpolate(model, z[:p], z[p:], num=K, encoded=True, batch_size=args.batch_size)
+        for j in range(p):
+            save_image_grid(x[j], os.path.join(out_dir, f"interp_{done + j:05d}.png"), nrow=K)
+        done += p
+        chain += 1
+        print(f"\r{done}/{pairs}", end="", flush=True)
+    print()
+    return out_dir
+
+
 def main(argv=None):
     args = parse_args(argv)
+    if args.interpolate or args.reconstruct:
+        return invert(args)
     if args.num_gpus > 1:
         import torch.multiprocessing as mp
         mp.set_start_method("spawn")

@@ -232,6 +232,35 @@ int ddpm_bpd_finish(const float* x_0, const float* losses, float* prior, float* 
 /* subsequence.gather(0, t) (ddim.py:101) and t += delta (t.fill_ in diffusion.py:172, device-side for graph replay) */
 int ddpm_gather_i64(const long long* idx, const long long* map, long long* out, int B, void* stream);
 int ddpm_add_i64(long long* t, int B, long long delta, void* stream);
+/* DDIM inversion (csrc/ddim.hip; Song et al. 2020 §4.3, eta = 0, eps parameterisation): one step of the sampler's ODE run from data to
+ * noise.  With ab[i] = alphas_bar[subsequence[i]], ab_prev[i] = ab[i-1], ab_prev[0] = 1, step i takes the state from level i-1 to level i on
+ * the network output at the timestep the sampling step i evaluates:
+ *   x_next  = cx[t] * x + ce[t] * model_out        cx = sqrt(ab / ab_prev),  ce = sqrt(1 - ab) - sqrt(ab * (1 - ab_prev) / ab_prev)
+ *   pred_x0 = sqrt_recip_ab_prev[t] * x - sqrt_recip_m1_ab_prev[t] * model_out        (optional: may be NULL; never clipped)
+ * fp32, [B][n], tables of length S, two products and a sum per output, each rounded (no contraction).  ddpm_p_sample_step on the eta = 0
+ * tables, the same t and the same model_out takes x_next back to x: the two share one index convention.  x_next may be x (an element is
+ * read once, then written).  A sample whose t is outside [0, S) is filled with NaN and no other sample is touched.  A sample whose row
+ * bases (x, model_out, x_next, pred_x0 at b * n) are all 16-byte aligned is moved 16 bytes per lane with a scalar tail, any other one
+ * element-wise.  n >= 1.  Status: B, n or S <= 0 (or B > 65535) DDPM_ERR_SHAPE, a pointer that is not a multiple of its element size
+ * DDPM_ERR_ALIGN.  Static LDS only, no atomics, no allocation: capturable as a first call. */
+int ddpm_ddim_encode_step(const float* x, const float* model_out, const long long* t, const float* cx, const float* ce,
+                          const float* sqrt_recip_ab_prev, const float* sqrt_recip_m1_ab_prev, float* x_next, float* pred_x0,
+                          int B, int n, int S, void* stream);
+/* Spherical interpolation of latents (Song et al. 2020 eq. 67), per pair p over the whole flattened sample: a, b [P][n], alpha [K],
+ * out [P][K][n], fp32.
+ *   c = clamp(<a,b> / (|a| |b|), -1, 1),  th = acos(c)
+ *   out[p][k] = w0 * a[p] + w1 * b[p],   (w0, w1) = (sin((1 - alpha[k]) th), sin(alpha[k] th)) / sin(th)
+ * Degenerate rule: when 1 - |c| < 1e-6 (nearly parallel or antiparallel) or c is not finite (a zero operand, an overflowing norm, NaN
+ * in the pair) the weights are the linear ones, (w0, w1) = (1 - alpha[k], alpha[k]).  There is no other special case: NaN in an operand
+ * reaches the outputs through the multiplies, and only those of its own pair.
+ * Two passes, no atomics: pass one writes (<a,b>, |a|^2, |b|^2) of every 2048-element chunk of every pair to ws (summed in double, stored
+ * as a (hi, lo) pair of floats each), pass two adds a pair's chunks up in double in a fixed order, forms the 2 K weights in double and writes out = fma(w0, a, w1 * b) — repeated launches are
+ * bit-identical, and a pair is spread over ceil(n / 2048) workgroups in both passes.  ws: ddpm_slerp_workspace_floats(P, n) floats
+ * (6 * P * ceil(n / 2048); 0 when P or n is 0, -1 when either is negative), overwritten by every call.  16-byte accesses when n % 4 == 0 and
+ * a, b, out are 16-byte aligned, element-wise otherwise.  Status: P, K or n <= 0 (or P > 65535) DDPM_ERR_SHAPE, a pointer that is not a
+ * multiple of 4 DDPM_ERR_ALIGN.  Static LDS only, no allocation: capturable as a first call. */
+int ddpm_slerp(const float* a, const float* b, const float* alpha, float* out, float* ws, int P, int K, int n, void* stream);
+long long ddpm_slerp_workspace_floats(int P, int n);
 /* out[r][:] = table[idx[r]][:], fp32 rows of row_len (% 4 == 0) floats; idx outside [0, table_rows) -> the row is NaN.  Sampling only: every
  * ResidualBlock's time bias fc(act(t_emb)) (unet.py:86, with UNet.embed :122-126,207 in front of it) depends on t alone, so the sampler
  * precomputes the [T][sum Cout] table once per weight version and each step gathers its rows instead of running the embedding MLP. */
