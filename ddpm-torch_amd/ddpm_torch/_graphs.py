@@ -10,11 +10,28 @@ else — ~1000 kernel launches per step — is replayed from a handful of graph 
 All segments share one private memory pool and are always replayed in capture order on one stream, so activations
 allocated in one segment and released in a later one keep their addresses from replay to replay.
 """
+import contextlib
 import gc
 
 import torch
 
-__all__ = ["SegmentedGraph"]
+__all__ = ["SegmentedGraph", "collector_off"]
+
+
+@contextlib.contextmanager
+def collector_off():
+    """Around a capture or a plan recording.  Releasing an allocator pool (an earlier launch plan's, a captured graph's) while
+    allocations are routed to another one trips an internal assertion of the caching allocator — and such owners usually sit in
+    reference cycles (trainer <-> step object), so it is the cyclic collector that frees them, whenever it happens to run.  Collect
+    NOW, then keep the collector off until the scope closes (what torch.cuda.graph() does around a capture, for the same reason)."""
+    gc.collect()
+    gc_was_on = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if gc_was_on:
+            gc.enable()
 
 
 class SegmentedGraph:
@@ -64,16 +81,8 @@ class SegmentedGraph:
         allocator would keep routing allocations to this graph's pool)."""
         self._on_abort = on_abort
         assert not self.segments and self._open is None
-        # (an allocator pool released in the middle of a capture — by the cyclic collector freeing an earlier graph or launch plan —
-        #  trips an internal assertion of the caching allocator: collect first, keep the collector off while capturing)
-        gc.collect()
-        gc_was_on = gc.isenabled()
-        gc.disable()
-        try:
+        with collector_off():
             return self._capture(body)
-        finally:
-            if gc_was_on:
-                gc.enable()
 
     def _capture(self, body):
         torch.cuda.synchronize(self.device)

@@ -4,7 +4,9 @@
 6-7 ms of interpreter + ctypes time per ~9.4 ms GPU step, so a slower host makes the step host-bound; a replayed hipGraph has no host
 cost but its executor serialises the two stream branches.  A plan keeps the eager step exactly as it is — same
 entry points, same arguments, same two ``hipStream_t`` s, RCCL calls issued from the host between segments — and walks it in C:
-one ``ddpm_plan_run`` per segment.
+one ``ddpm_plan_run`` per segment.  A plan only records and replays: whether a step is recorded, replayed or issued eagerly, and when a
+recorded plan is dropped because what it addresses was re-created, is decided in one place, ``_DirectStep.run`` of ``utils/train.py``,
+through ``_PlanForm`` (what a plan bakes in, its back-off) and ``_FormProbe`` (the measurement that chooses among the forms).
 
 Recording: ``LaunchPlan.record(body)`` runs ``body(cut)`` ONCE, eagerly (the recorded step is a real step), while ``_hip.call`` appends a
 copy of every call.  ``cut(fn)`` closes the current segment: ``fn`` (a communicator call) runs now and again at that point of every replay.
@@ -21,12 +23,12 @@ suite checks that a recorded body contains no torch arithmetic).
 """
 import contextlib
 import ctypes
-import gc
 import struct
 
 import torch
 
 from . import _hip
+from ._graphs import collector_off
 
 __all__ = ["LaunchPlan"]
 
@@ -80,21 +82,13 @@ class LaunchPlan:
             scope = torch.cuda.use_mem_pool(self.pool, device=self.device)
         else:
             scope = contextlib.nullcontext()
-        # Releasing an allocator pool (an earlier plan's, a captured graph's) while allocations are routed to another one trips an
-        # internal assertion of the caching allocator — and such owners usually sit in reference cycles (trainer <-> step object), so
-        # it is the cyclic collector that frees them, whenever it happens to run.  Collect NOW, then keep the collector off for the
-        # duration of the recording (what torch.cuda.graph() does around a capture, for the same reason).
-        gc.collect()
-        gc_was_on = gc.isenabled()
-        gc.disable()
-        prev = _hip.record_into(self)
-        try:
-            with scope:
-                body(self.cut)
-        finally:
-            _hip.record_into(prev)
-            if gc_was_on:
-                gc.enable()
+        with collector_off():
+            prev = _hip.record_into(self)
+            try:
+                with scope:
+                    body(self.cut)
+            finally:
+                _hip.record_into(prev)
         if on_gpu:
             try:
                 # The recorded addresses stay valid only while the private pool keeps every block the body allocated and released

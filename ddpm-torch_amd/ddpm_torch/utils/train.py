@@ -369,10 +369,184 @@ def _end_generator_capture(gen, device):
         warnings.warn(f"could not return the training generator to eager use after the failed capture ({type(e).__name__}: {e})")
 
 
+# ========================================================================================== the forms of the direct step
+class _EagerForm:
+    """Every launch issued from Python (~7 ms of host time per step: on a slow or busy host that is the bound).  The trivial member of
+    the family below: it bakes nothing in, so it is never stale, has nothing to build and cannot fail."""
+    kind, built, failed = "eager", True, False
+
+    def usable(self, step):
+        return True
+
+    def stale(self, ident, stream):
+        return False
+
+    def drop(self):
+        pass
+
+    def replay(self, step):
+        step.body()
+        step._warm = step.unet.engine().serial
+
+
+class _BakedForm:
+    """A form that replays what it ``built`` from one pass over ``step.body``: raw device addresses that were current at that moment.
+    ``baked`` is their identity (``_DirectStep._identity``); ``_DirectStep.run`` drops ``built`` before it could be replayed once that
+    moved.  ``build`` returns whether building ran the step and leaves ``built`` None when it could not be had (then ``failed``)."""
+
+    def __init__(self):
+        self.built = self.baked = None
+        self.failed = False
+
+    def stale(self, ident, stream):
+        return self.built is not None and self.baked != ident
+
+    def drop(self):
+        self.built = self.baked = None
+
+    def expire(self, step):
+        """``built`` went stale: capture / record again (or run eagerly) instead of replaying."""
+        self.drop()
+
+    def give_up(self, step):
+        """Not to be had here: no longer a candidate, the probe decides among the other forms."""
+        self.failed = True
+        self.drop()
+        step.probe.forget(self.kind)
+
+
+class _PlanForm(_BakedForm):
+    """The same launches on the same two streams, walked by ddpm_plan_run in C (csrc/plan.hip): eager semantics, no interpreter."""
+    kind = "plan"
+
+    def __init__(self):
+        super().__init__()
+        self.stale_count = 0                 # how often a recorded plan had to be dropped because what it baked in moved
+
+    def usable(self, step):
+        # loss_target of model_mean_type "mean" gathers its coefficients with torch ops: invisible to a plan.  (Host-emulated runs:
+        # only when asked for.)
+        return not self.failed and step.tr.diffusion.model_mean_type in ("eps", "x_0") and (step.x0.is_cuda or _TRAIN_GRAPH == "plan")
+
+    def stale(self, ident, stream):          # a plan also holds the stream handle it was recorded on
+        return self.built is not None and self.baked != (ident, stream)
+
+    def expire(self, step):
+        # Back-off (ADVICE r5): a plan that keeps going stale (stream handle or identity churn) would be re-recorded every step — an
+        # eager run + ~500 ctypes appends + a new MemPool each time — and an auto-probe waiting for plan samples would never settle.
+        self.drop()
+        self.stale_count += 1
+        step.probe.phase = None              # (a probe sample that spans a re-recording is not a sample)
+        if self.stale_count >= 4:
+            warnings.warn("the launch plan of the training step went stale 4 times (baked addresses or the stream keep changing); running it eagerly")
+            self.give_up(step)
+
+    def build(self, step):
+        # recording IS a step: the body runs eagerly once more while every call is copied into the plan
+        step.draw()
+        plan = LaunchPlan(step.x0.device)
+        plan.record(lambda cut: step.body(cut, draw=False))              # (an exception of the body itself propagates, as it would eagerly)
+        if plan.build_error is None:
+            self.built, self.baked = plan, (step._identity(), _hip.stream())
+        else:                                                            # the step is done; only its replays are not to be had
+            warnings.warn(f"the training step could not be turned into a launch plan ({plan.build_error}); running it eagerly")
+            self.give_up(step)
+        return True
+
+    def replay(self, step):
+        step.draw()
+        self.built.replay()
+
+
+class _GraphForm(_BakedForm):
+    """hipGraph replay (_graphs.SegmentedGraph): no host cost either, but the executor overlaps the two stream branches less well."""
+    kind = "graph"
+
+    def usable(self, step):
+        return step.x0.is_cuda and not self.failed and step.tr.input_source is None
+
+    def build(self, step):
+        tr, eng = step.tr, step.unet.engine()
+        g = SegmentedGraph(step.x0.device)
+        g.register_generator(tr.generator)
+        try:
+            self.built = g.capture(step.body, on_abort=eng.join_forked_streams)
+            self.baked = step._identity()
+        except Exception as e:                        # capture not possible here: keep training without it
+            warnings.warn(f"hipGraph capture of the training step failed ({type(e).__name__}: {e}); running it eagerly")
+            torch.cuda.synchronize()
+            del g
+            _end_generator_capture(tr.generator, step.x0.device)
+            self.give_up(step)
+        return False                                  # (a capture executes nothing: the step is still to be issued)
+
+    def replay(self, step):
+        self.built.replay()
+
+
+class _FormProbe:
+    """Auto mode: which form of the step is fastest HERE?  Each candidate is timed the way it will run — launches pipelined, the loss
+    read back a step late — over PROBE consecutive steps bracketed by device synchronisations; ``times`` holds seconds per step."""
+    PROBE = 4
+    FORMS = ("plan", "eager", "graph")          # order of preference among forms that measure within 2 % of the fastest
+
+    def __init__(self, on_gpu):
+        self.on_gpu = on_gpu
+        self.times, self.choice, self.phase = {}, None, None
+
+    def undecided(self):
+        return _TRAIN_GRAPH == "auto" and self.choice is None
+
+    def next(self, step):
+        """The form the next step takes: the first candidate still to be measured, then the choice."""
+        forms = step._candidates()
+        if self.choice is None:
+            unmeasured = [f for f in forms if f not in self.times]
+            if unmeasured:
+                return unmeasured[0]
+            self.decide(step)
+        return self.choice if self.choice in forms else "eager"
+
+    def decide(self, step):
+        best = min(self.times.values())
+        self.choice = next(f for f in self.FORMS if f in self.times and self.times[f] <= 1.02 * best)
+        for form in step.forms.values():        # the forms that lost own a private allocator pool with a full set of the step's
+            if form.kind != self.choice:        # activations each: give that memory back
+                form.drop()
+
+    def begin(self, kind, first, built):
+        """Before a step is issued as ``kind``.  Returns whether the step counts as a sample (``end`` is then called after it): not the
+        first call (lazy initialisation), not one that paid for a capture / recording, none at all on a host-emulated run."""
+        if self.undecided() and not self.on_gpu:
+            self.choice = "eager"                           # (nothing to measure)
+        if self.undecided() and not first and not built and kind not in self.times and self.phase is None:
+            torch.cuda.synchronize()
+            self.phase = [kind, 0, time.perf_counter()]
+        return not first and not built
+
+    def end(self, kind, step):
+        ph = self.phase
+        if ph is None or ph[0] != kind:
+            return
+        ph[1] += 1
+        if ph[1] == self.PROBE:
+            torch.cuda.synchronize()
+            self.times[kind] = (time.perf_counter() - ph[2]) / self.PROBE
+            self.phase = None
+            if all(f in self.times for f in step._candidates()):
+                self.decide(step)
+
+    def forget(self, kind):
+        """``kind`` failed: its measurement and a choice of it are void."""
+        self.times.pop(kind, None)
+        if self.choice == kind:
+            self.choice = None
+
+
 # ========================================================================================== the direct / captured step
 class _DirectStep:
     """State of the autograd-free training step for ONE input shape: persistent buffers, the pointer table of the fused
-    update over the engine's flat gradient buffer, and (on the GPU) the captured graphs."""
+    update over the engine's flat gradient buffer, the forms its body is re-issued in and the probe that chooses among them."""
 
     def __init__(self, trainer, unet, shape):
         self.tr, self.unet = trainer, unet
@@ -391,18 +565,20 @@ class _DirectStep:
         self.hyper_host = [self._pinned(torch.zeros(4, dtype=torch.int64)) for _ in range(4)]
         self.grad_ptrs = None
         self.calls = 0
-        self.graph = None
-        self.graph_failed = False
-        self.plan = None                     # _plan.LaunchPlan of this step (recorded once, replayed from C)
-        self.plan_failed = False
-        self.plan_stale = 0                  # how often a recorded plan had to be dropped because what it baked in moved
-        self._plan_baked = None
+        self.forms = {f.kind: f for f in (_EagerForm(), _PlanForm(), _GraphForm())}     # in probing order
+        self.probe = _FormProbe(on_gpu=self.x0.is_cuda)
         self.captures = 0                    # graph captures + plan recordings so far (bench.py asserts none happens inside a timed region)
-        self._baked = None                   # identity of everything whose ADDRESS the captured graph holds (see _identity)
         self._warm = None                    # serial of the engine that has run an EAGER step here (lazy tables / slabs / workspaces exist)
-        # auto mode: wall times (Trainer.step reports them) of a few eager and a few replayed steps decide which one stays
-        self.times = {}                      # auto mode: seconds per step of the "eager" / "graph" probe phases
-        self.last_kind, self.choice, self._phase = None, None, None
+        self.last_kind = None                # the form the latest step was issued in
+
+    # what bench.py, the tests and scripts/ read: the state lives in the form objects and in the probe
+    graph = property(lambda self: self.forms["graph"].built)
+    plan = property(lambda self: self.forms["plan"].built)             # (recorded once, replayed from C)
+    graph_failed = property(lambda self: self.forms["graph"].failed)
+    plan_failed = property(lambda self: self.forms["plan"].failed)
+    plan_stale = property(lambda self: self.forms["plan"].stale_count)
+    choice = property(lambda self: self.probe.choice)
+    times = property(lambda self: self.probe.times)
 
     @staticmethod
     def _pinned(t):
@@ -450,26 +626,9 @@ class _DirectStep:
         tr._fused.launch(tr.grad_norm, hyper_dev=self.hyper_dev.data_ptr(), have_sumsq=clip)
         eng.refresh_unconditionally()                                          # the next forward reads the re-derived copies
 
-    PROBE = 4
-    FORMS = ("plan", "eager", "graph")          # order of preference among forms that measure within 2 % of the fastest
-
-    # ---- auto mode: which form of the step is fastest HERE?  Each is timed the way it will run — launches pipelined, the loss read
-    # back a step late — over PROBE consecutive steps bracketed by device synchronisations:
-    #   eager  every launch issued from Python: ~7 ms of host time per step (on a slow or busy host that is the bound);
-    #   plan   the same launches on the same two streams, walked by ddpm_plan_run in C (csrc/plan.hip): eager semantics, no interpreter;
-    #   graph  hipGraph replay: no host cost either, but the executor overlaps the two stream branches less well.
     def _available(self):
         """Forms this step can take here, in probing order."""
-        forms = ["eager"]
-        if self._plan_ok() and (self.x0.is_cuda or _TRAIN_GRAPH == "plan"):     # (host-emulated runs: only when asked for)
-            forms.append("plan")
-        if self.x0.is_cuda and not self.graph_failed and self.tr.input_source is None:
-            forms.append("graph")
-        return forms
-
-    def _plan_ok(self):
-        # loss_target of model_mean_type "mean" gathers its coefficients with torch ops: invisible to a plan
-        return not self.plan_failed and self.tr.diffusion.model_mean_type in ("eps", "x_0")
+        return [kind for kind, form in self.forms.items() if form.usable(self)]
 
     def _candidates(self):
         """Forms the auto-probe measures.  With a process group the hipGraph form is not a candidate: between its segments sit the
@@ -482,66 +641,17 @@ class _DirectStep:
         return forms
 
     def _form(self):
-        """The form the NEXT step takes."""
-        forms = self._available()
-        if _TRAIN_GRAPH != "auto":
-            want = {False: "eager", True: "graph", "plan": "plan"}[_TRAIN_GRAPH]
-            return want if want in forms else "eager"
-        forms = self._candidates()
-        if self.choice is not None:
-            return self.choice if self.choice in forms else "eager"
-        for f in forms:
-            if f not in self.times:
-                return f
-        self._decide()
-        return self.choice
-
-    def _decide(self):
-        best = min(self.times.values())
-        self.choice = next(f for f in self.FORMS if f in self.times and self.times[f] <= 1.02 * best)
-        # the forms that lost own a private allocator pool with a full set of the step's activations each: give that memory back
-        if self.choice != "graph":
-            self.graph = None
-        if self.choice != "plan":
-            self.plan = None
-
-    def _wants_graph(self):
-        return self._form() == "graph"
-
-    def _probe_begin(self, kind):
-        if _TRAIN_GRAPH == "auto" and self.choice is None and not self.x0.is_cuda:
-            self.choice = "eager"                           # (host-emulated runs: nothing to measure)
-        if _TRAIN_GRAPH == "auto" and self.choice is None and kind not in self.times and self._phase is None:
-            torch.cuda.synchronize()
-            self._phase = [kind, 0, time.perf_counter()]
-
-    def _probe_end(self, kind):
-        ph = self._phase
-        if ph is None or ph[0] != kind:
-            return
-        ph[1] += 1
-        if ph[1] == self.PROBE:
-            torch.cuda.synchronize()
-            self.times[kind] = (time.perf_counter() - ph[2]) / self.PROBE
-            self._phase = None
-            if all(f in self.times for f in self._candidates()):
-                self._decide()
-
-    def observe(self, seconds):
-        """Kept for callers of the earlier interface: the probe now times whole phases itself."""
+        """The form the NEXT step takes (once this engine is warm): the forced one where it is available, else the probe's."""
+        if _TRAIN_GRAPH == "auto":
+            return self.probe.next(self)
+        want = {False: "eager", True: "graph", "plan": "plan"}[_TRAIN_GRAPH]
+        return want if want in self._available() else "eager"
 
     def settled(self):
         """True once the form of the step (eager launches, launch plan or graph replay) is final and recorded / captured."""
         if not self.x0.is_cuda:
             return True
-        if _TRAIN_GRAPH == "auto" and self.choice is None:
-            return False
-        form = self._form()
-        if form == "graph":
-            return self.graph is not None
-        if form == "plan":
-            return self.plan is not None
-        return True
+        return not self.probe.undecided() and self.forms[self._form()].built is not None
 
     def _identity(self):
         """Everything a captured or recorded step addresses by a raw pointer baked into its kernel arguments and that can be RE-CREATED
@@ -554,6 +664,7 @@ class _DirectStep:
 
     def run(self, x):
         tr, eng = self.tr, self.unet.engine()
+        # 1. stage the inputs
         self.x0.copy_(x, non_blocking=True)
         eng.ensure_fresh(need_dgrad=True)                                      # external writes since the last step (load_state_dict, EMA swap)
         if self.grad_ptrs is None:
@@ -561,84 +672,36 @@ class _DirectStep:
         params = tr._fused.prepare(grad_ptrs=self.grad_ptrs, stable_grads=True)
         assert len(params) == len(eng.params)
         self._write_hyper()
-        ident = None
+        # 2. drop what went stale — the ONLY place identities are compared: after it a form is built from the current addresses, or not built
         if self.graph is not None or self.plan is not None:
-            ident = self._identity()
-            if self.graph is not None and self._baked != ident:
-                self.graph = None                               # stale addresses: capture again (or run eagerly) instead of replaying
-            if self.plan is not None and self._plan_baked != (ident, _hip.stream()):
-                self.plan = None                                # ... and a plan also holds the stream handle it was recorded on
-                # Back-off: a plan that keeps going stale (stream handle or identity churn) would be re-recorded every step — an
-                # eager run + ~500 ctypes appends + a new MemPool each time — and an auto-probe waiting for plan samples would never settle.
-                self.plan_stale += 1
-                self._phase = None                              # (a probe sample that spans a re-recording is not a sample)
-                if self.plan_stale >= 4:
-                    warnings.warn("the launch plan of the training step went stale 4 times (baked addresses or the stream keep changing); running it eagerly")
-                    self.plan_failed = True                      # (no longer a candidate: the probe decides among the other forms)
-                    self.times.pop("plan", None)
-                    if self.choice == "plan":
-                        self.choice = None
-        # capture / record only what has run eagerly once with THIS engine: its first backward builds descriptor tables with host ->
-        # device copies (illegal under stream capture, invisible to a plan) and allocates the persistent slabs / staging buffers
+            ident, stream = self._identity(), _hip.stream()
+            for f in self.forms.values():
+                if f.stale(ident, stream):
+                    f.expire(self)
+        # 3. pick the form.  Capture / record only what has run eagerly once with THIS engine: its first backward builds descriptor tables
+        # with host -> device copies (illegal under stream capture, invisible to a plan) and allocates the persistent slabs / staging buffers
         warm = self._warm == eng.serial and not (self.x0.is_cuda and torch.cuda.is_current_stream_capturing())
-        form = self._form() if warm else "eager"
+        form = self.forms[self._form() if warm else "eager"]
         self.last_kind = None
-        fresh = False                                           # this step paid for a capture / recording: not a probe sample
-        if form == "graph" and self.graph is None:
-            g = SegmentedGraph(self.x0.device)
-            g.register_generator(tr.generator)
-            try:
-                self.graph = g.capture(self.body, on_abort=eng.join_forked_streams)
+        # 4. build if needed.  A plan recording IS the step; a graph capture executes nothing (and one that failed leaves the eager form)
+        built_now = ran = False
+        if form.built is None:
+            built_now, ran = True, form.build(self)
+            if form.built is not None:
                 self.captures += 1
-                self._baked = self._identity()
-            except Exception as e:                        # capture not possible here: keep training without it
-                warnings.warn(f"hipGraph capture of the training step failed ({type(e).__name__}: {e}); running it eagerly")
-                torch.cuda.synchronize()
-                del g
-                _end_generator_capture(tr.generator, self.x0.device)
-                self.graph_failed, self.graph = True, None
-                if self.choice == "graph":
-                    self.choice = None
-                    self.times.pop("graph", None)
-                form = "eager"
-            fresh = True
-        if form == "plan" and self.plan is None:
-            # recording IS a step: the body runs eagerly once more while every call is copied into the plan
-            self.draw()
-            plan = LaunchPlan(self.x0.device)
-            plan.record(lambda cut: self.body(cut, draw=False))          # (an exception of the body itself propagates, as it would eagerly)
+            elif not ran:
+                form = self.forms["eager"]
+        # 5. issue: ``form.built`` was built, and found current in 2., or it is not replayed
+        if ran:
             self.last_kind = "eager"
-            if plan.build_error is None:
-                self.plan = plan
-                self.captures += 1
-                self._plan_baked = (self._identity(), _hip.stream())
-            else:                                                        # the step is done; only its replays are not to be had
-                warnings.warn(f"the training step could not be turned into a launch plan ({plan.build_error}); running it eagerly")
-                self.plan_failed = True
-                if self.choice == "plan":
-                    self.choice = None
-                    self.times.pop("plan", None)
-        elif form == "plan":
-            self._probe_begin("plan")
-            self.draw()
-            self.plan.replay()
-            self.last_kind = "plan"
-            self._probe_end("plan")
-        elif form == "graph" and self.graph is not None:
-            if not fresh:
-                self._probe_begin("graph")
-            self.graph.replay()
-            self.last_kind = "graph"
-            if not fresh:
-                self._probe_end("graph")
         else:
-            if self.calls >= 1 and not fresh:
-                self._probe_begin("eager")                  # (nor is the very first step: lazy initialisation)
-            self.body()
-            self.last_kind = "eager"
-            self._warm = eng.serial
-            if self.calls >= 1 and not fresh:
-                self._probe_end("eager")
+            assert form.built is not None
+            sample = self.probe.begin(form.kind, first=self.calls == 0, built=built_now)
+            form.replay(self)
+            self.last_kind = form.kind
+            if sample:
+                self.probe.end(form.kind, self)
+        # 6. book-keep
         self.calls += 1
         tr._fused.committed()
         eng.mark_fresh(bumped=True)
@@ -747,16 +810,13 @@ class Trainer:
         return m
 
     def step(self, x, global_steps=1):
-        t_begin = time.perf_counter()
         x = x.to(self.device)
         unet = self._direct_unet() if os.environ.get("DDPM_TORCH_AMD_DIRECT_STEP", "1") != "0" else None
-        direct = None
         if unet is not None and x.dtype == torch.float32:
             key = (tuple(x.shape), bool(unet.training))
             if key not in self._direct:
                 self._direct[key] = _DirectStep(self, unet, key[0])
-            direct = self._direct[key]
-            loss = direct.run(x).clone()
+            loss = self._direct[key].run(x).clone()
             if self._ema_on:
                 self.ema.num_updates += 1
             self.scheduler.step()
@@ -813,8 +873,6 @@ class Trainer:
         else:
             self._collect_loss()
             RunningStatistics.update(self.stats, x.shape[0], loss=loss.item() * x.shape[0])      # the host waits for the step here
-        if direct is not None:
-            direct.observe(time.perf_counter() - t_begin)
 
     def _collect_loss(self):
         """Add the loss of the step whose read-back is still pending (if any) to the statistics."""
