@@ -914,6 +914,354 @@ extern "C" int ddpm_p_sample_step(const float* x_t, const float* model_out, cons
     return check_launch();
 }
 
+// ------------------------------------------------------------------ learned reverse-process variance (model_var_type "learned" /
+// "learned-range"; Nichol & Dhariwal 2021 eq. 15, 16).  The network emits rows of 2n floats: the mean output at b*2n + i (eps / x_0 / mean as
+// above) and v at b*2n + n + i; the kernels below address both halves in place (no de-interleave pass).  The model log-variance of an element:
+//   var_mode 1 : v itself                                            (diffusion.py:113-114)
+//   var_mode 2 : f lv_max[t] + (1 - f) lv_min[t], f = (v + 1) / 2    (lv_max = the "fixed-large" table, lv_min = posterior_logvar_clipped; f is
+//                not clamped).  Each product and sum is rounded on its own, so v = +1 / -1 give the table entries to the bit.
+//   var_mode 0 : (step only) the table entry, v ignored — what DDIM does with a 2C-channel model.
+// Everything else — model mean, KL, discretized decoder, the reductions — is the code of the fixed-variance kernels above, fed a
+// per-element log-variance.  No atomics, fixed reduction order.
+struct LvTables { const float *recip, *recip_m1, *coef1, *coef2, *lv_min, *lv_max; };
+// (`#pragma clang fp contract(off)`: the __f*_rn spellings are plain operators in this toolchain and do not keep the compiler from fusing a
+// product into a following sum; the pragma does.)
+__device__ __forceinline__ float lv_logvar(int var_mode, float v, float lv_min, float lv_max) {
+#pragma clang fp contract(off)
+    if (var_mode == 1) return v;
+    const float f = 0.5f * (v + 1.0f);
+    return f * lv_max + (1.0f - f) * lv_min;
+}
+// One element of the sampling update with p_step_kernel's arithmetic AS THAT KERNEL IS COMPILED, so that on equal log-variances the two
+// kernels give the same bits: every product and sum rounded on its own, except the two places where the compiler fuses p_step_kernel's —
+// the x_0 estimate of mean_type 2, fma(-x_t, c2 / c1, out / c1), and the final mean + (mask sd) z.  Written out here instead of left to the
+// optimiser, whose choice depends on the surrounding code.
+__device__ __forceinline__ void lv_step_elem(const VlbCoef& k, int mean_type, int clip, float xt, float o, float mask_sd, float z, float& x_prev,
+                                             float& x0) {
+#pragma clang fp contract(off)
+    if (mean_type == 0) x0 = k.recip * xt - k.recip_m1 * o;
+    else if (mean_type == 1) x0 = o;
+    else x0 = __builtin_fmaf(-xt, k.c2 / k.c1, o / k.c1);
+    if (clip) x0 = x0 != x0 ? x0 : fminf(fmaxf(x0, -1.f), 1.f);
+    const float mean = mean_type == 2 ? o : k.c1 * x0 + k.c2 * xt;
+    x_prev = __builtin_fmaf(z, mask_sd, mean);
+}
+// the per-row constants of bpd_const with the model log-variance of ONE element in the place of the table entry
+__device__ __forceinline__ BpdConst bpd_const_lv(const VlbCoef& row, float lv2) {
+    BpdConst c;
+    c.k = row; c.k.lv2 = lv2;
+    c.dlv = c.k.lv1 - lv2; c.e_dlv = expf(c.dlv); c.inv_var2 = expf(-lv2); c.inv_std = expf(-0.5f * lv2);
+    return c;
+}
+// d term / d mean (the expressions of vlb_terms_bwd_kernel) and d term / d logvar of bpd_elem's term (decoder 0) at one element
+__device__ __forceinline__ void lv_term_grads(const BpdConst& c, long long tt, float x, float xti, float mean, float& dmean, float& dlv) {
+    const VlbCoef& k = c.k;
+    if (tt > 0) {
+        const float m1 = __fadd_rn(__fmul_rn(k.c1, x), __fmul_rn(k.c2, xti)), d = m1 - mean;
+        dmean = -d * c.inv_var2;
+        dlv = 0.5f * (1.0f - d * d * c.inv_var2 - c.e_dlv);
+    } else {
+        const float xc = x - mean;
+        const float zu = c.inv_std * (xc + (1.0f / 255.0f)), zl = c.inv_std * (xc - (1.0f / 255.0f));
+        const float cu = x > 0.999f ? 1.0f : vlb_cdf(zu), cl = x < -0.999f ? 0.0f : vlb_cdf(zl);
+        const float p = cu - cl - 1e-12f;
+        // a constant tail contributes nothing; the floor cuts the gradient; d z / d logvar = -z / 2
+        const float gu = x > 0.999f ? 0.f : vlb_cdf_grad(zu), gl = x < -0.999f ? 0.f : vlb_cdf_grad(zl);
+        const float r = p > 0.f ? -1.0f / (p + 1e-12f) : 0.f;
+        dmean = r * (-c.inv_std * (gu - gl));
+        dlv = r * (-0.5f * (gu * zu - gl * zl));
+    }
+}
+
+__global__ void p_step_lv_kernel(const float* __restrict__ x_t, const float* __restrict__ out, const float* __restrict__ z,
+                                 const long long* __restrict__ t, LvTables tb, float* __restrict__ x_prev, float* __restrict__ pred_x0,
+                                 int B, int n, int mean_type, int clip, int var_mode, int T) {
+    const long long tot = (long long)B * n;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < tot; i += (long long)gridDim.x * blockDim.x) {
+        const long long b = i / n, j = i - b * n;
+        const long long tt = t[b];
+        if ((unsigned long long)tt >= (unsigned long long)T) {
+            x_prev[i] = __builtin_nanf("");
+            if (pred_x0) pred_x0[i] = __builtin_nanf("");
+            continue;
+        }
+        const float* row = out + b * 2 * n;
+        const VlbCoef k{tb.recip[tt], tb.recip_m1[tt], tb.coef1[tt], tb.coef2[tt], 0.f, 0.f};
+        const float lv = var_mode == 0 ? tb.lv_min[tt] : lv_logvar(var_mode, row[n + j], var_mode == 2 ? tb.lv_min[tt] : 0.f, var_mode == 2 ? tb.lv_max[tt] : 0.f);
+        const float mask = tt > 0 ? 1.f : 0.f;
+        const float sd = expf(0.5f * lv);
+        float x0, xp;
+        lv_step_elem(k, mean_type, clip, x_t[i], row[j], mask * sd, z[i], xp, x0);
+        x_prev[i] = xp;
+        if (pred_x0) pred_x0[i] = x0;
+    }
+}
+extern "C" int ddpm_p_sample_step_lv(const float* x_t, const float* model_out, const float* z, const long long* t,
+                                     const float* sqrt_recip_ab, const float* sqrt_recip_m1_ab, const float* post_coef1, const float* post_coef2,
+                                     const float* logvar_lo, const float* logvar_hi, float* x_prev, float* pred_x0,
+                                     int B, int n, int mean_type, int clip, int var_mode, int T, void* stream) {
+    if (!x_t || !model_out || !z || !t || !x_prev || !sqrt_recip_ab || !sqrt_recip_m1_ab || !post_coef1 || !post_coef2) return DDPM_ERR_NULL;
+    if (B <= 0 || n <= 0 || T <= 0 || mean_type < 0 || mean_type > 2 || var_mode < 0 || var_mode > 2) return DDPM_ERR_SHAPE;
+    if ((var_mode != 1 && !logvar_lo) || (var_mode == 2 && !logvar_hi)) return DDPM_ERR_NULL;
+    LvTables tb{sqrt_recip_ab, sqrt_recip_m1_ab, post_coef1, post_coef2, logvar_lo, logvar_hi};
+    hipLaunchKernelGGL(p_step_lv_kernel, dim3(grid_for((long long)B * n)), dim3(256), 0, (hipStream_t)stream, x_t, model_out, z, t, tb, x_prev, pred_x0,
+                       B, n, mean_type, clip, var_mode, T);
+    return check_launch();
+}
+
+// bound term of one element at the per-element log-variance: bpd_elem (decoder 0) on bpd_const_lv
+__device__ __forceinline__ void lv_elem(const VlbCoef& row, float lv_max, long long tt, int mean_type, int clip, int var_mode, float x, float xti,
+                                        float o, float v, float& term, float& sq) {
+    const BpdConst c = bpd_const_lv(row, lv_logvar(var_mode, v, row.lv1, lv_max));
+    bpd_elem(c, tt, mean_type, clip, 0, x, xti, o, term, sq);
+}
+// ddpm_vlb_terms' layout (one block of 256 per sample, its element order and reduction tree)
+__global__ __launch_bounds__(256) void vlb_terms_lv_kernel(const float* __restrict__ x0, const float* __restrict__ xt, const float* __restrict__ out,
+                                                           const long long* __restrict__ t, LvTables tb, float* __restrict__ loss,
+                                                           float* __restrict__ pred_x0, int n, int mean_type, int clip, int var_mode, int T) {
+    __shared__ float sh[4];
+    const int b = blockIdx.x;
+    const long long tt = t[b];
+    const long long base = (long long)b * n;
+    if ((unsigned long long)tt >= (unsigned long long)T) {
+        if (threadIdx.x == 0) loss[b] = __builtin_nanf("");
+        if (pred_x0) for (int i = threadIdx.x; i < n; i += blockDim.x) pred_x0[base + i] = __builtin_nanf("");
+        return;
+    }
+    const float* row = out + 2 * base;
+    const VlbCoef k{tb.recip[tt], tb.recip_m1[tt], tb.coef1[tt], tb.coef2[tt], tb.lv_min[tt], 0.f};
+    const float lmax = var_mode == 2 ? tb.lv_max[tt] : 0.f;
+    float acc = 0.f;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const float xti = xt[base + i], o = row[i];
+        float term, sq;
+        lv_elem(k, lmax, tt, mean_type, clip, var_mode, x0[base + i], xti, o, row[n + i], term, sq);
+        if (pred_x0) {
+            float mean, x0p;
+            vlb_model_mean(k, mean_type, clip, xti, o, mean, x0p);
+            pred_x0[base + i] = x0p;
+        }
+        acc += term;
+    }
+    acc = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) loss[b] = ((sh[0] + sh[1]) + (sh[2] + sh[3])) / (float)n / 0.6931471805599453f;
+}
+extern "C" int ddpm_vlb_terms_lv(const float* x_0, const float* x_t, const float* model_out, const long long* t,
+                                 const float* sqrt_recip_ab, const float* sqrt_recip_m1_ab, const float* post_coef1, const float* post_coef2,
+                                 const float* post_logvar, const float* logvar_max, float* loss, float* pred_x0,
+                                 int B, int n, int mean_type, int clip, int var_mode, int T, void* stream) {
+    if (!x_0 || !x_t || !model_out || !t || !sqrt_recip_ab || !sqrt_recip_m1_ab || !post_coef1 || !post_coef2 || !post_logvar || !loss) return DDPM_ERR_NULL;
+    if (B <= 0 || n <= 0 || T <= 0 || mean_type < 0 || mean_type > 2 || var_mode < 1 || var_mode > 2) return DDPM_ERR_SHAPE;
+    if (var_mode == 2 && !logvar_max) return DDPM_ERR_NULL;
+    LvTables tb{sqrt_recip_ab, sqrt_recip_m1_ab, post_coef1, post_coef2, post_logvar, logvar_max};
+    hipLaunchKernelGGL(vlb_terms_lv_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, x_0, x_t, model_out, t, tb, loss, pred_x0, n, mean_type, clip, var_mode, T);
+    return check_launch();
+}
+
+// ddpm_bpd_terms' three row layouts on the 2n-float rows
+struct BpdLvArgs {
+    const float *x0, *xt, *out;
+    const long long* t;
+    LvTables tb;
+    float *losses, *mses;
+    int B, n, ld, mean_type, clip, var_mode, T;
+};
+__global__ __launch_bounds__(256) void bpd_terms_lv_wave_kernel(BpdLvArgs a) {
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (b >= a.B) return;
+    const long long tt = a.t[b];
+    if ((unsigned long long)tt >= (unsigned long long)a.T) return;
+    const long long base = (long long)b * a.n;
+    const float* row = a.out + 2 * base;
+    const VlbCoef k{a.tb.recip[tt], a.tb.recip_m1[tt], a.tb.coef1[tt], a.tb.coef2[tt], a.tb.lv_min[tt], 0.f};
+    const float lmax = a.var_mode == 2 ? a.tb.lv_max[tt] : 0.f;
+    float acc = 0.f, acc2 = 0.f;
+    for (int i = lane; i < a.n; i += 64) {
+        float term, sq;
+        lv_elem(k, lmax, tt, a.mean_type, a.clip, a.var_mode, a.x0[base + i], a.xt[base + i], row[i], row[a.n + i], term, sq);
+        acc += term; acc2 += sq;
+    }
+    acc = wave_sum(acc); acc2 = wave_sum(acc2);
+    if (lane == 0) {
+        a.losses[(long long)b * a.ld + tt] = acc / (float)a.n / 0.6931471805599453f;
+        a.mses[(long long)b * a.ld + tt] = acc2 / (float)a.n;
+    }
+}
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void bpd_terms_lv_kernel(BpdLvArgs a) {
+    constexpr int WAVES = THREADS / 64;
+    __shared__ float sh[2][WAVES];
+    const int b = blockIdx.x;
+    const long long tt = a.t[b];
+    if ((unsigned long long)tt >= (unsigned long long)a.T) return;          // uniform over the block
+    const long long base = (long long)b * a.n;
+    const float *x0 = a.x0 + base, *xt = a.xt + base, *out = a.out + 2 * base, *vv = out + a.n;
+    const VlbCoef k{a.tb.recip[tt], a.tb.recip_m1[tt], a.tb.coef1[tt], a.tb.coef2[tt], a.tb.lv_min[tt], 0.f};
+    const float lmax = a.var_mode == 2 ? a.tb.lv_max[tt] : 0.f;
+    float acc = 0.f, acc2 = 0.f;
+    int nv = 0;
+    if (THREADS == 1024) {
+        const bool al = ((reinterpret_cast<unsigned long long>(x0) | reinterpret_cast<unsigned long long>(xt) | reinterpret_cast<unsigned long long>(out) |
+                          reinterpret_cast<unsigned long long>(vv)) & 15) == 0;
+        nv = al ? a.n >> 2 : 0;
+        int i = threadIdx.x;
+        for (; i + THREADS < nv; i += 2 * THREADS) {
+            f32x4 vx[2], vt[2], vo[2], vl[2];
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                vx[u] = reinterpret_cast<const f32x4*>(x0)[i + u * THREADS];
+                vt[u] = reinterpret_cast<const f32x4*>(xt)[i + u * THREADS];
+                vo[u] = reinterpret_cast<const f32x4*>(out)[i + u * THREADS];
+                vl[u] = reinterpret_cast<const f32x4*>(vv)[i + u * THREADS];
+            }
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    float term, sq;
+                    lv_elem(k, lmax, tt, a.mean_type, a.clip, a.var_mode, vx[u][e], vt[u][e], vo[u][e], vl[u][e], term, sq);
+                    acc += term; acc2 += sq;
+                }
+        }
+        for (; i < nv; i += THREADS) {
+            const f32x4 vx = reinterpret_cast<const f32x4*>(x0)[i], vt = reinterpret_cast<const f32x4*>(xt)[i], vo = reinterpret_cast<const f32x4*>(out)[i],
+                        vl = reinterpret_cast<const f32x4*>(vv)[i];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float term, sq;
+                lv_elem(k, lmax, tt, a.mean_type, a.clip, a.var_mode, vx[e], vt[e], vo[e], vl[e], term, sq);
+                acc += term; acc2 += sq;
+            }
+        }
+    }
+    for (int i = (nv << 2) + threadIdx.x; i < a.n; i += THREADS) {
+        float term, sq;
+        lv_elem(k, lmax, tt, a.mean_type, a.clip, a.var_mode, x0[i], xt[i], out[i], vv[i], term, sq);
+        acc += term; acc2 += sq;
+    }
+    acc = wave_sum(acc); acc2 = wave_sum(acc2);
+    if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = acc; sh[1][threadIdx.x >> 6] = acc2; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float tot, tot2;
+        if (WAVES == 4) {
+            tot = (sh[0][0] + sh[0][1]) + (sh[0][2] + sh[0][3]);
+            tot2 = (sh[1][0] + sh[1][1]) + (sh[1][2] + sh[1][3]);
+        } else {
+            tot = 0.f; tot2 = 0.f;
+            for (int w = 0; w < WAVES; ++w) { tot += sh[0][w]; tot2 += sh[1][w]; }
+        }
+        a.losses[(long long)b * a.ld + tt] = tot / (float)a.n / 0.6931471805599453f;
+        a.mses[(long long)b * a.ld + tt] = tot2 / (float)a.n;
+    }
+}
+extern "C" int ddpm_bpd_terms_lv(const float* x_0, const float* x_t, const float* model_out, const long long* t,
+                                 const float* sqrt_recip_ab, const float* sqrt_recip_m1_ab, const float* post_coef1, const float* post_coef2,
+                                 const float* post_logvar, const float* logvar_max, float* losses, float* mses,
+                                 int B, int n, int ld, int mean_type, int clip, int decoder, int var_mode, int T, void* stream) {
+    if (!x_0 || !x_t || !model_out || !t || !sqrt_recip_ab || !sqrt_recip_m1_ab || !post_coef1 || !post_coef2 || !post_logvar || !losses || !mses)
+        return DDPM_ERR_NULL;
+    if (B <= 0 || n <= 0 || T <= 0 || ld < T || mean_type < 0 || mean_type > 2 || decoder != 0 || var_mode < 1 || var_mode > 2) return DDPM_ERR_SHAPE;
+    if (var_mode == 2 && !logvar_max) return DDPM_ERR_NULL;
+    const BpdLvArgs a{x_0, x_t, model_out, t, LvTables{sqrt_recip_ab, sqrt_recip_m1_ab, post_coef1, post_coef2, post_logvar, logvar_max},
+                      losses, mses, B, n, ld, mean_type, clip, var_mode, T};
+    if (n <= 64) hipLaunchKernelGGL(bpd_terms_lv_wave_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, a);
+    else if (n < 16384) hipLaunchKernelGGL(bpd_terms_lv_kernel<256>, dim3(B), dim3(256), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(bpd_terms_lv_kernel<1024>, dim3(B), dim3(1024), 0, (hipStream_t)stream, a);
+    return check_launch();
+}
+
+// training loss of a learned-variance model and its gradient in ONE pass over x_0, x_t, model_out, target:
+//   loss[b] = w_mse mean_i (out_mean - target)^2 + w_vlb L_t(mean(out_mean), v)        (L_t in bits/dim, clip_denoised = False)
+//   gout[b][0..n)  = gloss[b] (w_mse 2 (out_mean - target) / n + [detach_mean = 0] w_vlb dL_t / d out_mean)
+//   gout[b][n..2n) = gloss[b] w_vlb dL_t / dv
+// A weight of 0 switches its term off (its inputs are then not read: target for w_mse, nothing of the bound for w_vlb, whose v-half
+// gradient is then exactly 0).  One block per sample, fixed reduction order.
+struct LearnedLossArgs {
+    const float *x0, *xt, *out, *target;
+    const long long* t;
+    LvTables tb;
+    const float* gloss;
+    float *loss, *gout;
+    int n, mean_type, var_mode, detach_mean, T;
+    float w_mse, w_vlb;
+};
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void learned_loss_kernel(LearnedLossArgs a) {
+    constexpr int WAVES = THREADS / 64;
+    __shared__ float sh[2][WAVES];
+    const int b = blockIdx.x, n = a.n;
+    const long long tt = a.t[b];
+    const long long base = (long long)b * n;
+    float* g = a.gout ? a.gout + 2 * base : nullptr;
+    if ((unsigned long long)tt >= (unsigned long long)a.T) {               // uniform over the block
+        if (threadIdx.x == 0) a.loss[b] = __builtin_nanf("");
+        if (g) for (int i = threadIdx.x; i < 2 * n; i += THREADS) g[i] = __builtin_nanf("");
+        return;
+    }
+    const float *x0 = a.x0 + base, *xt = a.xt + base, *out = a.out + 2 * base, *vv = out + n;
+    const bool mse = a.w_mse != 0.f, vlb = a.w_vlb != 0.f;
+    const float* tg = mse ? a.target + base : nullptr;
+    const VlbCoef k{a.tb.recip[tt], a.tb.recip_m1[tt], a.tb.coef1[tt], a.tb.coef2[tt], a.tb.lv_min[tt], 0.f};
+    const float lmax = a.var_mode == 2 ? a.tb.lv_max[tt] : 0.f;
+    const float gl = g ? a.gloss[b] : 0.f;
+    const float inv2 = 2.0f / (float)n;                                     // ddpm_mse_bwd's factor
+    const float sv = gl * a.w_vlb * (1.0f / ((float)n * 0.6931471805599453f));
+    const float dmean_dout = a.mean_type == 0 ? -k.c1 * k.recip_m1 : (a.mean_type == 1 ? k.c1 : 1.0f);
+    const float dlv_dv = a.var_mode == 2 ? 0.5f * (lmax - k.lv1) : 1.0f;
+    float acc = 0.f, acc2 = 0.f;
+    for (int i = threadIdx.x; i < n; i += THREADS) {
+        const float o = out[i];
+        float gm = 0.f, gv = 0.f;
+        if (mse) {
+            const float tgt = tg[i], d = tgt - o;
+            acc2 += d * d;
+            gm = a.w_mse * ((o - tgt) * inv2 * gl);
+        }
+        if (vlb) {
+            const float x = x0[i], xti = xt[i];
+            const BpdConst c = bpd_const_lv(k, lv_logvar(a.var_mode, vv[i], k.lv1, lmax));
+            float term, sq;
+            bpd_elem(c, tt, a.mean_type, 0, 0, x, xti, o, term, sq);
+            acc += term;
+            if (g) {
+                float mean, x0p, dmean, dlv;
+                vlb_model_mean(c.k, a.mean_type, 0, xti, o, mean, x0p);
+                lv_term_grads(c, tt, x, xti, mean, dmean, dlv);
+                if (!a.detach_mean) gm += sv * dmean * dmean_dout;
+                gv = sv * dlv * dlv_dv;
+            }
+        }
+        if (g) { g[i] = gm; g[n + i] = gv; }
+    }
+    acc = wave_sum(acc); acc2 = wave_sum(acc2);
+    if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = acc; sh[1][threadIdx.x >> 6] = acc2; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float tot = 0.f, tot2 = 0.f;
+        for (int w = 0; w < WAVES; ++w) { tot += sh[0][w]; tot2 += sh[1][w]; }
+        float l = 0.f;
+        if (mse) l = a.w_mse * (tot2 / (float)n);
+        if (vlb) l += a.w_vlb * (tot / (float)n / 0.6931471805599453f);
+        a.loss[b] = l;
+    }
+}
+extern "C" int ddpm_learned_loss(const float* x_0, const float* x_t, const float* model_out, const float* target, const long long* t,
+                                 const float* sqrt_recip_ab, const float* sqrt_recip_m1_ab, const float* post_coef1, const float* post_coef2,
+                                 const float* post_logvar, const float* logvar_max, const float* gloss, float* loss, float* gout,
+                                 int B, int n, int mean_type, int var_mode, int detach_mean, int T, float w_mse, float w_vlb, void* stream) {
+    if (!x_0 || !x_t || !model_out || !t || !sqrt_recip_ab || !sqrt_recip_m1_ab || !post_coef1 || !post_coef2 || !post_logvar || !loss) return DDPM_ERR_NULL;
+    if (B <= 0 || n <= 0 || T <= 0 || mean_type < 0 || mean_type > 2 || var_mode < 1 || var_mode > 2) return DDPM_ERR_SHAPE;
+    if ((var_mode == 2 && !logvar_max) || (w_mse != 0.f && !target) || (gout && !gloss)) return DDPM_ERR_NULL;
+    const LearnedLossArgs a{x_0, x_t, model_out, target, t, LvTables{sqrt_recip_ab, sqrt_recip_m1_ab, post_coef1, post_coef2, post_logvar, logvar_max},
+                            gloss, loss, gout, n, mean_type, var_mode, detach_mean, T, w_mse, w_vlb};
+    if (n < 16384) hipLaunchKernelGGL(learned_loss_kernel<256>, dim3(B), dim3(256), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(learned_loss_kernel<1024>, dim3(B), dim3(1024), 0, (hipStream_t)stream, a);
+    return check_launch();
+}
+
 // t[b] = map[t_idx[b]] (DDIM sub-sequence, ddim.py:101) and in-place decrement for graph-captured loops
 __global__ void gather_i64_kernel(const long long* __restrict__ idx, const long long* __restrict__ map, long long* __restrict__ out, int B) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -81,6 +81,7 @@ const EntryPoint kEntryPoints[] = {
     EP(ddpm_toy_time_table), EP(ddpm_toy_decoder_fwd), EP(ddpm_toy_decoder_bwd), EP(ddpm_toy_time_table_bwd),
     EP(ddpm_manifold_kth_f16), EP(ddpm_manifold_cover_f16), EP(ddpm_bpd_terms), EP(ddpm_bpd_finish), EP(ddpm_batch_gather),
     EP(ddpm_ddim_encode_step), EP(ddpm_slerp), EP_SIZE_OF(ddpm_slerp_workspace_floats),
+    EP(ddpm_p_sample_step_lv), EP(ddpm_vlb_terms_lv), EP(ddpm_bpd_terms_lv), EP(ddpm_learned_loss),
 };
 constexpr int kNumEntryPoints = (int)(sizeof(kEntryPoints) / sizeof(kEntryPoints[0]));
 

@@ -61,8 +61,10 @@ class DDIM(ddpm_torch.GaussianDiffusion):
         super().__init__(betas, model_mean_type, model_var_type, loss_type)
         self.eta = eta
         eta2 = eta ** 2
-        if eta2 != 1.0 and model_var_type != "fixed-small":
-            self.model_var_type = "fixed-small"          # silent coercion, as ddim.py:53-59
+        if (eta2 != 1.0 and model_var_type != "fixed-small") or self.learned_var:
+            # silent coercion, as ddim.py:53-59.  A learned-variance model is sampled on these eta-scaled tables too, at any eta: its mean
+            # half alone is read (``learned_var`` stays set: the network output is [B, 2C, H, W]; var_mode 0 of ddpm_p_sample_step_lv)
+            self.model_var_type = "fixed-small"
         ab = self.alphas_bar[subsequence]
         ab_prev = torch.cat([torch.ones(1, dtype=torch.float64), ab[:-1]], dim=0)
         self.alphas = ab / ab_prev
@@ -121,9 +123,14 @@ class DDIM(ddpm_torch.GaussianDiffusion):
             tabs = [self._tab(n_, dev) for n_ in ddpm_torch.diffusion._STEP_TABLES]
             z = torch.zeros_like(x_t)
             mean_code, clip = ddpm_torch.diffusion._MEAN_CODE[self.model_mean_type], int(bool(kind[1]))
+        C = shape[1] if len(shape) > 1 else None
 
         def body(cut=None):
-            out = denoise_fn(x_t, self._model_t(t)).contiguous().float()
+            out = denoise_fn(x_t, self._model_t(t))
+            if self.learned_var:                       # a 2C-channel model: the mean half, as a plain copy
+                self._check_two_halves(out, x_t)
+                out = out[:, :C]
+            out = out.contiguous().float()
             if encode:
                 _hip.call("ddpm_ddim_encode_step", x_t.data_ptr(), out.data_ptr(), t.data_ptr(), *[tb.data_ptr() for tb in tabs],
                           x_t.data_ptr(), _hip.ptr(pred), B, n, S, _hip.stream())             # in place: each element is read once, then written

@@ -61,6 +61,11 @@ PROTOTYPES = {
     "ddpm_vlb_terms_bwd": [P] * 12 + [I, I, I, I, P],
     "ddpm_bpd_terms": [P] * 12 + [I, I, I, I, I, I, I, P],
     "ddpm_bpd_finish": [P, P, P, P, I, I, I, I, F, F, P],
+    # learned reverse-process variance (csrc/elementwise.hip; model_out rows of 2n floats)
+    "ddpm_p_sample_step_lv": [P] * 12 + [I] * 6 + [P],
+    "ddpm_vlb_terms_lv": [P] * 12 + [I] * 6 + [P],
+    "ddpm_bpd_terms_lv": [P] * 12 + [I] * 8 + [P],
+    "ddpm_learned_loss": [P] * 14 + [I] * 6 + [F, F, P],
     "ddpm_gather_i64": [P, P, P, I, P],
     "ddpm_add_i64": [P, I, L, P],
     "ddpm_gather_rows_f32": [P, P, P, I, I, I, P],

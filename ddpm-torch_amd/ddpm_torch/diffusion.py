@@ -54,6 +54,11 @@ _MEAN_CODE = {"eps": 0, "x_0": 1, "mean": 2}
 _STEP_TABLES = ("sqrt_recip_alphas_bar", "sqrt_recip_m1_alphas_bar", "posterior_mean_coef1", "posterior_mean_coef2", "fixed_model_logvar")
 _VLB_TABLES = ("sqrt_recip_alphas_bar", "sqrt_recip_m1_alphas_bar", "posterior_mean_coef1", "posterior_mean_coef2", "posterior_logvar_clipped",
                "fixed_model_logvar")
+# learned variance (the network emits [B, 2C, H, W]: mean output | v): the kernels' var_mode, and the tables of the *_lv entry points —
+# the four mean coefficients, then lv_min = posterior_logvar_clipped and lv_max = the "fixed-large" table
+_VAR_MODE = {"learned": 1, "learned-range": 2}
+_LV_TABLES = ("sqrt_recip_alphas_bar", "sqrt_recip_m1_alphas_bar", "posterior_mean_coef1", "posterior_mean_coef2", "posterior_logvar_clipped",
+              "model_logvar_max")
 
 
 class _AutogradMSE(torch.autograd.Function):
@@ -99,6 +104,24 @@ class _AutogradVLB(torch.autograd.Function):
         return g, None, None, None, None, None, None
 
 
+class _AutogradLearnedLoss(torch.autograd.Function):
+    """Per-sample loss of a learned-variance model, w_mse * MSE(mean half, target) + w_vlb * L_t (bits / dim), by `ddpm_learned_loss`: the
+    forward asks for the loss alone, the backward runs the kernel again for d / d model_out (both halves; x_0, x_t, target are data)."""
+
+    @staticmethod
+    def forward(ctx, model_out, x_0, x_t, target, t, launch):
+        ctx.save_for_backward(model_out, x_0, x_t, target, t)
+        ctx.launch = launch
+        return launch(x_0, x_t, model_out, target, t, None, None)
+
+    @staticmethod
+    def backward(ctx, gloss):
+        model_out, x_0, x_t, target, t = ctx.saved_tensors
+        g = torch.empty_like(model_out)
+        ctx.launch(x_0, x_t, model_out, target, t, gloss.contiguous().float(), g)
+        return g, None, None, None, None, None
+
+
 class GaussianDiffusion:
     # whether the sampling loops (eager and captured) clamp the x_0 estimate to [-1, 1] (diffusion.py:152-158 pass clip_denoised=True);
     # the 2-D toy subclass never clips (toy/diffusion.py:32)
@@ -112,6 +135,14 @@ class GaussianDiffusion:
         self.model_var_type = model_var_type
         self.loss_type = loss_type
         self.timesteps = len(betas)
+        # the network's output is [B, 2C, H, W], mean output | v (a DDIM built for such a model keeps this set and samples on fixed tables)
+        self.learned_var = model_var_type in _VAR_MODE
+        if self.learned_var and loss_type == "mse":
+            raise ValueError(f"loss_type 'mse' gives the variance half of a {model_var_type!r} model no gradient (diffusion.py:229); use 'hybrid' or 'kl'")
+        if loss_type == "hybrid" and not self.learned_var:
+            raise ValueError(f"loss_type 'hybrid' trains a learned variance: model_var_type must be 'learned' or 'learned-range', got {model_var_type!r}")
+        # weight of the bound term in the hybrid loss (Nichol & Dhariwal 2021 eq. 16: lambda = 0.001 on the sum of T terms, carried by the one sampled)
+        self.vlb_weight = float(kwargs.get("vlb_weight", self.timesteps / 1000.0))
         self._build_tables(betas, torch.cumprod(1.0 - betas, dim=0), eta2=None)
 
     def _build_tables(self, betas, alphas_bar, eta2):
@@ -143,14 +174,15 @@ class GaussianDiffusion:
         else:
             self.posterior_mean_coef1 = betas * ab_prev.sqrt() / (1.0 - ab)
             self.posterior_mean_coef2 = (1.0 - betas).sqrt() * (1.0 - ab_prev) / (1.0 - ab)
+        self.model_logvar_max = log_patched(self.posterior_var[1:2], betas[1:])          # lv_max of "learned-range"; lv_min = posterior_logvar_clipped
         if self.model_var_type == "fixed-large":
             self.fixed_model_var = betas
-            self.fixed_model_logvar = log_patched(self.posterior_var[1:2], betas[1:])
+            self.fixed_model_logvar = self.model_logvar_max
         elif self.model_var_type == "fixed-small":
             self.fixed_model_var = self.posterior_var
             self.fixed_model_logvar = self.posterior_logvar_clipped
-        else:
-            raise KeyError(self.model_var_type)        # "learned" is dead in the reference too (diffusion.py:70-73)
+        elif self.model_var_type not in _VAR_MODE:        # the learned types have no fixed_model_var / fixed_model_logvar
+            raise KeyError(self.model_var_type)
         self._dev = {}                                  # (table name, device) -> fp32 device copy
         return ab_prev
 
@@ -203,6 +235,8 @@ class GaussianDiffusion:
         model_out = denoise_fn(x_t, t)
         x_0, x_t, model_out = self._prep(x_0, x_t, model_out)
         t = t.contiguous()
+        if self.learned_var:
+            return self._loss_term_bpd_lv(x_0, x_t, model_out, t, clip_denoised, return_pred)
         tabs = [self._tab(n_, x_0.device) for n_ in _VLB_TABLES]
         T, code = len(self.posterior_mean_coef1), _MEAN_CODE[self.model_mean_type]
         if torch.is_grad_enabled() and model_out.requires_grad:
@@ -216,9 +250,49 @@ class GaussianDiffusion:
                   loss.data_ptr(), _hip.ptr(pred), B, n, code, int(bool(clip_denoised)), T, _hip.stream())
         return (loss, pred) if return_pred else loss
 
+    # ---- learned variance: the *_lv entry points on the network's [B, 2C, H, W] output
+    def _var_mode(self):
+        """The kernels' var_mode: 1 / 2 for the learned types, 0 = fixed tables (a DDIM on a 2C-channel model: the v half is ignored)."""
+        return _VAR_MODE.get(self.model_var_type, 0)
+
+    def _lv_tabs(self, dev):
+        return [self._tab(n_, dev).data_ptr() for n_ in _LV_TABLES]
+
+    def _check_two_halves(self, model_out, x):
+        if model_out.shape[0] != x.shape[0] or model_out[0].numel() != 2 * x[0].numel():
+            raise ValueError(f"a {self.model_var_type!r} model emits twice the channels of its input (mean output | v): got "
+                             f"{tuple(model_out.shape)} for an input of {tuple(x.shape)}")
+
+    def learned_loss(self, x_0, x_t, model_out, target, t, gloss, gout, w_mse, w_vlb, detach_mean, loss=None):
+        """One `ddpm_learned_loss` launch on prepared fp32 tensors: loss [B] (and gout when given, see include/ddpm_hip.h)."""
+        self._check_two_halves(model_out, x_0)
+        B, n = x_0.shape[0], x_0[0].numel()
+        if loss is None:
+            loss = _hip.retain(torch.empty(B, dtype=torch.float32, device=x_0.device))
+        _hip.call("ddpm_learned_loss", x_0.data_ptr(), x_t.data_ptr(), model_out.data_ptr(), _hip.ptr(target), t.data_ptr(), *self._lv_tabs(x_0.device),
+                  _hip.ptr(gloss), loss.data_ptr(), _hip.ptr(gout), B, n, _MEAN_CODE[self.model_mean_type], self._var_mode(), int(bool(detach_mean)),
+                  len(self.posterior_mean_coef1), float(w_mse), float(w_vlb), _hip.stream())
+        return loss
+
+    def _loss_term_bpd_lv(self, x_0, x_t, model_out, t, clip_denoised, return_pred):
+        self._check_two_halves(model_out, x_0)
+        if torch.is_grad_enabled() and model_out.requires_grad:
+            if clip_denoised or return_pred:
+                raise NotImplementedError("the differentiable bound term is the training form: clip_denoised=False, return_pred=False")
+            launch = lambda x0, xt, out, tg, tt, gl, g: self.learned_loss(x0, xt, out, None, tt, gl, g, 0.0, 1.0, False)      # noqa: E731
+            return _AutogradLearnedLoss.apply(model_out, x_0, x_t, None, t, launch)
+        B, n = x_0.shape[0], x_0[0].numel()
+        loss = torch.empty(B, dtype=torch.float32, device=x_0.device)
+        pred = torch.empty_like(x_0) if return_pred else None
+        _hip.call("ddpm_vlb_terms_lv", x_0.data_ptr(), x_t.data_ptr(), model_out.data_ptr(), t.data_ptr(), *self._lv_tabs(x_0.device),
+                  loss.data_ptr(), _hip.ptr(pred), B, n, _MEAN_CODE[self.model_mean_type], int(bool(clip_denoised)), self._var_mode(),
+                  len(self.posterior_mean_coef1), _hip.stream())
+        return (loss, pred) if return_pred else loss
+
     def train_losses(self, denoise_fn, x_0, t, noise=None):
-        """diffusion.py:217-243 -> per-sample losses [B]: "mse" (unweighted) or "kl" (the variational-bound term, :222-224)."""
-        if self.loss_type not in ("mse", "kl"):
+        """diffusion.py:217-243 -> per-sample losses [B]: "mse" (unweighted), "kl" (the variational-bound term, :222-224) or, for a learned
+        variance, "hybrid" (Nichol & Dhariwal 2021 eq. 16): mean (out_mean - target)^2 + vlb_weight * L_t(stopgrad(out_mean), v)."""
+        if self.loss_type not in ("mse", "kl", "hybrid"):
             raise NotImplementedError(self.loss_type)
         if noise is None:
             noise = torch.randn_like(x_0)
@@ -227,6 +301,10 @@ class GaussianDiffusion:
             return self._loss_term_bpd(denoise_fn, x_0=x_0, x_t=x_t, t=t, clip_denoised=False, return_pred=False)
         target = self.loss_target(x_0, x_t, t, noise)
         model_out = denoise_fn(x_t, t)
+        if self.loss_type == "hybrid":
+            x_0, model_out, target = self._prep(x_0, model_out, target)
+            launch = lambda x0, xt, out, tg, tt, gl, g: self.learned_loss(x0, xt, out, tg, tt, gl, g, 1.0, self.vlb_weight, True)     # noqa: E731
+            return _AutogradLearnedLoss.apply(model_out, x_0, x_t, target, t.contiguous(), launch)
         pred, target = self._prep(model_out, target)
         return _AutogradMSE.apply(pred, target)
 
@@ -245,7 +323,10 @@ class GaussianDiffusion:
 
     def supports_direct_step(self):
         """True when Trainer may run its autograd-free step: the loss is the plain MSE on a target that does not depend on
-        the model (the reference's 'kl' loss would need the variance terms)."""
+        the model (the reference's 'kl' loss would need the variance terms), or the hybrid loss of a learned variance (one fused launch
+        forms it and its gradient)."""
+        if self.loss_type == "hybrid":
+            return self.model_var_type in _VAR_MODE and self.model_mean_type in _MEAN_CODE
         return self.loss_type == "mse" and self.model_mean_type in _MEAN_CODE
 
     # ------------------------------------------------------------------ reverse process
@@ -254,16 +335,41 @@ class GaussianDiffusion:
         dev = x_t.device
         out = torch.empty_like(x_t)
         pred = torch.empty_like(x_t) if want_pred else None
+        if self.learned_var:
+            self._check_two_halves(model_out, x_t)
+            self._step_lv_call(x_t, model_out, z, t, out, pred, clip_denoised)
+            return out, pred
         tabs = [self._tab(n, dev).data_ptr() for n in _STEP_TABLES]
         _hip.call("ddpm_p_sample_step", x_t.data_ptr(), model_out.data_ptr(), z.data_ptr(), t.data_ptr(), *tabs, out.data_ptr(),
              _hip.ptr(pred), x_t.shape[0], x_t[0].numel(), _MEAN_CODE[self.model_mean_type], int(bool(clip_denoised)),
              len(self.posterior_mean_coef1), _hip.stream())
         return out, pred
 
+    def _step_lv_call(self, x_t, model_out, z, t, out, pred, clip_denoised):
+        """`ddpm_p_sample_step_lv` on a [B, 2C, H, W] network output (``out`` may be ``x_t``).  var_mode 0 (a DDIM on such a model): the
+        sampler's own fixed table and the mean half alone."""
+        dev, mode = x_t.device, self._var_mode()
+        tabs = self._lv_tabs(dev) if mode else [self._tab(n_, dev).data_ptr() for n_ in _STEP_TABLES] + [0]
+        _hip.call("ddpm_p_sample_step_lv", x_t.data_ptr(), model_out.data_ptr(), z.data_ptr(), t.data_ptr(), *tabs, out.data_ptr(), _hip.ptr(pred),
+                  x_t.shape[0], x_t[0].numel(), _MEAN_CODE[self.model_mean_type], int(bool(clip_denoised)), mode, len(self.posterior_mean_coef1),
+                  _hip.stream())
+
+    def _model_logvar(self, model_out, x_t, t):
+        """Per-element log-variance of a learned-variance model from the v half (diffusion.py:113-114; eq. 15 for "learned-range")."""
+        v = model_out.contiguous().float().reshape(x_t.shape[0], 2, -1)[:, 1].reshape(x_t.shape)
+        if self.model_var_type == "learned":
+            return v
+        e = lambda name: self._tab(name, x_t.device).gather(0, t).reshape((-1,) + (1,) * (x_t.ndim - 1))        # noqa: E731
+        f = (v + 1.0) * 0.5
+        return f * e("model_logvar_max") + (1.0 - f) * e("posterior_logvar_clipped")
+
     def p_mean_var(self, denoise_fn, x_t, t, clip_denoised, return_pred):
         """diffusion.py:107-138 (mean / variance are read off a zero-noise fused step)."""
         out = denoise_fn(x_t, t)
         mean, pred = self._step(x_t, out, torch.zeros_like(x_t), t, clip_denoised, True)
+        if self._var_mode():
+            logvar = self._model_logvar(out, x_t, t)
+            return (mean, torch.exp(logvar), logvar, pred) if return_pred else (mean, torch.exp(logvar), logvar)
         var = self._tab("fixed_model_var", x_t.device).gather(0, t).reshape((-1,) + (1,) * (x_t.ndim - 1))
         logvar = self._tab("fixed_model_logvar", x_t.device).gather(0, t).reshape((-1,) + (1,) * (x_t.ndim - 1))
         return (mean, var, logvar, pred) if return_pred else (mean, var, logvar)
@@ -415,7 +521,7 @@ class GaussianDiffusion:
         B, n = shape[0], x_t[0].numel()
         t = torch.full((B,), self._num_steps() - 1, dtype=torch.int64, device=dev)
         rng = None if default_rng else torch.Generator(dev)
-        tabs = [self._tab(n_, dev) for n_ in _STEP_TABLES]
+        tabs = [] if self.learned_var else [self._tab(n_, dev) for n_ in _STEP_TABLES]
         mean_code = _MEAN_CODE[self.model_mean_type]
         T = len(self.posterior_mean_coef1)
 
@@ -423,8 +529,12 @@ class GaussianDiffusion:
             out = denoise_fn(x_t, self._model_t(t)).contiguous().float()
             if not external_z:
                 z.normal_(generator=rng)
-            _hip.call("ddpm_p_sample_step", x_t.data_ptr(), out.data_ptr(), z.data_ptr(), t.data_ptr(), *[tb.data_ptr() for tb in tabs],
-                      x_t.data_ptr(), 0, B, n, mean_code, int(self.clip_sampling), T, _hip.stream())   # in place: each element is read once, then written
+            if self.learned_var:
+                self._check_two_halves(out, x_t)
+                self._step_lv_call(x_t, out, z, t, x_t, None, self.clip_sampling)
+            else:
+                _hip.call("ddpm_p_sample_step", x_t.data_ptr(), out.data_ptr(), z.data_ptr(), t.data_ptr(), *[tb.data_ptr() for tb in tabs],
+                          x_t.data_ptr(), 0, B, n, mean_code, int(self.clip_sampling), T, _hip.stream())   # in place: each element is read once, then written
             _hip.call("ddpm_add_i64", t.data_ptr(), B, -1, _hip.stream())
 
         graph = self._capture_step(dev, rng, body, "sampling")
@@ -515,7 +625,8 @@ class GaussianDiffusion:
         losses = torch.full((B, T), float("nan"), dtype=torch.float32, device=dev)
         mses = torch.full_like(losses, float("nan"))
         qtabs = [self._tab(n_, dev) for n_ in ("sqrt_alphas_bar", "sqrt_one_minus_alphas_bar")]
-        tabs = [self._tab(n_, dev) for n_ in _VLB_TABLES]
+        lv = self._var_mode()
+        tabs = [self._tab(n_, dev) for n_ in (_LV_TABLES if lv else _VLB_TABLES)]
         code, clip, decoder = _MEAN_CODE[self.model_mean_type], int(bool(clip_denoised)), self.bpd_decoder
 
         def body(cut=None):
@@ -523,8 +634,13 @@ class GaussianDiffusion:
                 z.normal_(generator=rng)
             _hip.call("ddpm_q_sample", x_0.data_ptr(), z.data_ptr(), t.data_ptr(), *[tb.data_ptr() for tb in qtabs], x_t.data_ptr(), B, n, T, _hip.stream())
             out = denoise_fn(x_t, self._model_t(t)).contiguous().float()
-            _hip.call("ddpm_bpd_terms", x_0.data_ptr(), x_t.data_ptr(), out.data_ptr(), t.data_ptr(), *[tb.data_ptr() for tb in tabs],
-                      losses.data_ptr(), mses.data_ptr(), B, n, T, code, clip, decoder, T, _hip.stream())
+            if lv:
+                self._check_two_halves(out, x_0)
+                _hip.call("ddpm_bpd_terms_lv", x_0.data_ptr(), x_t.data_ptr(), out.data_ptr(), t.data_ptr(), *[tb.data_ptr() for tb in tabs],
+                          losses.data_ptr(), mses.data_ptr(), B, n, T, code, clip, decoder, lv, T, _hip.stream())
+            else:
+                _hip.call("ddpm_bpd_terms", x_0.data_ptr(), x_t.data_ptr(), out.data_ptr(), t.data_ptr(), *[tb.data_ptr() for tb in tabs],
+                          losses.data_ptr(), mses.data_ptr(), B, n, T, code, clip, decoder, T, _hip.stream())
             _hip.call("ddpm_add_i64", t.data_ptr(), B, -1, _hip.stream())
 
         return {"x_0": x_0, "z": z, "t": t, "losses": losses, "mses": mses, "rng": rng, "body": body, "ref": lambda: denoise_fn}

@@ -11,6 +11,9 @@ class GaussianDiffusion(diffusion.GaussianDiffusion):
     bpd_decoder = 1            # t = 0 term of the bound: continuous Gaussian likelihood (toy/diffusion.py:61)
 
     def __init__(self, betas, model_mean_type, model_var_type, loss_type, **kwargs):
+        if model_var_type in ("learned", "learned-range"):
+            raise NotImplementedError(f"model_var_type {model_var_type!r} is not served for the toy pipeline (its fused decoder emits the mean "
+                                      "output alone); use 'fixed-small' or 'fixed-large'")
         if loss_type == "kl":
             raise NotImplementedError("loss_type='kl' is not served for the toy pipeline (its t = 0 term is the continuous-Gaussian "
                                       "decoder likelihood); use loss_type='mse'")

@@ -614,11 +614,17 @@ class _DirectStep:
         target = dif.loss_target(self.x0, x_t, self.t, self.noise)
         tape = []
         out = eng.forward(x_t, self.t, self.unet.training, tape, seed_dev=self.hyper_dev.data_ptr() + 16)
-        losses = _hip.retain(torch.empty(B, dtype=torch.float32, device=out.device))
-        _hip.call("ddpm_mse_fwd", out.data_ptr(), target.data_ptr(), losses.data_ptr(), B, n, s())
-        _hip.call("ddpm_weighted_sum_f32", losses.data_ptr(), self.gloss.data_ptr(), self.loss.data_ptr(), B, s())   # mean over the batch
-        gout = _hip.retain(torch.empty_like(out))
-        _hip.call("ddpm_mse_bwd", out.data_ptr(), target.data_ptr(), self.gloss.data_ptr(), gout.data_ptr(), B, n, s())
+        if getattr(dif, "loss_type", None) == "hybrid":
+            # learned variance: the network's [B, 2C, H, W] output -> per-sample hybrid losses and the gradient of both halves, one launch
+            gout = _hip.retain(torch.empty_like(out))
+            losses = dif.learned_loss(self.x0, x_t, out, target.contiguous(), self.t, self.gloss, gout, 1.0, dif.vlb_weight, True)
+            _hip.call("ddpm_weighted_sum_f32", losses.data_ptr(), self.gloss.data_ptr(), self.loss.data_ptr(), B, s())   # mean over the batch
+        else:
+            losses = _hip.retain(torch.empty(B, dtype=torch.float32, device=out.device))
+            _hip.call("ddpm_mse_fwd", out.data_ptr(), target.data_ptr(), losses.data_ptr(), B, n, s())
+            _hip.call("ddpm_weighted_sum_f32", losses.data_ptr(), self.gloss.data_ptr(), self.loss.data_ptr(), B, s())   # mean over the batch
+            gout = _hip.retain(torch.empty_like(out))
+            _hip.call("ddpm_mse_bwd", out.data_ptr(), target.data_ptr(), self.gloss.data_ptr(), gout.data_ptr(), B, n, s())
         clip = bool(tr.grad_norm) and tr.grad_norm > 0
         # (the backward's last launch, which rewrites the staging buffer into the flat gradient, also produces its squared norm: per-block
         # partials added in a fixed order, so two replicas with the same gradients clip by the same coefficient, bit for bit)
@@ -660,7 +666,8 @@ class _DirectStep:
         and the engine's derived-copy tables.  A replay after any of these changed would write through dangling pointers."""
         eng, fused = self.unet.engine(), self.tr._fused
         return (eng.serial, fused.generation, fused.table.data_ptr(), eng.pack_table.data_ptr(), eng.fc_table.data_ptr(),
-                self.gflat.data_ptr(), self.unet.training, eng.pg is not None)
+                self.gflat.data_ptr(), self.unet.training, eng.pg is not None,
+                getattr(self.tr.diffusion, "model_var_type", None), getattr(self.tr.diffusion, "vlb_weight", None))
 
     def run(self, x):
         tr, eng = self.tr, self.unet.engine()
@@ -788,7 +795,7 @@ class Trainer:
                len(group["params"]) if group else 0, sum(1 for q in group["params"] if q.requires_grad) if group else 0, self.num_accum, type(self.optimizer),
                tuple(bool(group.get(k)) for k in ("amsgrad", "maximize", "weight_decay", "capturable", "differentiable", "fused")) if group else (),
                "get_input" in self.__dict__, "loss" in self.__dict__, id(self.diffusion), getattr(self.diffusion, "loss_type", None),
-               getattr(self.diffusion, "model_mean_type", None))
+               getattr(self.diffusion, "model_mean_type", None), getattr(self.diffusion, "model_var_type", None), getattr(self.diffusion, "vlb_weight", None))
         cached = getattr(self, "_direct_unet_cache", None)
         if cached is not None and cached[0] == key:
             return cached[1]

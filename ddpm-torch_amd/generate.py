@@ -95,8 +95,10 @@ def build(args, rank=0):
     shape = (info["channels"], info["resolution"][0], info["resolution"][0])
     dk = dict(meta["diffusion"])
     betas = ddpm_torch.get_beta_schedule(dk.pop("beta_schedule"), dk.pop("beta_start"), dk.pop("beta_end"), dk.pop("timesteps"))
+    learned = dk.get("model_var_type") in ("learned", "learned-range")        # the network emits 2C channels: mean output | v
     if args.use_ddim:
-        dk["model_var_type"] = "fixed-small"
+        if not learned:                                                       # (DDIM itself takes the mean half of a learned-variance model)
+            dk["model_var_type"] = "fixed-small"
         sub = ddim.get_selection_schedule(args.skip_schedule, size=args.subseq_size, timesteps=len(betas))
         process = ddim.DDIM(betas, **dk, eta=args.eta, subsequence=sub)
     else:
@@ -105,7 +107,7 @@ def build(args, rank=0):
     mk = dict(meta["model"])
     block = mk.pop("block_size", 1)
     mk["in_channels"] = mk.get("in_channels", info["channels"]) * block ** 2
-    model = ddpm_torch.UNet(out_channels=info["channels"] * block ** 2, **mk).set_compute_dtype(args.compute)
+    model = ddpm_torch.UNet(out_channels=(2 if learned else 1) * info["channels"] * block ** 2, **mk).set_compute_dtype(args.compute)
     if block > 1:
         model = ddpm_torch.ModelWrapper(model, torch.nn.PixelUnshuffle(block), torch.nn.PixelShuffle(block))
     model.to(device)

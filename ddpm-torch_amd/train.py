@@ -52,8 +52,8 @@ def parse_args(argv=None):
     add("--beta-start", default=1e-4, type=float)
     add("--beta-end", default=0.02, type=float)
     add("--model-mean-type", choices=["mean", "x_0", "eps"], default="eps")
-    add("--model-var-type", choices=["learned", "fixed-small", "fixed-large"], default="fixed-large")
-    add("--loss-type", choices=["kl", "mse"], default="mse")
+    add("--model-var-type", choices=["learned", "learned-range", "fixed-small", "fixed-large"], default="fixed-large")
+    add("--loss-type", choices=["kl", "mse", "hybrid"], default="mse")
     add("--num-workers", default=4, type=int)
     add("--train-device", default="cuda:0", type=str)
     add("--eval-device", default="cuda:0", type=str)
@@ -131,7 +131,7 @@ def run(rank=0, args=None, temp_dir=""):
 
     mcfg = dict(meta["model"])
     block = mcfg.pop("block_size", args.block_size)
-    out_channels = 2 * in_channels if dcfg.model_var_type == "learned" else in_channels
+    out_channels = 2 * in_channels if dcfg.model_var_type in ("learned", "learned-range") else in_channels
     mcfg.update(in_channels=in_channels * block ** 2, out_channels=out_channels * block ** 2)
     unet = ddpm_torch.UNet(**mcfg).set_compute_dtype(args.compute)
     net = unet if block == 1 else ddpm_torch.ModelWrapper(unet, torch.nn.PixelUnshuffle(block), torch.nn.PixelShuffle(block))

@@ -229,6 +229,44 @@ int ddpm_bpd_terms(const float* x_0, const float* x_t, const float* model_out, c
                    int B, int n, int ld, int mean_type, int clip, int decoder, int T, void* stream);
 int ddpm_bpd_finish(const float* x_0, const float* losses, float* prior, float* total, int B, int n, int T, int ld,
                     float sqrt_ab_last, float log_1m_ab_last, void* stream);
+/* Learned reverse-process variance (model_var_type "learned", diffusion.py:111-114, and "learned-range", Nichol & Dhariwal 2021 eq. 15).
+ * model_out is [B][2n] fp32: the mean output (eps / x_0 / mean by mean_type, as above) at b*2n + i and v at b*2n + n + i, both read in place.
+ * The model log-variance of an element is
+ *   var_mode 1: v;    var_mode 2: f*lv_max[t] + (1 - f)*lv_min[t] with f = (v + 1)/2, not clamped (each product and sum rounded on its
+ *   own: v = +1 / -1 give the table entries to the bit);    var_mode 0 (step only): the table entry logvar_lo[t], v ignored.
+ * Model mean, KL, discretized decoder (decoder 0 only), operation order and reduction trees are those of the fixed-variance siblings
+ * with that log-variance in the place of model_logvar[t].  fp32, no atomics, fixed reduction order: repeated launches are bit-identical.
+ * Tables have length T; a sample whose t is outside [0, T) is poisoned with NaN (step, terms, loss: every output of the sample) or writes
+ * nothing (ddpm_bpd_terms_lv), and no table is read for it.
+ * ddpm_p_sample_step_lv: ddpm_p_sample_step's update and noise mask.  var_mode 0: logvar_lo = the fixed table (logvar_hi may be NULL);
+ *   1: both may be NULL; 2: logvar_lo = lv_min (posterior_logvar_clipped), logvar_hi = lv_max (the "fixed-large" table).  pred_x0 may be
+ *   NULL; x_prev may be x_t (an element is read once, then written).
+ * ddpm_vlb_terms_lv / ddpm_bpd_terms_lv: ddpm_vlb_terms (loss [B], optional pred_x0) and ddpm_bpd_terms (column t[b] of the [B][ld]
+ *   tables; the three row layouts: a wave per row for n <= 64, 256 threads, 1024 threads with 16-byte loads where the four row bases are
+ *   16-byte aligned) with var_mode 1 | 2; post_logvar is the true posterior's table and lv_min, logvar_max (NULL allowed for var_mode 1) lv_max.
+ * ddpm_learned_loss: one pass over x_0, x_t, model_out, target (all [B][n] but model_out), clip_denoised = False:
+ *   loss[b]        = w_mse * mean_i (out_mean - target)^2 + w_vlb * L_t(out_mean, v)                     (L_t in bits/dim)
+ *   gout[b][i]     = gloss[b] * (w_mse * 2 (out_mean - target) / n + (detach_mean ? 0 : w_vlb * dL_t/d out_mean))       i < n
+ *   gout[b][n + i] = gloss[b] * w_vlb * dL_t/dv            (through logvar; var_mode 2: times (lv_max[t] - lv_min[t]) / 2)
+ *   The backward differentiates the forward's own expressions (tanh CDF, floor, open tails).  gout NULL: the loss alone (gloss unused).
+ *   A weight of exactly 0 switches its term off: target may be NULL when w_mse = 0; with w_vlb = 0 the v half of gout is 0.0.
+ *   (1, lambda, detach_mean 1) is the hybrid loss of eq. 16, (0, 1, 0) loss_type "kl" with its full gradient. */
+int ddpm_p_sample_step_lv(const float* x_t, const float* model_out, const float* z, const long long* t,
+                          const float* sqrt_recip_ab, const float* sqrt_recip_m1_ab, const float* post_coef1, const float* post_coef2,
+                          const float* logvar_lo, const float* logvar_hi, float* x_prev, float* pred_x0,
+                          int B, int n, int mean_type, int clip, int var_mode, int T, void* stream);
+int ddpm_vlb_terms_lv(const float* x_0, const float* x_t, const float* model_out, const long long* t,
+                      const float* sqrt_recip_ab, const float* sqrt_recip_m1_ab, const float* post_coef1, const float* post_coef2,
+                      const float* post_logvar, const float* logvar_max, float* loss, float* pred_x0,
+                      int B, int n, int mean_type, int clip, int var_mode, int T, void* stream);
+int ddpm_bpd_terms_lv(const float* x_0, const float* x_t, const float* model_out, const long long* t,
+                      const float* sqrt_recip_ab, const float* sqrt_recip_m1_ab, const float* post_coef1, const float* post_coef2,
+                      const float* post_logvar, const float* logvar_max, float* losses, float* mses,
+                      int B, int n, int ld, int mean_type, int clip, int decoder, int var_mode, int T, void* stream);
+int ddpm_learned_loss(const float* x_0, const float* x_t, const float* model_out, const float* target, const long long* t,
+                      const float* sqrt_recip_ab, const float* sqrt_recip_m1_ab, const float* post_coef1, const float* post_coef2,
+                      const float* post_logvar, const float* logvar_max, const float* gloss, float* loss, float* gout,
+                      int B, int n, int mean_type, int var_mode, int detach_mean, int T, float w_mse, float w_vlb, void* stream);
 /* subsequence.gather(0, t) (ddim.py:101) and t += delta (t.fill_ in diffusion.py:172, device-side for graph replay) */
 int ddpm_gather_i64(const long long* idx, const long long* map, long long* out, int B, void* stream);
 int ddpm_add_i64(long long* t, int B, long long delta, void* stream);
