@@ -469,7 +469,7 @@ extern "C" int ddpm_mse_bwd(const float* pred, const float* target, const float*
 //              tails beyond |x_0| = 0.999, the difference floored as the reference floors it (clamp(d - 1e-12, 0) + 1e-12).
 // The backward (d loss_b / d model_out, training: clip_denoised = False) differentiates exactly those expressions.
 struct VlbTables { const float *recip, *recip_m1, *coef1, *coef2, *post_logvar, *model_logvar; };
-struct VlbCoef { float recip, recip_m1, c1, c2, lv1, lv2; };
+// (struct VlbCoef { recip, recip_m1, c1, c2, lv1, lv2 }: common.h, shared with guidance.hip)
 __device__ __forceinline__ float vlb_cdf(float z) {
     return 0.5f * (1.0f + tanhf(0.7978845608028654f * (z + 0.044715f * z * z * z)));
 }
@@ -932,20 +932,8 @@ __device__ __forceinline__ float lv_logvar(int var_mode, float v, float lv_min, 
     const float f = 0.5f * (v + 1.0f);
     return f * lv_max + (1.0f - f) * lv_min;
 }
-// One element of the sampling update with p_step_kernel's arithmetic AS THAT KERNEL IS COMPILED, so that on equal log-variances the two
-// kernels give the same bits: every product and sum rounded on its own, except the two places where the compiler fuses p_step_kernel's —
-// the x_0 estimate of mean_type 2, fma(-x_t, c2 / c1, out / c1), and the final mean + (mask sd) z.  Written out here instead of left to the
-// optimiser, whose choice depends on the surrounding code.
-__device__ __forceinline__ void lv_step_elem(const VlbCoef& k, int mean_type, int clip, float xt, float o, float mask_sd, float z, float& x_prev,
-                                             float& x0) {
-#pragma clang fp contract(off)
-    if (mean_type == 0) x0 = k.recip * xt - k.recip_m1 * o;
-    else if (mean_type == 1) x0 = o;
-    else x0 = __builtin_fmaf(-xt, k.c2 / k.c1, o / k.c1);
-    if (clip) x0 = x0 != x0 ? x0 : fminf(fmaxf(x0, -1.f), 1.f);
-    const float mean = mean_type == 2 ? o : k.c1 * x0 + k.c2 * xt;
-    x_prev = __builtin_fmaf(z, mask_sd, mean);
-}
+// (lv_step_elem — one element of the sampling update with p_step_kernel's arithmetic as that kernel is compiled — is in common.h: the
+// guided step of guidance.hip is built on the same function.)
 // the per-row constants of bpd_const with the model log-variance of ONE element in the place of the table entry
 __device__ __forceinline__ BpdConst bpd_const_lv(const VlbCoef& row, float lv2) {
     BpdConst c;

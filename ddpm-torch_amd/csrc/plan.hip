@@ -82,6 +82,7 @@ const EntryPoint kEntryPoints[] = {
     EP(ddpm_manifold_kth_f16), EP(ddpm_manifold_cover_f16), EP(ddpm_bpd_terms), EP(ddpm_bpd_finish), EP(ddpm_batch_gather),
     EP(ddpm_ddim_encode_step), EP(ddpm_slerp), EP_SIZE_OF(ddpm_slerp_workspace_floats),
     EP(ddpm_p_sample_step_lv), EP(ddpm_vlb_terms_lv), EP(ddpm_bpd_terms_lv), EP(ddpm_learned_loss),
+    EP(ddpm_class_embed_fwd), EP(ddpm_class_embed_bwd), EP(ddpm_p_sample_step_cfg),
 };
 constexpr int kNumEntryPoints = (int)(sizeof(kEntryPoints) / sizeof(kEntryPoints[0]));
 

@@ -94,9 +94,11 @@ class DDIM(ddpm_torch.GaussianDiffusion):
         return super().p_sample_step(lambda x, tt: denoise_fn(x, self._model_t(tt)), x_t, t, clip_denoised, return_pred, generator)
 
     @torch.inference_mode()
-    def p_sample(self, denoise_fn, shape, device=torch.device("cpu"), noise=None, seed=None):
-        """ddim.py:96-113: S = len(subsequence) steps, same RNG consumption order as the ancestral loop."""
-        return self._sample_loop(denoise_fn, shape, device, noise, seed)
+    def p_sample(self, denoise_fn, shape, device=torch.device("cpu"), noise=None, seed=None, y=None, guidance_scale=1.0):
+        """ddim.py:96-113: S = len(subsequence) steps, same RNG consumption order as the ancestral loop.  ``y`` / ``guidance_scale``
+        (not in the reference): class labels and classifier-free guidance as in ``GaussianDiffusion.p_sample`` — the guided step kernel on
+        this sampler's own tables."""
+        return self._sample_loop(denoise_fn, shape, device, noise, seed, y=y, guidance_scale=guidance_scale)
 
     # ------------------------------------------------------------------ the sampler's ODE in both directions
     def _check_invertible(self):
@@ -145,6 +147,8 @@ class DDIM(ddpm_torch.GaussianDiffusion):
         return {"x_t": x_t, "t": t, "z": z, "pred": pred, "rng": None, "body": body, "ref": lambda: denoise_fn}
 
     def _capture_kind_step(self, denoise_fn, shape, device, default_rng, external_z, kind):
+        if kind[0] not in ("encode", "decode"):                    # the conditional / guided sampling step: the base class captures it
+            return super()._capture_kind_step(denoise_fn, shape, device, default_rng, external_z, kind)
         ent = self._ode_state(denoise_fn, shape, device, kind)
         ent["graph"] = self._capture_step(device, None, ent["body"], "DDIM " + kind[0])
         return ent if ent["graph"] is not None else None
@@ -173,28 +177,33 @@ class DDIM(ddpm_torch.GaussianDiffusion):
                 on_step(i, ent["pred"])
         return ent["x_t"].clone()
 
-    def encode(self, denoise_fn, x_0, return_pred=False):
+    def encode(self, denoise_fn, x_0, return_pred=False, y=None):
         """The latent x_T that the eta = 0 sampler takes back to ``x_0`` (up to the discretisation error of S steps): S network
         evaluations at ``subsequence[0 ... S-1]`` with the fused update of the module docstring behind each.  No clipping, no RNG.
         ``return_pred``: also the x_0 estimates of the S steps, ``[S, B, ...]`` on the device (this per-step read-back runs the eager
-        loop).  Raises ValueError for eta != 0 and NotImplementedError for the x_0 / mean parameterisations."""
+        loop).  Raises ValueError for eta != 0 and NotImplementedError for the x_0 / mean parameterisations.  ``y``: class labels of a
+        class-conditional network, evaluated conditionally (guidance scale 1; guided inversion is not served)."""
         self._check_invertible()
+        if y is not None:
+            denoise_fn = ddpm_torch.diffusion.Conditioned(denoise_fn, y.to(x_0.device))
         preds = []
         keep = (lambda i, pred: preds.append(pred.clone())) if return_pred else None
         with torch.inference_mode(), self._time_tables(denoise_fn):
             latent = self._ode_loop(denoise_fn, x_0, ("encode",), on_step=keep)
             return (latent, torch.stack(preds)) if return_pred else latent
 
-    def decode(self, denoise_fn, latent, clip_denoised=True):
+    def decode(self, denoise_fn, latent, clip_denoised=True, y=None):
         """The sampling loop started from ``latent`` (level S-1) with an explicit clip flag: x_0, float32 on the latent's device.  At
-        eta = 0 it is deterministic and touches no generator."""
+        eta = 0 it is deterministic and touches no generator.  ``y``: as in ``encode``."""
+        if y is not None:
+            denoise_fn = ddpm_torch.diffusion.Conditioned(denoise_fn, y.to(latent.device))
         with torch.inference_mode(), self._time_tables(denoise_fn):
             return self._ode_loop(denoise_fn, latent, ("decode", bool(clip_denoised)))
 
-    def reconstruct(self, denoise_fn, x_0, clip_denoised=False):
+    def reconstruct(self, denoise_fn, x_0, clip_denoised=False, y=None):
         """``decode(encode(x_0))`` -> ``(x_rec, latent)`` (Song et al. 2020 §5.4, Table 2)."""
-        latent = self.encode(denoise_fn, x_0)
-        return self.decode(denoise_fn, latent, clip_denoised), latent
+        latent = self.encode(denoise_fn, x_0, y=y)
+        return self.decode(denoise_fn, latent, clip_denoised, y=y), latent
 
     def interpolate(self, denoise_fn, x_a, x_b, num=9, encoded=False, clip_denoised=True, batch_size=None):
         """Semantic interpolation of the pairs ``x_a[p], x_b[p]`` (Song et al. 2020 §5.3): both ends are encoded in one batch of 2 P

@@ -105,6 +105,10 @@ PROTOTYPES = {
     "ddpm_ddim_encode_step": [P] * 9 + [I, I, I, P],
     "ddpm_slerp": [P, P, P, P, P, I, I, I, P],
     "ddpm_slerp_workspace_floats": [I, I],
+    # class conditioning and classifier-free guidance (csrc/guidance.hip; driven by models/unet.py and the samplers)
+    "ddpm_class_embed_fwd": [P, P, P, P, P, I, I, I, P],
+    "ddpm_class_embed_bwd": [P, P, P, I, I, I, P],
+    "ddpm_p_sample_step_cfg": [P] * 9 + [F, P, P] + [I] * 6 + [P],
     # launch plans (csrc/plan.hip; driven by _plan.LaunchPlan)
     "ddpm_stream_order": [P, P],
     "ddpm_fill_zero": [P, L, P],

@@ -11,9 +11,12 @@ the accelerated hot path, so the four datasets are read from 
 * ``CelebA_HQ``  ``<root>/celeba_hq/img_celeba_hq/*.png`` in ProGAN's legacy order (numeric sort, ``RandomState(123).shuffle``), flip
                  (:156-198).
 
-Every class yields one image per item and no label: a float ``[C, H, W]`` tensor in [-1, 1] (``ToTensor`` + ``Normalize(0.5, 0.5)``),
+Every class yields one image per item and, by default, no label: a float ``[C, H, W]`` tensor in [-1, 1] (``ToTensor`` + ``Normalize(0.5, 0.5)``),
 or — ``transform=None`` / ``raw=True``, what the evaluation code reads — the uint8 ``[C, H, W]`` tensor.  ``DATASET_INFO`` carries the
-class constants (resolution, channels, split sizes) the CLIs size their models and sample grids from.
+class constants (resolution, channels, split sizes) the CLIs size their models and sample grids from.  ``labels=True`` (class-conditional
+training; not in the reference, whose loaders drop them) makes the readers whose format carries a class — MNIST's idx1 label files,
+CIFAR-10's ``labels`` lists, a tensor file saved as ``{"images": ..., "labels": ...}``, the synthetic stand-in (``index % num_classes``) —
+yield ``(image, label)`` pairs; a data set without classes raises ``ValueError``.
 
 Two more sources exist for boxes without the datasets (this build container and the GPU box have neither the files nor a network):
 a **tensor file** ``<root>/<dataset>[_<split>].pt`` (uint8 or [-1, 1] float ``[N, C, H, W]``; tried FIRST, it is also the fastest way to
@@ -69,14 +72,18 @@ class _Images(Dataset):
     """Common part: ``_load(i)`` -> uint8 [C, H, W]; ``transform=None`` (the reference's raw form) returns it, the default training form
     flips (where the reference's transform does) and normalises.  ``transform`` may also be any callable on the uint8 tensor."""
     flip = False
+    num_classes = None                                         # classes of the on-disk labels; None: the format carries none
 
-    def __init__(self, root=ROOT, split="train", transform="train"):
+    def __init__(self, root=ROOT, split="train", transform="train", labels=False):
         self.root, self.split, self.transform = os.path.expanduser(root), split, transform
+        if labels and self.num_classes is None:
+            raise ValueError(f"{type(self).__name__} carries no class labels")
+        self.labels = None                                     # int64 [N] when asked for (filled by the subclass): items are (image, label)
 
     def _load(self, index):
         raise NotImplementedError
 
-    def __getitem__(self, index):
+    def _image(self, index):
         x = self._load(index)
         if self.transform is None:
             return x
@@ -85,6 +92,10 @@ class _Images(Dataset):
         if self.flip and torch.rand(1) < 0.5:                  # RandomHorizontalFlip: one uniform draw per image
             x = x.flip(-1)
         return _to_unit(x)
+
+    def __getitem__(self, index):
+        x = self._image(index)
+        return x if self.labels is None else (x, int(self.labels[index]))
 
 
 def _read_idx_images(path):
@@ -99,21 +110,42 @@ def _read_idx_images(path):
     return data.reshape(n, h, w)
 
 
+def _read_idx_labels(path):
+    opener = gzip.open if path.endswith(".gz") else open
+    with opener(path, "rb") as f:
+        magic, n = struct.unpack(">II", f.read(8))
+        if magic != 2049:
+            raise ValueError(f"{path}: not an idx1-ubyte label file (magic {magic})")
+        data = np.frombuffer(f.read(n), dtype=np.uint8)
+    if data.size != n:
+        raise ValueError(f"{path}: truncated ({data.size} of {n} bytes)")
+    return torch.from_numpy(data.astype(np.int64))
+
+
 @_register
 class MNIST(_Images):
     resolution = (32, 32)
     channels = 1
     train_size = 60000
     test_size = 10000
+    num_classes = 10
 
-    def __init__(self, root=ROOT, split="train", transform="train"):
-        super().__init__(root, split, transform)
+    def __init__(self, root=ROOT, split="train", transform="train", labels=False):
+        super().__init__(root, split, transform, labels)
         stem = "t10k" if split == "test" else "train"
         base = os.path.join(self.root, "MNIST", "raw", f"{stem}-images-idx3-ubyte")
         path = next((p for p in (base, base + ".gz") if os.path.exists(p)), None)
         if path is None:
             raise FileNotFoundError(base)
         self.data = _read_idx_images(path)
+        if labels:
+            base = os.path.join(self.root, "MNIST", "raw", f"{stem}-labels-idx1-ubyte")
+            path = next((p for p in (base, base + ".gz") if os.path.exists(p)), None)
+            if path is None:
+                raise FileNotFoundError(base)
+            self.labels = _read_idx_labels(path)
+            if len(self.labels) != len(self.data):
+                raise ValueError(f"{path}: {len(self.labels)} labels for {len(self.data)} images")
 
     def __len__(self):
         return len(self.data)
@@ -142,12 +174,13 @@ class CIFAR10(_Images):
     train_size = 50000
     test_size = 10000
     flip = True
+    num_classes = 10
 
-    def __init__(self, root=ROOT, split="train", transform="train"):
-        super().__init__(root, split, transform)
+    def __init__(self, root=ROOT, split="train", transform="train", labels=False):
+        super().__init__(root, split, transform, labels)
         folder = os.path.join(self.root, "cifar-10-batches-py")
         names = ["test_batch"] if split == "test" else [f"data_batch_{i}" for i in range(1, 6)]
-        parts = []
+        parts, classes = [], []
         for fn in names:
             path = os.path.join(folder, fn)
             if not os.path.exists(path):
@@ -155,7 +188,11 @@ class CIFAR10(_Images):
             with open(path, "rb") as f:
                 entry = _ArraysOnly(io.BytesIO(f.read()), encoding="latin1").load()
             parts.append(np.asarray(entry["data"], dtype=np.uint8).reshape(-1, 3, 32, 32))
+            if labels:
+                classes.append(np.asarray(entry["labels"], dtype=np.int64))
         self.data = np.concatenate(parts)
+        if labels:
+            self.labels = torch.from_numpy(np.concatenate(classes))
 
     def __len__(self):
         return len(self.data)
@@ -184,8 +221,8 @@ class CelebA(_Images):
     test_size = 19962
     flip = True
 
-    def __init__(self, root=ROOT, split="train", transform="train"):
-        super().__init__(root, split, transform)
+    def __init__(self, root=ROOT, split="train", transform="train", labels=False):
+        super().__init__(root, split, transform, labels)
         want = {"train": 0, "valid": 1, "test": 2, "all": None}[split.lower()]
         part = os.path.join(self.root, self.base_folder, "list_eval_partition.txt")
         if not os.path.exists(part):
@@ -216,8 +253,8 @@ class CelebA_HQ(_Images):
     train_size = 24000                       # (this package's CLI reports progress against it; the reference trains on all 30000)
     flip = True
 
-    def __init__(self, root=ROOT, split="train", transform="train"):
-        super().__init__(root, split, transform)             # split is unused, as in the reference
+    def __init__(self, root=ROOT, split="train", transform="train", labels=False):
+        super().__init__(root, split, transform, labels)     # split is unused, as in the reference
         folder = os.path.join(self.root, self.base_folder, "img_celeba_hq")
         if not os.path.isdir(folder):
             raise FileNotFoundError(folder)
@@ -252,17 +289,25 @@ class ImageFolder(Dataset):
 
 
 class TensorImages(Dataset):
-    """Images held in one tensor; ``__getitem__`` returns a float image in [-1, 1] (unconditional: no label), or the stored uint8 image
-    when ``raw``."""
+    """Images held in one tensor; ``__getitem__`` returns a float image in [-1, 1], or the stored uint8 image when ``raw`` — and, with
+    ``labels`` (int64 ``[N]``), the pair (image, label)."""
 
-    def __init__(self, data, flip=False, raw=False):
+    def __init__(self, data, flip=False, raw=False, labels=None):
         assert data.ndim == 4, "expected [N, C, H, W]"
         self.data, self.flip, self.raw = data, flip, raw
+        if labels is not None:
+            labels = torch.as_tensor(labels).to(torch.int64)
+            assert labels.shape == (data.shape[0],), "expected one label per image"
+        self.labels = labels
 
     def __len__(self):
         return self.data.shape[0]
 
     def __getitem__(self, i):
+        x = self._image(i)
+        return x if self.labels is None else (x, int(self.labels[i]))
+
+    def _image(self, i):
         x = self.data[i]
         if self.raw:
             return x if x.dtype == torch.uint8 else (x * 127.5 + 128).clamp(0, 255).to(torch.uint8)
@@ -303,7 +348,7 @@ def _resident(data, num_workers):
             images = torch.from_numpy(data.data)
         else:                                                    # decode (and resize) every image once, in the caller's worker processes
             raw = copy.copy(data)
-            raw.transform = None
+            raw.transform, raw.labels = None, None
             images, at = None, 0                                 # filled chunk by chunk: the data set is held once (CelebA-HQ is 5.9 GB)
             for chunk in DataLoader(raw, batch_size=256, num_workers=num_workers):
                 if images is None:
@@ -313,6 +358,14 @@ def _resident(data, num_workers):
         return images, None, _to_unit(every_byte)
     raise TypeError(f"{type(data).__name__}: not a data set DeviceLoader can hold on the device (TensorImages of uint8 / float32 in its "
                     f"training form, the dataset classes of this module in theirs, or a Subset of one)")
+
+
+def _resident_labels(data):
+    """int64 labels aligned with the images ``_resident`` returns (before its positions are applied), None for an unlabelled data set."""
+    while isinstance(data, Subset):
+        data = data.dataset
+    labels = getattr(data, "labels", None)
+    return None if labels is None else torch.as_tensor(labels).to(torch.int64)
 
 
 class _Epoch:
@@ -334,7 +387,9 @@ class _Epoch:
         out = torch.empty((hi - lo, c, h, w), dtype=torch.float32, device=data.device)
         _hip.call("ddpm_batch_gather", data.data_ptr(), 0 if data.dtype == torch.uint8 else 1, self.index.data_ptr() + 8 * lo, _hip.ptr(lut),
                   out.data_ptr(), hi - lo, n, c, h, w, int(self.loader.flip), self.seed, _hip.stream())
-        return out
+        if self.loader.labels is None:
+            return out
+        return out, self.loader.labels.index_select(0, self.index[lo:hi])      # the labels of the same images, by the same indices
 
 
 class DeviceLoader:
@@ -349,7 +404,10 @@ class DeviceLoader:
 
     Flips do not consume the global generator: image i is mirrored iff the top bit of the library's counter hash of
     ``((random_seed or 0) << 32 | epoch, i)`` is set, ``epoch`` = ``sampler.epoch`` where the sampler has one, else the number of
-    earlier ``iter()`` calls — the same for any batch size and any number of ranks."""
+    earlier ``iter()`` calls — the same for any batch size and any number of ranks.
+
+    A labelled data set (``TensorImages(..., labels=)``, a dataset class opened with ``labels=True``) also keeps its int64 labels on the
+    device, and every batch is the pair ``(images, labels)``: the labels gathered by the indices the images were."""
 
     def __init__(self, data, batch_size, device, shuffle=False, sampler=None, drop_last=False, flip=None, random_seed=None, num_workers=0):
         images, self._positions, lut = _resident(data, num_workers)
@@ -361,6 +419,8 @@ class DeviceLoader:
         self.device = torch.device(device)
         self.data = images.contiguous().to(self.device)
         self.lut = None if lut is None else lut.to(self.device)
+        labels = _resident_labels(data)
+        self.labels = None if labels is None else labels.contiguous().to(self.device)
         _hip.require_cuda(self.data)
         self.flip, self.sampler, self.random_seed = bool(flip), sampler, random_seed or 0
         self.batch_size = batch_size
@@ -384,38 +444,55 @@ class DeviceLoader:
         return _Epoch(self, index.to(self.device, non_blocking=True), ends, seed)
 
 
-def _open(name, root, split, raw=False):
-    """Tensor file, then the dataset's own files, then (if asked for) synthetic images."""
+def _open(name, root, split, raw=False, labels=False, num_classes=None):
+    """Tensor file, then the dataset's own files, then (if asked for) synthetic images.  ``labels``: items are (image, label) pairs;
+    ``num_classes`` (default: the data set's own count) is what the synthetic labels are taken modulo and what every label must be below."""
     info = DATASET_INFO[name]
+    if labels and info.get("num_classes") is None:
+        raise ValueError(f"{name} carries no class labels")
+    data = _open_source(name, info, root, split, raw, labels, num_classes or info.get("num_classes"))
+    if labels and num_classes is not None and len(data) and not 0 <= int(data.labels.min()) <= int(data.labels.max()) < num_classes:
+        raise ValueError(f"{name}: labels span [{int(data.labels.min())}, {int(data.labels.max())}], the model has {num_classes} classes")
+    return data
+
+
+def _open_source(name, info, root, split, raw, labels, modulus):
     shape = (info["channels"],) + tuple(info["resolution"])
     root = os.path.expanduser(root)
     for fn in (f"{name}_{split}.pt", f"{name}.pt"):
         path = os.path.join(root, fn)
         if os.path.exists(path):
-            data = torch.load(path, map_location="cpu")
+            data, classes = torch.load(path, map_location="cpu"), None
+            if isinstance(data, dict):                          # {"images": [N, C, H, W], "labels": [N]}
+                data, classes = data["images"], data.get("labels")
             assert tuple(data.shape[1:]) == shape, f"{path}: images of shape {tuple(data.shape[1:])}, expected {shape}"
-            return TensorImages(data, flip=(DATASET_DICT[name].flip and split != "test"), raw=raw)
+            if labels and classes is None:
+                raise ValueError(f"{path} has no 'labels' entry next to its images")
+            return TensorImages(data, flip=(DATASET_DICT[name].flip and split != "test"), raw=raw, labels=classes if labels else None)
     try:
-        return DATASET_DICT[name](root=root, split=split, transform=None if raw else "train")
+        return DATASET_DICT[name](root=root, split=split, transform=None if raw else "train", **({"labels": True} if labels else {}))
     except FileNotFoundError as e:
         missing = e
     n = int(os.environ.get("DDPM_TORCH_AMD_SYNTHETIC_DATA", "0"))
     if n > 0:
         g = torch.Generator().manual_seed(1234)
-        return TensorImages(torch.rand((n,) + shape, generator=g) * 2 - 1, raw=raw)
+        return TensorImages(torch.rand((n,) + shape, generator=g) * 2 - 1, raw=raw,
+                            labels=torch.arange(n) % modulus if labels else None)
     raise FileNotFoundError(
         f"{name}: neither a tensor file {name}.pt under {root} ([N, C, H, W] uint8 or float) nor the dataset's own files ({missing}).  "
         f"Set DDPM_TORCH_AMD_SYNTHETIC_DATA=<N> for N synthetic images of shape {shape}.")
 
 
 def get_dataloader(dataset, batch_size, split, val_size=0., random_seed=None, root=ROOT, pin_memory=False, drop_last=False,
-                   num_workers=0, distributed=False, raw=False, device=None, **kwargs):
+                   num_workers=0, distributed=False, raw=False, device=None, labels=False, num_classes=None, **kwargs):
     """(DataLoader, sampler) with the reference's batch / shard semantics (datasets.py:225-266).  ``device``: the same batches, in the same
     order, from a ``DeviceLoader`` that holds the data set on that GPU (training form only; ``num_workers`` then only serves the one-off
-    decode of a dataset read from image files)."""
+    decode of a dataset read from image files).  ``labels``: batches are ``(images, int64 labels)`` pairs (class-conditional training);
+    ``ValueError`` for a data set without classes, or one whose labels do not all lie below ``num_classes`` (the model's class count, when
+    given; the synthetic stand-in takes its labels modulo it)."""
     if device is not None and raw:
         raise ValueError("device= serves the training form only: the evaluation readers (raw=True) stay on the host path")
-    data = _open(dataset, root, split, raw=raw)
+    data = _open(dataset, root, split, raw=raw, labels=labels, num_classes=num_classes)
     flip = data.flip and split != "test"
     if distributed:
         batch_size = batch_size // int(os.environ.get("WORLD_SIZE", "1"))

@@ -122,6 +122,20 @@ class _AutogradLearnedLoss(torch.autograd.Function):
         return g, None, None, None, None, None
 
 
+class Conditioned(torch.nn.Module):
+    """``denoise_fn`` with its class labels bound: ``forward(x, t) = denoise_fn(x, t, y)``.  What the loops without a label input of their own
+    (``calc_all_bpd``, ``DDIM.encode`` / ``decode``) evaluate a class-conditional network through, at guidance scale 1.  A module, so the
+    engines of the UNets inside it are found; a new object per call, so its captured step is captured for that call."""
+
+    def __init__(self, denoise_fn, y):
+        super().__init__()
+        self.fn, self.y = denoise_fn, y
+        self.training = bool(getattr(denoise_fn, "training", False))
+
+    def forward(self, x, t):
+        return self.fn(x, t, self.y)
+
+
 class GaussianDiffusion:
     # whether the sampling loops (eager and captured) clamp the x_0 estimate to [-1, 1] (diffusion.py:152-158 pass clip_denoised=True);
     # the 2-D toy subclass never clips (toy/diffusion.py:32)
@@ -289,11 +303,15 @@ class GaussianDiffusion:
                   len(self.posterior_mean_coef1), _hip.stream())
         return (loss, pred) if return_pred else loss
 
-    def train_losses(self, denoise_fn, x_0, t, noise=None):
+    def train_losses(self, denoise_fn, x_0, t, noise=None, y=None):
         """diffusion.py:217-243 -> per-sample losses [B]: "mse" (unweighted), "kl" (the variational-bound term, :222-224) or, for a learned
-        variance, "hybrid" (Nichol & Dhariwal 2021 eq. 16): mean (out_mean - target)^2 + vlb_weight * L_t(stopgrad(out_mean), v)."""
+        variance, "hybrid" (Nichol & Dhariwal 2021 eq. 16): mean (out_mean - target)^2 + vlb_weight * L_t(stopgrad(out_mean), v).
+        ``y`` (class-conditional models; not in the reference): int64 [B] labels handed to the network as its third input."""
         if self.loss_type not in ("mse", "kl", "hybrid"):
             raise NotImplementedError(self.loss_type)
+        if y is not None:
+            net = denoise_fn
+            denoise_fn = lambda x, tt: net(x, tt, y)                    # noqa: E731
         if noise is None:
             noise = torch.randn_like(x_0)
         x_t = self.q_sample(x_0, t, noise=noise)
@@ -354,6 +372,39 @@ class GaussianDiffusion:
                   x_t.shape[0], x_t[0].numel(), _MEAN_CODE[self.model_mean_type], int(bool(clip_denoised)), mode, len(self.posterior_mean_coef1),
                   _hip.stream())
 
+    def _step_cfg_call(self, state, out2, z, t, scale, pred, B):
+        """`ddpm_p_sample_step_cfg` in place on the doubled state ``[2B, ...]``: rows [0, B) are read, both halves are written (dup)."""
+        dev = state.device
+        tabs = [self._tab(n_, dev).data_ptr() for n_ in _STEP_TABLES]
+        _hip.call("ddpm_p_sample_step_cfg", state.data_ptr(), out2.data_ptr(), z.data_ptr(), t.data_ptr(), *tabs, float(scale), state.data_ptr(),
+                  _hip.ptr(pred), B, state[0].numel(), _MEAN_CODE[self.model_mean_type], int(bool(self.clip_sampling)), 1,
+                  len(self.posterior_mean_coef1), _hip.stream())
+
+    @staticmethod
+    def _null_class(denoise_fn):
+        """Index of the null class of the class-conditional network behind ``denoise_fn`` (its ``num_classes``)."""
+        k = getattr(denoise_fn, "num_classes", None)
+        if k is None and isinstance(denoise_fn, torch.nn.Module):
+            k = next((m.num_classes for m in denoise_fn.modules() if getattr(m, "num_classes", None) is not None), None)
+        if k is None:
+            raise ValueError("classifier-free guidance needs a class-conditional network (an attribute num_classes names its null class)")
+        return int(k)
+
+    def _guidance_form(self, denoise_fn, y, guidance_scale):
+        """How a sampling loop calls the network and which step kernel follows it: None (no labels: the unconditional call), ``("cond",)``
+        (labels at scale 1: a B-row call with ``y`` and the plain step) or ``("cfg", scale, null)`` — classifier-free guidance (Ho & Salimans
+        2022): ONE network call on the doubled batch [x | x] with labels [y | null], then `ddpm_p_sample_step_cfg` on
+        scale * out_c + (1 - scale) * out_u.  Also the ``kind`` a captured step of the form is cached under."""
+        if y is None:
+            return None
+        scale = float(guidance_scale)
+        if scale == 1.0:
+            return ("cond",)
+        if self.learned_var:
+            raise NotImplementedError("classifier-free guidance (guidance_scale != 1) of a learned-variance model: the guided step kernel "
+                                      "combines the mean output on a fixed variance table; sample such a model at guidance_scale = 1")
+        return ("cfg", scale, self._null_class(denoise_fn))
+
     def _model_logvar(self, model_out, x_t, t):
         """Per-element log-variance of a learned-variance model from the v half (diffusion.py:113-114; eq. 15 for "learned-range")."""
         v = model_out.contiguous().float().reshape(x_t.shape[0], 2, -1)[:, 1].reshape(x_t.shape)
@@ -384,13 +435,15 @@ class GaussianDiffusion:
     def _model_t(self, t):
         return t
 
-    def _sample_loop(self, denoise_fn, shape, device, noise, seed, on_step=None, z_stream=None):
+    def _sample_loop(self, denoise_fn, shape, device, noise, seed, on_step=None, z_stream=None, y=None, guidance_scale=1.0):
+        form = self._guidance_form(denoise_fn, y, guidance_scale)
         with self._time_tables(denoise_fn):
-            return self._sample_loop_impl(denoise_fn, shape, device, noise, seed, on_step, z_stream)
+            return self._sample_loop_impl(denoise_fn, shape, device, noise, seed, on_step, z_stream, y, form)
 
-    def _sample_loop_impl(self, denoise_fn, shape, device, noise, seed, on_step=None, z_stream=None):
+    def _sample_loop_impl(self, denoise_fn, shape, device, noise, seed, on_step=None, z_stream=None, y=None, form=None):
         """The T-step (or S-step) loop.  ``z_stream`` (parity tests only) is an iterator of per-step noise tensors
-        that replaces the generator draws, so an identical (x_T, z_1..z_T) stream can be injected.
+        that replaces the generator draws, so an identical (x_T, z_1..z_T) stream can be injected.  ``y`` / ``form``: class labels and
+        the way they are used (``_guidance_form``); the RNG consumption of every form is that of the unconditional loop.
 
         The step body (model call, noise draw, fused update, t -= 1) has static shapes, so it is captured ONCE into a
         hipGraph and replayed: at 32x32 the eager loop is bound by ~250 kernel launches per step, not by the GPU.
@@ -401,9 +454,13 @@ class GaussianDiffusion:
         _hip.require_cuda(torch.empty(0, device=device))        # no CPU fallback: sampling runs on the GPU only
         B = (shape or noise.shape)[0]
         steps = self._num_steps()
+        if form is not None:
+            y = torch.as_tensor(y).to(device=device, dtype=torch.int64).contiguous()
+            if y.shape != (B,):
+                raise ValueError(f"expected class labels y of shape [{B}], got {tuple(y.shape)}")
         if (on_step is None and steps >= 4 and device.type == "cuda"
                 and os.environ.get("DDPM_TORCH_AMD_GRAPH", "1") != "0" and not torch.cuda.is_current_stream_capturing()):
-            done = self._graph_loop(denoise_fn, tuple(shape or noise.shape), device, noise, seed, steps, z_stream)
+            done = self._graph_loop(denoise_fn, tuple(shape or noise.shape), device, noise, seed, steps, z_stream, y, form)
             if done is not None:
                 return done
         rng = torch.Generator(device).manual_seed(seed) if seed is not None else None       # diffusion.py:164-166
@@ -413,14 +470,34 @@ class GaussianDiffusion:
             x_t = noise.to(device)
         t = torch.full((B,), steps - 1, dtype=torch.int64, device=device)
         x_t = x_t.contiguous().float().clone()
+        if form is not None and form[0] == "cfg":
+            return self._guided_eager_loop(denoise_fn, x_t, y, form, steps, rng, on_step, z_stream)
         for ti in range(steps - 1, -1, -1):
             t.fill_(ti)
-            out = denoise_fn(x_t, self._model_t(t))
+            out = denoise_fn(x_t, self._model_t(t)) if form is None else denoise_fn(x_t, self._model_t(t), y)
             z = torch.empty_like(x_t).normal_(generator=rng) if z_stream is None else next(z_stream).to(x_t)
             x_t, pred = self._step(x_t, out, z, t, self.clip_sampling, on_step is not None)
             if on_step is not None:
                 on_step(ti, pred)
         return x_t
+
+    def _guided_eager_loop(self, denoise_fn, x_T, y, form, steps, rng, on_step, z_stream):
+        """The guided loop, eagerly: the launches of the captured guided step (``_capture_sample_step``), one by one."""
+        _, scale, null = form
+        B, dev = x_T.shape[0], x_T.device
+        state = torch.cat([x_T, x_T], dim=0)                                                # the doubled state [x | x]; the step keeps both halves
+        y2 = torch.cat([y, torch.full_like(y, null)], dim=0)                                # [y | null]
+        t = torch.full((2 * B,), steps - 1, dtype=torch.int64, device=dev)
+        x_t = state[:B]
+        pred = torch.empty_like(x_T) if on_step is not None else None
+        for ti in range(steps - 1, -1, -1):
+            t.fill_(ti)
+            out2 = denoise_fn(state, self._model_t(t), y2).contiguous().float()
+            z = torch.empty_like(x_T).normal_(generator=rng) if z_stream is None else next(z_stream).to(x_T).contiguous()
+            self._step_cfg_call(state, out2, z, t, scale, pred, B)
+            if on_step is not None:
+                on_step(ti, pred)
+        return x_t.clone()
 
     # ---- captured sampling step
     @contextlib.contextmanager
@@ -481,13 +558,17 @@ class GaussianDiffusion:
                 cache[key] = ent
         return ent
 
-    def _graph_loop(self, denoise_fn, shape, device, noise, seed, steps, z_stream=None):
+    def _graph_loop(self, denoise_fn, shape, device, noise, seed, steps, z_stream=None, y=None, form=None):
         """Replay the captured sampling step ``steps`` times; returns None if capture is not possible (the caller then
         runs the eager loop; no RNG state has been consumed).  ``z_stream`` (parity tests only): per-step noise tensors that are copied
-        into the captured step's noise buffer instead of being drawn inside it."""
-        ent = self._graph_entry(denoise_fn, shape, device, default_rng=seed is None, external_z=z_stream is not None)
+        into the captured step's noise buffer instead of being drawn inside it.  ``form`` (``_guidance_form``) extends the cache key: a
+        conditional or guided step (the scale is a kernel argument frozen into it) never serves another form; ``y`` refills the label
+        buffer the captured network call reads."""
+        ent = self._graph_entry(denoise_fn, shape, device, default_rng=seed is None, external_z=z_stream is not None, kind=form)
         if ent is None:
             return None
+        if form is not None:
+            ent["y"][:shape[0]].copy_(y)
         x_t, t, rng, graph = ent["x_t"], ent["t"], ent["rng"], ent["graph"]
         for e in self._engines_of(denoise_fn) or ():
             e.ensure_fresh()
@@ -497,12 +578,20 @@ class GaussianDiffusion:
             x_t.normal_(generator=rng)                            # x_T first, then one z per step (diffusion.py:166-171)
         else:
             x_t.copy_(noise)
+        if ent.get("x_dup") is not None:
+            ent["x_dup"].copy_(x_t)                               # the unconditional half of the doubled state; every step then keeps it
         t.fill_(steps - 1)
         for _ in range(steps):
             if z_stream is not None:
                 ent["z"].copy_(next(z_stream))
             graph.replay()
         return x_t.clone()
+
+    def _capture_kind_step(self, denoise_fn, shape, device, default_rng, external_z, kind):
+        """Capture a step the cache knows under an extended key: here the conditional and the guided sampling step (``_guidance_form``)."""
+        if kind[0] in ("cond", "cfg"):
+            return self._capture_sample_step(denoise_fn, shape, device, default_rng, external_z, form=kind)
+        raise NotImplementedError(kind)
 
     def prepare_sampler(self, denoise_fn, shape, device, seeded=True):
         """Capture (and cache) the hipGraph of one sampling step for ``(denoise_fn, shape)`` without running a chain, so that the
@@ -514,33 +603,43 @@ class GaussianDiffusion:
         with torch.inference_mode(), self._time_tables(denoise_fn):
             return self._graph_entry(denoise_fn, tuple(shape), device, default_rng=not seeded) is not None
 
-    def _capture_sample_step(self, denoise_fn, shape, device, default_rng, external_z=False):
+    def _capture_sample_step(self, denoise_fn, shape, device, default_rng, external_z=False, form=None):
+        """``form`` (``_guidance_form``): None, ("cond",) — the network also reads the label buffer ``y`` — or ("cfg", scale, null): state,
+        labels and timesteps have 2 B rows ([x | x], [y | null]), the network runs once on all of them and the guided step kernel reads the
+        first B rows of the state and writes both halves; ``x_t`` and ``z`` of the entry are the B rows the caller sees."""
         dev = device
-        x_t = torch.zeros(shape, dtype=torch.float32, device=dev)
-        z = torch.empty_like(x_t)
-        B, n = shape[0], x_t[0].numel()
-        t = torch.full((B,), self._num_steps() - 1, dtype=torch.int64, device=dev)
+        guided = form is not None and form[0] == "cfg"
+        B = shape[0]
+        rows = 2 * B if guided else B
+        state = torch.zeros((rows,) + tuple(shape[1:]), dtype=torch.float32, device=dev)
+        x_t = state[:B]
+        z = torch.empty(shape, dtype=torch.float32, device=dev)
+        n = x_t[0].numel()
+        t = torch.full((rows,), self._num_steps() - 1, dtype=torch.int64, device=dev)
+        y = None if form is None else torch.full((rows,), form[2] if guided else 0, dtype=torch.int64, device=dev)
         rng = None if default_rng else torch.Generator(dev)
         tabs = [] if self.learned_var else [self._tab(n_, dev) for n_ in _STEP_TABLES]
         mean_code = _MEAN_CODE[self.model_mean_type]
         T = len(self.posterior_mean_coef1)
 
         def body(cut=None):
-            out = denoise_fn(x_t, self._model_t(t)).contiguous().float()
+            out = (denoise_fn(state, self._model_t(t)) if y is None else denoise_fn(state, self._model_t(t), y)).contiguous().float()
             if not external_z:
                 z.normal_(generator=rng)
-            if self.learned_var:
+            if guided:
+                self._step_cfg_call(state, out, z, t, form[1], None, B)
+            elif self.learned_var:
                 self._check_two_halves(out, x_t)
                 self._step_lv_call(x_t, out, z, t, x_t, None, self.clip_sampling)
             else:
                 _hip.call("ddpm_p_sample_step", x_t.data_ptr(), out.data_ptr(), z.data_ptr(), t.data_ptr(), *[tb.data_ptr() for tb in tabs],
                           x_t.data_ptr(), 0, B, n, mean_code, int(self.clip_sampling), T, _hip.stream())   # in place: each element is read once, then written
-            _hip.call("ddpm_add_i64", t.data_ptr(), B, -1, _hip.stream())
+            _hip.call("ddpm_add_i64", t.data_ptr(), rows, -1, _hip.stream())
 
         graph = self._capture_step(dev, rng, body, "sampling")
         if graph is None:
             return None
-        return {"x_t": x_t, "t": t, "z": z, "rng": rng, "graph": graph, "ref": lambda: denoise_fn}
+        return {"x_t": x_t, "t": t, "z": z, "rng": rng, "graph": graph, "ref": lambda: denoise_fn, "y": y, "x_dup": state[B:] if guided else None}
 
     @staticmethod
     def _capture_step(dev, rng, body, what):
@@ -571,12 +670,16 @@ class GaussianDiffusion:
         return self.timesteps
 
     @torch.inference_mode()
-    def p_sample(self, denoise_fn, shape=None, device=torch.device("cpu"), noise=None, seed=None):
-        """diffusion.py:160-174."""
-        return self._sample_loop(denoise_fn, shape, device, noise, seed)
+    def p_sample(self, denoise_fn, shape=None, device=torch.device("cpu"), noise=None, seed=None, y=None, guidance_scale=1.0):
+        """diffusion.py:160-174.  Not in the reference: ``y`` (int64 [B] class labels of a class-conditional network) and
+        ``guidance_scale`` (classifier-free guidance, Ho & Salimans 2022: the step runs on scale * out(x, y) + (1 - scale) * out(x, null);
+        1 = plain conditional sampling, any other value evaluates both branches as one 2B-row network call).  Learned-variance models
+        are sampled at scale 1 only (NotImplementedError otherwise).  RNG consumption is that of the unconditional loop."""
+        return self._sample_loop(denoise_fn, shape, device, noise, seed, y=y, guidance_scale=guidance_scale)
 
     @torch.inference_mode()
-    def p_sample_progressive(self, denoise_fn, shape, device=torch.device("cpu"), noise=None, pred_freq=10, seed=None, z_stream=None):
+    def p_sample_progressive(self, denoise_fn, shape, device=torch.device("cpu"), noise=None, pred_freq=10, seed=None, z_stream=None, y=None,
+                             guidance_scale=1.0):
         """diffusion.py:176-198: the same loop, also returning pred_x0 of every ``pred_freq``-th step (on the host), filled from
         the back: ``preds[L-1]`` is the first one kept (t = T-1 when T is a multiple of pred_freq), ``preds[0]`` the one at
         t = pred_freq - 1.  The per-step read-back needs the eager loop (no graph replay).  ``z_stream`` (parity tests only): as in
@@ -592,7 +695,7 @@ class GaussianDiffusion:
                 box[0] -= 1
                 preds[box[0]] = pred.cpu()
 
-        x = self._sample_loop(denoise_fn, shape, device, noise, seed, on_step=keep, z_stream=z_stream)
+        x = self._sample_loop(denoise_fn, shape, device, noise, seed, on_step=keep, z_stream=z_stream, y=y, guidance_scale=guidance_scale)
         return x.cpu(), preds
 
     # ------------------------------------------------------------------ negative log-likelihood in bits per dimension
@@ -651,14 +754,17 @@ class GaussianDiffusion:
         ent["graph"] = self._capture_step(device, rng, ent["body"], "bits/dim evaluation")
         return ent if ent["graph"] is not None else None
 
-    def calc_all_bpd(self, denoise_fn, x_0, clip_denoised=True, seed=None, noise_stream=None):
-        """diffusion.py:252-268 as it was meant: ``(total_bpd [B], losses [B, T], prior_bpd [B], mses [B, T])`` with
+    def calc_all_bpd(self, denoise_fn, x_0, clip_denoised=True, seed=None, noise_stream=None, y=None):
+        """``y``: int64 [B] class labels of a class-conditional network, evaluated conditionally (no guidance).
+        diffusion.py:252-268 as it was meant: ``(total_bpd [B], losses [B, T], prior_bpd [B], mses [B, T])`` with
         ``total = L_T + sum_t L_t``, float32 ON ``x_0``'s DEVICE (the reference preallocates on the host and would synchronise T times).
 
         For t = T-1 ... 0: one standard-normal draw of x_0's shape (from a generator seeded with ``seed`` on x_0's device, else the default
         one; ``noise_stream`` — parity tests — is an iterator of per-step noise tensors that replaces the draws), q_sample, the network, and
         one fused kernel that puts L_t and mean (pred_x_0 - x_0)^2 into column t.  The step is captured once and replayed T times like the
         sampling step (same cache, same fallback to the eager loop; DDPM_TORCH_AMD_GRAPH=0 forces eager); both forms give the same bits."""
+        if y is not None:
+            denoise_fn = Conditioned(denoise_fn, y.to(x_0.device))
         with torch.inference_mode(), self._time_tables(denoise_fn):
             return self._calc_all_bpd_impl(denoise_fn, x_0, clip_denoised, seed, noise_stream)
 

@@ -112,8 +112,11 @@ class UNet(nn.Module):
     """Same constructor / forward contract as the reference (unet.py:96-107, :205)."""
 
     def __init__(self, in_channels, hid_channels, out_channels, ch_multipliers, num_res_blocks, apply_attn,
-                 time_embedding_dim=None, drop_rate=0., resample_with_conv=True):
+                 time_embedding_dim=None, drop_rate=0., resample_with_conv=True, num_classes=None):
         super().__init__()
+        if num_classes is not None and (isinstance(num_classes, bool) or int(num_classes) != num_classes or num_classes < 1):
+            raise ValueError(f"num_classes must be a positive integer or None, got {num_classes!r}")
+        self.num_classes = None if num_classes is None else int(num_classes)
         self.in_channels, self.hid_channels, self.out_channels = in_channels, hid_channels, out_channels
         self.time_embedding_dim = time_embedding_dim or 4 * hid_channels
         self.levels = levels = len(ch_multipliers)
@@ -151,6 +154,12 @@ class UNet(nn.Module):
                 mods.append(_seq(_Slot(), _Conv(chs[i], chs[i], 3)) if resample_with_conv else _seq(_Slot()))
             self.upsamples[f"level_{i}"] = nn.ModuleList(mods)
         self.out_conv = _seq(_Norm(hid_channels), _Slot(), _Conv(hid_channels, out_channels, 3, init_scale=0.0))
+        # class conditioning (not in the reference): one embedding row per class plus the null class (row num_classes: a dropped or absent
+        # label), added to the time embedding in front of the SiLU every ResidualBlock shares.  Registered after every module of the
+        # reference and drawn last, so an unconditional model's parameters, their order and their seeded values are what they were.
+        if self.num_classes is not None:
+            self.class_embed = _Slot()
+            self.class_embed.weight = nn.Parameter(torch.randn(self.num_classes + 1, E))
 
         self.compute_dtype = _DTYPES[os.environ.get("DDPM_TORCH_AMD_COMPUTE", "fp32").lower()]
         self._eng = None
@@ -194,24 +203,28 @@ class UNet(nn.Module):
             self._eng.apply_reserved_cus()
         return self._eng
 
-    def forward(self, x, t):
-        _hip.require_cuda(x, t)
+    def forward(self, x, t, y=None):
+        """``y`` (class-conditional models only): int64 ``[B]`` class labels on the device, ``num_classes`` standing for the null class;
+        ``None`` conditions every sample on the null class.  An unconditional model takes no ``y``."""
+        _hip.require_cuda(x, t, y)
+        if y is not None and self.num_classes is None:
+            raise ValueError("this UNet is unconditional (num_classes=None): it takes no class labels y")
         eng = self.engine()
         params = eng.params
         # (x.requires_grad: the reference returns d/dx through autograd, unet.py:205-233; here the backward's last step — in_conv's data
         #  gradient, otherwise skipped: training never needs it, x_t is data — is run when the autograd graph asks for it)
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
-            return _UNetFn.apply(x, t, eng, self.training, *params)
-        return eng.forward(x, t, self.training, None)
+            return _UNetFn.apply(x, t, eng, self.training, y, *params)
+        return eng.forward(x, t, self.training, None, y=y)
 
 
 class _UNetFn(torch.autograd.Function):
     """One autograd node for the whole network: forward runs the engine with a tape, backward replays it."""
 
     @staticmethod
-    def forward(ctx, x, t, eng, training, *params):
+    def forward(ctx, x, t, eng, training, y, *params):
         tape = []
-        out = eng.forward(x, t, training, tape)
+        out = eng.forward(x, t, training, tape, y=y)                # y: class labels, not differentiable
         ctx.eng, ctx.tape = eng, tape
         eng.last_tape = tape if eng.debug_keep_tape else None     # introspection hook for tests (dropout seeds, saved activations)
         return out
@@ -223,7 +236,7 @@ class _UNetFn(torch.autograd.Function):
         dx = ctx.eng.last_dx if want_dx else None
         ctx.eng.last_dx = None
         ctx.tape = None
-        return (dx, None, None, None) + tuple(grads)
+        return (dx, None, None, None, None) + tuple(grads)
 
 
 # ====================================================================================================== engine
@@ -301,6 +314,8 @@ class _Engine:
         self.fc_ver = None
         self.tt = None                                    # [T][sum Cout] time biases of every timestep (sampling only; see time_table)
         self.tt_T, self.tt_key, self.tt_idx, self.tt_on = 0, None, None, False
+        self.cond = getattr(m, "num_classes", None) is not None    # class-conditional: the biases depend on (t, y), no table of all t
+        self._null_y = {}                                          # batch size -> [B] labels of the null class (forward without y)
         self._ws = None
         self._ws_need, self._ws_retired = {}, []
         self.drop_calls = 0
@@ -432,8 +447,13 @@ class _Engine:
     # and each step gathers its rows — one launch instead of the embedding MLP's six (sinusoid, 3 fp32 GEMMs, 2 SiLUs: ~60 us of a
     # 3-ms step).  Only forwards issued by a sampler (tt_on, set around its loop / capture) read it: t is known to lie inside the schedule
     # there; training and plain eval calls run the MLP.
+    # A class-conditional engine has no such table: its biases depend on the pair (t, y), not on t alone, so it ignores both
+    # enable_time_table and tt_on and runs the embedding MLP (with the class-embedding add) in every step.
     def enable_time_table(self, T):
-        """Called by the samplers (GaussianDiffusion / DDIM) with the length of the schedule the model is evaluated on."""
+        """Called by the samplers (GaussianDiffusion / DDIM) with the length of the schedule the model is evaluated on.  A no-op on a
+        class-conditional engine."""
+        if self.cond:
+            return
         if T > self.tt_T:
             self.tt_T, self.tt_key = int(T), None
             if self.tt is not None:
@@ -446,8 +466,10 @@ class _Engine:
         m = self.m
         return tuple((p._version, p.data_ptr()) for p in (m.embed[0].weight, m.embed[0].bias, m.embed[2].weight, m.embed[2].bias))
 
-    def _time_biases(self, t, B):
-        """[B][sum Cout] time biases (+ conv1 biases) of timesteps ``t``, and what the backward of the path needs."""
+    def _time_biases(self, t, B, y=None):
+        """[B][sum Cout] time biases (+ conv1 biases) of timesteps ``t``, and what the backward of the path needs.  Class-conditional
+        (``y`` given): the SiLU every block shares is taken of ``pre = t_emb + class_embed[y]``, formed by the same launch, and ``pre`` is
+        what the backward keeps in the place of ``t_emb``."""
         m, E = self.m, self.E
         temb = self._f32(B, self.hid)
         _hip.call("ddpm_timestep_embedding", t.data_ptr(), self.freqs.data_ptr(), temb.data_ptr(), B, self.hid, _hip.stream())
@@ -456,7 +478,14 @@ class _Engine:
         _hip.call("ddpm_silu_fwd", e1.data_ptr(), s1.data_ptr(), B * E, _hip.stream())
         t_emb = self._linear(s1, m.embed[2].weight, m.embed[2].bias, B, E, E)
         s_t = self._f32(B, E)                                  # SiLU(t_emb): shared by every block (unet.py:86)
-        _hip.call("ddpm_silu_fwd", t_emb.data_ptr(), s_t.data_ptr(), B * E, _hip.stream())
+        if y is None:
+            _hip.call("ddpm_silu_fwd", t_emb.data_ptr(), s_t.data_ptr(), B * E, _hip.stream())
+        else:
+            table = m.class_embed.weight
+            pre = self._f32(B, E)
+            _hip.call("ddpm_class_embed_fwd", t_emb.data_ptr(), table.data_ptr(), y.data_ptr(), pre.data_ptr(), s_t.data_ptr(), B, E, table.shape[0],
+                      _hip.stream())
+            t_emb = pre
         fc_w, fc_b = self._fc_all()
         tb = self._linear(s_t, fc_w, fc_b, B, self.tb_total, E)   # [B, sum Cout]: every block's time bias (+conv1 bias)
         return tb, (temb, e1, s1, t_emb, s_t, fc_w)
@@ -485,7 +514,7 @@ class _Engine:
         master parameters — what forward() does on entry; callers replaying a captured graph do it before the replay."""
         self._refresh_packs(need_dgrad)
         self._fc_all()
-        if self.tt_on:                                   # only a sampler reads the [T][sum Cout] table: a training step after the per-epoch
+        if self.tt_on and not self.cond:                 # only a sampler reads the [T][sum Cout] table: a training step after the per-epoch
             self.time_table()                            # sample grid must not rebuild it (1000-row embedding MLP) before every replay
 
     def refresh_unconditionally(self):
@@ -823,15 +852,22 @@ class _Engine:
         v.ginit = True
         return v.grad, acc
 
+    def _null_labels(self, B):
+        if B not in self._null_y:
+            with torch.inference_mode(False):                    # (a sampler calls under inference_mode; the buffer outlives it)
+                self._null_y[B] = torch.full((B,), self.m.num_classes, dtype=torch.int64, device=self.device)
+        return self._null_y[B]
+
     def _linear(self, a, w, bias, M, N, K):
         out = self._f32(M, N)
         ops.gemm(a.data_ptr(), K, 0, 0, w.data_ptr(), K, 0, 0, out.data_ptr(), N, 0, M, N, K, _hip.F32, bias=_hip.ptr(bias), out_mode=1)
         return out
 
     # ================================================================ forward
-    def forward(self, x, t, training, tape, seed_dev=0):
+    def forward(self, x, t, training, tape, seed_dev=0, y=None):
         """``seed_dev``: address of a device uint64 holding the per-step part of the dropout seed (captured training step:
-        the host rewrites that word before every replay); 0 = the whole seed travels by value."""
+        the host rewrites that word before every replay); 0 = the whole seed travels by value.  ``y``: int64 [B] class labels of a
+        class-conditional model (None: the null class for every sample)."""
         m = self.m
         if x.dim() != 4 or x.shape[1] != m.in_channels:
             raise ValueError(f"expected x of shape [B, {m.in_channels}, H, W], got {tuple(x.shape)}")
@@ -842,6 +878,14 @@ class _Engine:
             raise ValueError("spatial size must be divisible by 2**(levels-1)")
         x = x.contiguous().float()
         t = t.contiguous().to(torch.int64)
+        if self.cond:
+            if y is None:
+                y = self._null_labels(B)
+            elif y.shape != (B,) or y.dtype != torch.int64:
+                raise ValueError(f"expected int64 class labels y of shape [{B}], got {y.dtype} {tuple(y.shape)}")
+            y = y.contiguous()
+        elif y is not None:
+            raise ValueError("this UNet is unconditional (num_classes=None): it takes no class labels y")
         save = tape is not None
         self._refresh_packs(save)
         ws = self._workspace(B, H, W)
@@ -855,13 +899,14 @@ class _Engine:
             st["seed"] = 0
 
         # ---- time embedding path (fp32; functions.py:10-26, unet.py:122-126,207)
-        if not save and self.tt_on:                              # inside a sampler: the rows of the precomputed table (see time_table)
+        if not save and self.tt_on and not self.cond:            # inside a sampler: the rows of the precomputed table (see time_table)
             tb = self._f32(B, self.tb_total)
             _hip.call("ddpm_gather_rows_f32", self.time_table().data_ptr(), t.data_ptr(), tb.data_ptr(), B, self.tb_total, self.tt_T, _hip.stream())
         else:
-            tb, saved = self._time_biases(t, B)
+            tb, saved = self._time_biases(t, B, y) if self.cond else self._time_biases(t, B)
             if save:
                 st["temb_saved"] = saved
+                st["y"] = y
         st["tb"] = tb
 
         # ---- decoder concat buffers: encoder outputs are written straight into their slice
@@ -1349,6 +1394,9 @@ class _Engine:
         dt_emb = self._f32(B, E)
         _hip.call("ddpm_silu_bwd", t_emb.data_ptr(), ds_t.data_ptr(), dt_emb.data_ptr(), B * E, 0, _hip.stream())
         ctx["dt_emb"] = dt_emb                                  # d/d(t_emb): what the reference's ResidualBlock hands back to the embedding MLP
+        if self.cond:                                           # (t_emb above is pre = t_emb + class_embed[y]: d/d pre is d/d t_emb too)
+            table = m.class_embed.weight
+            _hip.call("ddpm_class_embed_bwd", dt_emb.data_ptr(), st["y"].data_ptr(), self._pptr(ctx, table), B, E, table.shape[0], _hip.stream())
         lin2, lin1 = m.embed[2], m.embed[0]
         # (K = E = 512 over 4 output tiles would leave 252 CUs idle for ~75 us at the very end of the backward: split-K with fp32 atomics
         #  like the fc product above — output tiles x E / 64 K slices)

@@ -43,7 +43,9 @@ class GaussianDiffusion(diffusion.GaussianDiffusion):
         self._bind(denoise_fn)
         return super().p_sample_step(denoise_fn, x_t, t, clip_denoised, return_pred, generator)
 
-    def _sample_loop(self, denoise_fn, shape, device, noise, seed, on_step=None, z_stream=None):
+    def _sample_loop(self, denoise_fn, shape, device, noise, seed, on_step=None, z_stream=None, y=None, guidance_scale=1.0):
+        if y is not None:
+            raise NotImplementedError("the 2-D toy decoder is unconditional: it takes no class labels")
         self._bind(denoise_fn)
         return super()._sample_loop(denoise_fn, shape, device, noise, seed, on_step, z_stream)
 

@@ -718,8 +718,11 @@ class _DirectStep:
 class Trainer:
     def __init__(self, model, optimizer, diffusion, epochs, trainloader, sampler=None, scheduler=None, num_accum=1,
                  use_ema=False, grad_norm=1.0, shape=None, device=torch.device("cpu"), chkpt_intv=5, image_intv=1,
-                 num_samples=64, ema_decay=0.9999, distributed=False, rank=0, dry_run=False):
+                 num_samples=64, ema_decay=0.9999, distributed=False, rank=0, dry_run=False, label_drop=0.1):
         self.model, self.optimizer, self.diffusion = model, optimizer, diffusion
+        if not 0.0 <= label_drop <= 1.0:
+            raise ValueError(f"label_drop is a probability, got {label_drop}")
+        self.label_drop = float(label_drop)             # class-conditional models: P(a sample's label is replaced by the null class)
         self.epochs, self.start_epoch = epochs, 0
         self.trainloader, self.sampler = trainloader, sampler
         if shape is None:
@@ -768,16 +771,44 @@ class Trainer:
     def _ema_on(self):
         return self.use_ema and isinstance(self.ema, EMA)
 
+    @property
+    def num_classes(self):
+        """``num_classes`` of the class-conditional network being trained, None for an unconditional one."""
+        m = self.model.module if isinstance(self.model, DDP) else self.model
+        if hasattr(m, "num_classes"):
+            return m.num_classes
+        cached = self.__dict__.get("_num_classes_cache")
+        if cached is None or cached[0] is not m:            # a wrapper (ModelWrapper): the network inside it, looked up once
+            k = next((q.num_classes for q in m.modules() if getattr(q, "num_classes", None) is not None), None) if isinstance(m, nn.Module) else None
+            cached = self._num_classes_cache = (m, k)
+        return cached[1]
+
     def get_input(self, x):
-        """Draw order per step: t first, then noise (utils/train.py:134-141)."""
+        """Draw order per step: t first, then noise (utils/train.py:134-141).  A class-conditional model takes the pair ``(x, y)``: after
+        those two draws, B uniforms from the same generator decide which labels are replaced by the null class (``u < label_drop``;
+        classifier-free guidance training, Ho & Salimans 2022) — an unconditional trainer's draws are untouched."""
+        y = None
+        if isinstance(x, (list, tuple)):
+            x, y = x
+        k = self.num_classes
+        if k is None and y is not None:
+            raise ValueError("class labels were given to the trainer of an unconditional model (num_classes=None)")
+        if k is not None and y is None:
+            raise ValueError("a class-conditional model trains on (image, label) pairs; got bare images")
         x = x.to(self.device)
         t = torch.empty((x.shape[0],), dtype=torch.int64, device=self.device).random_(to=self.timesteps, generator=self.generator)
         noise = torch.empty_like(x).normal_(generator=self.generator)
-        return {"x_0": x, "t": t, "noise": noise}
+        if k is None:
+            return {"x_0": x, "t": t, "noise": noise}
+        y = y.to(device=self.device, dtype=torch.int64)
+        u = torch.rand((x.shape[0],), device=self.device, generator=self.generator)
+        y = torch.where(u < self.label_drop, torch.full_like(y, k), y)
+        return {"x_0": x, "t": t, "noise": noise, "y": y}
 
     def loss(self, x):
-        loss = self.diffusion.train_losses(self.model, **self.get_input(x))
-        assert loss.shape == (x.shape[0],)
+        inputs = self.get_input(x)
+        loss = self.diffusion.train_losses(self.model, **inputs)
+        assert loss.shape == (inputs["x_0"].shape[0],)
         return loss
 
     # ------------------------------------------------------------------ one optimisation step
@@ -806,6 +837,8 @@ class Trainer:
     def _direct_unet_scan(self, m, UNet):
         if not isinstance(m, UNet) or self.num_accum != 1 or not self._fused.eligible():
             return None
+        if m.num_classes is not None:
+            return None                                 # class-conditional: the generic autograd step (the launch plan has no label input yet)
         if "get_input" in self.__dict__ or "loss" in self.__dict__ or type(self).get_input is not Trainer.get_input or type(self).loss is not Trainer.loss:
             return None                                 # a customised input / loss: keep the generic autograd step
         if not getattr(self.diffusion, "supports_direct_step", False) or not self.diffusion.supports_direct_step():
@@ -817,6 +850,10 @@ class Trainer:
         return m
 
     def step(self, x, global_steps=1):
+        """One optimisation step on a batch of images, or on an ``(images, labels)`` pair for a class-conditional model."""
+        y = None
+        if isinstance(x, (list, tuple)):
+            x, y = x
         x = x.to(self.device)
         unet = self._direct_unet() if os.environ.get("DDPM_TORCH_AMD_DIRECT_STEP", "1") != "0" else None
         if unet is not None and x.dtype == torch.float32:
@@ -828,7 +865,7 @@ class Trainer:
                 self.ema.num_updates += 1
             self.scheduler.step()
         else:
-            loss = self.loss(x).mean()
+            loss = self.loss(x if y is None else (x, y)).mean()
             loss.div(self.num_accum).backward()
             if global_steps % self.num_accum == 0:
                 ema_w = self.ema.weight_of_next_update() if self._ema_on else 0.0
@@ -893,8 +930,11 @@ class Trainer:
     def sample_fn(self, sample_size=None, noise=None, diffusion=None, sample_seed=None):
         per_rank = ((sample_size // self.world_size,) + self.shape) if noise is None else tuple(noise.shape)
         process = self.diffusion if diffusion is None else diffusion
+        cond = {}
+        if self.num_classes is not None:                # the per-epoch grid of a class-conditional model: classes 0, 1, ... in turn, unguided
+            cond["y"] = torch.arange(per_rank[0], device=self.device) % self.num_classes
         with self.ema:
-            sample = process.p_sample(denoise_fn=self.model, shape=per_rank, device=self.device, noise=noise, seed=sample_seed)
+            sample = process.p_sample(denoise_fn=self.model, shape=per_rank, device=self.device, noise=noise, seed=sample_seed, **cond)
         if self.distributed:
             parts = [torch.zeros(per_rank, device=self.device) for _ in range(self.world_size)]
             dist.all_gather(parts, sample)
@@ -913,7 +953,10 @@ class Trainer:
         for batch in self.trainloader:
             images = batch[0] if isinstance(batch, (list, tuple)) else batch       # unconditional: labels are dropped
             steps += 1
-            self.step(images.to(self.device), global_steps=steps)
+            if self.num_classes is not None and isinstance(batch, (list, tuple)):
+                self.step((images.to(self.device), batch[1].to(self.device)), global_steps=steps)
+            else:
+                self.step(images.to(self.device), global_steps=steps)
             if self.dry_run and steps % self.num_accum == 0:
                 break
         # (the reference refreshes a progress-bar postfix from current_stats after every step, utils/train.py:209-212; reading the

@@ -52,6 +52,10 @@ def parse_args(argv=None):
     add("--num-gpus", default=1, type=int)
     add("--compute", choices=["bf16", "fp32"], default="bf16")
     add("--seed", default=None, type=int, help="seeds x_T AND the per-step noise of every chain (default: nondeterministic, like the reference)")
+    add("--labels", default="", type=str, help="class-conditional checkpoints: the classes to generate, a comma list repeated over the images "
+        "(\"3,5\") or \"cycle\" for 0, 1, ..., K-1 repeated; K is read off the checkpoint's class_embed.weight.  Default: the null class")
+    add("--guidance-scale", default=1.0, type=float, help="classifier-free guidance scale w of w * out(x, y) + (1 - w) * out(x, null) "
+        "(Ho & Salimans 2022); 1 = plain conditional sampling; needs --labels; learned-variance models take 1 only")
     add("--interpolate", default=0, type=int, metavar="K", help="write K-step spherical interpolations between pairs of latents (--total-size "
         "pairs of drawn latents, or the consecutive pairs of --source), one grid picture per pair; needs --use-ddim --eta 0")
     add("--reconstruct", action="store_true", help="encode every --source image and decode it again; writes input | reconstruction and prints "
@@ -73,6 +77,10 @@ def parse_args(argv=None):
             p.error(f"{what} runs on one GPU")
     elif args.source:
         p.error("--source is read by --interpolate and --reconstruct only")
+    if args.guidance_scale != 1.0 and not args.labels:
+        p.error("--guidance-scale guides towards the classes of --labels")
+    if args.labels and (args.interpolate or args.reconstruct):
+        p.error("--labels serves plain generation: --interpolate and --reconstruct run unconditionally (the null class)")
     return args
 
 
@@ -107,13 +115,16 @@ def build(args, rank=0):
     mk = dict(meta["model"])
     block = mk.pop("block_size", 1)
     mk["in_channels"] = mk.get("in_channels", info["channels"]) * block ** 2
+    chkpt_path = args.chkpt_path or os.path.join(args.chkpt_dir, f"ddpm_{dataset}.pt")
+    use_ema = meta.get("train", {}).get("use_ema", args.use_ema)
+    weights = weights_from(torch.load(chkpt_path, map_location=device), use_ema)
+    table = next((v for k, v in weights.items() if k.endswith("class_embed.weight")), None)
+    mk["num_classes"] = None if table is None else table.shape[0] - 1          # the checkpoint decides: one row per class + the null class
     model = ddpm_torch.UNet(out_channels=(2 if learned else 1) * info["channels"] * block ** 2, **mk).set_compute_dtype(args.compute)
     if block > 1:
         model = ddpm_torch.ModelWrapper(model, torch.nn.PixelUnshuffle(block), torch.nn.PixelShuffle(block))
     model.to(device)
-    chkpt_path = args.chkpt_path or os.path.join(args.chkpt_dir, f"ddpm_{dataset}.pt")
-    use_ema = meta.get("train", {}).get("use_ema", args.use_ema)
-    model.load_state_dict(weights_from(torch.load(chkpt_path, map_location=device), use_ema))
+    model.load_state_dict(weights)
     model.eval()
     for prm in model.parameters():
         prm.requires_grad_(False)
@@ -132,21 +143,38 @@ def write_png(arr, out_dir):
     Image.fromarray(arr.squeeze(-1) if arr.shape[-1] == 1 else arr).save(os.path.join(out_dir, f"{uuid.uuid4()}.png"))
 
 
+def labels_of(spec, num_classes, start, n, device):
+    """int64 [n] class labels of images ``start`` ... ``start + n - 1`` of a run: ``spec`` is "cycle" (0, 1, ..., K-1 repeated) or a comma
+    list repeated over the images."""
+    if num_classes is None:
+        raise ValueError("--labels needs a class-conditional checkpoint (one with class_embed.weight)")
+    pattern = list(range(num_classes)) if spec.strip() == "cycle" else [int(v) for v in spec.split(",") if v.strip()]
+    if not pattern or min(pattern) < 0 or max(pattern) >= num_classes:
+        raise ValueError(f"--labels {spec!r}: expected classes in [0, {num_classes})")
+    idx = (torch.arange(n) + start) % len(pattern)
+    return torch.tensor(pattern, dtype=torch.int64)[idx].to(device)
+
+
 def generate(rank, args):
     process, model, device, shape, out_dir = build(args, rank)
     os.makedirs(out_dir, exist_ok=True)
     world = max(args.num_gpus, 1)
     mine = args.total_size // world + (1 if rank < args.total_size % world else 0)
+    first = rank * (args.total_size // world) + min(rank, args.total_size % world)          # index of this rank's first image in the run
+    num_classes = next((m.num_classes for m in model.modules() if getattr(m, "num_classes", None) is not None), None)
     done = chain = 0
     with ThreadPoolExecutor(max_workers=args.max_workers) as pool:
         while done < mine:
             n = min(args.batch_size, mine - done)
+            cond = {}
+            if args.labels:
+                cond = {"y": labels_of(args.labels, num_classes, first + done, n, device), "guidance_scale": args.guidance_scale}
             if args.seed is None:                    # the reference's behaviour (generate.py:126-128): x_T and every z from the default RNG
-                x = process.p_sample(model, shape=(n,) + shape, device=device, noise=torch.randn((n,) + shape, device=device))
+                x = process.p_sample(model, shape=(n,) + shape, device=device, noise=torch.randn((n,) + shape, device=device), **cond)
             else:
                 # reproducible runs: ONE seeded generator per chain feeds x_T and then every per-step z (diffusion.py:164-171), so the
                 # whole chain — not only its starting point — repeats; chains and ranks get distinct streams
-                x = process.p_sample(model, shape=(n,) + shape, device=device, seed=args.seed + 1000003 * rank + chain)
+                x = process.p_sample(model, shape=(n,) + shape, device=device, seed=args.seed + 1000003 * rank + chain, **cond)
             chain += 1
             list(pool.map(lambda a: write_png(a, out_dir), list(to_uint8(x))))
             done += n

@@ -81,6 +81,9 @@ def parse_args(argv=None):
     add("--dry-run", action="store_true", help="stop after the first parameter update; checkpoint and sample once")
     add("--compute", choices=["bf16", "fp32"], default="bf16", help="arithmetic of the UNet kernels (not in the reference)")
     add("--ddp-wrapper", action="store_true", help="wrap the model in DistributedDataParallel instead of the native reducer")
+    add("--num-classes", default=0, type=int, help="train a class-conditional model on this many classes (not in the reference; the data "
+                                                  "set must carry labels: cifar10, mnist).  0: unconditional")
+    add("--label-drop", default=0.1, type=float, help="probability of training a sample on the null class (classifier-free guidance)")
     add("--device-data", action="store_true", help="hold the data set on the training GPU and assemble every batch there (not in the "
                                                    "reference); --num-workers then only serves a one-off decode of image files")
     return p.parse_args(argv)
@@ -133,6 +136,10 @@ def run(rank=0, args=None, temp_dir=""):
     block = mcfg.pop("block_size", args.block_size)
     out_channels = 2 * in_channels if dcfg.model_var_type in ("learned", "learned-range") else in_channels
     mcfg.update(in_channels=in_channels * block ** 2, out_channels=out_channels * block ** 2)
+    num_classes = mcfg.get("num_classes") or args.num_classes or None
+    mcfg.pop("num_classes", None)
+    if num_classes:
+        mcfg["num_classes"] = int(num_classes)
     unet = ddpm_torch.UNet(**mcfg).set_compute_dtype(args.compute)
     net = unet if block == 1 else ddpm_torch.ModelWrapper(unet, torch.nn.PixelUnshuffle(block), torch.nn.PixelShuffle(block))
 
@@ -162,7 +169,8 @@ def run(rank=0, args=None, temp_dir=""):
     loader, sampler = ddpm_torch.get_dataloader(dataset, batch_size=tcfg.batch_size, split="all" if dataset == "celeba" else "train", val_size=0.,
                                                 random_seed=seed, root=os.path.expanduser(args.root), drop_last=True, pin_memory=True,
                                                 num_workers=args.num_workers, distributed=args.distributed,
-                                                device=device if args.device_data else None)
+                                                device=device if args.device_data else None,
+                                                **({"labels": True, "num_classes": int(num_classes)} if num_classes else {}))
     if args.dry_run:
         say("This is a dry run.")
         args.chkpt_intv = tcfg.image_intv = 1
@@ -181,7 +189,8 @@ def run(rank=0, args=None, temp_dir=""):
     trainer = ddpm_torch.Trainer(model=model, optimizer=opt, diffusion=diffusion, epochs=tcfg.epochs, trainloader=loader, sampler=sampler,
                                  scheduler=sched, num_accum=args.num_accum, use_ema=tcfg.use_ema, grad_norm=tcfg.grad_norm, shape=shape,
                                  device=device, chkpt_intv=args.chkpt_intv, image_intv=tcfg.image_intv, num_samples=tcfg.num_samples,
-                                 ema_decay=args.ema_decay, rank=rank, distributed=args.distributed, dry_run=args.dry_run)
+                                 ema_decay=args.ema_decay, rank=rank, distributed=args.distributed, dry_run=args.dry_run,
+                                 label_drop=args.label_drop)
     if args.eval:
         sampler_proc = diffusion
         if args.use_ddim:

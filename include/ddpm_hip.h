@@ -267,6 +267,33 @@ int ddpm_learned_loss(const float* x_0, const float* x_t, const float* model_out
                       const float* sqrt_recip_ab, const float* sqrt_recip_m1_ab, const float* post_coef1, const float* post_coef2,
                       const float* post_logvar, const float* logvar_max, const float* gloss, float* loss, float* gout,
                       int B, int n, int mean_type, int var_mode, int detach_mean, int T, float w_mse, float w_vlb, void* stream);
+/* Class conditioning and classifier-free guidance (csrc/guidance.hip; Ho & Salimans 2022).  fp32; y and t are int64; every product and sum
+ * is rounded on its own (no contraction) except the two fused operations of ddpm_p_sample_step's update.  Static LDS only, no atomics, no
+ * allocation: each is capturable as a first call.  Status: a required pointer NULL DDPM_ERR_NULL; B, E, K1, n or T <= 0, K1 > 65535
+ * (ddpm_class_embed_bwd), B > 65535 or mean_type outside 0..2 (ddpm_p_sample_step_cfg) DDPM_ERR_SHAPE; a pointer that is not a multiple of
+ * its element size DDPM_ERR_ALIGN.
+ * ddpm_class_embed_fwd: table is [K1][E], K1 = num_classes + 1, row K1 - 1 the null class (the label of a dropped or absent condition).
+ *   pre[b] = t_emb[b] + table[y[b]],  s[b] = SiLU(pre[b]) with ddpm_silu_fwd's expression: s equals ddpm_silu_fwd(pre) bit for bit.
+ *   t_emb, pre, s are [B][E].  A sample whose y[b] is outside [0, K1) gets NaN rows in pre and s, and no table row is read for it.
+ * ddpm_class_embed_bwd: dtable[k][e] = sum of dpre[b][e] over the samples with y[b] == k, added in ascending b (a fixed order: repeated
+ *   launches are bit-identical); a class without a sample gets 0.0.  Plain stores to every element of dtable [K1][E], so nothing the
+ *   buffer held before survives.  A y[b] outside [0, K1) contributes nothing.
+ * ddpm_p_sample_step_cfg: the sampling step on the guided combination of a doubled batch.  model_out2 is [2B][n]: rows [0, B) the
+ *   conditional network output, rows [B, 2B) the unconditional one (eps, x_0 or mean alike: the two weights sum to one).
+ *     g = scale * out_c + (1 - scale) * out_u      (1 - scale formed once in fp32; two products and one sum, three roundings)
+ *   followed by exactly ddpm_p_sample_step's operations on g, tables, mean_type, clip, noise mask and T as there.  For finite inputs
+ *   scale = 1 gives the bits of ddpm_p_sample_step on out_c and scale = 0 those on out_u (up to the sign of a zero network output).
+ *   x_t is read from rows [0, B) of its buffer; x_prev is written to row b and, when dup != 0, also to row b + B of a [2B][n] buffer (the
+ *   doubled state of the next network call).  x_prev may be x_t (an element is read once, then written; rows [B, 2B) are never read).
+ *   z is [B][n]; pred_x0 ([B][n]) may be NULL.  A sample whose t is outside [0, T) gets NaN in every row written for it, no table is read
+ *   for it and no other sample is touched.  A sample whose row bases are all 16-byte aligned is moved 16 bytes per lane with a scalar
+ *   tail, any other one element-wise; both paths give the same bits. */
+int ddpm_class_embed_fwd(const float* t_emb, const float* table, const long long* y, float* pre, float* s, int B, int E, int K1, void* stream);
+int ddpm_class_embed_bwd(const float* dpre, const long long* y, float* dtable, int B, int E, int K1, void* stream);
+int ddpm_p_sample_step_cfg(const float* x_t, const float* model_out2, const float* z, const long long* t,
+                           const float* sqrt_recip_ab, const float* sqrt_recip_m1_ab, const float* post_coef1, const float* post_coef2,
+                           const float* logvar, float scale, float* x_prev, float* pred_x0, int B, int n, int mean_type, int clip,
+                           int dup, int T, void* stream);
 /* subsequence.gather(0, t) (ddim.py:101) and t += delta (t.fill_ in diffusion.py:172, device-side for graph replay) */
 int ddpm_gather_i64(const long long* idx, const long long* map, long long* out, int B, void* stream);
 int ddpm_add_i64(long long* t, int B, long long delta, void* stream);
