@@ -1,7 +1,9 @@
-// Single-head attention of AttentionBlock (ddpm_torch/models/unet.py:41-52 of tqch/ddpm-torch) at ANY token count: streaming
+// Attention of AttentionBlock (ddpm_torch/models/unet.py:41-52 of tqch/ddpm-torch) at ANY token count and any head count: streaming
 // flash forward and backward (gfx950, bf16 operands, fp32 accumulation).  attention.hip keeps one 128 x L score block on chip and
 // therefore stops at 256 tokens; here the other side of the score matrix is streamed through LDS in tiles of BN tokens and the
-// softmax is the online one, so no L x L object exists anywhere and no L appears as a memory row.
+// softmax is the online one, so no L x L object exists anywhere and no L appears as a memory row.  The reference's block is the
+// single head (C = the block's channels); with heads > 1 (ADM's QKVAttention ordering) a problem is one (image, head) pair and C
+// below is the head's width — see StreamArgs.
 //
 //     S = Q K^T / sqrt(C)      P = softmax_keys(S)      O = P V                                  (forward)
 //     dV = P^T dO      dP = dO V^T      dS = P o (dP - D),  D = rowsum(dO o O)      dQ = dS K / sqrt(C)      dK = dS^T Q / sqrt(C)
@@ -60,13 +62,16 @@ __device__ __forceinline__ void vm_wait_units(int n) {
     }
 }
 
+// One problem = one (image b, head h): blockIdx.y = b * heads + h.  The kernels see C = the HEAD's width d; the thirds of the packed
+// buffer are heads * C apart, and head h of every operand and output is channels [h C, (h + 1) C) of its third — a base offset of
+// h C elements and a descriptor that spans C channels from there, so the ring's `ch < C` zero-fill and every bound below are per head.
 struct StreamArgs {
-    const bf16_t *q, *k, *v;  long long qkv_ld;   // packed projection buffer: q at +0, k at +C, v at +2C (pointers already offset)
+    const bf16_t *q, *k, *v;  long long qkv_ld;   // packed projection buffer: q at +0, k at +heads C, v at +2 heads C (pointers already offset)
     const bf16_t *o, *d_o;    long long o_ld, do_ld;
     bf16_t *out;              long long out_ld;    // forward: O
     bf16_t *dq, *dk, *dv;     long long dqkv_ld;
-    float *lse, *dvec;                             // [B][L] fp32: row log-sum-exp of the scaled logits; D = rowsum(dO o O)
-    int B, L, C;
+    float *lse, *dvec;                             // [B][heads][L] fp32: row log-sum-exp of the scaled logits; D = rowsum(dO o O)
+    int B, L, C, heads;
     float scale;
 };
 
@@ -263,11 +268,11 @@ void attn_stream_fwd_kernel(StreamArgs a) {
     __shared__ __attribute__((aligned(16))) char smem[Smem<CB, MT>::BYTES];
     const int tid = threadIdx.x, lane = tid & 63, ln = lane & 15, g = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int b = blockIdx.y, wr0 = blockIdx.x * (64 * MT) + wave * (16 * MT);
+    const int bh = blockIdx.y, b = bh / a.heads, hc = (bh - b * a.heads) * a.C, wr0 = blockIdx.x * (64 * MT) + wave * (16 * MT);
     const Rt rt = make_rt(a.L, a.C, G::BN);
-    const Opnd Q = make_opnd(a.q + (long long)b * a.L * a.qkv_ld, a.qkv_ld, a.L, a.C);
-    const Opnd K = make_opnd(a.k + (long long)b * a.L * a.qkv_ld, a.qkv_ld, a.L, a.C);
-    const Opnd V = make_opnd(a.v + (long long)b * a.L * a.qkv_ld, a.qkv_ld, a.L, a.C);
+    const Opnd Q = make_opnd(a.q + (long long)b * a.L * a.qkv_ld + hc, a.qkv_ld, a.L, a.C);
+    const Opnd K = make_opnd(a.k + (long long)b * a.L * a.qkv_ld + hc, a.qkv_ld, a.L, a.C);
+    const Opnd V = make_opnd(a.v + (long long)b * a.L * a.qkv_ld + hc, a.qkv_ld, a.L, a.C);
     u32x4 qf[MT][G::KST];
     load_own<CB, MT>(qf, Q, wr0, a.L, a.C, ln, g);
     Ring<CB> ring;
@@ -351,9 +356,9 @@ void attn_stream_fwd_kernel(StreamArgs a) {
 #pragma unroll
         for (int ct = 0; ct < G::NCTT; ++ct) o[mt][ct] *= inv;
         const int q = wr0 + mt * 16 + ln;
-        if (a.lse && g == 0 && q < a.L) a.lse[(long long)b * a.L + q] = m[mt] + __logf(lt);
+        if (a.lse && g == 0 && q < a.L) a.lse[(long long)bh * a.L + q] = m[mt] + __logf(lt);
     }
-    store_own<MT, G::NCTT>(o, a.out + (long long)b * a.L * a.out_ld, a.out_ld, wr0, a.L, 0, a.C, ln, g);
+    store_own<MT, G::NCTT>(o, a.out + (long long)b * a.L * a.out_ld + hc, a.out_ld, wr0, a.L, 0, a.C, ln, g);
 }
 
 // ------------------------------------------------------------------------------------------------ backward: dQ (and D)
@@ -364,13 +369,13 @@ void attn_stream_dq_kernel(StreamArgs a) {
     __shared__ __attribute__((aligned(16))) char smem[Smem<CB, MT>::BYTES];
     const int tid = threadIdx.x, lane = tid & 63, ln = lane & 15, g = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int b = blockIdx.y, wr0 = blockIdx.x * (64 * MT) + wave * (16 * MT);
+    const int bh = blockIdx.y, b = bh / a.heads, hc = (bh - b * a.heads) * a.C, wr0 = blockIdx.x * (64 * MT) + wave * (16 * MT);
     const Rt rt = make_rt(a.L, a.C, G::BN);
-    const Opnd Q = make_opnd(a.q + (long long)b * a.L * a.qkv_ld, a.qkv_ld, a.L, a.C);
-    const Opnd K = make_opnd(a.k + (long long)b * a.L * a.qkv_ld, a.qkv_ld, a.L, a.C);
-    const Opnd V = make_opnd(a.v + (long long)b * a.L * a.qkv_ld, a.qkv_ld, a.L, a.C);
-    const Opnd dO = make_opnd(a.d_o + (long long)b * a.L * a.do_ld, a.do_ld, a.L, a.C);
-    const Opnd O = make_opnd(a.o + (long long)b * a.L * a.o_ld, a.o_ld, a.L, a.C);
+    const Opnd Q = make_opnd(a.q + (long long)b * a.L * a.qkv_ld + hc, a.qkv_ld, a.L, a.C);
+    const Opnd K = make_opnd(a.k + (long long)b * a.L * a.qkv_ld + hc, a.qkv_ld, a.L, a.C);
+    const Opnd V = make_opnd(a.v + (long long)b * a.L * a.qkv_ld + hc, a.qkv_ld, a.L, a.C);
+    const Opnd dO = make_opnd(a.d_o + (long long)b * a.L * a.do_ld + hc, a.do_ld, a.L, a.C);
+    const Opnd O = make_opnd(a.o + (long long)b * a.L * a.o_ld + hc, a.o_ld, a.L, a.C);
     u32x4 qf[MT][G::KST], dof[MT][G::KST];
     load_own<CB, MT>(qf, Q, wr0, a.L, a.C, ln, g);
     load_own<CB, MT>(dof, dO, wr0, a.L, a.C, ln, g);
@@ -393,8 +398,8 @@ void attn_stream_dq_kernel(StreamArgs a) {
         acc += __shfl_xor(acc, 16, 64);
         acc += __shfl_xor(acc, 32, 64);
         dsum[mt] = acc;
-        lrow[mt] = q < a.L ? a.lse[(long long)b * a.L + q] : 0.f;
-        if (g == 0 && q < a.L) a.dvec[(long long)b * a.L + q] = acc;
+        lrow[mt] = q < a.L ? a.lse[(long long)bh * a.L + q] : 0.f;
+        if (g == 0 && q < a.L) a.dvec[(long long)bh * a.L + q] = acc;
     }
     Ring<CB> ring;
     ring.init(smem, tid, rt);
@@ -447,7 +452,7 @@ void attn_stream_dq_kernel(StreamArgs a) {
             }
         });
     }
-    store_own<MT, G::NCTT>(z, a.dq + (long long)b * a.L * a.dqkv_ld, a.dqkv_ld, wr0, a.L, 0, a.C, ln, g);
+    store_own<MT, G::NCTT>(z, a.dq + (long long)b * a.L * a.dqkv_ld + hc, a.dqkv_ld, wr0, a.L, 0, a.C, ln, g);
 }
 
 // ------------------------------------------------------------------------------------------------ backward: dK, dV
@@ -460,12 +465,13 @@ void attn_stream_dkv_kernel(StreamArgs a) {
     __shared__ __attribute__((aligned(16))) char smem[Smem<CB, MT>::BYTES];
     const int tid = threadIdx.x, lane = tid & 63, ln = lane & 15, g = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int b = blockIdx.y, hz = blockIdx.z, wr0 = blockIdx.x * (64 * MT) + wave * (16 * MT);       // wr0: first KEY of the wave
+    const int bh = blockIdx.y, b = bh / a.heads, hc = (bh - b * a.heads) * a.C, hz = blockIdx.z;
+    const int wr0 = blockIdx.x * (64 * MT) + wave * (16 * MT);                                          // wr0: first KEY of the wave
     const Rt rt = make_rt(a.L, a.C, G::BN);
-    const Opnd Q = make_opnd(a.q + (long long)b * a.L * a.qkv_ld, a.qkv_ld, a.L, a.C);
-    const Opnd K = make_opnd(a.k + (long long)b * a.L * a.qkv_ld, a.qkv_ld, a.L, a.C);
-    const Opnd V = make_opnd(a.v + (long long)b * a.L * a.qkv_ld, a.qkv_ld, a.L, a.C);
-    const Opnd dO = make_opnd(a.d_o + (long long)b * a.L * a.do_ld, a.do_ld, a.L, a.C);
+    const Opnd Q = make_opnd(a.q + (long long)b * a.L * a.qkv_ld + hc, a.qkv_ld, a.L, a.C);
+    const Opnd K = make_opnd(a.k + (long long)b * a.L * a.qkv_ld + hc, a.qkv_ld, a.L, a.C);
+    const Opnd V = make_opnd(a.v + (long long)b * a.L * a.qkv_ld + hc, a.qkv_ld, a.L, a.C);
+    const Opnd dO = make_opnd(a.d_o + (long long)b * a.L * a.do_ld + hc, a.do_ld, a.L, a.C);
     u32x4 kf[MT][G::KST], vf[MT][G::KST];
     load_own<CB, MT>(kf, K, wr0, a.L, a.C, ln, g);
     load_own<CB, MT>(vf, V, wr0, a.L, a.C, ln, g);
@@ -497,8 +503,8 @@ void attn_stream_dkv_kernel(StreamArgs a) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int q = q0 + j * 16 + g * 4 + r;
-                lq[j][r] = q < a.L ? a.lse[(long long)b * a.L + q] : 0.f;
-                dq_[j][r] = q < a.L ? a.dvec[(long long)b * a.L + q] : 0.f;
+                lq[j][r] = q < a.L ? a.lse[(long long)bh * a.L + q] : 0.f;
+                dq_[j][r] = q < a.L ? a.dvec[(long long)bh * a.L + q] : 0.f;
             }
         f32x4 s[MT][G::NJ], dp[MT][G::NJ];
 #pragma unroll
@@ -542,14 +548,17 @@ void attn_stream_dkv_kernel(StreamArgs a) {
         }
     }
     const int cend = min(a.C, hz * 256 + 256);
-    store_own<MT, G::NCTH>(zv, a.dv + (long long)b * a.L * a.dqkv_ld, a.dqkv_ld, wr0, a.L, hz * 256, cend, ln, g);
-    store_own<MT, G::NCTH>(zk, a.dk + (long long)b * a.L * a.dqkv_ld, a.dqkv_ld, wr0, a.L, hz * 256, cend, ln, g);
+    store_own<MT, G::NCTH>(zv, a.dv + (long long)b * a.L * a.dqkv_ld + hc, a.dqkv_ld, wr0, a.L, hz * 256, cend, ln, g);
+    store_own<MT, G::NCTH>(zk, a.dk + (long long)b * a.L * a.dqkv_ld + hc, a.dqkv_ld, wr0, a.L, hz * 256, cend, ln, g);
 }
 
-static int check_stream(const void* qkv, long long ld, int B, int L, int C, int dtype) {
+// C: the width of one third of the packed buffer = heads * d.  heads = 1 is the single-head contract, with its status codes.
+static int check_stream(const void* qkv, long long ld, int B, int L, int C, int heads, int dtype) {
     if (!qkv) return DDPM_ERR_NULL;
     if (dtype != DDPM_BF16) return DDPM_ERR_DTYPE;
-    if (B <= 0 || B > 65535 || L <= 0 || C <= 0 || C > 512 || C % 32 || ld < 3 * C) return DDPM_ERR_SHAPE;
+    if (B <= 0 || L <= 0 || C <= 0 || heads < 1 || C % heads || (long long)B * heads > 65535) return DDPM_ERR_SHAPE;      // blockIdx.y = (b, h)
+    const int d = C / heads;
+    if (d > 512 || d % 32 || ld < 3LL * C) return DDPM_ERR_SHAPE;
     if (!aligned16(qkv) || ld % 8) return DDPM_ERR_ALIGN;
     if ((long long)L * ld * 2 > BUF_OOB) return DDPM_ERR_SHAPE;
     return DDPM_OK;
@@ -561,27 +570,57 @@ static int launch(K kernel, dim3 grid, hipStream_t st, const StreamArgs& a) {
     return check_launch();
 }
 
-}  // namespace
-
-// Forward at any token count:  out[b][i][:] = sum_j softmax_j(q_i . k_j * scale) v_j ;  lse[b][i] = log sum_j exp(q_i . k_j * scale)
-// (optional).  qkv: packed [B][L][ld] with q at channel 0, k at C, v at 2C.  bf16; any L >= 1 with L * ld * 2 within the buffer
-// descriptors' range; C <= 512, C % 32 == 0.
-extern "C" int ddpm_attention_stream_fwd(const void* qkv, long long ld, void* out, long long out_ld, float* lse, int B, int L, int C,
-                                         float scale, int dtype, void* stream) {
-    int rc = check_stream(qkv, ld, B, L, C, dtype);
+// the forward of `heads` heads of width C / heads each; bucket and MT follow the HEAD's width
+static int stream_fwd(const void* qkv, long long ld, void* out, long long out_ld, float* lse, int B, int L, int C, int heads, float scale,
+                      int dtype, void* stream) {
+    int rc = check_stream(qkv, ld, B, L, C, heads, dtype);
     if (rc) return rc;
     if (!out) return DDPM_ERR_NULL;
     if (!aligned16(out) || out_ld % 8) return DDPM_ERR_ALIGN;
     if (out_ld < C) return DDPM_ERR_SHAPE;
+    const int d = C / heads, BH = B * heads;
     StreamArgs a; memset(&a, 0, sizeof(a));
     a.q = (const bf16_t*)qkv; a.k = a.q + C; a.v = a.q + 2 * C; a.qkv_ld = ld;
     a.out = (bf16_t*)out; a.out_ld = out_ld; a.lse = lse;
-    a.B = B; a.L = L; a.C = C; a.scale = scale;
+    a.B = B; a.L = L; a.C = d; a.heads = heads; a.scale = scale;
     hipStream_t st = (hipStream_t)stream;
-    if (C <= 64) return launch(&attn_stream_fwd_kernel<64, 2>, dim3((L + 127) / 128, B), st, a);
-    if (C <= 128) return launch(&attn_stream_fwd_kernel<128, 2>, dim3((L + 127) / 128, B), st, a);
-    if (C <= 256) return launch(&attn_stream_fwd_kernel<256, 2>, dim3((L + 127) / 128, B), st, a);
-    return launch(&attn_stream_fwd_kernel<512, 1>, dim3((L + 63) / 64, B), st, a);
+    if (d <= 64) return launch(&attn_stream_fwd_kernel<64, 2>, dim3((L + 127) / 128, BH), st, a);
+    if (d <= 128) return launch(&attn_stream_fwd_kernel<128, 2>, dim3((L + 127) / 128, BH), st, a);
+    if (d <= 256) return launch(&attn_stream_fwd_kernel<256, 2>, dim3((L + 127) / 128, BH), st, a);
+    return launch(&attn_stream_fwd_kernel<512, 1>, dim3((L + 63) / 64, BH), st, a);
+}
+
+static int stream_bwd(const void* qkv, long long ld, const void* o, long long o_ld, const void* d_o, long long do_ld, const float* lse,
+                      float* dvec, void* dqkv, long long dqkv_ld, int B, int L, int C, int heads, float scale, int dtype, void* stream) {
+    int rc = check_stream(qkv, ld, B, L, C, heads, dtype);
+    if (rc) return rc;
+    if (!o || !d_o || !lse || !dvec || !dqkv) return DDPM_ERR_NULL;
+    if (!aligned16(o) || !aligned16(d_o) || !aligned16(dqkv) || o_ld % 8 || do_ld % 8 || dqkv_ld % 8 || dqkv_ld < 3LL * C) return DDPM_ERR_ALIGN;
+    if (o_ld < C || do_ld < C || (long long)L * o_ld * 2 > BUF_OOB || (long long)L * do_ld * 2 > BUF_OOB) return DDPM_ERR_SHAPE;
+    const int d = C / heads, BH = B * heads;
+    StreamArgs a; memset(&a, 0, sizeof(a));
+    a.q = (const bf16_t*)qkv; a.k = a.q + C; a.v = a.q + 2 * C; a.qkv_ld = ld;
+    a.o = (const bf16_t*)o; a.o_ld = o_ld; a.d_o = (const bf16_t*)d_o; a.do_ld = do_ld;
+    a.dq = (bf16_t*)dqkv; a.dk = a.dq + C; a.dv = a.dq + 2 * C; a.dqkv_ld = dqkv_ld;
+    a.lse = const_cast<float*>(lse); a.dvec = dvec;
+    a.B = B; a.L = L; a.C = d; a.heads = heads; a.scale = scale;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 g2((L + 127) / 128, BH), g1((L + 63) / 64, BH), g1z((L + 63) / 64, BH, 2);
+    if (d <= 64) { rc = launch(&attn_stream_dq_kernel<64, 2>, g2, st, a); return rc ? rc : launch(&attn_stream_dkv_kernel<64, 2>, g2, st, a); }
+    if (d <= 128) { rc = launch(&attn_stream_dq_kernel<128, 2>, g2, st, a); return rc ? rc : launch(&attn_stream_dkv_kernel<128, 2>, g2, st, a); }
+    if (d <= 256) { rc = launch(&attn_stream_dq_kernel<256, 1>, g1, st, a); return rc ? rc : launch(&attn_stream_dkv_kernel<256, 1>, g1, st, a); }
+    rc = launch(&attn_stream_dq_kernel<512, 1>, g1, st, a);
+    return rc ? rc : launch(&attn_stream_dkv_kernel<512, 1>, g1z, st, a);
+}
+
+}  // namespace
+
+// Forward at any token count:  out[b][i][:] = sum_j softmax_j(q_i . k_j * scale) v_j ;  lse[b][i] = log sum_j exp(q_i . k_j * scale)
+// (optional).  qkv: packed [B][L][ld] with q at channel 0, k at C, v at 2C.  bf16; any L >= 1 with L * ld * 2 within the buffer
+// descriptors' range; C <= 512, C % 32 == 0.  (The heads = 1 case of the multi-head entry below: the same code.)
+extern "C" int ddpm_attention_stream_fwd(const void* qkv, long long ld, void* out, long long out_ld, float* lse, int B, int L, int C,
+                                         float scale, int dtype, void* stream) {
+    return stream_fwd(qkv, ld, out, out_ld, lse, B, L, C, 1, scale, dtype, stream);
 }
 
 // Backward of the above given the saved output o, its gradient d_o and lse: writes dq / dk / dv into the packed gradient buffer
@@ -590,22 +629,22 @@ extern "C" int ddpm_attention_stream_fwd(const void* qkv, long long ld, void* ou
 extern "C" int ddpm_attention_stream_bwd(const void* qkv, long long ld, const void* o, long long o_ld, const void* d_o, long long do_ld,
                                          const float* lse, float* dvec, void* dqkv, long long dqkv_ld, int B, int L, int C, float scale,
                                          int dtype, void* stream) {
-    int rc = check_stream(qkv, ld, B, L, C, dtype);
-    if (rc) return rc;
-    if (!o || !d_o || !lse || !dvec || !dqkv) return DDPM_ERR_NULL;
-    if (!aligned16(o) || !aligned16(d_o) || !aligned16(dqkv) || o_ld % 8 || do_ld % 8 || dqkv_ld % 8 || dqkv_ld < 3 * C) return DDPM_ERR_ALIGN;
-    if (o_ld < C || do_ld < C || (long long)L * o_ld * 2 > BUF_OOB || (long long)L * do_ld * 2 > BUF_OOB) return DDPM_ERR_SHAPE;
-    StreamArgs a; memset(&a, 0, sizeof(a));
-    a.q = (const bf16_t*)qkv; a.k = a.q + C; a.v = a.q + 2 * C; a.qkv_ld = ld;
-    a.o = (const bf16_t*)o; a.o_ld = o_ld; a.d_o = (const bf16_t*)d_o; a.do_ld = do_ld;
-    a.dq = (bf16_t*)dqkv; a.dk = a.dq + C; a.dv = a.dq + 2 * C; a.dqkv_ld = dqkv_ld;
-    a.lse = const_cast<float*>(lse); a.dvec = dvec;
-    a.B = B; a.L = L; a.C = C; a.scale = scale;
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 g2((L + 127) / 128, B), g1((L + 63) / 64, B), g1z((L + 63) / 64, B, 2);
-    if (C <= 64) { rc = launch(&attn_stream_dq_kernel<64, 2>, g2, st, a); return rc ? rc : launch(&attn_stream_dkv_kernel<64, 2>, g2, st, a); }
-    if (C <= 128) { rc = launch(&attn_stream_dq_kernel<128, 2>, g2, st, a); return rc ? rc : launch(&attn_stream_dkv_kernel<128, 2>, g2, st, a); }
-    if (C <= 256) { rc = launch(&attn_stream_dq_kernel<256, 1>, g1, st, a); return rc ? rc : launch(&attn_stream_dkv_kernel<256, 1>, g1, st, a); }
-    rc = launch(&attn_stream_dq_kernel<512, 1>, g1, st, a);
-    return rc ? rc : launch(&attn_stream_dkv_kernel<512, 1>, g1z, st, a);
+    return stream_bwd(qkv, ld, o, o_ld, d_o, do_ld, lse, dvec, dqkv, dqkv_ld, B, L, C, 1, scale, dtype, stream);
+}
+
+// Multi-head: d = C / heads, head h of q, k, v = channels [h d, (h + 1) d) of its third of the packed buffer (qkv.chunk(3) and then a
+// split of each third into heads), and of out, o, d_o and the thirds of dqkv likewise:
+//     out[b][i][h d + c] = sum_j softmax_j(q_h[b][i] . k_h[b][j] * scale) v_h[b][j][c]
+// lse, dvec: [B][heads][L] fp32.  The caller passes scale (1 / sqrt(d) for the usual attention).  heads >= 1, C % heads == 0,
+// d % 32 == 0, d <= 512 (any C), B * heads <= 65535; everything else as the pair above, which is its heads = 1 case.  One launch per
+// kernel over B * heads problems: a head reads and writes only its own [L][d] of every operand and output.
+extern "C" int ddpm_attention_mh_fwd(const void* qkv, long long ld, void* out, long long out_ld, float* lse, int B, int L, int C, int heads,
+                                     float scale, int dtype, void* stream) {
+    return stream_fwd(qkv, ld, out, out_ld, lse, B, L, C, heads, scale, dtype, stream);
+}
+
+extern "C" int ddpm_attention_mh_bwd(const void* qkv, long long ld, const void* o, long long o_ld, const void* d_o, long long do_ld,
+                                     const float* lse, float* dvec, void* dqkv, long long dqkv_ld, int B, int L, int C, int heads,
+                                     float scale, int dtype, void* stream) {
+    return stream_bwd(qkv, ld, o, o_ld, d_o, do_ld, lse, dvec, dqkv, dqkv_ld, B, L, C, heads, scale, dtype, stream);
 }

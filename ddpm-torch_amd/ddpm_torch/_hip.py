@@ -47,6 +47,8 @@ PROTOTYPES = {
     "ddpm_attention_bwd": [P, L, P, L, P, L, P, P, P, L, I, I, I, F, I, P],
     "ddpm_attention_stream_fwd": [P, L, P, L, P, I, I, I, F, I, P],
     "ddpm_attention_stream_bwd": [P, L, P, L, P, L, P, P, P, L, I, I, I, F, I, P],
+    "ddpm_attention_mh_fwd": [P, L, P, L, P, I, I, I, I, F, I, P],
+    "ddpm_attention_mh_bwd": [P, L, P, L, P, L, P, P, P, L, I, I, I, I, F, I, P],
     "ddpm_timestep_embedding": [P, P, P, I, I, P],
     "ddpm_nchw_to_nhwc": [P, P, I, I, I, I, I, P],
     "ddpm_pack_weight": [P, P, P, I, I, I, I, I, I, I, P],

@@ -94,11 +94,16 @@ class ResidualBlock(nn.Module):
 
 
 class AttentionBlock(nn.Module):
-    """unet.py:23-60 — norm, project_in (C -> 3C, 1x1), project_out (init_scale 0); single head, d = C."""
+    """unet.py:23-60 — norm, project_in (C -> 3C, 1x1), project_out (init_scale 0).  The reference is the single head, d = C.
+    ``num_heads`` (not in the reference): project_in's 3C output rows are q | k | v and each third is split into ``num_heads``
+    heads of d = C / num_heads channels (qkv.chunk(3) then the split, the ordering of ADM's QKVAttention), every head with its own
+    softmax at scale 1/sqrt(d).  The parameters do not depend on it."""
 
-    def __init__(self, in_channels):
+    def __init__(self, in_channels, num_heads=1):
         super().__init__()
-        self.in_channels = in_channels
+        if isinstance(num_heads, bool) or int(num_heads) != num_heads or num_heads < 1 or in_channels % int(num_heads):
+            raise ValueError(f"num_heads must be a positive integer that divides the {in_channels} channels, got {num_heads!r}")
+        self.in_channels, self.num_heads = in_channels, int(num_heads)
         self.norm = _Norm(in_channels)
         self.project_in = _Conv(in_channels, 3 * in_channels, 1)
         self.project_out = _Conv(in_channels, in_channels, 1, init_scale=0.0)
@@ -112,8 +117,16 @@ class UNet(nn.Module):
     """Same constructor / forward contract as the reference (unet.py:96-107, :205)."""
 
     def __init__(self, in_channels, hid_channels, out_channels, ch_multipliers, num_res_blocks, apply_attn,
-                 time_embedding_dim=None, drop_rate=0., resample_with_conv=True, num_classes=None):
+                 time_embedding_dim=None, drop_rate=0., resample_with_conv=True, num_classes=None, num_heads=1, num_head_channels=None):
         super().__init__()
+        for name, val in (("num_heads", num_heads), ("num_head_channels", num_head_channels)):
+            if val is not None and (isinstance(val, bool) or int(val) != val or val < 1):
+                raise ValueError(f"{name} must be a positive integer, got {val!r}")
+        if num_heads is None:
+            num_heads = 1
+        if num_heads != 1 and num_head_channels is not None:
+            raise ValueError(f"give num_heads or num_head_channels, not both (got num_heads={num_heads}, num_head_channels={num_head_channels})")
+        self.num_heads, self.num_head_channels = int(num_heads), None if num_head_channels is None else int(num_head_channels)
         if num_classes is not None and (isinstance(num_classes, bool) or int(num_classes) != num_classes or num_classes < 1):
             raise ValueError(f"num_classes must be a positive integer or None, got {num_classes!r}")
         self.num_classes = None if num_classes is None else int(num_classes)
@@ -128,9 +141,25 @@ class UNet(nn.Module):
         E, n = self.time_embedding_dim, num_res_blocks
         chs = [hid_channels * m for m in ch_multipliers]
 
+        def heads_of(c, where):
+            """Head count of an attention block over ``c`` channels (``where`` names it in the error)."""
+            k = self.num_head_channels
+            if k is not None:
+                if c % k:
+                    raise ValueError(f"num_head_channels={k} does not divide the {c} channels of {where}")
+                return c // k
+            if c % self.num_heads:
+                raise ValueError(f"num_heads={self.num_heads} does not divide the {c} channels of {where}")
+            return self.num_heads
+
+        for i in range(levels):                   # (checked before anything is drawn: a refused model consumes no random numbers)
+            if apply_attn[i]:
+                heads_of(chs[i], f"level_{i}")
+        heads_of(chs[-1], f"the middle block (level_{levels - 1})")
+
         def block(level, cin, cout):
             res = ResidualBlock(cin, cout, E, drop_rate)
-            return _seq(res, AttentionBlock(cout)) if apply_attn[level] else res
+            return _seq(res, AttentionBlock(cout, heads_of(cout, f"level_{level}"))) if apply_attn[level] else res
 
         # construction order == the reference's, so seeded initialisation is bit-identical
         self.embed = _seq(_Linear(hid_channels, E), _Slot(), _Linear(E, E))
@@ -143,7 +172,7 @@ class UNet(nn.Module):
                 mods.append(_seq(_Slot(), _Conv(chs[i], chs[i], 3)) if resample_with_conv else _Slot())
             self.downsamples[f"level_{i}"] = nn.ModuleList(mods)
         mid = chs[-1]
-        self.middle = _seq(ResidualBlock(mid, mid, E, drop_rate), AttentionBlock(mid), ResidualBlock(mid, mid, E, drop_rate))
+        self.middle = _seq(ResidualBlock(mid, mid, E, drop_rate), AttentionBlock(mid, heads_of(mid, "the middle block")), ResidualBlock(mid, mid, E, drop_rate))
         self.upsamples = nn.ModuleDict()
         for i in range(levels):
             nxt = hid_channels if i == 0 else chs[i - 1]
@@ -163,6 +192,17 @@ class UNet(nn.Module):
 
         self.compute_dtype = _DTYPES[os.environ.get("DDPM_TORCH_AMD_COMPUTE", "fp32").lower()]
         self._eng = None
+
+    @staticmethod
+    def head_options(model_cfg, num_heads=1, num_head_channels=0):
+        """For the command lines: a config's ``model`` section that names ``num_heads`` or ``num_head_channels`` wins; one that names
+        neither takes the flags' values (1 and 0: the single head).  Edits and returns ``model_cfg``."""
+        if "num_heads" not in model_cfg and "num_head_channels" not in model_cfg:
+            if num_heads and num_heads != 1:
+                model_cfg["num_heads"] = int(num_heads)
+            if num_head_channels:
+                model_cfg["num_head_channels"] = int(num_head_channels)
+        return model_cfg
 
     # ------------------------------------------------------------------ precision knob (not in the reference)
     def set_compute_dtype(self, dtype):
@@ -1088,7 +1128,9 @@ class _Engine:
         # (csrc/attention_stream.hip): no L x L tensor, no L as a memory row.  (L <= 256 with L % 8 == 0 keeps the kernels it had.)
         stream = (self.T == torch.bfloat16 and not flash and not fused and (Lk > 256 or Lk % 8) and C <= 512 and C % 32 == 0
                   and Lk * qkv.ld * 2 <= 0x7ffffff0)
-        if fused:
+        if ab.num_heads > 1:
+            prob, lse = self._attn_heads(ab, qkv, o, B, Lk, save)
+        elif fused:
             # inference over more tokens than the kernel below serves: one kernel, the L x L logits / probabilities stay in LDS and
             # registers (unet.py:41-52).  (Up to 256 tokens the training forward — DMA rings, one-butterfly softmax — is the faster
             # one, 27 vs 32 us at B=128, L=256, C=256, and serves inference too.)
@@ -1100,12 +1142,7 @@ class _Engine:
             _hip.call("ddpm_attention_fwd_lse" if flash else "ddpm_attention_stream_fwd", qkv.ptr, qkv.ld, o.ptr, o.ld,
                       lse.data_ptr() if save else 0, B, Lk, C, scale, self.dcode, _hip.stream())
         else:
-            if Lk % self.vec:
-                # (the probability matrix [B][L][L] is an operand of the second product: its rows must be 16-byte multiples.  The bf16
-                #  mode never gets here with C <= 512, C % 32 == 0: its streaming kernels serve any token count)
-                raise NotImplementedError(f"attention over {Lk} tokens in the {'bf16' if self.T == torch.bfloat16 else 'fp32'} mode: this path "
-                                          f"needs a token count that is a multiple of {self.vec} (the bf16 mode attends over any token count "
-                                          f"when the channel count is a multiple of 32 up to 512)")
+            self._need_vec_tokens(Lk)
             q, kk, v = qkv.ptr, qkv.ptr + C * es, qkv.ptr + 2 * C * es
             logits = self._f32(B, Lk, Lk)                       # S = Q K^T / sqrt(C)   (unet.py:46-48)
             ops.gemm(q, 3 * C, bs, 0, kk, 3 * C, bs, 0, logits.data_ptr(), Lk, Lk * Lk, Lk, Lk, C, self.dcode, batch=B,
@@ -1118,6 +1155,78 @@ class _Engine:
                    res_ptr=x.ptr, res_ld=x.ld, splitk=self.splitk)
         if save:
             st["tape"].append(("attn", ab, x, out, hn, stats, qkv, prob, o, lse))
+
+    def _need_vec_tokens(self, Lk):
+        """The materialised attention path's restriction on the token count."""
+        if Lk % self.vec:
+            # (the probability matrix [..][L][L] is an operand of the second product: its rows must be 16-byte multiples.  The bf16
+            #  mode never gets here with a (head) width <= 512 that is a multiple of 32: its streaming kernels serve any token count)
+            raise NotImplementedError(f"attention over {Lk} tokens in the {'bf16' if self.T == torch.bfloat16 else 'fp32'} mode: this path "
+                                      f"needs a token count that is a multiple of {self.vec} (the bf16 mode attends over any token count "
+                                      f"when the channel count is a multiple of 32 up to 512)")
+
+    def _mh_streams(self, ab, qkv, B, Lk):
+        """Whether the head-indexed streaming kernels (ddpm_attention_mh_*) serve this block: bf16, a head width they have a bucket for."""
+        d = ab.in_channels // ab.num_heads
+        return (self.T == torch.bfloat16 and d % 32 == 0 and d <= 512 and B * ab.num_heads <= 65535
+                and Lk * qkv.ld * 2 <= 0x7ffffff0)
+
+    def _attn_heads(self, ab, qkv, o, B, Lk, save):
+        """The attention core of a block with num_heads > 1: head h of q, k, v and o is channels [h d, (h + 1) d) of its third of
+        the packed buffer / of o, every head with its own softmax at scale 1/sqrt(d).  Returns (prob, lse) for the tape."""
+        C, H = ab.in_channels, ab.num_heads
+        d = C // H
+        scale = 1.0 / math.sqrt(d)
+        if self._mh_streams(ab, qkv, B, Lk):
+            # the streaming kernels with a head index, at every token count: one launch over B * H problems, lse [B][H][L]
+            lse = self._f32(B, H, Lk) if save else None
+            _hip.call("ddpm_attention_mh_fwd", qkv.ptr, qkv.ld, o.ptr, o.ld, lse.data_ptr() if save else 0, B, Lk, C, H, scale,
+                      self.dcode, _hip.stream())
+            return None, lse
+        # fp32 mode, or a head width the kernels have no bucket for: the materialised products of the single head, per head — the
+        # operands are d-wide column slices of the same rows (pitch 3C, K = d); logits / probabilities [H][B][L][L], ONE softmax launch
+        self._need_vec_tokens(Lk)
+        if d % self.vec:                              # (a head's column slice of every operand starts at h d elements: 16-byte multiples)
+            raise NotImplementedError(f"attention with {H} heads of {d} channels in the {'bf16' if self.T == torch.bfloat16 else 'fp32'} mode: "
+                                      f"the head width must be a multiple of {self.vec}")
+        es, bs, LL = self.es, Lk * 3 * C, Lk * Lk
+        logits = self._f32(H, B, Lk, Lk)
+        for h in range(H):
+            q, kk = qkv.ptr + h * d * es, qkv.ptr + (C + h * d) * es
+            ops.gemm(q, 3 * C, bs, 0, kk, 3 * C, bs, 0, logits.data_ptr() + h * B * LL * 4, Lk, LL, Lk, Lk, d, self.dcode, batch=B,
+                     alpha=scale, out_mode=1)
+        prob = _hip.retain(torch.empty((H, B, Lk, Lk), dtype=self.T, device=self.device))
+        _hip.call("ddpm_softmax_fwd", logits.data_ptr(), prob.data_ptr(), H * B * Lk, Lk, self.dcode, _hip.stream())
+        for h in range(H):
+            v = qkv.ptr + (2 * C + h * d) * es
+            ops.gemm(prob.data_ptr() + h * B * LL * es, Lk, LL, 0, v, 3 * C, bs, 1, o.ptr + h * d * es, C, Lk * C, Lk, d, Lk, self.dcode, batch=B)
+        return prob, None
+
+    def _attn_heads_bwd(self, ab, qkv, prob, o, lse, do, dqkv, B, Lk):
+        """Backward of _attn_heads: dq | dk | dv into dqkv, in the head layout of qkv."""
+        C, H = ab.in_channels, ab.num_heads
+        d = C // H
+        scale = 1.0 / math.sqrt(d)
+        if lse is not None:
+            dvec = self._f32(B, H, Lk)
+            _hip.call("ddpm_attention_mh_bwd", qkv.ptr, qkv.ld, o.ptr, o.ld, do.ptr, do.ld, lse.data_ptr(), dvec.data_ptr(), dqkv.ptr, dqkv.ld,
+                      B, Lk, C, H, scale, self.dcode, _hip.stream())
+            return
+        es, bs, LL = self.es, Lk * 3 * C, Lk * Lk
+        dp = self._f32(H, B, Lk, Lk)
+        for h in range(H):
+            v, dv = qkv.ptr + (2 * C + h * d) * es, dqkv.ptr + (2 * C + h * d) * es
+            doh, ph = do.ptr + h * d * es, prob.data_ptr() + h * B * LL * es
+            ops.gemm(doh, C, Lk * C, 0, v, 3 * C, bs, 0, dp.data_ptr() + h * B * LL * 4, Lk, LL, Lk, Lk, d, self.dcode, batch=B, out_mode=1)   # dP = dO V^T
+            ops.gemm(ph, Lk, LL, 1, doh, C, Lk * C, 1, dv, 3 * C, bs, Lk, d, Lk, self.dcode, batch=B)                                          # dV = P^T dO
+        ds = _hip.retain(torch.empty((H, B, Lk, Lk), dtype=self.T, device=self.device))
+        _hip.call("ddpm_softmax_bwd", prob.data_ptr(), dp.data_ptr(), ds.data_ptr(), H * B * Lk, Lk, self.dcode, _hip.stream())
+        for h in range(H):
+            q, kk = qkv.ptr + h * d * es, qkv.ptr + (C + h * d) * es
+            dq, dk = dqkv.ptr + h * d * es, dqkv.ptr + (C + h * d) * es
+            dsh = ds.data_ptr() + h * B * LL * es
+            ops.gemm(dsh, Lk, LL, 0, kk, 3 * C, bs, 1, dq, 3 * C, bs, Lk, d, Lk, self.dcode, batch=B, alpha=scale)   # dQ = dS K
+            ops.gemm(dsh, Lk, LL, 1, q, 3 * C, bs, 1, dk, 3 * C, bs, Lk, d, Lk, self.dcode, batch=B, alpha=scale)    # dK = dS^T Q
 
     # ================================================================ backward
     def _open_backward(self, st, gflat=None, cut=None):
@@ -1343,7 +1452,9 @@ class _Engine:
         dqkv = self._new(B, x.H, x.W, 3 * C)
         dq, dk, dv = dqkv.ptr, dqkv.ptr + C * es, dqkv.ptr + 2 * C * es
         scale = 1.0 / math.sqrt(C)
-        if lse is not None:
+        if ab.num_heads > 1:
+            self._attn_heads_bwd(ab, qkv, prob, o, lse, do, dqkv, B, Lk)
+        elif lse is not None:
             # flash-style: P is rebuilt from q, k and the saved log-sum-exp inside the kernels (dQ; then dK and dV)
             dvec = self._f32(B, Lk)
             # (up to 256 tokens in multiples of 16 the forward was ddpm_attention_fwd_lse; every other record with an lse was streamed)

@@ -39,6 +39,8 @@ def parse_args(argv=None):
     add("--device", default="cuda:0", type=str)
     add("--use-ema", action="store_true")
     add("--compute", choices=["bf16", "fp32"], default="bf16")
+    add("--num-heads", default=1, type=int, help="as generate.py: attention heads, for a config whose model section does not name them")
+    add("--num-head-channels", default=0, type=int, help="as generate.py: channels per attention head; 0: use --num-heads")
     add("--clip-denoised", dest="clip_denoised", action="store_true", default=True)
     add("--no-clip-denoised", dest="clip_denoised", action="store_false")
     add("--seed", default=None, type=int, help="seeds the per-step noise of every batch (default: the device's default generator)")

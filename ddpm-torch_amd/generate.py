@@ -52,6 +52,9 @@ def parse_args(argv=None):
     add("--num-gpus", default=1, type=int)
     add("--compute", choices=["bf16", "fp32"], default="bf16")
     add("--seed", default=None, type=int, help="seeds x_T AND the per-step noise of every chain (default: nondeterministic, like the reference)")
+    add("--num-heads", default=1, type=int, help="attention heads of the model, for a config whose model section names neither num_heads nor "
+        "num_head_channels (the section wins; no checkpoint records the head count)")
+    add("--num-head-channels", default=0, type=int, help="channels per attention head instead of a head count; 0: use --num-heads")
     add("--labels", default="", type=str, help="class-conditional checkpoints: the classes to generate, a comma list repeated over the images "
         "(\"3,5\") or \"cycle\" for 0, 1, ..., K-1 repeated; K is read off the checkpoint's class_embed.weight.  Default: the null class")
     add("--guidance-scale", default=1.0, type=float, help="classifier-free guidance scale w of w * out(x, y) + (1 - w) * out(x, null) "
@@ -120,6 +123,8 @@ def build(args, rank=0):
     weights = weights_from(torch.load(chkpt_path, map_location=device), use_ema)
     table = next((v for k, v in weights.items() if k.endswith("class_embed.weight")), None)
     mk["num_classes"] = None if table is None else table.shape[0] - 1          # the checkpoint decides: one row per class + the null class
+    # (the head count changes no parameter: no checkpoint can tell it, so the config — or, for a config without the keys, the flags — must)
+    ddpm_torch.UNet.head_options(mk, getattr(args, "num_heads", 1), getattr(args, "num_head_channels", 0))
     model = ddpm_torch.UNet(out_channels=(2 if learned else 1) * info["channels"] * block ** 2, **mk).set_compute_dtype(args.compute)
     if block > 1:
         model = ddpm_torch.ModelWrapper(model, torch.nn.PixelUnshuffle(block), torch.nn.PixelShuffle(block))

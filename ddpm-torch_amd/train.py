@@ -83,6 +83,10 @@ def parse_args(argv=None):
     add("--ddp-wrapper", action="store_true", help="wrap the model in DistributedDataParallel instead of the native reducer")
     add("--num-classes", default=0, type=int, help="train a class-conditional model on this many classes (not in the reference; the data "
                                                   "set must carry labels: cifar10, mnist).  0: unconditional")
+    add("--num-heads", default=1, type=int, help="heads of every attention block (not in the reference, which has one); the config's model "
+                                                "section wins when it names num_heads or num_head_channels")
+    add("--num-head-channels", default=0, type=int, help="channels per attention head instead of a head count: a block over C channels gets "
+                                                        "C / K heads.  0: use --num-heads")
     add("--label-drop", default=0.1, type=float, help="probability of training a sample on the null class (classifier-free guidance)")
     add("--device-data", action="store_true", help="hold the data set on the training GPU and assemble every batch there (not in the "
                                                    "reference); --num-workers then only serves a one-off decode of image files")
@@ -140,6 +144,7 @@ def run(rank=0, args=None, temp_dir=""):
     mcfg.pop("num_classes", None)
     if num_classes:
         mcfg["num_classes"] = int(num_classes)
+    ddpm_torch.UNet.head_options(mcfg, args.num_heads, args.num_head_channels)
     unet = ddpm_torch.UNet(**mcfg).set_compute_dtype(args.compute)
     net = unet if block == 1 else ddpm_torch.ModelWrapper(unet, torch.nn.PixelUnshuffle(block), torch.nn.PixelShuffle(block))
 

@@ -145,6 +145,23 @@ int ddpm_attention_stream_bwd(const void* qkv, long long ld, const void* o, long
                               const float* lse, float* dvec, void* dqkv, long long dqkv_ld, int B, int L, int C, float scale,
                               int dtype, void* stream);
 
+/* Multi-head attention at any token count: the streaming pair with a head index (the same kernels; the pair above is heads = 1 of
+ * this code, bit for bit).  d = C / heads.  Head h of q, k and v is channels [h d, (h + 1) d) of its third of the packed buffer — q at
+ * channel 0, k at C, v at 2C, i.e. qkv.chunk(3) followed by a split of each third into heads (the ordering of ADM's QKVAttention):
+ *     out[b][i][h d + c] = sum_j softmax_j(q_h[b][i] . k_h[b][j] * scale) v_h[b][j][c]
+ * out, o, d_o and the thirds of dqkv use the same head layout.  lse and dvec are [B][heads][L] fp32 (lse may be NULL in the forward).
+ * The caller passes scale: 1 / sqrt(d) for the usual attention.  Validation, on the host before any launch: everything the streaming
+ * pair validates with its status codes (pitch rules on the full 3C / C rows, C <= ld / 3), and DDPM_ERR_SHAPE unless heads >= 1,
+ * C % heads == 0, d % 32 == 0, d <= 512 and B * heads <= 65535; bf16 only.  C itself is not bounded by 512.  The kernel bucket
+ * follows d as the streaming pair's follows C (d = 32 runs in the 64-channel bucket).  No allocation, synchronisation or attribute
+ * call; no atomics or split accumulation (a repeated backward is bit-identical); a head reads only its own [L][d] of each operand and
+ * writes only its own [L][d] of each output. */
+int ddpm_attention_mh_fwd(const void* qkv, long long ld, void* out, long long out_ld, float* lse, int B, int L, int C, int heads,
+                          float scale, int dtype, void* stream);
+int ddpm_attention_mh_bwd(const void* qkv, long long ld, const void* o, long long o_ld, const void* d_o, long long do_ld,
+                          const float* lse, float* dvec, void* dqkv, long long dqkv_ld, int B, int L, int C, int heads, float scale,
+                          int dtype, void* stream);
+
 /* nn.GroupNorm(32, C, eps=1e-6) -> SiLU -> Dropout(p) (unet.py:18-20,15,81,85-87,139-140; :57 without SiLU):
  *   y = drop(silu((x - mean_g) * rstd_g * gamma_c + beta_c)),  biased variance over (C/G)*HW elements.
  * stats (optional) receives [B][G][2] = (mean, rstd) for the backward.  workspace: ddpm_gn_workspace_floats().

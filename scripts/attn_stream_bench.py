@@ -6,7 +6,15 @@
 Same inputs, one process, the sides alternating inside every block; device events; every shape and side warmed up; the median of seven
 blocks.  The materialised sequence is timed TWICE per block ("again"): the ratio of its two medians is the run-to-run spread any
 comparison has to clear.  Prints ms, achieved FLOP/s from the algorithmic 4 B L^2 C (forward) and 10 B L^2 C (backward), the share of
-the bf16 matrix peak (2.5 PFLOP/s dense) and torch.cuda.max_memory_allocated of each side (operands included)."""
+the bf16 matrix peak (2.5 PFLOP/s dense) and torch.cuda.max_memory_allocated of each side (operands included).
+
+    python scripts/attn_stream_bench.py --heads
+
+times the multi-head entry points (ddpm_attention_mh_fwd / _bwd) instead: B = 128, C = 256, L in {256, 1024}, heads in {1, 4, 8}.  One
+multi-head call against `heads` single-head streaming calls at width d = C / heads on per-head packed buffers of their own (the same
+work in `heads` launches), the multi-head call timed twice per block for the spread, and at L = 256 the on-chip pair
+(ddpm_attention_fwd_lse / ddpm_attention_bwd) at C = 256 for context."""
+import argparse
 import math
 import os
 import statistics
@@ -108,5 +116,70 @@ def main():
         torch.cuda.empty_cache()
 
 
+def heads_main():
+    dev, bf, BF16, st = "cuda", torch.bfloat16, _hip.BF16, _hip.stream()
+    B, C = 128, 256
+    for L in (256, 1024):
+        for H in (1, 4, 8):
+            d = C // H
+            gen = torch.Generator(device=dev).manual_seed(1)
+            qkv = (torch.randn(B * L, 3, H, d, device=dev, generator=gen) * 1.2).to(bf)
+            d_o = torch.randn(B * L, H, d, device=dev, generator=gen).to(bf)
+            o, dqkv = torch.empty(B * L, C, device=dev, dtype=bf), torch.empty(B * L, 3 * C, device=dev, dtype=bf)
+            lse, dvec = torch.empty(B * H * L, device=dev), torch.empty(B * H * L, device=dev)
+            # every head's slices in a packed [B][L][3d] buffer of its own, with its own outputs
+            per = [dict(qkv=qkv[:, :, h].reshape(B * L, 3 * d).contiguous(), d_o=d_o[:, h].contiguous(), o=torch.empty(B * L, d, device=dev, dtype=bf),
+                        dqkv=torch.empty(B * L, 3 * d, device=dev, dtype=bf), lse=torch.empty(B * L, device=dev), dvec=torch.empty(B * L, device=dev))
+                   for h in range(H)]
+            sc = 1.0 / math.sqrt(d)
+
+            def mh_fwd():
+                _hip.call("ddpm_attention_mh_fwd", qkv.data_ptr(), 3 * C, o.data_ptr(), C, lse.data_ptr(), B, L, C, H, sc, BF16, st)
+
+            def mh_bwd():
+                _hip.call("ddpm_attention_mh_bwd", qkv.data_ptr(), 3 * C, o.data_ptr(), C, d_o.data_ptr(), C, lse.data_ptr(), dvec.data_ptr(),
+                          dqkv.data_ptr(), 3 * C, B, L, C, H, sc, BF16, st)
+
+            def pair(fwd, bwd, width, scale):
+                def f():
+                    for p in per:
+                        _hip.call(fwd, p["qkv"].data_ptr(), 3 * width, p["o"].data_ptr(), width, p["lse"].data_ptr(), B, L, width, scale, BF16, st)
+
+                def b():
+                    for p in per:
+                        _hip.call(bwd, p["qkv"].data_ptr(), 3 * width, p["o"].data_ptr(), width, p["d_o"].data_ptr(), width, p["lse"].data_ptr(),
+                                  p["dvec"].data_ptr(), p["dqkv"].data_ptr(), 3 * width, B, L, width, scale, BF16, st)
+                return f, b
+
+            one_fwd, one_bwd = pair("ddpm_attention_stream_fwd", "ddpm_attention_stream_bwd", d, sc)
+            sides = [("multi-head", mh_fwd, mh_bwd), (f"{H} x single-head d={d}", one_fwd, one_bwd), ("multi-head again", mh_fwd, mh_bwd)]
+            if L == 256 and H == 1:                               # context: the on-chip pair the single-head engine takes at this L
+                sides.append(("on-chip pair C=256", *pair("ddpm_attention_fwd_lse", "ddpm_attention_bwd", C, sc)))
+            flop = {"fwd": 4.0 * B * L * L * d * H, "bwd": 10.0 * B * L * L * d * H}          # H heads of width d: B H L^2 d = B L^2 C
+            n = max(2, int(2e12 / (flop["fwd"] + flop["bwd"])))
+            print(f"B={B} L={L} C={C} heads={H} d={d}  ({n} calls per block, median of {BLOCKS} blocks)", flush=True)
+            for leg in ("fwd", "bwd"):
+                fns = [(nm, f if leg == "fwd" else b) for nm, f, b in sides]
+                for _, f, _b in sides:                            # the backward reads the forward's o and lse
+                    f()
+                for _, fn in fns:
+                    for _ in range(3):
+                        fn()
+                torch.cuda.synchronize()
+                times = {nm: [] for nm, _ in fns}
+                for _ in range(BLOCKS):
+                    for nm, fn in fns:
+                        times[nm].append(block_ms(fn, n))
+                for nm, _ in fns:
+                    ms = statistics.median(times[nm])
+                    fl = flop[leg] / (ms * 1e-3)
+                    print(f"  {leg:4s} {nm:24s} {ms:8.4f} ms  (blocks {min(times[nm]):.4f} .. {max(times[nm]):.4f})  {fl / 1e12:7.1f} TFLOP/s  "
+                          f"{100 * fl / PEAK:5.2f} % of peak", flush=True)
+            del qkv, d_o, o, dqkv, per
+            torch.cuda.empty_cache()
+
+
 if __name__ == "__main__":
-    main()
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--heads", action="store_true", help="time the multi-head entry points against per-head single-head calls")
+    heads_main() if ap.parse_args().heads else main()
