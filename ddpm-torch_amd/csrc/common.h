@@ -146,13 +146,13 @@ __device__ __forceinline__ float silu_grad_fast_(float z) {
 // Per-row constants of the reverse-process kernels (elementwise.hip, guidance.hip): the four coefficient-table entries of a sample's
 // timestep, the true posterior's log-variance and the model's.
 struct VlbCoef { float recip, recip_m1, c1, c2, lv1, lv2; };
-// One element of the sampling update with p_step_kernel's arithmetic AS THAT KERNEL IS COMPILED, so that on equal log-variances the
-// kernels built on it give the same bits: every product and sum rounded on its own, except the two places where the compiler fuses p_step_kernel's —
-// the x_0 estimate of mean_type 2, fma(-x_t, c2 / c1, out / c1), and the final mean + (mask sd) z.  Written out here instead of left to the
-// optimiser, whose choice depends on the surrounding code.  (`#pragma clang fp contract(off)`: the __f*_rn spellings are plain operators
-// in this toolchain and do not keep the compiler from fusing a product into a following sum; the pragma does.)
-__device__ __forceinline__ void lv_step_elem(const VlbCoef& k, int mean_type, int clip, float xt, float o, float mask_sd, float z, float& x_prev,
-                                             float& x0) {
+// One element of the sampling update — the definition for the plain, the learned-variance and the guided step, which therefore agree to
+// the bit on equal inputs: every product and sum is rounded on its own, except the two fused operations spelled as fma below — the x_0
+// estimate of mean_type 2, fma(-x_t, c2 / c1, out / c1), and the final mean + (mask sd) z.  (`#pragma clang fp contract(off)`: the
+// __f*_rn spellings are plain operators in this toolchain and do not keep the compiler from fusing a product into a following sum; the
+// pragma does.)
+__device__ __forceinline__ void step_elem(const VlbCoef& k, int mean_type, int clip, float xt, float o, float mask_sd, float z, float& x_prev,
+                                          float& x0) {
 #pragma clang fp contract(off)
     if (mean_type == 0) x0 = k.recip * xt - k.recip_m1 * o;
     else if (mean_type == 1) x0 = o;

@@ -468,8 +468,18 @@ extern "C" int ddpm_mse_bwd(const float* pred, const float* target, const float*
 //   t[b] = 0 : mean of -log(Phi((x_0 - mu + 1/255) / sigma) - Phi((x_0 - mu - 1/255) / sigma)) / ln 2, tanh approximation of Phi, open
 //              tails beyond |x_0| = 0.999, the difference floored as the reference floors it (clamp(d - 1e-12, 0) + 1e-12).
 // The backward (d loss_b / d model_out, training: clip_denoised = False) differentiates exactly those expressions.
-struct VlbTables { const float *recip, *recip_m1, *coef1, *coef2, *post_logvar, *model_logvar; };
+// The per-timestep tables of every reverse-process kernel of this file: the four mean coefficients, then two log-variance slots —
+// (posterior_logvar, model_logvar) for a fixed-variance model, (lv_min, lv_max) for a learned one (lv_min IS the posterior's clipped
+// log-variance; lv_max the "fixed-large" table, read in var_mode 2 only).  The sampling step reads lv1 alone as its fixed table.
+struct VlbTables { const float *recip, *recip_m1, *coef1, *coef2, *lv1, *lv2; };
 // (struct VlbCoef { recip, recip_m1, c1, c2, lv1, lv2 }: common.h, shared with guidance.hip)
+// The row header of those kernels: false when the timestep lies outside the tables (the caller poisons or skips the row; no table is
+// read), else the four mean coefficients in k, whose log-variances (0 here) are the caller's to fill.
+__device__ __forceinline__ bool row_coef(const VlbTables& tb, long long tt, int T, VlbCoef& k) {
+    if ((unsigned long long)tt >= (unsigned long long)T) return false;
+    k = VlbCoef{tb.recip[tt], tb.recip_m1[tt], tb.coef1[tt], tb.coef2[tt], 0.f, 0.f};
+    return true;
+}
 __device__ __forceinline__ float vlb_cdf(float z) {
     return 0.5f * (1.0f + tanhf(0.7978845608028654f * (z + 0.044715f * z * z * z)));
 }
@@ -485,37 +495,108 @@ __device__ __forceinline__ void vlb_model_mean(const VlbCoef& k, int mean_type, 
     if (clip) x0p = x0p != x0p ? x0p : fminf(fmaxf(x0p, -1.f), 1.f);
     mean = mean_type == 2 ? o : __fadd_rn(__fmul_rn(k.c1, x0p), __fmul_rn(k.c2, xt));
 }
+// what the bound term needs of a row's coefficients and ONE model log-variance lv2 (a table entry, or an element's own)
+struct BpdConst { VlbCoef k; float dlv, e_dlv, inv_var2, inv_std; };
+__device__ __forceinline__ BpdConst bpd_const(const VlbCoef& row, float lv2) {
+    BpdConst c;
+    c.k = row; c.k.lv2 = lv2;
+    c.dlv = c.k.lv1 - lv2; c.e_dlv = expf(c.dlv); c.inv_var2 = expf(-lv2); c.inv_std = expf(-0.5f * lv2);
+    return c;
+}
+// The bound term and (pred_x_0 - x_0)^2 of one element.  decoder (t = 0): 0 = discretized Gaussian, 1 = the toy pipeline's continuous
+// Gaussian likelihood (functions.py:68-72).
+__device__ __forceinline__ float bound_term(const BpdConst& c, long long tt, int decoder, float x, float xti, float mean) {
+    const VlbCoef& k = c.k;
+    float term;
+    if (tt > 0) {
+        const float m1 = __fadd_rn(__fmul_rn(k.c1, x), __fmul_rn(k.c2, xti)), d = m1 - mean;
+        term = 0.5f * ((-1.0f - c.dlv) + d * d * c.inv_var2 + c.e_dlv);
+    } else if (decoder == 0) {
+        const float xc = x - mean;
+        const float cu = x > 0.999f ? 1.0f : vlb_cdf(c.inv_std * (xc + (1.0f / 255.0f)));
+        const float cl = x < -0.999f ? 0.0f : vlb_cdf(c.inv_std * (xc - (1.0f / 255.0f)));
+        term = -logf(fmaxf(cu - cl - 1e-12f, 0.f) + 1e-12f);
+    } else {
+        const float xc = x - mean;
+        term = 0.5f * (xc * xc * c.inv_var2 + 1.8378770664093453f + k.lv2);          // ln(2 pi)
+    }
+    return term;
+}
+__device__ __forceinline__ void bpd_elem(const BpdConst& c, long long tt, int mean_type, int clip, int decoder, float x, float xti, float o,
+                                         float& term, float& sq) {
+    float mean, x0p;
+    vlb_model_mean(c.k, mean_type, clip, xti, o, mean, x0p);
+    term = bound_term(c, tt, decoder, x, xti, mean);
+    const float e = x0p - x;
+    sq = e * e;
+}
+
+// Learned reverse-process variance (model_var_type "learned" / "learned-range"; Nichol & Dhariwal 2021 eq. 15, 16).  The network emits rows
+// of 2n floats: the mean output at b*2n + i (eps / x_0 / mean as above) and v at b*2n + n + i; the kernels address both halves in place (no
+// de-interleave pass).  The model log-variance of an element:
+//   var_mode 1 : v itself                                            (diffusion.py:113-114)
+//   var_mode 2 : f lv_max[t] + (1 - f) lv_min[t], f = (v + 1) / 2    (f is not clamped).  Each product and sum is rounded on its own, so
+//                v = +1 / -1 give the table entries to the bit.
+//   var_mode 0 : (step only) the table entry, v ignored — what DDIM does with a 2C-channel model.
+// (`#pragma clang fp contract(off)`: the __f*_rn spellings are plain operators in this toolchain and do not keep the compiler from fusing a
+// product into a following sum; the pragma does.)
+__device__ __forceinline__ float lv_logvar(int var_mode, float v, float lv_min, float lv_max) {
+#pragma clang fp contract(off)
+    if (var_mode == 1) return v;
+    const float f = 0.5f * (v + 1.0f);
+    return f * lv_max + (1.0f - f) * lv_min;
+}
+// The variance policy the bound kernels below are compiled for: where an element's BpdConst comes from, whether the network's rows carry
+// a v half (HAS_V: rows of PITCH * n floats, v at +n), and which t = 0 decoders exist.  `opt` is the policy's one launch option.
+struct FixedVar {                       // both log-variances are table entries: the constants are formed once per row; opt = decoder
+    static constexpr bool HAS_V = false;
+    static constexpr int PITCH = 1;
+    BpdConst c;
+    int decoder;
+    __device__ __forceinline__ FixedVar(const VlbTables& tb, VlbCoef k, long long tt, int opt) : decoder(opt) {
+        k.lv1 = tb.lv1[tt];
+        c = bpd_const(k, tb.lv2[tt]);
+    }
+    __device__ __forceinline__ const BpdConst& at(float) const { return c; }
+};
+struct LearnedVar {                     // the model log-variance is the element's own (lv_logvar): constants per element; opt = var_mode (1 | 2)
+    static constexpr bool HAS_V = true;
+    static constexpr int PITCH = 2;
+    static constexpr int decoder = 0;
+    VlbCoef k;
+    float lv_max;
+    int var_mode;
+    __device__ __forceinline__ LearnedVar(const VlbTables& tb, VlbCoef k_, long long tt, int opt) : k(k_), var_mode(opt) {
+        k.lv1 = tb.lv1[tt];
+        lv_max = var_mode == 2 ? tb.lv2[tt] : 0.f;
+    }
+    __device__ __forceinline__ BpdConst at(float v) const { return bpd_const(k, lv_logvar(var_mode, v, k.lv1, lv_max)); }
+};
+
+// one block of 256 per sample; t = 0 is always the discretized decoder (neither entry has a decoder argument)
+template <class V>
 __global__ __launch_bounds__(256) void vlb_terms_kernel(const float* __restrict__ x0, const float* __restrict__ xt, const float* __restrict__ out,
                                                         const long long* __restrict__ t, VlbTables tb, float* __restrict__ loss,
-                                                        float* __restrict__ pred_x0, int n, int mean_type, int clip, int T) {
+                                                        float* __restrict__ pred_x0, int n, int mean_type, int clip, int opt, int T) {
     __shared__ float sh[4];
     const int b = blockIdx.x;
     const long long tt = t[b];
     const long long base = (long long)b * n;
-    if ((unsigned long long)tt >= (unsigned long long)T) {               // index outside the tables: poison instead of reading out of bounds
+    VlbCoef k;
+    if (!row_coef(tb, tt, T, k)) {                                        // index outside the tables: poison instead of reading out of bounds
         if (threadIdx.x == 0) loss[b] = __builtin_nanf("");
         if (pred_x0) for (int i = threadIdx.x; i < n; i += blockDim.x) pred_x0[base + i] = __builtin_nanf("");
         return;
     }
-    const VlbCoef k{tb.recip[tt], tb.recip_m1[tt], tb.coef1[tt], tb.coef2[tt], tb.post_logvar[tt], tb.model_logvar[tt]};
-    const float dlv = k.lv1 - k.lv2, e_dlv = expf(dlv), inv_var2 = expf(-k.lv2), inv_std = expf(-0.5f * k.lv2);
+    const V var(tb, k, tt, opt);
+    const float* row = out + V::PITCH * base;
     float acc = 0.f;
     for (int i = threadIdx.x; i < n; i += blockDim.x) {
         const float x = x0[base + i], xti = xt[base + i];
         float mean, x0p;
-        vlb_model_mean(k, mean_type, clip, xti, out[base + i], mean, x0p);
+        vlb_model_mean(k, mean_type, clip, xti, row[i], mean, x0p);
         if (pred_x0) pred_x0[base + i] = x0p;
-        float term;
-        if (tt > 0) {
-            const float m1 = __fadd_rn(__fmul_rn(k.c1, x), __fmul_rn(k.c2, xti)), d = m1 - mean;
-            term = 0.5f * ((-1.0f - dlv) + d * d * inv_var2 + e_dlv);
-        } else {
-            const float xc = x - mean;
-            const float cu = x > 0.999f ? 1.0f : vlb_cdf(inv_std * (xc + (1.0f / 255.0f)));
-            const float cl = x < -0.999f ? 0.0f : vlb_cdf(inv_std * (xc - (1.0f / 255.0f)));
-            term = -logf(fmaxf(cu - cl - 1e-12f, 0.f) + 1e-12f);
-        }
-        acc += term;
+        acc += bound_term(var.at(V::HAS_V ? row[n + i] : 0.f), tt, 0, x, xti, mean);
     }
     acc = wave_sum(acc);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
@@ -530,8 +611,9 @@ __global__ void vlb_terms_bwd_kernel(const float* __restrict__ x0, const float* 
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < tot; i += (long long)gridDim.x * blockDim.x) {
         const int b = (int)(i / n);
         const long long tt = t[b];
-        if ((unsigned long long)tt >= (unsigned long long)T) { gout[i] = __builtin_nanf(""); continue; }
-        const VlbCoef k{tb.recip[tt], tb.recip_m1[tt], tb.coef1[tt], tb.coef2[tt], tb.post_logvar[tt], tb.model_logvar[tt]};
+        VlbCoef k;
+        if (!row_coef(tb, tt, T, k)) { gout[i] = __builtin_nanf(""); continue; }
+        k.lv2 = tb.lv2[tt];
         const float x = x0[i], xti = xt[i];
         float mean, x0p;
         vlb_model_mean(k, mean_type, 0, xti, out[i], mean, x0p);
@@ -560,7 +642,8 @@ extern "C" int ddpm_vlb_terms(const float* x_0, const float* x_t, const float* m
         return DDPM_ERR_NULL;
     if (B <= 0 || n <= 0 || T <= 0 || mean_type < 0 || mean_type > 2) return DDPM_ERR_SHAPE;
     VlbTables tb{sqrt_recip_ab, sqrt_recip_m1_ab, post_coef1, post_coef2, post_logvar, model_logvar};
-    hipLaunchKernelGGL(vlb_terms_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, x_0, x_t, model_out, t, tb, loss, pred_x0, n, mean_type, clip, T);
+    hipLaunchKernelGGL(vlb_terms_kernel<FixedVar>, dim3(B), dim3(256), 0, (hipStream_t)stream, x_0, x_t, model_out, t, tb, loss, pred_x0, n, mean_type, clip,
+                       0, T);
     return check_launch();
 }
 extern "C" int ddpm_vlb_terms_bwd(const float* x_0, const float* x_t, const float* model_out, const long long* t,
@@ -580,54 +663,29 @@ extern "C" int ddpm_vlb_terms_bwd(const float* x_0, const float* x_t, const floa
 // One step of the evaluation loop behind the network: the bound term L_t of vlb_terms_kernel (same vlb_model_mean, same expressions, and in
 // the 256-thread layout the same reduction) AND mean_i (pred_x_0 - x_0)^2 from the one pass over x_0, x_t, model_out; pred_x_0 is never
 // stored.  Both land in column t[b] of their [B][ld] tables, so the T-step loop needs no host round trip and no column copy.  A sample whose
-// t is outside [0, T) has no column: it writes nothing (the caller pre-fills the tables with NaN).  decoder 1 = the toy pipeline's
-// continuous Gaussian likelihood at t = 0 (functions.py:68-72).  No atomics, fixed reduction order.
-struct BpdConst { VlbCoef k; float dlv, e_dlv, inv_var2, inv_std; };
-__device__ __forceinline__ BpdConst bpd_const(const VlbTables& tb, long long tt) {
-    BpdConst c;
-    c.k = VlbCoef{tb.recip[tt], tb.recip_m1[tt], tb.coef1[tt], tb.coef2[tt], tb.post_logvar[tt], tb.model_logvar[tt]};
-    c.dlv = c.k.lv1 - c.k.lv2; c.e_dlv = expf(c.dlv); c.inv_var2 = expf(-c.k.lv2); c.inv_std = expf(-0.5f * c.k.lv2);
-    return c;
-}
-__device__ __forceinline__ void bpd_elem(const BpdConst& c, long long tt, int mean_type, int clip, int decoder, float x, float xti, float o,
-                                         float& term, float& sq) {
-    const VlbCoef& k = c.k;
-    float mean, x0p;
-    vlb_model_mean(k, mean_type, clip, xti, o, mean, x0p);
-    if (tt > 0) {
-        const float m1 = __fadd_rn(__fmul_rn(k.c1, x), __fmul_rn(k.c2, xti)), d = m1 - mean;
-        term = 0.5f * ((-1.0f - c.dlv) + d * d * c.inv_var2 + c.e_dlv);
-    } else if (decoder == 0) {
-        const float xc = x - mean;
-        const float cu = x > 0.999f ? 1.0f : vlb_cdf(c.inv_std * (xc + (1.0f / 255.0f)));
-        const float cl = x < -0.999f ? 0.0f : vlb_cdf(c.inv_std * (xc - (1.0f / 255.0f)));
-        term = -logf(fmaxf(cu - cl - 1e-12f, 0.f) + 1e-12f);
-    } else {
-        const float xc = x - mean;
-        term = 0.5f * (xc * xc * c.inv_var2 + 1.8378770664093453f + k.lv2);          // ln(2 pi)
-    }
-    const float e = x0p - x;
-    sq = e * e;
-}
+// t is outside [0, T) has no column: it writes nothing (the caller pre-fills the tables with NaN).  No atomics, fixed reduction order.
 struct BpdArgs {
     const float *x0, *xt, *out;
     const long long* t;
     VlbTables tb;
     float *losses, *mses;
-    int B, n, ld, mean_type, clip, decoder, T;
+    int B, n, ld, mean_type, clip, opt, T;                    // opt: the variance policy's option (FixedVar: decoder, LearnedVar: var_mode)
 };
 // rows of n <= 64 elements: one wave per row, four rows per block (the toy evaluates tens of thousands of 2-element rows)
+template <class V>
 __global__ __launch_bounds__(256) void bpd_terms_wave_kernel(BpdArgs a) {
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (b >= a.B) return;
     const long long tt = a.t[b];
-    if ((unsigned long long)tt >= (unsigned long long)a.T) return;
+    VlbCoef k;
+    if (!row_coef(a.tb, tt, a.T, k)) return;
     const long long base = (long long)b * a.n;
-    const BpdConst c = bpd_const(a.tb, tt);
+    const float* row = a.out + V::PITCH * base;
+    const V var(a.tb, k, tt, a.opt);
     float acc = 0.f, acc2 = 0.f;
     for (int i = lane; i < a.n; i += 64) {
         float term, sq;
-        bpd_elem(c, tt, a.mean_type, a.clip, a.decoder, a.x0[base + i], a.xt[base + i], a.out[base + i], term, sq);
+        bpd_elem(var.at(V::HAS_V ? row[a.n + i] : 0.f), tt, a.mean_type, a.clip, var.decoder, a.x0[base + i], a.xt[base + i], row[i], term, sq);
         acc += term; acc2 += sq;
     }
     acc = wave_sum(acc); acc2 = wave_sum(acc2);
@@ -637,8 +695,9 @@ __global__ __launch_bounds__(256) void bpd_terms_wave_kernel(BpdArgs a) {
     }
 }
 // one block per row.  256 threads (n < 16384): element order and reduction tree of vlb_terms_kernel.  1024 threads (n >= 16384): 16-byte
-// loads, two vectors of each operand in flight per thread, when the three row bases are 16-byte aligned; the scalar form otherwise.
-template <int THREADS>
+// loads, two vectors of each operand in flight per thread, when the row bases (v's too, where there is one) are 16-byte aligned; the scalar
+// form otherwise.
+template <class V, int THREADS>
 __global__ __launch_bounds__(THREADS) void bpd_terms_kernel(BpdArgs a) {
     constexpr int WAVES = THREADS / 64;
     __shared__ float sh[2][WAVES];
@@ -646,44 +705,50 @@ __global__ __launch_bounds__(THREADS) void bpd_terms_kernel(BpdArgs a) {
     const long long tt = a.t[b];
     if ((unsigned long long)tt >= (unsigned long long)a.T) return;          // uniform over the block
     const long long base = (long long)b * a.n;
-    const float *x0 = a.x0 + base, *xt = a.xt + base, *out = a.out + base;
-    const BpdConst c = bpd_const(a.tb, tt);
+    const float *x0 = a.x0 + base, *xt = a.xt + base, *out = a.out + V::PITCH * base, *vv = V::HAS_V ? out + a.n : nullptr;
+    const f32x4 no_v = {0.f, 0.f, 0.f, 0.f};
+    // row_coef written out: the table loads have to follow the row pointers for the FixedVar instantiations to keep their instructions
+    const VlbCoef k{a.tb.recip[tt], a.tb.recip_m1[tt], a.tb.coef1[tt], a.tb.coef2[tt], 0.f, 0.f};
+    const V var(a.tb, k, tt, a.opt);
     float acc = 0.f, acc2 = 0.f;
     int nv = 0;
     if (THREADS == 1024) {
-        const bool al = ((reinterpret_cast<unsigned long long>(x0) | reinterpret_cast<unsigned long long>(xt) | reinterpret_cast<unsigned long long>(out)) & 15) == 0;
+        const bool al = ((reinterpret_cast<unsigned long long>(x0) | reinterpret_cast<unsigned long long>(xt) | reinterpret_cast<unsigned long long>(out) |
+                          reinterpret_cast<unsigned long long>(vv)) & 15) == 0;
         nv = al ? a.n >> 2 : 0;
         int i = threadIdx.x;
         for (; i + THREADS < nv; i += 2 * THREADS) {
-            f32x4 vx[2], vt[2], vo[2];
+            f32x4 vx[2], vt[2], vo[2], vl[2];
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 vx[u] = reinterpret_cast<const f32x4*>(x0)[i + u * THREADS];
                 vt[u] = reinterpret_cast<const f32x4*>(xt)[i + u * THREADS];
                 vo[u] = reinterpret_cast<const f32x4*>(out)[i + u * THREADS];
+                vl[u] = V::HAS_V ? reinterpret_cast<const f32x4*>(vv)[i + u * THREADS] : no_v;
             }
 #pragma unroll
             for (int u = 0; u < 2; ++u)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     float term, sq;
-                    bpd_elem(c, tt, a.mean_type, a.clip, a.decoder, vx[u][e], vt[u][e], vo[u][e], term, sq);
+                    bpd_elem(var.at(vl[u][e]), tt, a.mean_type, a.clip, var.decoder, vx[u][e], vt[u][e], vo[u][e], term, sq);
                     acc += term; acc2 += sq;
                 }
         }
         for (; i < nv; i += THREADS) {
-            const f32x4 vx = reinterpret_cast<const f32x4*>(x0)[i], vt = reinterpret_cast<const f32x4*>(xt)[i], vo = reinterpret_cast<const f32x4*>(out)[i];
+            const f32x4 vx = reinterpret_cast<const f32x4*>(x0)[i], vt = reinterpret_cast<const f32x4*>(xt)[i], vo = reinterpret_cast<const f32x4*>(out)[i],
+                        vl = V::HAS_V ? reinterpret_cast<const f32x4*>(vv)[i] : no_v;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 float term, sq;
-                bpd_elem(c, tt, a.mean_type, a.clip, a.decoder, vx[e], vt[e], vo[e], term, sq);
+                bpd_elem(var.at(vl[e]), tt, a.mean_type, a.clip, var.decoder, vx[e], vt[e], vo[e], term, sq);
                 acc += term; acc2 += sq;
             }
         }
     }
     for (int i = (nv << 2) + threadIdx.x; i < a.n; i += THREADS) {
         float term, sq;
-        bpd_elem(c, tt, a.mean_type, a.clip, a.decoder, x0[i], xt[i], out[i], term, sq);
+        bpd_elem(var.at(V::HAS_V ? vv[i] : 0.f), tt, a.mean_type, a.clip, var.decoder, x0[i], xt[i], out[i], term, sq);
         acc += term; acc2 += sq;
     }
     acc = wave_sum(acc); acc2 = wave_sum(acc2);
@@ -702,6 +767,13 @@ __global__ __launch_bounds__(THREADS) void bpd_terms_kernel(BpdArgs a) {
         a.mses[(long long)b * a.ld + tt] = tot2 / (float)a.n;
     }
 }
+template <class V>
+static int bpd_terms_launch(const BpdArgs& a, void* stream) {
+    if (a.n <= 64) hipLaunchKernelGGL((bpd_terms_wave_kernel<V>), dim3((a.B + 3) / 4), dim3(256), 0, (hipStream_t)stream, a);
+    else if (a.n < 16384) hipLaunchKernelGGL((bpd_terms_kernel<V, 256>), dim3(a.B), dim3(256), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((bpd_terms_kernel<V, 1024>), dim3(a.B), dim3(1024), 0, (hipStream_t)stream, a);
+    return check_launch();
+}
 extern "C" int ddpm_bpd_terms(const float* x_0, const float* x_t, const float* model_out, const long long* t,
                               const float* sqrt_recip_ab, const float* sqrt_recip_m1_ab, const float* post_coef1, const float* post_coef2,
                               const float* post_logvar, const float* model_logvar, float* losses, float* mses,
@@ -711,10 +783,7 @@ extern "C" int ddpm_bpd_terms(const float* x_0, const float* x_t, const float* m
     if (B <= 0 || n <= 0 || T <= 0 || ld < T || mean_type < 0 || mean_type > 2 || decoder < 0 || decoder > 1) return DDPM_ERR_SHAPE;
     const BpdArgs a{x_0, x_t, model_out, t, VlbTables{sqrt_recip_ab, sqrt_recip_m1_ab, post_coef1, post_coef2, post_logvar, model_logvar},
                     losses, mses, B, n, ld, mean_type, clip, decoder, T};
-    if (n <= 64) hipLaunchKernelGGL(bpd_terms_wave_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, a);
-    else if (n < 16384) hipLaunchKernelGGL(bpd_terms_kernel<256>, dim3(B), dim3(256), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(bpd_terms_kernel<1024>, dim3(B), dim3(1024), 0, (hipStream_t)stream, a);
-    return check_launch();
+    return bpd_terms_launch<FixedVar>(a, stream);
 }
 // after the loop: prior[b] = mean_i KL(N(sqrt_ab_last x_0, 1 - ab_last) || N(0, 1)) / ln 2 (diffusion.py:245-250 with the tensors it meant:
 // normal_kl with mean2 = logvar2 = 0) and total[b] = sum_t losses[b][t] + prior[b]; one block per sample, fixed order.
@@ -869,38 +938,30 @@ extern "C" int ddpm_atb_f32(const float* a, long long lda, const float* b, long 
     return check_launch();
 }
 
-// One fused sampling step for model_mean_type in {eps, x_0, mean} with a fixed variance table
-// (diffusion.py:107-158): pred_x0 -> clamp -> posterior mean -> + 1[t>0]*exp(0.5*logvar)*z.
-// tab = 7 fp32 tables of length T, concatenated: recip, recip_m1, coef1, coef2, logvar, (unused), (unused)
-struct StepTables { const float *recip, *recip_m1, *coef1, *coef2, *logvar; };
+// One fused sampling step for model_mean_type in {eps, x_0, mean} (diffusion.py:107-158): pred_x0 -> clamp -> posterior mean ->
+// + 1[t>0]*exp(0.5*logvar)*z, the update itself being step_elem (common.h).  Sample b's network output starts at out + b*pitch: pitch n
+// for a C-channel model, 2n (mean output | v) for a 2C-channel one.  The log-variance is the lv1 table entry (var_mode 0) or the element's
+// own (var_mode 1 | 2: lv_logvar on v, lv1 = lv_min, lv2 = lv_max).  A timestep outside the tables poisons the sample's row.
 __global__ void p_step_kernel(const float* __restrict__ x_t, const float* __restrict__ out, const float* __restrict__ z,
-                              const long long* __restrict__ t, StepTables tb, float* __restrict__ x_prev, float* __restrict__ pred_x0,
-                              int B, int n, int mean_type, int clip, int T) {
+                              const long long* __restrict__ t, VlbTables tb, float* __restrict__ x_prev, float* __restrict__ pred_x0,
+                              int B, int n, long long pitch, int mean_type, int clip, int var_mode, int T) {
     const long long tot = (long long)B * n;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < tot; i += (long long)gridDim.x * blockDim.x) {
-        const int b = (int)(i / n);
+        const long long b = i / n, j = i - b * n;
         const long long tt = t[b];
-        if ((unsigned long long)tt >= (unsigned long long)T) {          // index outside the tables: poison instead of reading out of bounds
+        VlbCoef k;
+        if (!row_coef(tb, tt, T, k)) {
             x_prev[i] = __builtin_nanf("");
             if (pred_x0) pred_x0[i] = __builtin_nanf("");
             continue;
         }
-        const float xt = x_t[i], o = out[i];
-        float x0, mean;
-        if (mean_type == 0) {            // eps (diffusion.py:145-148)
-            x0 = __fsub_rn(__fmul_rn(tb.recip[tt], xt), __fmul_rn(tb.recip_m1[tt], o));
-        } else if (mean_type == 1) {     // x_0
-            x0 = o;
-        } else {                         // mean (diffusion.py:140-143)
-            const float c1 = tb.coef1[tt], c2 = tb.coef2[tt];
-            x0 = __fsub_rn(__fdiv_rn(o, c1), __fmul_rn(__fdiv_rn(c2, c1), xt));
-        }
-        if (clip) x0 = x0 != x0 ? x0 : fminf(fmaxf(x0, -1.f), 1.f);      // torch.clamp propagates NaN (a diverged model must stay visible)
-        if (mean_type == 2) mean = o;
-        else mean = __fadd_rn(__fmul_rn(tb.coef1[tt], x0), __fmul_rn(tb.coef2[tt], xt));
+        const float* row = out + b * pitch;
+        const float lv = var_mode == 0 ? tb.lv1[tt] : lv_logvar(var_mode, row[n + j], var_mode == 2 ? tb.lv1[tt] : 0.f, var_mode == 2 ? tb.lv2[tt] : 0.f);
         const float mask = tt > 0 ? 1.f : 0.f;
-        const float sd = expf(__fmul_rn(0.5f, tb.logvar[tt]));
-        x_prev[i] = __fadd_rn(mean, __fmul_rn(__fmul_rn(mask, sd), z[i]));
+        const float sd = expf(0.5f * lv);
+        float x0, xp;
+        step_elem(k, mean_type, clip, x_t[i], row[j], mask * sd, z[i], xp, x0);
+        x_prev[i] = xp;
         if (pred_x0) pred_x0[i] = x0;
     }
 }
@@ -909,39 +970,52 @@ extern "C" int ddpm_p_sample_step(const float* x_t, const float* model_out, cons
                                   const float* logvar, float* x_prev, float* pred_x0, int B, int n, int mean_type, int clip, int T, void* stream) {
     if (!x_t || !model_out || !z || !t || !x_prev || !sqrt_recip_ab || !sqrt_recip_m1_ab || !post_coef1 || !post_coef2 || !logvar) return DDPM_ERR_NULL;
     if (B <= 0 || n <= 0 || T <= 0 || mean_type < 0 || mean_type > 2) return DDPM_ERR_SHAPE;
-    StepTables tb{sqrt_recip_ab, sqrt_recip_m1_ab, post_coef1, post_coef2, logvar};
-    hipLaunchKernelGGL(p_step_kernel, dim3(grid_for((long long)B * n)), dim3(256), 0, (hipStream_t)stream, x_t, model_out, z, t, tb, x_prev, pred_x0, B, n, mean_type, clip, T);
+    VlbTables tb{sqrt_recip_ab, sqrt_recip_m1_ab, post_coef1, post_coef2, logvar, nullptr};
+    hipLaunchKernelGGL(p_step_kernel, dim3(grid_for((long long)B * n)), dim3(256), 0, (hipStream_t)stream, x_t, model_out, z, t, tb, x_prev, pred_x0,
+                       B, n, (long long)n, mean_type, clip, 0, T);
+    return check_launch();
+}
+extern "C" int ddpm_p_sample_step_lv(const float* x_t, const float* model_out, const float* z, const long long* t,
+                                     const float* sqrt_recip_ab, const float* sqrt_recip_m1_ab, const float* post_coef1, const float* post_coef2,
+                                     const float* logvar_lo, const float* logvar_hi, float* x_prev, float* pred_x0,
+                                     int B, int n, int mean_type, int clip, int var_mode, int T, void* stream) {
+    if (!x_t || !model_out || !z || !t || !x_prev || !sqrt_recip_ab || !sqrt_recip_m1_ab || !post_coef1 || !post_coef2) return DDPM_ERR_NULL;
+    if (B <= 0 || n <= 0 || T <= 0 || mean_type < 0 || mean_type > 2 || var_mode < 0 || var_mode > 2) return DDPM_ERR_SHAPE;
+    if ((var_mode != 1 && !logvar_lo) || (var_mode == 2 && !logvar_hi)) return DDPM_ERR_NULL;
+    VlbTables tb{sqrt_recip_ab, sqrt_recip_m1_ab, post_coef1, post_coef2, logvar_lo, logvar_hi};
+    hipLaunchKernelGGL(p_step_kernel, dim3(grid_for((long long)B * n)), dim3(256), 0, (hipStream_t)stream, x_t, model_out, z, t, tb, x_prev, pred_x0,
+                       B, n, 2ll * n, mean_type, clip, var_mode, T);
     return check_launch();
 }
 
-// ------------------------------------------------------------------ learned reverse-process variance (model_var_type "learned" /
-// "learned-range"; Nichol & Dhariwal 2021 eq. 15, 16).  The network emits rows of 2n floats: the mean output at b*2n + i (eps / x_0 / mean as
-// above) and v at b*2n + n + i; the kernels below address both halves in place (no de-interleave pass).  The model log-variance of an element:
-//   var_mode 1 : v itself                                            (diffusion.py:113-114)
-//   var_mode 2 : f lv_max[t] + (1 - f) lv_min[t], f = (v + 1) / 2    (lv_max = the "fixed-large" table, lv_min = posterior_logvar_clipped; f is
-//                not clamped).  Each product and sum is rounded on its own, so v = +1 / -1 give the table entries to the bit.
-//   var_mode 0 : (step only) the table entry, v ignored — what DDIM does with a 2C-channel model.
-// Everything else — model mean, KL, discretized decoder, the reductions — is the code of the fixed-variance kernels above, fed a
-// per-element log-variance.  No atomics, fixed reduction order.
-struct LvTables { const float *recip, *recip_m1, *coef1, *coef2, *lv_min, *lv_max; };
-// (`#pragma clang fp contract(off)`: the __f*_rn spellings are plain operators in this toolchain and do not keep the compiler from fusing a
-// product into a following sum; the pragma does.)
-__device__ __forceinline__ float lv_logvar(int var_mode, float v, float lv_min, float lv_max) {
-#pragma clang fp contract(off)
-    if (var_mode == 1) return v;
-    const float f = 0.5f * (v + 1.0f);
-    return f * lv_max + (1.0f - f) * lv_min;
+// ------------------------------------------------------------------ learned reverse-process variance: the bound kernels above compiled
+// for LearnedVar on the network's 2n-float rows, and the training loss.  No atomics, fixed reduction order.
+extern "C" int ddpm_vlb_terms_lv(const float* x_0, const float* x_t, const float* model_out, const long long* t,
+                                 const float* sqrt_recip_ab, const float* sqrt_recip_m1_ab, const float* post_coef1, const float* post_coef2,
+                                 const float* post_logvar, const float* logvar_max, float* loss, float* pred_x0,
+                                 int B, int n, int mean_type, int clip, int var_mode, int T, void* stream) {
+    if (!x_0 || !x_t || !model_out || !t || !sqrt_recip_ab || !sqrt_recip_m1_ab || !post_coef1 || !post_coef2 || !post_logvar || !loss) return DDPM_ERR_NULL;
+    if (B <= 0 || n <= 0 || T <= 0 || mean_type < 0 || mean_type > 2 || var_mode < 1 || var_mode > 2) return DDPM_ERR_SHAPE;
+    if (var_mode == 2 && !logvar_max) return DDPM_ERR_NULL;
+    VlbTables tb{sqrt_recip_ab, sqrt_recip_m1_ab, post_coef1, post_coef2, post_logvar, logvar_max};
+    hipLaunchKernelGGL(vlb_terms_kernel<LearnedVar>, dim3(B), dim3(256), 0, (hipStream_t)stream, x_0, x_t, model_out, t, tb, loss, pred_x0, n, mean_type, clip,
+                       var_mode, T);
+    return check_launch();
 }
-// (lv_step_elem — one element of the sampling update with p_step_kernel's arithmetic as that kernel is compiled — is in common.h: the
-// guided step of guidance.hip is built on the same function.)
-// the per-row constants of bpd_const with the model log-variance of ONE element in the place of the table entry
-__device__ __forceinline__ BpdConst bpd_const_lv(const VlbCoef& row, float lv2) {
-    BpdConst c;
-    c.k = row; c.k.lv2 = lv2;
-    c.dlv = c.k.lv1 - lv2; c.e_dlv = expf(c.dlv); c.inv_var2 = expf(-lv2); c.inv_std = expf(-0.5f * lv2);
-    return c;
+extern "C" int ddpm_bpd_terms_lv(const float* x_0, const float* x_t, const float* model_out, const long long* t,
+                                 const float* sqrt_recip_ab, const float* sqrt_recip_m1_ab, const float* post_coef1, const float* post_coef2,
+                                 const float* post_logvar, const float* logvar_max, float* losses, float* mses,
+                                 int B, int n, int ld, int mean_type, int clip, int decoder, int var_mode, int T, void* stream) {
+    if (!x_0 || !x_t || !model_out || !t || !sqrt_recip_ab || !sqrt_recip_m1_ab || !post_coef1 || !post_coef2 || !post_logvar || !losses || !mses)
+        return DDPM_ERR_NULL;
+    if (B <= 0 || n <= 0 || T <= 0 || ld < T || mean_type < 0 || mean_type > 2 || decoder != 0 || var_mode < 1 || var_mode > 2) return DDPM_ERR_SHAPE;
+    if (var_mode == 2 && !logvar_max) return DDPM_ERR_NULL;
+    const BpdArgs a{x_0, x_t, model_out, t, VlbTables{sqrt_recip_ab, sqrt_recip_m1_ab, post_coef1, post_coef2, post_logvar, logvar_max},
+                    losses, mses, B, n, ld, mean_type, clip, var_mode, T};
+    return bpd_terms_launch<LearnedVar>(a, stream);
 }
-// d term / d mean (the expressions of vlb_terms_bwd_kernel) and d term / d logvar of bpd_elem's term (decoder 0) at one element
+
+// d term / d mean and d term / d logvar of bpd_elem's term (decoder 0) at one element
 __device__ __forceinline__ void lv_term_grads(const BpdConst& c, long long tt, float x, float xti, float mean, float& dmean, float& dlv) {
     const VlbCoef& k = c.k;
     if (tt > 0) {
@@ -961,206 +1035,6 @@ __device__ __forceinline__ void lv_term_grads(const BpdConst& c, long long tt, f
     }
 }
 
-__global__ void p_step_lv_kernel(const float* __restrict__ x_t, const float* __restrict__ out, const float* __restrict__ z,
-                                 const long long* __restrict__ t, LvTables tb, float* __restrict__ x_prev, float* __restrict__ pred_x0,
-                                 int B, int n, int mean_type, int clip, int var_mode, int T) {
-    const long long tot = (long long)B * n;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < tot; i += (long long)gridDim.x * blockDim.x) {
-        const long long b = i / n, j = i - b * n;
-        const long long tt = t[b];
-        if ((unsigned long long)tt >= (unsigned long long)T) {
-            x_prev[i] = __builtin_nanf("");
-            if (pred_x0) pred_x0[i] = __builtin_nanf("");
-            continue;
-        }
-        const float* row = out + b * 2 * n;
-        const VlbCoef k{tb.recip[tt], tb.recip_m1[tt], tb.coef1[tt], tb.coef2[tt], 0.f, 0.f};
-        const float lv = var_mode == 0 ? tb.lv_min[tt] : lv_logvar(var_mode, row[n + j], var_mode == 2 ? tb.lv_min[tt] : 0.f, var_mode == 2 ? tb.lv_max[tt] : 0.f);
-        const float mask = tt > 0 ? 1.f : 0.f;
-        const float sd = expf(0.5f * lv);
-        float x0, xp;
-        lv_step_elem(k, mean_type, clip, x_t[i], row[j], mask * sd, z[i], xp, x0);
-        x_prev[i] = xp;
-        if (pred_x0) pred_x0[i] = x0;
-    }
-}
-extern "C" int ddpm_p_sample_step_lv(const float* x_t, const float* model_out, const float* z, const long long* t,
-                                     const float* sqrt_recip_ab, const float* sqrt_recip_m1_ab, const float* post_coef1, const float* post_coef2,
-                                     const float* logvar_lo, const float* logvar_hi, float* x_prev, float* pred_x0,
-                                     int B, int n, int mean_type, int clip, int var_mode, int T, void* stream) {
-    if (!x_t || !model_out || !z || !t || !x_prev || !sqrt_recip_ab || !sqrt_recip_m1_ab || !post_coef1 || !post_coef2) return DDPM_ERR_NULL;
-    if (B <= 0 || n <= 0 || T <= 0 || mean_type < 0 || mean_type > 2 || var_mode < 0 || var_mode > 2) return DDPM_ERR_SHAPE;
-    if ((var_mode != 1 && !logvar_lo) || (var_mode == 2 && !logvar_hi)) return DDPM_ERR_NULL;
-    LvTables tb{sqrt_recip_ab, sqrt_recip_m1_ab, post_coef1, post_coef2, logvar_lo, logvar_hi};
-    hipLaunchKernelGGL(p_step_lv_kernel, dim3(grid_for((long long)B * n)), dim3(256), 0, (hipStream_t)stream, x_t, model_out, z, t, tb, x_prev, pred_x0,
-                       B, n, mean_type, clip, var_mode, T);
-    return check_launch();
-}
-
-// bound term of one element at the per-element log-variance: bpd_elem (decoder 0) on bpd_const_lv
-__device__ __forceinline__ void lv_elem(const VlbCoef& row, float lv_max, long long tt, int mean_type, int clip, int var_mode, float x, float xti,
-                                        float o, float v, float& term, float& sq) {
-    const BpdConst c = bpd_const_lv(row, lv_logvar(var_mode, v, row.lv1, lv_max));
-    bpd_elem(c, tt, mean_type, clip, 0, x, xti, o, term, sq);
-}
-// ddpm_vlb_terms' layout (one block of 256 per sample, its element order and reduction tree)
-__global__ __launch_bounds__(256) void vlb_terms_lv_kernel(const float* __restrict__ x0, const float* __restrict__ xt, const float* __restrict__ out,
-                                                           const long long* __restrict__ t, LvTables tb, float* __restrict__ loss,
-                                                           float* __restrict__ pred_x0, int n, int mean_type, int clip, int var_mode, int T) {
-    __shared__ float sh[4];
-    const int b = blockIdx.x;
-    const long long tt = t[b];
-    const long long base = (long long)b * n;
-    if ((unsigned long long)tt >= (unsigned long long)T) {
-        if (threadIdx.x == 0) loss[b] = __builtin_nanf("");
-        if (pred_x0) for (int i = threadIdx.x; i < n; i += blockDim.x) pred_x0[base + i] = __builtin_nanf("");
-        return;
-    }
-    const float* row = out + 2 * base;
-    const VlbCoef k{tb.recip[tt], tb.recip_m1[tt], tb.coef1[tt], tb.coef2[tt], tb.lv_min[tt], 0.f};
-    const float lmax = var_mode == 2 ? tb.lv_max[tt] : 0.f;
-    float acc = 0.f;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const float xti = xt[base + i], o = row[i];
-        float term, sq;
-        lv_elem(k, lmax, tt, mean_type, clip, var_mode, x0[base + i], xti, o, row[n + i], term, sq);
-        if (pred_x0) {
-            float mean, x0p;
-            vlb_model_mean(k, mean_type, clip, xti, o, mean, x0p);
-            pred_x0[base + i] = x0p;
-        }
-        acc += term;
-    }
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) loss[b] = ((sh[0] + sh[1]) + (sh[2] + sh[3])) / (float)n / 0.6931471805599453f;
-}
-extern "C" int ddpm_vlb_terms_lv(const float* x_0, const float* x_t, const float* model_out, const long long* t,
-                                 const float* sqrt_recip_ab, const float* sqrt_recip_m1_ab, const float* post_coef1, const float* post_coef2,
-                                 const float* post_logvar, const float* logvar_max, float* loss, float* pred_x0,
-                                 int B, int n, int mean_type, int clip, int var_mode, int T, void* stream) {
-    if (!x_0 || !x_t || !model_out || !t || !sqrt_recip_ab || !sqrt_recip_m1_ab || !post_coef1 || !post_coef2 || !post_logvar || !loss) return DDPM_ERR_NULL;
-    if (B <= 0 || n <= 0 || T <= 0 || mean_type < 0 || mean_type > 2 || var_mode < 1 || var_mode > 2) return DDPM_ERR_SHAPE;
-    if (var_mode == 2 && !logvar_max) return DDPM_ERR_NULL;
-    LvTables tb{sqrt_recip_ab, sqrt_recip_m1_ab, post_coef1, post_coef2, post_logvar, logvar_max};
-    hipLaunchKernelGGL(vlb_terms_lv_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, x_0, x_t, model_out, t, tb, loss, pred_x0, n, mean_type, clip, var_mode, T);
-    return check_launch();
-}
-
-// ddpm_bpd_terms' three row layouts on the 2n-float rows
-struct BpdLvArgs {
-    const float *x0, *xt, *out;
-    const long long* t;
-    LvTables tb;
-    float *losses, *mses;
-    int B, n, ld, mean_type, clip, var_mode, T;
-};
-__global__ __launch_bounds__(256) void bpd_terms_lv_wave_kernel(BpdLvArgs a) {
-    const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (b >= a.B) return;
-    const long long tt = a.t[b];
-    if ((unsigned long long)tt >= (unsigned long long)a.T) return;
-    const long long base = (long long)b * a.n;
-    const float* row = a.out + 2 * base;
-    const VlbCoef k{a.tb.recip[tt], a.tb.recip_m1[tt], a.tb.coef1[tt], a.tb.coef2[tt], a.tb.lv_min[tt], 0.f};
-    const float lmax = a.var_mode == 2 ? a.tb.lv_max[tt] : 0.f;
-    float acc = 0.f, acc2 = 0.f;
-    for (int i = lane; i < a.n; i += 64) {
-        float term, sq;
-        lv_elem(k, lmax, tt, a.mean_type, a.clip, a.var_mode, a.x0[base + i], a.xt[base + i], row[i], row[a.n + i], term, sq);
-        acc += term; acc2 += sq;
-    }
-    acc = wave_sum(acc); acc2 = wave_sum(acc2);
-    if (lane == 0) {
-        a.losses[(long long)b * a.ld + tt] = acc / (float)a.n / 0.6931471805599453f;
-        a.mses[(long long)b * a.ld + tt] = acc2 / (float)a.n;
-    }
-}
-template <int THREADS>
-__global__ __launch_bounds__(THREADS) void bpd_terms_lv_kernel(BpdLvArgs a) {
-    constexpr int WAVES = THREADS / 64;
-    __shared__ float sh[2][WAVES];
-    const int b = blockIdx.x;
-    const long long tt = a.t[b];
-    if ((unsigned long long)tt >= (unsigned long long)a.T) return;          // uniform over the block
-    const long long base = (long long)b * a.n;
-    const float *x0 = a.x0 + base, *xt = a.xt + base, *out = a.out + 2 * base, *vv = out + a.n;
-    const VlbCoef k{a.tb.recip[tt], a.tb.recip_m1[tt], a.tb.coef1[tt], a.tb.coef2[tt], a.tb.lv_min[tt], 0.f};
-    const float lmax = a.var_mode == 2 ? a.tb.lv_max[tt] : 0.f;
-    float acc = 0.f, acc2 = 0.f;
-    int nv = 0;
-    if (THREADS == 1024) {
-        const bool al = ((reinterpret_cast<unsigned long long>(x0) | reinterpret_cast<unsigned long long>(xt) | reinterpret_cast<unsigned long long>(out) |
-                          reinterpret_cast<unsigned long long>(vv)) & 15) == 0;
-        nv = al ? a.n >> 2 : 0;
-        int i = threadIdx.x;
-        for (; i + THREADS < nv; i += 2 * THREADS) {
-            f32x4 vx[2], vt[2], vo[2], vl[2];
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                vx[u] = reinterpret_cast<const f32x4*>(x0)[i + u * THREADS];
-                vt[u] = reinterpret_cast<const f32x4*>(xt)[i + u * THREADS];
-                vo[u] = reinterpret_cast<const f32x4*>(out)[i + u * THREADS];
-                vl[u] = reinterpret_cast<const f32x4*>(vv)[i + u * THREADS];
-            }
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float term, sq;
-                    lv_elem(k, lmax, tt, a.mean_type, a.clip, a.var_mode, vx[u][e], vt[u][e], vo[u][e], vl[u][e], term, sq);
-                    acc += term; acc2 += sq;
-                }
-        }
-        for (; i < nv; i += THREADS) {
-            const f32x4 vx = reinterpret_cast<const f32x4*>(x0)[i], vt = reinterpret_cast<const f32x4*>(xt)[i], vo = reinterpret_cast<const f32x4*>(out)[i],
-                        vl = reinterpret_cast<const f32x4*>(vv)[i];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float term, sq;
-                lv_elem(k, lmax, tt, a.mean_type, a.clip, a.var_mode, vx[e], vt[e], vo[e], vl[e], term, sq);
-                acc += term; acc2 += sq;
-            }
-        }
-    }
-    for (int i = (nv << 2) + threadIdx.x; i < a.n; i += THREADS) {
-        float term, sq;
-        lv_elem(k, lmax, tt, a.mean_type, a.clip, a.var_mode, x0[i], xt[i], out[i], vv[i], term, sq);
-        acc += term; acc2 += sq;
-    }
-    acc = wave_sum(acc); acc2 = wave_sum(acc2);
-    if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = acc; sh[1][threadIdx.x >> 6] = acc2; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float tot, tot2;
-        if (WAVES == 4) {
-            tot = (sh[0][0] + sh[0][1]) + (sh[0][2] + sh[0][3]);
-            tot2 = (sh[1][0] + sh[1][1]) + (sh[1][2] + sh[1][3]);
-        } else {
-            tot = 0.f; tot2 = 0.f;
-            for (int w = 0; w < WAVES; ++w) { tot += sh[0][w]; tot2 += sh[1][w]; }
-        }
-        a.losses[(long long)b * a.ld + tt] = tot / (float)a.n / 0.6931471805599453f;
-        a.mses[(long long)b * a.ld + tt] = tot2 / (float)a.n;
-    }
-}
-extern "C" int ddpm_bpd_terms_lv(const float* x_0, const float* x_t, const float* model_out, const long long* t,
-                                 const float* sqrt_recip_ab, const float* sqrt_recip_m1_ab, const float* post_coef1, const float* post_coef2,
-                                 const float* post_logvar, const float* logvar_max, float* losses, float* mses,
-                                 int B, int n, int ld, int mean_type, int clip, int decoder, int var_mode, int T, void* stream) {
-    if (!x_0 || !x_t || !model_out || !t || !sqrt_recip_ab || !sqrt_recip_m1_ab || !post_coef1 || !post_coef2 || !post_logvar || !losses || !mses)
-        return DDPM_ERR_NULL;
-    if (B <= 0 || n <= 0 || T <= 0 || ld < T || mean_type < 0 || mean_type > 2 || decoder != 0 || var_mode < 1 || var_mode > 2) return DDPM_ERR_SHAPE;
-    if (var_mode == 2 && !logvar_max) return DDPM_ERR_NULL;
-    const BpdLvArgs a{x_0, x_t, model_out, t, LvTables{sqrt_recip_ab, sqrt_recip_m1_ab, post_coef1, post_coef2, post_logvar, logvar_max},
-                      losses, mses, B, n, ld, mean_type, clip, var_mode, T};
-    if (n <= 64) hipLaunchKernelGGL(bpd_terms_lv_wave_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, a);
-    else if (n < 16384) hipLaunchKernelGGL(bpd_terms_lv_kernel<256>, dim3(B), dim3(256), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(bpd_terms_lv_kernel<1024>, dim3(B), dim3(1024), 0, (hipStream_t)stream, a);
-    return check_launch();
-}
-
 // training loss of a learned-variance model and its gradient in ONE pass over x_0, x_t, model_out, target:
 //   loss[b] = w_mse mean_i (out_mean - target)^2 + w_vlb L_t(mean(out_mean), v)        (L_t in bits/dim, clip_denoised = False)
 //   gout[b][0..n)  = gloss[b] (w_mse 2 (out_mean - target) / n + [detach_mean = 0] w_vlb dL_t / d out_mean)
@@ -1170,7 +1044,7 @@ extern "C" int ddpm_bpd_terms_lv(const float* x_0, const float* x_t, const float
 struct LearnedLossArgs {
     const float *x0, *xt, *out, *target;
     const long long* t;
-    LvTables tb;
+    VlbTables tb;
     const float* gloss;
     float *loss, *gout;
     int n, mean_type, var_mode, detach_mean, T;
@@ -1192,8 +1066,9 @@ __global__ __launch_bounds__(THREADS) void learned_loss_kernel(LearnedLossArgs a
     const float *x0 = a.x0 + base, *xt = a.xt + base, *out = a.out + 2 * base, *vv = out + n;
     const bool mse = a.w_mse != 0.f, vlb = a.w_vlb != 0.f;
     const float* tg = mse ? a.target + base : nullptr;
-    const VlbCoef k{a.tb.recip[tt], a.tb.recip_m1[tt], a.tb.coef1[tt], a.tb.coef2[tt], a.tb.lv_min[tt], 0.f};
-    const float lmax = a.var_mode == 2 ? a.tb.lv_max[tt] : 0.f;
+    // row_coef written out, as in bpd_terms_kernel: the table loads follow the row pointers and the kernel keeps its instructions
+    const VlbCoef k{a.tb.recip[tt], a.tb.recip_m1[tt], a.tb.coef1[tt], a.tb.coef2[tt], a.tb.lv1[tt], 0.f};
+    const float lmax = a.var_mode == 2 ? a.tb.lv2[tt] : 0.f;
     const float gl = g ? a.gloss[b] : 0.f;
     const float inv2 = 2.0f / (float)n;                                     // ddpm_mse_bwd's factor
     const float sv = gl * a.w_vlb * (1.0f / ((float)n * 0.6931471805599453f));
@@ -1210,7 +1085,7 @@ __global__ __launch_bounds__(THREADS) void learned_loss_kernel(LearnedLossArgs a
         }
         if (vlb) {
             const float x = x0[i], xti = xt[i];
-            const BpdConst c = bpd_const_lv(k, lv_logvar(a.var_mode, vv[i], k.lv1, lmax));
+            const BpdConst c = bpd_const(k, lv_logvar(a.var_mode, vv[i], k.lv1, lmax));
             float term, sq;
             bpd_elem(c, tt, a.mean_type, 0, 0, x, xti, o, term, sq);
             acc += term;
@@ -1243,7 +1118,7 @@ extern "C" int ddpm_learned_loss(const float* x_0, const float* x_t, const float
     if (!x_0 || !x_t || !model_out || !t || !sqrt_recip_ab || !sqrt_recip_m1_ab || !post_coef1 || !post_coef2 || !post_logvar || !loss) return DDPM_ERR_NULL;
     if (B <= 0 || n <= 0 || T <= 0 || mean_type < 0 || mean_type > 2 || var_mode < 1 || var_mode > 2) return DDPM_ERR_SHAPE;
     if ((var_mode == 2 && !logvar_max) || (w_mse != 0.f && !target) || (gout && !gloss)) return DDPM_ERR_NULL;
-    const LearnedLossArgs a{x_0, x_t, model_out, target, t, LvTables{sqrt_recip_ab, sqrt_recip_m1_ab, post_coef1, post_coef2, post_logvar, logvar_max},
+    const LearnedLossArgs a{x_0, x_t, model_out, target, t, VlbTables{sqrt_recip_ab, sqrt_recip_m1_ab, post_coef1, post_coef2, post_logvar, logvar_max},
                             gloss, loss, gout, n, mean_type, var_mode, detach_mean, T, w_mse, w_vlb};
     if (n < 16384) hipLaunchKernelGGL(learned_loss_kernel<256>, dim3(B), dim3(256), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(learned_loss_kernel<1024>, dim3(B), dim3(1024), 0, (hipStream_t)stream, a);

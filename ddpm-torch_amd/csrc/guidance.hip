@@ -6,7 +6,7 @@
 #include "../../include/ddpm_hip.h"
 
 // Every product and sum below is rounded on its own (see csrc/ddim.hip: plain operators under this pragma, not __fmul_rn / __fadd_rn, which
-// the compiler contracts all the same).  The two fused operations of the sampling update live in lv_step_elem (common.h), spelled as fma.
+// the compiler contracts all the same).  The two fused operations of the sampling update live in step_elem (common.h), spelled as fma.
 #pragma clang fp contract(off)
 
 namespace {
@@ -61,7 +61,7 @@ struct CfgTables { const float *recip, *recip_m1, *coef1, *coef2, *logvar; };
 __device__ __forceinline__ void cfg_elem(const VlbCoef& k, float scale, float rest, int mean_type, int clip, float xt, float oc, float ou, float mask_sd,
                                          float z, float& x_prev, float& x0) {
     const float g = scale * oc + rest * ou;
-    lv_step_elem(k, mean_type, clip, xt, g, mask_sd, z, x_prev, x0);
+    step_elem(k, mean_type, clip, xt, g, mask_sd, z, x_prev, x0);
 }
 
 // grid = (column blocks, B).  Sample b reads x_t[b], out2[b] (conditional), out2[B + b] (unconditional), z[b] and writes x_prev[b], with

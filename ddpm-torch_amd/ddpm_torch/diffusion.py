@@ -244,24 +244,28 @@ class GaussianDiffusion:
 
     def _loss_term_bpd(self, denoise_fn, x_0, x_t, t, clip_denoised, return_pred):
         """diffusion.py:203-215: L_t in bits per dimension — KL(q(x_{t-1}|x_t,x_0) || p(x_{t-1}|x_t)) for t > 0, the discretized-Gaussian decoder
-        NLL at t = 0 — per sample, one fused kernel behind the network (csrc/elementwise.hip `vlb_terms_kernel`).  With grad enabled and
-        clip_denoised = False (how `train_losses` calls it) the result carries the fused backward to the network output."""
+        NLL at t = 0 — per sample, one fused kernel behind the network (csrc/elementwise.hip `vlb_terms_kernel`, compiled for a fixed and
+        for a learned variance).  With grad enabled and clip_denoised = False (how `train_losses` calls it) the result carries the fused
+        backward to the network output."""
         model_out = denoise_fn(x_t, t)
         x_0, x_t, model_out = self._prep(x_0, x_t, model_out)
         t = t.contiguous()
+        entry, tabs, mode = self._bound_entry("ddpm_vlb_terms", x_0.device)
         if self.learned_var:
-            return self._loss_term_bpd_lv(x_0, x_t, model_out, t, clip_denoised, return_pred)
-        tabs = [self._tab(n_, x_0.device) for n_ in _VLB_TABLES]
+            self._check_two_halves(model_out, x_0)
         T, code = len(self.posterior_mean_coef1), _MEAN_CODE[self.model_mean_type]
         if torch.is_grad_enabled() and model_out.requires_grad:
             if clip_denoised or return_pred:
                 raise NotImplementedError("the differentiable bound term is the training form: clip_denoised=False, return_pred=False")
+            if self.learned_var:
+                launch = lambda x0, xt, out, tg, tt, gl, g: self.learned_loss(x0, xt, out, None, tt, gl, g, 0.0, 1.0, False)      # noqa: E731
+                return _AutogradLearnedLoss.apply(model_out, x_0, x_t, None, t, launch)
             return _AutogradVLB.apply(model_out, x_0, x_t, t, tabs, code, T)
         B, n = x_0.shape[0], x_0[0].numel()
         loss = torch.empty(B, dtype=torch.float32, device=x_0.device)
         pred = torch.empty_like(x_0) if return_pred else None
-        _hip.call("ddpm_vlb_terms", x_0.data_ptr(), x_t.data_ptr(), model_out.data_ptr(), t.data_ptr(), *[tb.data_ptr() for tb in tabs],
-                  loss.data_ptr(), _hip.ptr(pred), B, n, code, int(bool(clip_denoised)), T, _hip.stream())
+        _hip.call(entry, x_0.data_ptr(), x_t.data_ptr(), model_out.data_ptr(), t.data_ptr(), *[tb.data_ptr() for tb in tabs],
+                  loss.data_ptr(), _hip.ptr(pred), B, n, code, int(bool(clip_denoised)), *mode, T, _hip.stream())
         return (loss, pred) if return_pred else loss
 
     # ---- learned variance: the *_lv entry points on the network's [B, 2C, H, W] output
@@ -271,6 +275,13 @@ class GaussianDiffusion:
 
     def _lv_tabs(self, dev):
         return [self._tab(n_, dev).data_ptr() for n_ in _LV_TABLES]
+
+    def _bound_entry(self, name, dev):
+        """How this model calls the bound kernel ``name`` (`ddpm_vlb_terms`, `ddpm_bpd_terms`): (entry point, its six tables, the extra
+        var_mode argument) — the plain entry on _VLB_TABLES, or the *_lv one on _LV_TABLES with var_mode in front of T."""
+        if self.learned_var:
+            return name + "_lv", [self._tab(n_, dev) for n_ in _LV_TABLES], [self._var_mode()]
+        return name, [self._tab(n_, dev) for n_ in _VLB_TABLES], []
 
     def _check_two_halves(self, model_out, x):
         if model_out.shape[0] != x.shape[0] or model_out[0].numel() != 2 * x[0].numel():
@@ -287,21 +298,6 @@ class GaussianDiffusion:
                   _hip.ptr(gloss), loss.data_ptr(), _hip.ptr(gout), B, n, _MEAN_CODE[self.model_mean_type], self._var_mode(), int(bool(detach_mean)),
                   len(self.posterior_mean_coef1), float(w_mse), float(w_vlb), _hip.stream())
         return loss
-
-    def _loss_term_bpd_lv(self, x_0, x_t, model_out, t, clip_denoised, return_pred):
-        self._check_two_halves(model_out, x_0)
-        if torch.is_grad_enabled() and model_out.requires_grad:
-            if clip_denoised or return_pred:
-                raise NotImplementedError("the differentiable bound term is the training form: clip_denoised=False, return_pred=False")
-            launch = lambda x0, xt, out, tg, tt, gl, g: self.learned_loss(x0, xt, out, None, tt, gl, g, 0.0, 1.0, False)      # noqa: E731
-            return _AutogradLearnedLoss.apply(model_out, x_0, x_t, None, t, launch)
-        B, n = x_0.shape[0], x_0[0].numel()
-        loss = torch.empty(B, dtype=torch.float32, device=x_0.device)
-        pred = torch.empty_like(x_0) if return_pred else None
-        _hip.call("ddpm_vlb_terms_lv", x_0.data_ptr(), x_t.data_ptr(), model_out.data_ptr(), t.data_ptr(), *self._lv_tabs(x_0.device),
-                  loss.data_ptr(), _hip.ptr(pred), B, n, _MEAN_CODE[self.model_mean_type], int(bool(clip_denoised)), self._var_mode(),
-                  len(self.posterior_mean_coef1), _hip.stream())
-        return (loss, pred) if return_pred else loss
 
     def train_losses(self, denoise_fn, x_0, t, noise=None, y=None):
         """diffusion.py:217-243 -> per-sample losses [B]: "mse" (unweighted), "kl" (the variational-bound term, :222-224) or, for a learned
@@ -350,26 +346,26 @@ class GaussianDiffusion:
     # ------------------------------------------------------------------ reverse process
     def _step(self, x_t, model_out, z, t, clip_denoised, want_pred):
         x_t, model_out, z = self._prep(x_t, model_out, z)
-        dev = x_t.device
         out = torch.empty_like(x_t)
         pred = torch.empty_like(x_t) if want_pred else None
-        if self.learned_var:
-            self._check_two_halves(model_out, x_t)
-            self._step_lv_call(x_t, model_out, z, t, out, pred, clip_denoised)
-            return out, pred
-        tabs = [self._tab(n, dev).data_ptr() for n in _STEP_TABLES]
-        _hip.call("ddpm_p_sample_step", x_t.data_ptr(), model_out.data_ptr(), z.data_ptr(), t.data_ptr(), *tabs, out.data_ptr(),
-             _hip.ptr(pred), x_t.shape[0], x_t[0].numel(), _MEAN_CODE[self.model_mean_type], int(bool(clip_denoised)),
-             len(self.posterior_mean_coef1), _hip.stream())
+        self._step_call(x_t, model_out, z, t, out, pred, clip_denoised)
         return out, pred
 
-    def _step_lv_call(self, x_t, model_out, z, t, out, pred, clip_denoised):
-        """`ddpm_p_sample_step_lv` on a [B, 2C, H, W] network output (``out`` may be ``x_t``).  var_mode 0 (a DDIM on such a model): the
-        sampler's own fixed table and the mean half alone."""
+    def _step_call(self, x_t, model_out, z, t, out, pred, clip_denoised):
+        """The launch of one sampling update on prepared fp32 tensors (``out`` may be ``x_t``: each element is read once, then written):
+        `ddpm_p_sample_step` on _STEP_TABLES, or, for a [B, 2C, H, W] network output, `ddpm_p_sample_step_lv` — on _LV_TABLES with the
+        model's var_mode; at var_mode 0 (a DDIM on such a model) on the sampler's own fixed table and the mean half alone."""
         dev, mode = x_t.device, self._var_mode()
-        tabs = self._lv_tabs(dev) if mode else [self._tab(n_, dev).data_ptr() for n_ in _STEP_TABLES] + [0]
-        _hip.call("ddpm_p_sample_step_lv", x_t.data_ptr(), model_out.data_ptr(), z.data_ptr(), t.data_ptr(), *tabs, out.data_ptr(), _hip.ptr(pred),
-                  x_t.shape[0], x_t[0].numel(), _MEAN_CODE[self.model_mean_type], int(bool(clip_denoised)), mode, len(self.posterior_mean_coef1),
+        # a learned type (var_mode 1 | 2) has no fixed table, var_mode 0 has the sampler's own
+        tabs = self._lv_tabs(dev) if mode else [self._tab(n_, dev).data_ptr() for n_ in _STEP_TABLES]
+        entry, extra = "ddpm_p_sample_step", []
+        if self.learned_var:
+            self._check_two_halves(model_out, x_t)
+            entry, extra = "ddpm_p_sample_step_lv", [mode]
+            if not mode:
+                tabs = tabs + [0]                                       # nothing in the entry's logvar_hi slot
+        _hip.call(entry, x_t.data_ptr(), model_out.data_ptr(), z.data_ptr(), t.data_ptr(), *tabs, out.data_ptr(), _hip.ptr(pred),
+                  x_t.shape[0], x_t[0].numel(), _MEAN_CODE[self.model_mean_type], int(bool(clip_denoised)), *extra, len(self.posterior_mean_coef1),
                   _hip.stream())
 
     def _step_cfg_call(self, state, out2, z, t, scale, pred, B):
@@ -614,13 +610,9 @@ class GaussianDiffusion:
         state = torch.zeros((rows,) + tuple(shape[1:]), dtype=torch.float32, device=dev)
         x_t = state[:B]
         z = torch.empty(shape, dtype=torch.float32, device=dev)
-        n = x_t[0].numel()
         t = torch.full((rows,), self._num_steps() - 1, dtype=torch.int64, device=dev)
         y = None if form is None else torch.full((rows,), form[2] if guided else 0, dtype=torch.int64, device=dev)
         rng = None if default_rng else torch.Generator(dev)
-        tabs = [] if self.learned_var else [self._tab(n_, dev) for n_ in _STEP_TABLES]
-        mean_code = _MEAN_CODE[self.model_mean_type]
-        T = len(self.posterior_mean_coef1)
 
         def body(cut=None):
             out = (denoise_fn(state, self._model_t(t)) if y is None else denoise_fn(state, self._model_t(t), y)).contiguous().float()
@@ -628,12 +620,8 @@ class GaussianDiffusion:
                 z.normal_(generator=rng)
             if guided:
                 self._step_cfg_call(state, out, z, t, form[1], None, B)
-            elif self.learned_var:
-                self._check_two_halves(out, x_t)
-                self._step_lv_call(x_t, out, z, t, x_t, None, self.clip_sampling)
             else:
-                _hip.call("ddpm_p_sample_step", x_t.data_ptr(), out.data_ptr(), z.data_ptr(), t.data_ptr(), *[tb.data_ptr() for tb in tabs],
-                          x_t.data_ptr(), 0, B, n, mean_code, int(self.clip_sampling), T, _hip.stream())   # in place: each element is read once, then written
+                self._step_call(x_t, out, z, t, x_t, None, self.clip_sampling)         # in place
             _hip.call("ddpm_add_i64", t.data_ptr(), rows, -1, _hip.stream())
 
         graph = self._capture_step(dev, rng, body, "sampling")
@@ -728,8 +716,7 @@ class GaussianDiffusion:
         losses = torch.full((B, T), float("nan"), dtype=torch.float32, device=dev)
         mses = torch.full_like(losses, float("nan"))
         qtabs = [self._tab(n_, dev) for n_ in ("sqrt_alphas_bar", "sqrt_one_minus_alphas_bar")]
-        lv = self._var_mode()
-        tabs = [self._tab(n_, dev) for n_ in (_LV_TABLES if lv else _VLB_TABLES)]
+        entry, tabs, mode = self._bound_entry("ddpm_bpd_terms", dev)
         code, clip, decoder = _MEAN_CODE[self.model_mean_type], int(bool(clip_denoised)), self.bpd_decoder
 
         def body(cut=None):
@@ -737,13 +724,10 @@ class GaussianDiffusion:
                 z.normal_(generator=rng)
             _hip.call("ddpm_q_sample", x_0.data_ptr(), z.data_ptr(), t.data_ptr(), *[tb.data_ptr() for tb in qtabs], x_t.data_ptr(), B, n, T, _hip.stream())
             out = denoise_fn(x_t, self._model_t(t)).contiguous().float()
-            if lv:
+            if self.learned_var:
                 self._check_two_halves(out, x_0)
-                _hip.call("ddpm_bpd_terms_lv", x_0.data_ptr(), x_t.data_ptr(), out.data_ptr(), t.data_ptr(), *[tb.data_ptr() for tb in tabs],
-                          losses.data_ptr(), mses.data_ptr(), B, n, T, code, clip, decoder, lv, T, _hip.stream())
-            else:
-                _hip.call("ddpm_bpd_terms", x_0.data_ptr(), x_t.data_ptr(), out.data_ptr(), t.data_ptr(), *[tb.data_ptr() for tb in tabs],
-                          losses.data_ptr(), mses.data_ptr(), B, n, T, code, clip, decoder, T, _hip.stream())
+            _hip.call(entry, x_0.data_ptr(), x_t.data_ptr(), out.data_ptr(), t.data_ptr(), *[tb.data_ptr() for tb in tabs],
+                      losses.data_ptr(), mses.data_ptr(), B, n, T, code, clip, decoder, *mode, T, _hip.stream())
             _hip.call("ddpm_add_i64", t.data_ptr(), B, -1, _hip.stream())
 
         return {"x_0": x_0, "z": z, "t": t, "losses": losses, "mses": mses, "rng": rng, "body": body, "ref": lambda: denoise_fn}

@@ -108,7 +108,7 @@ def main():
         _hip.call("ddpm_p_sample_step", x_t.data_ptr(), out3.data_ptr(), z.data_ptr(), t.data_ptr(), *tabs, xp.data_ptr(), 0, B, n, 0, 1, T, s)
 
     def step_lv():
-        dif._step_lv_call(x_t, out6, z, t, xp, None, True)
+        dif._step_call(x_t, out6, z, t, xp, None, True)
 
     for name, fn in (("ddpm_mse_fwd + ddpm_mse_bwd", mse_pair), ("ddpm_learned_loss (hybrid, with gradient)", learned),
                      ("ddpm_p_sample_step", step_old), ("ddpm_p_sample_step_lv (var_mode 2)", step_lv)):

@@ -1,11 +1,14 @@
 """Kernel-by-kernel comparison of the gfx950 device code of two csrc/ directories (hipcc cross-compiles: no GPU needed).
-    python scripts/isa_diff.py PARENT_CSRC BRANCH_CSRC [--allow NAME ...] [--show] [--only SOURCE ...]
+    python scripts/isa_diff.py PARENT_CSRC BRANCH_CSRC [--allow NAME ...] [--map OLD=NEW ...] [--show] [--only SOURCE ...]
 
 Every file of build.SOURCES is compiled from both directories with build.FLAGS + -S --cuda-device-only.  Per kernel symbol the text from
 its label to its end plus its .amdhsa_kernel descriptor is kept, comments and white space stripped, the per-file function number in
 local labels (.LBB<n>_, .LJTI<n>_, .Ltmp<n>: they shift when a function before them comes or goes) and the __hip_cuid_* symbol masked.
 Prints identical / differ / disappeared / appeared with demangled names; exits 1 when a kernel whose demangled name contains none of the
---allow strings differs, disappears or appears.  --show adds a unified diff of each kernel that differs."""
+--allow strings differs, disappears or appears.  --show adds a unified diff of each kernel that differs.  --map OLD=NEW (substrings of
+demangled names, repeatable) pairs a parent kernel that has no branch kernel of its symbol with the renamed or re-templated branch kernel
+that replaces it: the two are compared as one kernel (listed as "OLD -> NEW") with the symbol masked; each side must match exactly once
+per file, and a --map that pairs nothing in any file is an error."""
 import argparse, concurrent.futures, difflib, os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "ddpm-torch_amd", "csrc"))
@@ -58,6 +61,7 @@ def main():
     ap.add_argument("parent_csrc")
     ap.add_argument("branch_csrc")
     ap.add_argument("--allow", nargs="*", default=[], metavar="NAME", help="kernels (substring of the demangled name) that may differ")
+    ap.add_argument("--map", action="append", default=[], metavar="OLD=NEW", help="compare parent kernel OLD with branch kernel NEW (substrings of demangled names)")
     ap.add_argument("--show", action="store_true", help="print a unified diff of each kernel that differs")
     ap.add_argument("--only", nargs="*", metavar="SOURCE", help="compare these files of build.SOURCES only (while looking for a spelling)")
     args = ap.parse_args()
@@ -68,9 +72,20 @@ def main():
         asm = {k: kernels(j.result()) for k, j in jobs.items()}
     rows = {"identical": [], "differ": [], "disappeared": [], "appeared": []}
     diffs = []
+    paired = set()
     for s in sources:
         p, b = asm[("p", s)], asm[("b", s)]
         names = demangle(sorted(set(p) | set(b)))
+        for m in args.map:
+            old, new = m.split("=", 1)
+            po, bn = [n for n in p if n not in b and old in names[n]], [n for n in b if n not in p and new in names[n]]
+            if len(po) == 1 and len(bn) == 1:
+                paired.add(m)
+                names[po[0]] += " -> " + names[bn[0]]
+                p[po[0]] = [ln.replace(po[0], "@KERNEL") for ln in p[po[0]]]
+                b[po[0]] = [ln.replace(bn[0], "@KERNEL") for ln in b.pop(bn[0])]
+            elif po or bn:
+                sys.exit("--map %s=%s in %s: %d parent and %d branch kernels match (want one each)" % (old, new, s, len(po), len(bn)))
         for n in list(p) + [n for n in b if n not in p]:
             state = "disappeared" if n not in b else "appeared" if n not in p else "identical" if p[n] == b[n] else "differ"
             rows[state].append((s.replace(".hip", ".s"), names[n]))
@@ -78,6 +93,8 @@ def main():
                 d = list(difflib.unified_diff(p[n], b[n], "parent", "branch", lineterm="", n=2))
                 changed = sum(1 for ln in d[2:] if ln[0] in "+-")
                 diffs.append((names[n], changed, len(p[n]), len(b[n]), d))
+    if set(args.map) - paired:
+        sys.exit("--map paired nothing in any file: " + ", ".join(sorted(set(args.map) - paired)))
     print("parent kernels %d, branch kernels %d: identical %d, differ %d, disappeared %d, appeared %d" % (
         sum(len(asm[("p", s)]) for s in sources), sum(len(asm[("b", s)]) for s in sources),
         *(len(rows[k]) for k in ("identical", "differ", "disappeared", "appeared"))))
