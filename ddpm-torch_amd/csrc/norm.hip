@@ -13,6 +13,7 @@
 //   register-resident (gn_reg_fwd / gn_reg_bwd): the first single-launch form, kept as the fallback for geometries the staged plan
 //       declines.
 // SiLU and the dropout mask are recomputed in the backward (one hash word per two channels).
+// Scale-shift norm (ddpm_groupnorm_mod_silu_fwd / _bwd): the same kernels instantiated with a per-sample affine, see GnApplyMod.
 #include "common.h"
 #include <stdlib.h>
 
@@ -97,12 +98,59 @@ struct GnApply {
     float* stats;              // [B][G][2] (mean, rstd) saved for backward, or null
 };
 
+// Scale-shift modulation (AdaGN: y = norm(x) * (1 + scale_b) + shift_b, the timestep embedding entering a block through its second
+// GroupNorm).  A block of every kernel below works on ONE sample, so the modulated affine is the plain one with per-block constants
+//   g_eff[b,c] = gamma[c] (1 + s[b,c]),   b_eff[b,c] = beta[c] (1 + s[b,c]) + h[b,c]
+// held where gamma / beta are held; the kernels take it as a compile-time policy (MOD) whose `false` instantiations are the plain
+// kernels, argument list included.  At s = h = 0 the products are exact: the modulated entry points then give the plain ones' bits.
+struct GnApplyMod : GnApply {
+    const float* mod; long long mod_ld;      // [B][mod_ld]: scale in columns [0, C), shift in [C, 2C)
+    float* dmod; long long dmod_ld;          // backward: [dscale | dshift] in the same layout, one plain store per (b, c)
+};
+template <bool MOD> struct GnArgs { typedef GnApply type; };
+template <> struct GnArgs<true> { typedef GnApplyMod type; };
+
+// the affine of (sample b, channel c)
+template <bool MOD, typename A>
+__device__ __forceinline__ void gn_affine(const A& a, int b, int C, int c, float& g, float& bt) {
+    g = a.gamma[c]; bt = a.beta[c];
+    if constexpr (MOD) {
+        const float* m = a.mod + (long long)b * a.mod_ld + c;
+        const float s1 = 1.0f + m[0];
+        g = g * s1; bt = bt * s1 + m[C];
+        // (opaque from here on, like the loaded gamma / beta of the plain kernels: what hipcc contracts into an fma downstream must
+        //  not depend on these being products — at mod == 0 the two forms are held to the same bits)
+        asm volatile("" : "+v"(g), "+v"(bt));
+    }
+}
+// ... of a thread's vector column whose gamma / beta are already in registers
+template <bool MOD, int VEC, typename A>
+__device__ __forceinline__ void gn_modulate(const A& a, int b, int C, int c_first, bool ok, float (&gm)[VEC], float (&bt)[VEC]) {
+    if constexpr (MOD) {
+        const float* m = a.mod + (long long)b * a.mod_ld + c_first;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            const float s1 = 1.0f + (ok ? m[e] : 0.f), h = ok ? m[C + e] : 0.f;
+            gm[e] = gm[e] * s1; bt[e] = bt[e] * s1 + h;
+            asm volatile("" : "+v"(gm[e]), "+v"(bt[e]));           // (opaque: see gn_affine)
+        }
+    }
+}
+// the owner of (b, c) finishes the modulation's gradients from the channel sums A = sum dz xhat, D = sum dz (plain stores) and returns
+// 1 + s, the factor of this sample's share of dgamma / dbeta
+template <typename A>
+__device__ __forceinline__ float gn_mod_grads(const A& a, int b, int C, int c, float A1, float D) {
+    a.dmod[(long long)b * a.dmod_ld + c] = a.gamma[c] * A1 + a.beta[c] * D;
+    a.dmod[(long long)b * a.dmod_ld + C + c] = D;
+    return 1.0f + a.mod[(long long)b * a.mod_ld + c];
+}
+
 __device__ __forceinline__ unsigned long long gn_seed(const GnApply& a) {
     return (a.drop_p > 0.f && a.seed_dev) ? a.seed + a.seed_dev[0] : a.seed;
 }
 
-template <typename T>
-__global__ void gn_apply_kernel(const T* __restrict__ x, T* __restrict__ y, GnShape s, const float* __restrict__ partial, GnApply a) {
+template <typename T, bool MOD = false>
+__global__ void gn_apply_kernel(const T* __restrict__ x, T* __restrict__ y, GnShape s, const float* __restrict__ partial, typename GnArgs<MOD>::type a) {
     constexpr int VEC = Elem<T>::VEC;
     __shared__ float sh_a[GN_MAXC], sh_b[GN_MAXC];
     __shared__ float sh_mean[64], sh_rstd[64];
@@ -114,8 +162,10 @@ __global__ void gn_apply_kernel(const T* __restrict__ x, T* __restrict__ y, GnSh
     __syncthreads();
     for (int c = t; c < s.C; c += nt) {
         const int g = c / s.cpg;
-        const float sc = sh_rstd[g] * a.gamma[c];
-        sh_a[c] = sc; sh_b[c] = a.beta[c] - sh_mean[g] * sc;
+        float gmc, btc;
+        gn_affine<MOD>(a, b, s.C, c, gmc, btc);
+        const float sc = sh_rstd[g] * gmc;
+        sh_a[c] = sc; sh_b[c] = btc - sh_mean[g] * sc;
     }
     __syncthreads();
     const int cx = threadIdx.x, py = threadIdx.y, PY = blockDim.y;
@@ -184,9 +234,10 @@ __global__ __launch_bounds__(64) void gn_stats_finalize_kernel(const T* __restri
 // slab) x 64 / CL slab lanes, eight loads in flight per thread; the slab lanes meet in a butterfly over the upper lane bits.
 // CL = 16 while a lane gets <= 16 slabs (fewest, widest blocks: B = 128 means S = 24 and C / 4 x 128 single-wave blocks otherwise),
 // 4 for the long reductions of the big-image / small-batch tensors (S = 512).
-template <int CL>
+// AM (at most one GnApplyMod): the modulated backward — this kernel owns every (b, c), so it also stores dscale / dshift.
+template <int CL, typename... AM>
 __global__ __launch_bounds__(64) void gn_bwd_finalize_kernel(GnShape s, const float* __restrict__ partial /*[B][S][C][2]*/, float* __restrict__ fin /*[B][C][2]*/,
-                                                              float* __restrict__ dgamma, float* __restrict__ dbeta) {
+                                                              float* __restrict__ dgamma, float* __restrict__ dbeta, AM... am) {
     constexpr int KL = 64 / CL;
     const int b = blockIdx.y, t = threadIdx.x, cl = t % CL, k = t / CL, c = blockIdx.x * CL + cl;
     float a1 = 0.f, a2 = 0.f;
@@ -206,6 +257,7 @@ __global__ __launch_bounds__(64) void gn_bwd_finalize_kernel(GnShape s, const fl
     for (int off = CL; off < 64; off <<= 1) { a1 += __shfl_xor(a1, off, 64); a2 += __shfl_xor(a2, off, 64); }
     if (t < CL && c < s.C) {
         fin[((long long)b * s.C + c) * 2] = a1; fin[((long long)b * s.C + c) * 2 + 1] = a2;
+        if constexpr (sizeof...(AM) > 0) { const float s1 = gn_mod_grads(am..., b, s.C, c, a1, a2); a1 *= s1; a2 *= s1; }
         if (dgamma) atomicAdd(dgamma + c, a1);
         if (dbeta) atomicAdd(dbeta + c, a2);
     }
@@ -281,9 +333,9 @@ __device__ __forceinline__ void gn_block_channel_sum(const float (&part)[VEC], c
     __syncthreads();
 }
 
-template <typename T, int NV, int NT>
+template <typename T, int NV, int NT, bool MOD = false>
 __global__ __launch_bounds__(NT)
-void gn_reg_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, GnShape s, GnFused f, GnApply a) {
+void gn_reg_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, GnShape s, GnFused f, typename GnArgs<MOD>::type a) {
     constexpr int VEC = Elem<T>::VEC;
     extern __shared__ __attribute__((aligned(16))) float gsh[];
     float* sh_row = gsh;                                              // [rows_per_iter][seg_ch]
@@ -351,6 +403,7 @@ void gn_reg_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, GnShape s, Gn
     float ca[VEC], cb[VEC];
     gn_ld_channels<VEC>(a.gamma + c0 + j * VEC, true, ca);
     gn_ld_channels<VEC>(a.beta + c0 + j * VEC, true, cb);
+    gn_modulate<MOD>(a, b, s.C, c0 + j * VEC, true, ca, cb);
 #pragma unroll
     for (int e = 0; e < VEC; ++e) {
         ca[e] *= sh_rstd[gn_gidx(j * VEC + e, s.cpg)];
@@ -381,10 +434,10 @@ void gn_reg_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, GnShape s, Gn
 
 // backward twin: x and dy slices in registers; pass 1 per-channel sums A1 = sum dz*xhat, A2 = sum dz -> dgamma / dbeta
 // (atomics across samples) and the group coefficients; pass 2 dx = rstd * (dz*gamma - xhat*c1 - c2) from the registers.
-template <typename T, int NV, int NT>
+template <typename T, int NV, int NT, bool MOD = false>
 __global__ __launch_bounds__(NT)
 void gn_reg_bwd_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __restrict__ dx, GnShape s, GnFused f, long long dy_ld,
-                       long long dx_ld, const float* __restrict__ stats, float* __restrict__ dgamma, float* __restrict__ dbeta, GnApply a,
+                       long long dx_ld, const float* __restrict__ stats, float* __restrict__ dgamma, float* __restrict__ dbeta, typename GnArgs<MOD>::type a,
                        int accumulate, const T* __restrict__ addp, long long add_ld, float* __restrict__ dx_colsum, long long colsum_ld) {
     constexpr int VEC = Elem<T>::VEC;
     extern __shared__ __attribute__((aligned(16))) float gsh[];
@@ -392,6 +445,7 @@ void gn_reg_bwd_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __r
     float* sh_ch = sh_row + f.rows_per_iter * f.seg_ch;
     float* sh_c1 = sh_ch + f.seg_ch;
     float* sh_c2 = sh_c1 + 32;
+    float* sh_A = sh_c2 + 32;                                         // MOD: [seg_ch] the channel sums A, kept until D is known
     const int b = blockIdx.y, c0 = blockIdx.x * f.seg_ch, tid = threadIdx.x;
     const bool active = tid < f.nta;
     const int j = tid % f.seg_vecs, prow = tid / f.seg_vecs;
@@ -409,6 +463,7 @@ void gn_reg_bwd_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __r
     gn_group_stats<VEC>(stats, (long long)b * s.G, c0 + j * VEC, s.cpg, active, mean, rstd);
     gn_ld_channels<VEC>(a.gamma + c0 + j * VEC, active, gm);
     gn_ld_channels<VEC>(a.beta + c0 + j * VEC, active, bt);
+    gn_modulate<MOD>(a, b, s.C, c0 + j * VEC, active, gm, bt);
     const float keep_scale = a.drop_p > 0.f ? 1.0f / (1.0f - a.drop_p) : 1.0f;
     const unsigned long long seed = gn_seed(a);
     auto dz_of = [&](int p, int e, float xh, float d) -> float {
@@ -440,8 +495,15 @@ void gn_reg_bwd_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __r
     const float inv_n = 1.0f / ((float)s.HW * s.cpg);
     gn_block_channel_sum<VEC>(a1, f, active, j, prow, tid, sh_row, sh_ch);
     for (int c = tid; c < f.seg_ch; c += NT) {
+        if constexpr (MOD) {
+            float gmc, btc;
+            gn_affine<MOD>(a, b, s.C, c0 + c, gmc, btc);
+            sh_A[c] = sh_ch[c];                                       // (read back by this thread only)
+            sh_ch[c] *= gmc;
+        } else {
         if (dgamma) atomicAdd(dgamma + c0 + c, sh_ch[c]);
         sh_ch[c] *= a.gamma[c0 + c];
+        }
     }
     __syncthreads();
     if (tid < f.GPB) {
@@ -451,8 +513,17 @@ void gn_reg_bwd_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __r
     }
     gn_block_channel_sum<VEC>(a2, f, active, j, prow, tid, sh_row, sh_ch);
     for (int c = tid; c < f.seg_ch; c += NT) {
+        if constexpr (MOD) {
+            float gmc, btc;
+            gn_affine<MOD>(a, b, s.C, c0 + c, gmc, btc);
+            const float A1 = sh_A[c], D = sh_ch[c], s1 = gn_mod_grads(a, b, s.C, c0 + c, A1, D);
+            if (dgamma) atomicAdd(dgamma + c0 + c, A1 * s1);
+            if (dbeta) atomicAdd(dbeta + c0 + c, D * s1);
+            sh_ch[c] *= gmc;
+        } else {
         if (dbeta) atomicAdd(dbeta + c0 + c, sh_ch[c]);
         sh_ch[c] *= a.gamma[c0 + c];
+        }
     }
     __syncthreads();
     if (tid < f.GPB) {
@@ -694,10 +765,10 @@ __device__ __forceinline__ void gn_block_slice(const GnFused& f, int& b, int& ch
 //   backward pass 1: A1[c] = sum dz*xhat, A2[c] = sum dz -> dgamma / dbeta atomics, group coefficients c1, c2
 //            pass 2: dx = rstd * (dz*gamma - xhat*c1 - c2) (+= when accumulate), optionally the per-(sample, channel) sums of dx
 //                    (the time-bias gradient of the block, ddpm_torch/models/unet.py:86: no separate column-sum launch).
-template <typename T, int NV>
+template <typename T, int NV, bool MOD = false>
 __global__ __launch_bounds__(512, 4)
 void gn_lds_bwd8_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __restrict__ dx, GnShape s, GnFused f, long long dy_ld,
-                       long long dx_ld, const float* __restrict__ stats, float* __restrict__ dgamma, float* __restrict__ dbeta, GnApply a,
+                       long long dx_ld, const float* __restrict__ stats, float* __restrict__ dgamma, float* __restrict__ dbeta, typename GnArgs<MOD>::type a,
                        int accumulate, float* __restrict__ dx_colsum, long long colsum_ld, const T* __restrict__ addp, long long add_ld) {
     constexpr int VEC = Elem<T>::VEC, ES = (int)sizeof(T);
     extern __shared__ __attribute__((aligned(16))) char lsm[];
@@ -720,7 +791,9 @@ void gn_lds_bwd8_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __
     gn_group_stats<VEC>(stats, (long long)b * s.G, c0 + j * VEC, s.cpg, active, mean, rstd);
     gn_ld_channels<VEC>(a.gamma + c0 + j * VEC, active, gm);
     gn_ld_channels<VEC>(a.beta + c0 + j * VEC, active, bt);
-    const float gam_c = tid < f.seg_ch ? a.gamma[c0 + tid] : 0.f;      // (seg_ch <= 512) requested before the DMA, parked in LDS after pass 1
+    gn_modulate<MOD>(a, b, s.C, c0 + j * VEC, active, gm, bt);
+    float gam_c = 0.f;                                                 // (seg_ch <= 512) requested before the DMA, parked in LDS after pass 1
+    if (tid < f.seg_ch) { float unused; gn_affine<MOD>(a, b, s.C, c0 + tid, gam_c, unused); }
     const T* db = dy + ((long long)b * s.HW) * dy_ld + c0 + j * VEC;
     u32x4 vd[NV];
 #pragma unroll
@@ -773,10 +846,17 @@ void gn_lds_bwd8_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __
     if (tid < f.seg_ch) sh_gam[tid] = gam_c;                      // published by the first barrier of the reduction
     const float inv_n = 1.0f / ((float)s.HW * s.cpg);
     gn_block_channel_sum2_w<VEC>(a1, a2, f, active, j, tid, sh_row, sh_ch);        // sh_ch = [A1 | A2]
+    float* sh_s1 = sh_gam + f.seg_ch;                                               // MOD: 1 + s of the block's channels
+    if constexpr (MOD) {
+        if (tid < f.seg_ch) sh_s1[tid] = gn_mod_grads(a, b, s.C, c0 + tid, sh_ch[tid], sh_ch[f.seg_ch + tid]);
+        __syncthreads();                                                            // both sums read before either is scaled below
+    }
     for (int c = tid; c < 2 * f.seg_ch; c += 512) {
         const bool second = c >= f.seg_ch;
         const int cc = second ? c - f.seg_ch : c;
         float* dst = second ? dbeta : dgamma;
+        if constexpr (MOD) { if (dst) atomicAdd(dst + c0 + cc, sh_ch[c] * sh_s1[cc]); }
+        else
         if (dst) atomicAdd(dst + c0 + cc, sh_ch[c]);
         sh_ch[c] *= sh_gam[cc];
     }
@@ -805,7 +885,11 @@ void gn_lds_bwd8_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __
 #pragma unroll
             for (int e = 0; e < VEC; ++e) {
                 const float xh = (fx[e] - mean[e]) * rstd[e];
-                float r = rstd[e] * (fd[e] * gm[e] - xh * c1[e] - c2[e]);          // fd holds dz here
+                float r;
+                // (MOD: the contraction hipcc picks for the plain instantiation — xh * c1 fused, dz * gamma rounded — spelled out; left to
+                //  choose it fuses the other product here, and dx at mod == 0 is held to the plain entry point's bits)
+                if constexpr (MOD) r = rstd[e] * (__builtin_fmaf(-xh, c1[e], fd[e] * gm[e]) - c2[e]);
+                else r = rstd[e] * (fd[e] * gm[e] - xh * c1[e] - c2[e]);          // fd holds dz here
                 if (addp) r += ad[e];
                 o[e] = accumulate ? o[e] + r : r;
             }
@@ -885,10 +969,10 @@ __device__ __forceinline__ void gn_lds_barrier() {
 // operands of a vector alive across the flag branches: 33 spilled registers at NV = 8); FL < 0: read from the arguments.
 // FL >= 0: SiLU (bit 0) and dropout (bit 1) are compile-time facts, so that a vector's four element pairs are ONE basic block and their
 // dependent chains (exp -> rcp -> fma ...) interleave; FL < 0: read from the arguments (a branch per pair: 64 per pass).
-template <typename T, int NV, int NT, bool P2, int FL = -1>
+template <typename T, int NV, int NT, bool P2, int FL = -1, bool MOD = false>
 __global__ __launch_bounds__(NT, NT == 512 ? 4 : 2)
 void gn_lds_bwd_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __restrict__ dx, GnShape s, GnFused f, long long dy_ld,
-                       long long dx_ld, const float* __restrict__ stats, float* __restrict__ dgamma, float* __restrict__ dbeta, GnApply a,
+                       long long dx_ld, const float* __restrict__ stats, float* __restrict__ dgamma, float* __restrict__ dbeta, typename GnArgs<MOD>::type a,
                        int accumulate, float* __restrict__ dx_colsum, long long colsum_ld, const T* __restrict__ addp, long long add_ld) {
     constexpr int VEC = Elem<T>::VEC, ES = (int)sizeof(T);
     const bool do_silu = FL < 0 ? a.silu != 0 : (FL & 1) != 0, do_drop = FL < 0 ? a.drop_p > 0.f : (FL & 2) != 0;
@@ -915,6 +999,8 @@ void gn_lds_bwd_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __r
     // (all threads load, channel index clamped: no branch around VMEM)
     const int kc = c0 + min(tid, f.seg_ch - 1);
     const float in_g = a.gamma[kc], in_b = a.beta[kc];
+    float in_s = 0.f, in_h = 0.f;                                // MOD: the sample's scale / shift of the channel, requested with them
+    if constexpr (MOD) { in_s = a.mod[(long long)b * a.mod_ld + kc]; in_h = a.mod[(long long)b * a.mod_ld + s.C + kc]; }
     const gn_f32x2 in_st = *reinterpret_cast<const gn_f32x2*>(stats + ((long long)b * s.G + gn_gidx(kc, s.cpg)) * 2);
     const __amdgpu_buffer_rsrc_t rdy = gn_slice_rsrc(dy + ((long long)b * s.HW) * dy_ld + c0, ((long long)(s.HW - 1) * dy_ld + f.seg_ch) * ES);
     const __amdgpu_buffer_rsrc_t rdx = gn_slice_rsrc(dx + ((long long)b * s.HW) * dx_ld + c0, ((long long)(s.HW - 1) * dx_ld + f.seg_ch) * ES);
@@ -936,10 +1022,11 @@ void gn_lds_bwd_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __r
         vd[i] = gn_buf_ld16(rdy, od);
     }
     if (tid < f.seg_ch) {
-        const float rs = in_st.y, mean = in_st.x, ca = rs * in_g;
+        const float s1 = 1.0f + in_s, eff_g = MOD ? in_g * s1 : in_g, eff_b = MOD ? in_b * s1 + in_h : in_b;      // (gn_affine)
+        const float rs = in_st.y, mean = in_st.x, ca = rs * eff_g;
         const unsigned ad = k0 + (unsigned)(tid * 4);
         gn_lds_wr4(ad + K_RS * kstride, rs); gn_lds_wr4(ad + K_MS * kstride, -mean * rs); gn_lds_wr4(ad + K_MEAN * kstride, mean);
-        gn_lds_wr4(ad + K_CA * kstride, ca); gn_lds_wr4(ad + K_CB * kstride, in_b); gn_lds_wr4(ad + K_GAM * kstride, in_g);
+        gn_lds_wr4(ad + K_CA * kstride, ca); gn_lds_wr4(ad + K_CB * kstride, eff_b); gn_lds_wr4(ad + K_GAM * kstride, eff_g);
     }
     gn_lds_barrier();
     constexpr int NM = P2 ? 2 : VEC;                   // distinct means / pass-2 coefficients of a vector column
@@ -1069,8 +1156,14 @@ void gn_lds_bwd_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __r
             for (int w = 0; w < NW; ++w) { t1 += sh_row[w * f.seg_ch + tid]; t2 += sh_row[(NW + w) * f.seg_ch + tid]; }
             const float rs = sh_k[K_RS * f.seg_ch + tid], gam = sh_k[K_GAM * f.seg_ch + tid];
             t1 *= rs;                                                   // A1 = rstd * sum dz (x - mean)
+            if constexpr (MOD) {                                        // this thread owns (b, c0 + tid): dscale / dshift, then the sample's share of dgamma / dbeta
+                const float s1 = gn_mod_grads(a, b, s.C, c0 + tid, t1, t2);
+                if (dgamma) atomicAdd(dgamma + c0 + tid, t1 * s1);
+                if (dbeta) atomicAdd(dbeta + c0 + tid, t2 * s1);
+            } else {
             if (dgamma) atomicAdd(dgamma + c0 + tid, t1);
             if (dbeta) atomicAdd(dbeta + c0 + tid, t2);
+            }
             const float c1 = gn_group_lanes_sum(t1 * gam, s.cpg) * inv_n, c2 = gn_group_lanes_sum(t2 * gam, s.cpg) * inv_n;
             // dx = dz*ca + xhat*k2 + k3 with xhat = x*rs + ms, k2 = -rstd*c1, k3 = -rstd*c2  ->  dx = dz*ca + x*q2 + q3 (two fmas per element)
             const float k2 = -rs * c1, k3 = -rs * c2;
@@ -1081,11 +1174,19 @@ void gn_lds_bwd_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __r
         __builtin_amdgcn_s_setprio(0);
     } else {
     gn_block_channel_sum2_w<VEC, NW>(a1, a2, f, active, j, tid, sh_row, sh_ch);        // sh_ch = [sum dz (x - mean) | sum dz]
+        float* sh_s1 = sh_k + K_K2 * f.seg_ch;                    // MOD: 1 + s per channel, in the slot the pass-2 coefficients take over later
+        if constexpr (MOD) {
+            for (int c = tid; c < f.seg_ch; c += NT)
+                sh_s1[c] = gn_mod_grads(a, b, s.C, c0 + c, sh_ch[c] * sh_k[K_RS * f.seg_ch + c], sh_ch[f.seg_ch + c]);
+            __syncthreads();                                      // both sums read before either is scaled below
+        }
         for (int c = tid; c < 2 * f.seg_ch; c += NT) {
             const bool second = c >= f.seg_ch;
             const int cc = second ? c - f.seg_ch : c;
             const float v = second ? sh_ch[c] : sh_ch[c] * sh_k[K_RS * f.seg_ch + cc];      // A1 = rstd * sum dz (x - mean)
             float* dst = second ? dbeta : dgamma;
+            if constexpr (MOD) { if (dst) atomicAdd(dst + c0 + cc, v * sh_s1[cc]); }
+            else
             if (dst) atomicAdd(dst + c0 + cc, v);
             sh_ch[c] = v * sh_k[K_GAM * f.seg_ch + cc];
         }
@@ -1207,9 +1308,9 @@ void gn_lds_bwd_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __r
 // forward twin: x slice in LDS; pivot-shifted moments accumulated while the slice lands (one pass), then
 // y = drop(silu(x * a_c + b_c)) streamed out.
 // FL as in gn_lds_bwd_kernel: >= 0 bakes SiLU (bit 0) / dropout (bit 1) in, < 0 reads them from the arguments.
-template <typename T, int NV, int NT, int FL = -1>
+template <typename T, int NV, int NT, int FL = -1, bool MOD = false>
 __global__ __launch_bounds__(NT, NT == 512 ? 4 : 2)
-void gn_lds_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, GnShape s, GnFused f, GnApply a) {
+void gn_lds_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, GnShape s, GnFused f, typename GnArgs<MOD>::type a) {
     constexpr int VEC = Elem<T>::VEC, ES = (int)sizeof(T), NW = NT / 64;
     const bool do_silu = FL < 0 ? a.silu != 0 : (FL & 1) != 0, do_drop = FL < 0 ? a.drop_p > 0.f : (FL & 2) != 0;
     extern __shared__ __attribute__((aligned(16))) char lsm[];
@@ -1234,6 +1335,8 @@ void gn_lds_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, GnShape s, Gn
     // raw until after the DMA is out — its conversion would otherwise wait for the load right here
     const int kc = c0 + min(tid, f.seg_ch - 1);
     const float in_g = a.gamma[kc], in_b = a.beta[kc];
+    float in_s = 0.f, in_h = 0.f;                                // MOD: the sample's scale / shift of the channel, requested with them
+    if constexpr (MOD) { in_s = a.mod[(long long)b * a.mod_ld + kc]; in_h = a.mod[(long long)b * a.mod_ld + s.C + kc]; }
     const T* pivp = x + (long long)b * s.HW * s.x_ld + gn_gidx(kc, s.cpg) * s.cpg;          // the three elements of gn_pivot
     T in_praw = pivp[0], in_praw1 = pivp[(long long)(s.HW / 2) * s.x_ld], in_praw2 = pivp[(long long)(s.HW - 1) * s.x_ld];
     const unsigned x_o = (unsigned)((prow * s.x_ld + j * VEC) * ES), x_st = (unsigned)(f.rows_per_iter * s.x_ld * ES);
@@ -1246,7 +1349,8 @@ void gn_lds_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, GnShape s, Gn
     }
     if (tid < f.seg_ch) {
         const unsigned ad = k0 + (unsigned)(tid * 4);
-        gn_lds_wr4(ad + K_GAM * kstride, in_g); gn_lds_wr4(ad + K_BET * kstride, in_b); gn_lds_wr4(ad + K_PIV * kstride, gn_median3(Elem<T>::ld(&in_praw), Elem<T>::ld(&in_praw1), Elem<T>::ld(&in_praw2)));
+        const float s1 = 1.0f + in_s, eff_g = MOD ? in_g * s1 : in_g, eff_b = MOD ? in_b * s1 + in_h : in_b;      // (gn_affine)
+        gn_lds_wr4(ad + K_GAM * kstride, eff_g); gn_lds_wr4(ad + K_BET * kstride, eff_b); gn_lds_wr4(ad + K_PIV * kstride, gn_median3(Elem<T>::ld(&in_praw), Elem<T>::ld(&in_praw1), Elem<T>::ld(&in_praw2)));
     }
     gn_lds_barrier();
     float piv[VEC];
@@ -1480,9 +1584,9 @@ static bool gn_fused_plan(const GnShape& s, int esize, GnFused& f, size_t& lds_b
 
 // ---- backward
 // dz = dy * mask/(1-p) * silu'(z), z = gamma*xhat + beta.  Per (b, c): A1 = sum dz*xhat, A2 = sum dz.
-template <typename T>
+template <typename T, bool MOD = false>
 __global__ __launch_bounds__(GN_THREADS) void gn_bwd_reduce_kernel(const T* __restrict__ x, const T* __restrict__ dy, GnShape s, long long dy_ld,
-                                     const float* __restrict__ stats, GnApply a, float* __restrict__ partial /*[B][S][C][2]*/) {
+                                     const float* __restrict__ stats, typename GnArgs<MOD>::type a, float* __restrict__ partial /*[B][S][C][2]*/) {
     constexpr int VEC = Elem<T>::VEC;
     __shared__ float sh1[GN_MAXC], sh2[GN_MAXC];
     const int b = blockIdx.y, slab = blockIdx.x;
@@ -1494,7 +1598,17 @@ __global__ __launch_bounds__(GN_THREADS) void gn_bwd_reduce_kernel(const T* __re
     for (int j = 0; j < VEC; ++j) {
         const int c = cx * VEC + j, g = c / s.cpg;
         mean[j] = stats[((long long)b * s.G + g) * 2]; rstd[j] = stats[((long long)b * s.G + g) * 2 + 1];
-        gm[j] = a.gamma[c]; bt[j] = a.beta[c]; a1[j] = a2[j] = 0.f;
+        if constexpr (!MOD) gn_affine<MOD>(a, b, s.C, c, gm[j], bt[j]);
+        a1[j] = a2[j] = 0.f;
+    }
+    if constexpr (MOD) {
+        // the sample's affine through LDS, one channel per thread: per-thread loads of s and h (2 VEC more VMEM instructions in front of
+        // a slab of a few pixel iterations) cost the B = 2 tensors 35 - 55 % of the backward (scripts/gn_bench.py --mod)
+        for (int c = t; c < s.C; c += nt) { float gc, bc; gn_affine<MOD>(a, b, s.C, c, gc, bc); sh1[c] = gc; sh2[c] = bc; }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) { gm[j] = sh1[cx * VEC + j]; bt[j] = sh2[cx * VEC + j]; }
+        __syncthreads();                                  // (the scratch is written again behind the pixel loop)
     }
     const float keep_scale = a.drop_p > 0.f ? 1.0f / (1.0f - a.drop_p) : 1.0f;
     const unsigned long long seed = gn_seed(a);
@@ -1531,10 +1645,10 @@ __global__ __launch_bounds__(GN_THREADS) void gn_bwd_reduce_kernel(const T* __re
 }
 
 // dx = rstd * (dz*gamma - xhat*c1 - c2)   [+= when accumulate]
-template <typename T>
+template <typename T, bool MOD = false>
 __global__ void gn_bwd_apply_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __restrict__ dx, GnShape s, long long dy_ld,
                                     long long dx_ld, const float* __restrict__ stats, const float* __restrict__ partial,
-                                    float* __restrict__ dgamma, float* __restrict__ dbeta, GnApply a, int accumulate,
+                                    float* __restrict__ dgamma, float* __restrict__ dbeta, typename GnArgs<MOD>::type a, int accumulate,
                                     const T* __restrict__ addp, long long add_ld) {
     constexpr int VEC = Elem<T>::VEC;
     __shared__ float sh1[GN_MAXC], sh2[GN_MAXC];
@@ -1546,7 +1660,8 @@ __global__ void gn_bwd_apply_kernel(const T* __restrict__ x, const T* __restrict
     // group coefficients of this sample from its FINISHED channel sums [B][C][2] (gn_bwd_finalize_kernel; every block used to re-sum
     // the S per-slab partials here first — serial, S up to 256 — and block 0 issued the dgamma / dbeta atomics)
     for (int c = t; c < s.C; c += nt) {
-        const float gmc = a.gamma[c];
+        float gmc, btc;
+        gn_affine<MOD>(a, b, s.C, c, gmc, btc);
         sh1[c] = partial[((long long)b * s.C + c) * 2] * gmc; sh2[c] = partial[((long long)b * s.C + c) * 2 + 1] * gmc;
     }
     __syncthreads();
@@ -1564,7 +1679,13 @@ __global__ void gn_bwd_apply_kernel(const T* __restrict__ x, const T* __restrict
         const int c = cx * VEC + j, g = c / s.cpg;
         mean[j] = stats[((long long)b * s.G + g) * 2]; rstd[j] = stats[((long long)b * s.G + g) * 2 + 1];
         c1[j] = sh_c1[g]; c2[j] = sh_c2[g];
-        gm[j] = a.gamma[c]; bt[j] = a.beta[c];
+        if constexpr (!MOD) gn_affine<MOD>(a, b, s.C, c, gm[j], bt[j]);
+    }
+    if constexpr (MOD) {                                      // (as in gn_bwd_reduce_kernel; sh1 / sh2 are free behind the barrier above)
+        for (int c = t; c < s.C; c += nt) { float gc, bc; gn_affine<MOD>(a, b, s.C, c, gc, bc); sh1[c] = gc; sh2[c] = bc; }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) { gm[j] = sh1[cx * VEC + j]; bt[j] = sh2[cx * VEC + j]; }
     }
     const float keep_scale = a.drop_p > 0.f ? 1.0f / (1.0f - a.drop_p) : 1.0f;
     const unsigned long long seed = gn_seed(a);
@@ -1635,17 +1756,23 @@ extern "C" long long ddpm_gn_workspace_floats(int B, int HW, int C, int G, int d
     return (long long)B * s.S * C * 2 + (long long)B * C * 2 + (long long)B * G * 2;     // per-slab partials | finished channel sums | finished statistics
 }
 
-extern "C" int ddpm_groupnorm_silu_fwd(const void* x, long long x_ld, void* y, long long y_ld, const float* gamma, const float* beta,
-                                       float* stats, float* workspace, int B, int HW, int C, int G, float eps, int silu,
-                                       float drop_p, unsigned long long seed, const unsigned long long* seed_dev, int dtype, void* stream) {
-    if (!x || !y || !gamma || !beta || !workspace) return DDPM_ERR_NULL;
+// one dispatcher for the plain (MOD = false: mod / mod_ld unused) and the modulated entry point: same plans, same geometry
+template <bool MOD>
+static int gn_fwd_dispatch(const void* x, long long x_ld, void* y, long long y_ld, const float* gamma, const float* beta,
+                           float* stats, float* workspace, int B, int HW, int C, int G, float eps, int silu,
+                           float drop_p, unsigned long long seed, const unsigned long long* seed_dev, const float* mod, long long mod_ld,
+                           int dtype, void* stream) {
+    if (!x || !y || !gamma || !beta || !workspace || (MOD && !mod)) return DDPM_ERR_NULL;
     if (!aligned16(x) || !aligned16(y)) return DDPM_ERR_ALIGN;
     GnShape s; dim3 block, grid;
     const int es = dtype == DDPM_BF16 ? 2 : 4;
     if (dtype != DDPM_BF16 && dtype != DDPM_F32) return DDPM_ERR_DTYPE;
     int rc = gn_geometry(B, HW, C, G, x_ld, y_ld, es, s, block, grid);
     if (rc) return rc;
-    GnApply a = make_apply(gamma, beta, eps, silu, drop_p, seed, stats, seed_dev);
+    if (MOD && mod_ld < 2ll * C) return DDPM_ERR_SHAPE;
+    typename GnArgs<MOD>::type a;
+    static_cast<GnApply&>(a) = make_apply(gamma, beta, eps, silu, drop_p, seed, stats, seed_dev);
+    if constexpr (MOD) { a.mod = mod; a.mod_ld = mod_ld; a.dmod = nullptr; a.dmod_ld = 0; }
     hipStream_t st = (hipStream_t)stream;
     GnFused f; size_t lds = 0;
     GnFused fl; size_t lds_l = 0;
@@ -1655,12 +1782,14 @@ extern "C" int ddpm_groupnorm_silu_fwd(const void* x, long long x_ld, void* y, l
     if (small) { fl = f; fl.xcd_remap = 0; lds_l = gn_lds_bytes(f.nv <= 1 ? 1 : 2, 256, f.seg_ch); }
     if (small || (!(reg_ok && f.nv <= 2) && gn_lds_plan(s, es, fl, lds_l))) {        // x staged in LDS: single launch, 1 read + 1 write of HBM
         const dim3 fgrid(G / fl.GPB, B);
-#define GN_LF(T, NV, NT, FLV) do { static DevOnce attr; if (!attr) { if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gn_lds_fwd_kernel<T, NV, NT, FLV>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return DDPM_ERR_LAUNCH; attr = true; } \
-        hipLaunchKernelGGL((gn_lds_fwd_kernel<T, NV, NT, FLV>), fgrid, dim3(NT), lds_l, st, (const T*)x, (T*)y, s, fl, a); } while (0)
+#define GN_LF(T, NV, NT, FLV) do { static DevOnce attr; if (!attr) { if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gn_lds_fwd_kernel<T, NV, NT, FLV, MOD>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return DDPM_ERR_LAUNCH; attr = true; } \
+        hipLaunchKernelGGL((gn_lds_fwd_kernel<T, NV, NT, FLV, MOD>), fgrid, dim3(NT), lds_l, st, (const T*)x, (T*)y, s, fl, a); } while (0)
 #define GN_LF_NV(T, FLV) do { if (small) { if (fl.nv <= 1) GN_LF(T, 1, 256, FLV); else GN_LF(T, 2, 256, FLV); } else if (fl.nv <= 2) GN_LF(T, 2, 512, FLV); else if (fl.nv <= 4) GN_LF(T, 4, 512, FLV); else GN_LF(T, 8, 512, FLV); } while (0)
         if (dtype == DDPM_BF16) {
             const int flg = (silu ? 1 : 0) | (drop_p > 0.f ? 2 : 0);       // the three combinations the UNet uses are baked in
-            if (flg == 1) GN_LF_NV(bf16_t, 1); else if (flg == 3) GN_LF_NV(bf16_t, 3); else if (flg == 0) GN_LF_NV(bf16_t, 0); else GN_LF_NV(bf16_t, -1);
+            // (a modulated norm is always followed by the SiLU: its other two combinations read the flags at run time)
+            constexpr int FL0 = MOD ? -1 : 0;
+            if (flg == 1) GN_LF_NV(bf16_t, 1); else if (flg == 3) GN_LF_NV(bf16_t, 3); else if (flg == 0) GN_LF_NV(bf16_t, FL0); else GN_LF_NV(bf16_t, -1);
         } else GN_LF_NV(float, -1);
 #undef GN_LF_NV
 #undef GN_LF
@@ -1668,7 +1797,7 @@ extern "C" int ddpm_groupnorm_silu_fwd(const void* x, long long x_ld, void* y, l
     }
     if (reg_ok) {      // register-resident single launch (1 read + 1 write of HBM)
         const dim3 fgrid(G / f.GPB, B);
-#define GN_FWD(T, NV) hipLaunchKernelGGL((gn_reg_fwd_kernel<T, NV, 256>), fgrid, dim3(256), lds, st, (const T*)x, (T*)y, s, f, a)
+#define GN_FWD(T, NV) hipLaunchKernelGGL((gn_reg_fwd_kernel<T, NV, 256, MOD>), fgrid, dim3(256), lds, st, (const T*)x, (T*)y, s, f, a)
 #define GN_FWD_NV(T) do { if (f.nv <= 1) GN_FWD(T, 1); else if (f.nv <= 2) GN_FWD(T, 2); else if (f.nv <= 4) GN_FWD(T, 4); else if (f.nv <= 8) GN_FWD(T, 8); else GN_FWD(T, 16); } while (0)
         if (dtype == DDPM_BF16) GN_FWD_NV(bf16_t); else GN_FWD_NV(float);
 #undef GN_FWD_NV
@@ -1679,21 +1808,36 @@ extern "C" int ddpm_groupnorm_silu_fwd(const void* x, long long x_ld, void* y, l
     if (dtype == DDPM_BF16) {
         hipLaunchKernelGGL(gn_stats_kernel<bf16_t>, grid, block, 0, st, (const bf16_t*)x, s, workspace);
         hipLaunchKernelGGL(gn_stats_finalize_kernel<bf16_t>, dim3(G, B), dim3(64), 0, st, (const bf16_t*)x, s, workspace, eps, fin, stats);
-        hipLaunchKernelGGL(gn_apply_kernel<bf16_t>, grid, block, 0, st, (const bf16_t*)x, (bf16_t*)y, s, fin, a);
+        hipLaunchKernelGGL((gn_apply_kernel<bf16_t, MOD>), grid, block, 0, st, (const bf16_t*)x, (bf16_t*)y, s, fin, a);
     } else {
         hipLaunchKernelGGL(gn_stats_kernel<float>, grid, block, 0, st, (const float*)x, s, workspace);
         hipLaunchKernelGGL(gn_stats_finalize_kernel<float>, dim3(G, B), dim3(64), 0, st, (const float*)x, s, workspace, eps, fin, stats);
-        hipLaunchKernelGGL(gn_apply_kernel<float>, grid, block, 0, st, (const float*)x, (float*)y, s, fin, a);
+        hipLaunchKernelGGL((gn_apply_kernel<float, MOD>), grid, block, 0, st, (const float*)x, (float*)y, s, fin, a);
     }
     return check_launch();
 }
 
-extern "C" int ddpm_groupnorm_silu_bwd(const void* x, long long x_ld, const void* dy, long long dy_ld, void* dx, long long dx_ld,
-                                       const float* gamma, const float* beta, const float* stats, float* dgamma, float* dbeta,
-                                       float* workspace, int B, int HW, int C, int G, int silu, float drop_p, unsigned long long seed,
-                                       const unsigned long long* seed_dev, int accumulate, float* dx_colsum, long long colsum_ld,
-                                       const void* add, long long add_ld, int dtype, void* stream) {
-    if (!x || !dy || !dx || !gamma || !beta || !stats || !workspace) return DDPM_ERR_NULL;
+extern "C" int ddpm_groupnorm_silu_fwd(const void* x, long long x_ld, void* y, long long y_ld, const float* gamma, const float* beta,
+                                       float* stats, float* workspace, int B, int HW, int C, int G, float eps, int silu,
+                                       float drop_p, unsigned long long seed, const unsigned long long* seed_dev, int dtype, void* stream) {
+    return gn_fwd_dispatch<false>(x, x_ld, y, y_ld, gamma, beta, stats, workspace, B, HW, C, G, eps, silu, drop_p, seed, seed_dev, nullptr, 0, dtype, stream);
+}
+
+extern "C" int ddpm_groupnorm_mod_silu_fwd(const void* x, long long x_ld, void* y, long long y_ld, const float* gamma, const float* beta,
+                                           float* stats, float* workspace, int B, int HW, int C, int G, float eps, int silu,
+                                           float drop_p, unsigned long long seed, const unsigned long long* seed_dev,
+                                           const float* mod, long long mod_ld, int dtype, void* stream) {
+    return gn_fwd_dispatch<true>(x, x_ld, y, y_ld, gamma, beta, stats, workspace, B, HW, C, G, eps, silu, drop_p, seed, seed_dev, mod, mod_ld, dtype, stream);
+}
+
+template <bool MOD>
+static int gn_bwd_dispatch(const void* x, long long x_ld, const void* dy, long long dy_ld, void* dx, long long dx_ld,
+                           const float* gamma, const float* beta, const float* stats, float* dgamma, float* dbeta,
+                           float* workspace, int B, int HW, int C, int G, int silu, float drop_p, unsigned long long seed,
+                           const unsigned long long* seed_dev, int accumulate, float* dx_colsum, long long colsum_ld,
+                           const void* add, long long add_ld, const float* mod, long long mod_ld, float* dmod, long long dmod_ld,
+                           int dtype, void* stream) {
+    if (!x || !dy || !dx || !gamma || !beta || !stats || !workspace || (MOD && (!mod || !dmod))) return DDPM_ERR_NULL;
     if (!aligned16(x) || !aligned16(dy) || !aligned16(dx)) return DDPM_ERR_ALIGN;
     if (dtype != DDPM_BF16 && dtype != DDPM_F32) return DDPM_ERR_DTYPE;
     GnShape s; dim3 block, grid;
@@ -1701,7 +1845,10 @@ extern "C" int ddpm_groupnorm_silu_bwd(const void* x, long long x_ld, const void
     int rc = gn_geometry(B, HW, C, G, x_ld, x_ld, es, s, block, grid);
     if (rc) return rc;
     if (dy_ld % (16 / es) || dx_ld % (16 / es) || (add && (add_ld % (16 / es) || !aligned16(add)))) return DDPM_ERR_ALIGN;
-    GnApply a = make_apply(gamma, beta, 0.f, silu, drop_p, seed, nullptr, seed_dev);
+    if (MOD && (mod_ld < 2ll * C || dmod_ld < 2ll * C)) return DDPM_ERR_SHAPE;
+    typename GnArgs<MOD>::type a;
+    static_cast<GnApply&>(a) = make_apply(gamma, beta, 0.f, silu, drop_p, seed, nullptr, seed_dev);
+    if constexpr (MOD) { a.mod = mod; a.mod_ld = mod_ld; a.dmod = dmod; a.dmod_ld = dmod_ld; }
     hipStream_t st = (hipStream_t)stream;
     GnFused f; size_t lds = 0;
     // register-resident single launch (x, dy read once, dx written once) — for the small slices only: with x AND dy held in
@@ -1717,21 +1864,22 @@ extern "C" int ddpm_groupnorm_silu_bwd(const void* x, long long x_ld, const void
         const dim3 fgrid(G / fl.GPB, B);
 #define GN_LDS(K, NT, ...) do { static DevOnce attr; if (!attr) { if (hipFuncSetAttribute(reinterpret_cast<const void*>(&K<__VA_ARGS__>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return DDPM_ERR_LAUNCH; attr = true; } \
         hipLaunchKernelGGL((K<__VA_ARGS__>), fgrid, dim3(NT), lds_l, st, (const T_*)x, (const T_*)dy, (T_*)dx, s, fl, dy_ld, dx_ld, stats, dgamma, dbeta, a, accumulate, dx_colsum, colsum_ld, (const T_*)add, add_ld); } while (0)
-#define GN_LDS_NV(P2V, K8, ...) do { if (small_lds) { if (fl.nv <= 1) GN_LDS(gn_lds_bwd_kernel, 256, T_, 1, 256, P2V); else GN_LDS(gn_lds_bwd_kernel, 256, T_, 2, 256, P2V); } \
-                         else if (fl.nv <= 2) GN_LDS(gn_lds_bwd_kernel, 512, T_, 2, 512, P2V); else if (fl.nv <= 4) GN_LDS(gn_lds_bwd_kernel, 512, T_, 4, 512, P2V); else GN_LDS(K8, 512, T_, 8, ##__VA_ARGS__); } while (0)
+#define GN_LDS_NV(P2V, K8, ...) do { if (small_lds) { if (fl.nv <= 1) GN_LDS(gn_lds_bwd_kernel, 256, T_, 1, 256, P2V, -1, MOD); else GN_LDS(gn_lds_bwd_kernel, 256, T_, 2, 256, P2V, -1, MOD); } \
+                         else if (fl.nv <= 2) GN_LDS(gn_lds_bwd_kernel, 512, T_, 2, 512, P2V, -1, MOD); else if (fl.nv <= 4) GN_LDS(gn_lds_bwd_kernel, 512, T_, 4, 512, P2V, -1, MOD); else GN_LDS(K8, 512, T_, 8, ##__VA_ARGS__, MOD); } while (0)
         // P2: every group is a power-of-two run of channels that the halves of a 16-byte vector column do not straddle
         const bool p2 = (s.cpg & (s.cpg - 1)) == 0 && s.cpg >= (16 / es) / 2 && s.cpg <= 64 && (fl.seg_vecs & (fl.seg_vecs - 1)) == 0;
         if (dtype == DDPM_BF16) {
             typedef bf16_t T_;
             if (p2) {
                 // the three flag combinations the UNet uses, baked in (norm1 / out: SiLU; norm2 in training: SiLU + dropout; attention: neither)
-#define GN_LDS_FL(FLV) do { if (small_lds) { if (fl.nv <= 1) GN_LDS(gn_lds_bwd_kernel, 256, T_, 1, 256, true, FLV); else GN_LDS(gn_lds_bwd_kernel, 256, T_, 2, 256, true, FLV); } \
-                         else if (fl.nv <= 2) GN_LDS(gn_lds_bwd_kernel, 512, T_, 2, 512, true, FLV); else if (fl.nv <= 4) GN_LDS(gn_lds_bwd_kernel, 512, T_, 4, 512, true, FLV); \
-                         else GN_LDS(gn_lds_bwd_kernel, 512, T_, 8, 512, true, FLV); } while (0)
+#define GN_LDS_FL(FLV) do { if (small_lds) { if (fl.nv <= 1) GN_LDS(gn_lds_bwd_kernel, 256, T_, 1, 256, true, FLV, MOD); else GN_LDS(gn_lds_bwd_kernel, 256, T_, 2, 256, true, FLV, MOD); } \
+                         else if (fl.nv <= 2) GN_LDS(gn_lds_bwd_kernel, 512, T_, 2, 512, true, FLV, MOD); else if (fl.nv <= 4) GN_LDS(gn_lds_bwd_kernel, 512, T_, 4, 512, true, FLV, MOD); \
+                         else GN_LDS(gn_lds_bwd_kernel, 512, T_, 8, 512, true, FLV, MOD); } while (0)
                 const int flg = (silu ? 1 : 0) | (drop_p > 0.f ? 2 : 0);
-                if (flg == 1) GN_LDS_FL(1); else if (flg == 3) GN_LDS_FL(3); else if (flg == 0) GN_LDS_FL(0); else GN_LDS_FL(-1);
+                constexpr int FL0 = MOD ? -1 : 0;              // (a modulated norm is always followed by the SiLU: its other two combinations read the flags at run time)
+                if (flg == 1) GN_LDS_FL(1); else if (flg == 3) GN_LDS_FL(3); else if (flg == 0) GN_LDS_FL(FL0); else GN_LDS_FL(-1);
 #undef GN_LDS_FL
-            } else GN_LDS_NV(false, gn_lds_bwd_kernel, 512, false);
+            } else GN_LDS_NV(false, gn_lds_bwd_kernel, 512, false, -1);
         } else {
             typedef float T_;
             if (p2) GN_LDS_NV(true, gn_lds_bwd8_kernel); else GN_LDS_NV(false, gn_lds_bwd8_kernel);
@@ -1747,7 +1895,8 @@ extern "C" int ddpm_groupnorm_silu_bwd(const void* x, long long x_ld, const void
     } colsum_after{dx, dx_ld, dx_colsum, colsum_ld, B, HW, C, dtype, stream};
     if (small) {
         const dim3 fgrid(G / f.GPB, B);
-#define GN_BWD(T, NV) hipLaunchKernelGGL((gn_reg_bwd_kernel<T, NV, 256>), fgrid, dim3(256), lds, st, (const T*)x, (const T*)dy, (T*)dx, s, f, dy_ld, dx_ld, stats, dgamma, dbeta, a, accumulate, (const T*)add, add_ld, dx_colsum, colsum_ld)
+        if (MOD) lds += (size_t)f.seg_ch * sizeof(float);      // (the kept channel sums A: see the kernel)
+#define GN_BWD(T, NV) hipLaunchKernelGGL((gn_reg_bwd_kernel<T, NV, 256, MOD>), fgrid, dim3(256), lds, st, (const T*)x, (const T*)dy, (T*)dx, s, f, dy_ld, dx_ld, stats, dgamma, dbeta, a, accumulate, (const T*)add, add_ld, dx_colsum, colsum_ld)
 #define GN_BWD_NV(T) do { if (f.nv <= 1) GN_BWD(T, 1); else GN_BWD(T, 2); } while (0)      // (small: <= 2 vectors per thread)
         if (dtype == DDPM_BF16) GN_BWD_NV(bf16_t); else GN_BWD_NV(float);
 #undef GN_BWD_NV
@@ -1757,16 +1906,41 @@ extern "C" int ddpm_groupnorm_silu_bwd(const void* x, long long x_ld, const void
     float* partial = workspace;                                   // [B][S][C][2]
     float* fin2 = workspace + (long long)B * s.S * C * 2;         // [B][C][2]
     if (dtype == DDPM_BF16)
-        hipLaunchKernelGGL(gn_bwd_reduce_kernel<bf16_t>, grid, block, 0, st, (const bf16_t*)x, (const bf16_t*)dy, s, dy_ld, stats, a, partial);
+        hipLaunchKernelGGL((gn_bwd_reduce_kernel<bf16_t, MOD>), grid, block, 0, st, (const bf16_t*)x, (const bf16_t*)dy, s, dy_ld, stats, a, partial);
     else
-        hipLaunchKernelGGL(gn_bwd_reduce_kernel<float>, grid, block, 0, st, (const float*)x, (const float*)dy, s, dy_ld, stats, a, partial);
+        hipLaunchKernelGGL((gn_bwd_reduce_kernel<float, MOD>), grid, block, 0, st, (const float*)x, (const float*)dy, s, dy_ld, stats, a, partial);
+    if constexpr (MOD) {
+        if (s.S <= 64) hipLaunchKernelGGL((gn_bwd_finalize_kernel<16, GnApplyMod>), dim3((C + 15) / 16, B), dim3(64), 0, st, s, partial, fin2, dgamma, dbeta, a);
+        else if (s.S <= 192) hipLaunchKernelGGL((gn_bwd_finalize_kernel<8, GnApplyMod>), dim3((C + 7) / 8, B), dim3(64), 0, st, s, partial, fin2, dgamma, dbeta, a);
+        else hipLaunchKernelGGL((gn_bwd_finalize_kernel<4, GnApplyMod>), dim3((C + 3) / 4, B), dim3(64), 0, st, s, partial, fin2, dgamma, dbeta, a);
+    } else {
     if (s.S <= 64) hipLaunchKernelGGL(gn_bwd_finalize_kernel<16>, dim3((C + 15) / 16, B), dim3(64), 0, st, s, partial, fin2, dgamma, dbeta);
     else if (s.S <= 192) hipLaunchKernelGGL(gn_bwd_finalize_kernel<8>, dim3((C + 7) / 8, B), dim3(64), 0, st, s, partial, fin2, dgamma, dbeta);
     else hipLaunchKernelGGL(gn_bwd_finalize_kernel<4>, dim3((C + 3) / 4, B), dim3(64), 0, st, s, partial, fin2, dgamma, dbeta);
+    }
     if (dtype == DDPM_BF16)
-        hipLaunchKernelGGL(gn_bwd_apply_kernel<bf16_t>, grid, block, 0, st, (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)dx, s, dy_ld, dx_ld, stats, fin2, dgamma, dbeta, a, accumulate, (const bf16_t*)add, add_ld);
+        hipLaunchKernelGGL((gn_bwd_apply_kernel<bf16_t, MOD>), grid, block, 0, st, (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)dx, s, dy_ld, dx_ld, stats, fin2, dgamma, dbeta, a, accumulate, (const bf16_t*)add, add_ld);
     else
-        hipLaunchKernelGGL(gn_bwd_apply_kernel<float>, grid, block, 0, st, (const float*)x, (const float*)dy, (float*)dx, s, dy_ld, dx_ld, stats, fin2, dgamma, dbeta, a, accumulate, (const float*)add, add_ld);
+        hipLaunchKernelGGL((gn_bwd_apply_kernel<float, MOD>), grid, block, 0, st, (const float*)x, (const float*)dy, (float*)dx, s, dy_ld, dx_ld, stats, fin2, dgamma, dbeta, a, accumulate, (const float*)add, add_ld);
     const int rc3 = check_launch();
     return rc3 ? rc3 : colsum_after.run();
+}
+
+extern "C" int ddpm_groupnorm_silu_bwd(const void* x, long long x_ld, const void* dy, long long dy_ld, void* dx, long long dx_ld,
+                                       const float* gamma, const float* beta, const float* stats, float* dgamma, float* dbeta,
+                                       float* workspace, int B, int HW, int C, int G, int silu, float drop_p, unsigned long long seed,
+                                       const unsigned long long* seed_dev, int accumulate, float* dx_colsum, long long colsum_ld,
+                                       const void* add, long long add_ld, int dtype, void* stream) {
+    return gn_bwd_dispatch<false>(x, x_ld, dy, dy_ld, dx, dx_ld, gamma, beta, stats, dgamma, dbeta, workspace, B, HW, C, G, silu, drop_p, seed,
+                                  seed_dev, accumulate, dx_colsum, colsum_ld, add, add_ld, nullptr, 0, nullptr, 0, dtype, stream);
+}
+
+extern "C" int ddpm_groupnorm_mod_silu_bwd(const void* x, long long x_ld, const void* dy, long long dy_ld, void* dx, long long dx_ld,
+                                           const float* gamma, const float* beta, const float* stats, float* dgamma, float* dbeta,
+                                           float* workspace, int B, int HW, int C, int G, int silu, float drop_p, unsigned long long seed,
+                                           const unsigned long long* seed_dev, int accumulate, float* dx_colsum, long long colsum_ld,
+                                           const void* add, long long add_ld, const float* mod, long long mod_ld, float* dmod, long long dmod_ld,
+                                           int dtype, void* stream) {
+    return gn_bwd_dispatch<true>(x, x_ld, dy, dy_ld, dx, dx_ld, gamma, beta, stats, dgamma, dbeta, workspace, B, HW, C, G, silu, drop_p, seed,
+                                 seed_dev, accumulate, dx_colsum, colsum_ld, add, add_ld, mod, mod_ld, dmod, dmod_ld, dtype, stream);
 }

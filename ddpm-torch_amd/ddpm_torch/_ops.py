@@ -171,10 +171,15 @@ def gn_workspace_floats(B, HW, C, dtype):
     return n
 
 
-def gn_fwd(x, y, gamma, beta, stats, ws, silu, drop_p=0.0, seed=0, seed_dev=0):
+def gn_fwd(x, y, gamma, beta, stats, ws, silu, drop_p=0.0, seed=0, seed_dev=0, mod_ptr=0, mod_ld=0):
     """seed_dev: address of a device uint64 added to `seed` inside the kernel (0 = none) — the per-step part of the dropout
-    seed when the step is a replayed hipGraph."""
+    seed when the step is a replayed hipGraph.  mod_ptr: [B][mod_ld] fp32 rows [scale | shift] of the scale-shift norm (0 = the plain norm)."""
     es = 2 if x.dtype == _hip.BF16 else 4
+    if mod_ptr:
+        return _timed("hbm_gn_fwd", 2.0 * x.B * x.H * x.W * x.C * es + 8.0 * x.B * x.C, lambda: _hip.call(
+            "ddpm_groupnorm_mod_silu_fwd", x.ptr, x.ld, y.ptr, y.ld, _hip.ptr(gamma), _hip.ptr(beta), _hip.ptr(stats), _hip.ptr(ws),
+            x.B, x.H * x.W, x.C, GN_GROUPS, GN_EPS, int(silu), float(drop_p), seed, seed_dev, mod_ptr, mod_ld, x.dtype, _hip.stream()),
+            f"GroupNorm fwd B={x.B} HW={x.H * x.W} C={x.C}" + (" +dropout" if drop_p > 0 else "") + " +mod")
     # (bench.py's HBM roofline leg: algorithmic bytes = read x once + write y once, SURVEY.md section 8d)
     _timed("hbm_gn_fwd", 2.0 * x.B * x.H * x.W * x.C * es, lambda: _hip.call(
         "ddpm_groupnorm_silu_fwd", x.ptr, x.ld, y.ptr, y.ld, _hip.ptr(gamma), _hip.ptr(beta), _hip.ptr(stats), _hip.ptr(ws),
@@ -182,10 +187,18 @@ def gn_fwd(x, y, gamma, beta, stats, ws, silu, drop_p=0.0, seed=0, seed_dev=0):
         f"GroupNorm fwd B={x.B} HW={x.H * x.W} C={x.C}" + (" +dropout" if drop_p > 0 else ""))
 
 
-def gn_bwd(x, dy, dx, gamma, beta, stats, dgamma_ptr, dbeta_ptr, ws, silu, drop_p=0.0, seed=0, accumulate=0, seed_dev=0, colsum_ptr=0, colsum_ld=0, add=None):
+def gn_bwd(x, dy, dx, gamma, beta, stats, dgamma_ptr, dbeta_ptr, ws, silu, drop_p=0.0, seed=0, accumulate=0, seed_dev=0, colsum_ptr=0, colsum_ld=0, add=None,
+           mod_ptr=0, mod_ld=0, dmod_ptr=0, dmod_ld=0):
     """colsum_ptr: zero-initialised [B][colsum_ld] fp32 buffer that receives the per-sample channel sums of dx (0 = not wanted).
-    add: View of a second gradient contribution summed into dx in the same pass (the identity branch of a residual connection)."""
+    add: View of a second gradient contribution summed into dx in the same pass (the identity branch of a residual connection).
+    mod_ptr / dmod_ptr: the scale-shift norm's [scale | shift] rows and where their gradients are stored (0 = the plain norm)."""
     es = 2 if x.dtype == _hip.BF16 else 4
+    if mod_ptr:
+        return _timed("hbm_gn_bwd", (3.0 + (add is not None) + (1 if accumulate else 0)) * x.B * x.H * x.W * x.C * es + 16.0 * x.B * x.C, lambda: _hip.call(
+            "ddpm_groupnorm_mod_silu_bwd", x.ptr, x.ld, dy.ptr, dy.ld, dx.ptr, dx.ld, _hip.ptr(gamma), _hip.ptr(beta), _hip.ptr(stats), dgamma_ptr, dbeta_ptr,
+            _hip.ptr(ws), x.B, x.H * x.W, x.C, GN_GROUPS, int(silu), float(drop_p), seed, seed_dev, accumulate, colsum_ptr, colsum_ld,
+            add.ptr if add is not None else 0, add.ld if add is not None else 0, mod_ptr, mod_ld, dmod_ptr, dmod_ld, x.dtype, _hip.stream()),
+            f"GroupNorm bwd B={x.B} HW={x.H * x.W} C={x.C}" + (" +dropout" if drop_p > 0 else "") + (" +add" if add is not None else "") + " +mod")
     # algorithmic bytes: read x and dy, write dx (+ read the identity-residual gradient it adds, + read dx when it accumulates)
     _timed("hbm_gn_bwd", (3.0 + (add is not None) + (1 if accumulate else 0)) * x.B * x.H * x.W * x.C * es, lambda: _hip.call(
         "ddpm_groupnorm_silu_bwd", x.ptr, x.ld, dy.ptr, dy.ld, dx.ptr, dx.ld, _hip.ptr(gamma), _hip.ptr(beta), _hip.ptr(stats), dgamma_ptr, dbeta_ptr,

@@ -78,14 +78,20 @@ class _Slot(nn.Module):
 
 
 class ResidualBlock(nn.Module):
-    """unet.py:63-89 — norm1, conv1, fc, norm2, conv2 (init_scale 0), skip (1x1 when channels change)."""
+    """unet.py:63-89 — norm1, conv1, fc, norm2, conv2 (init_scale 0), skip (1x1 when channels change).
+    ``use_scale_shift_norm`` (not in the reference; the name and the semantics are those of the Improved-DDPM / ADM ResBlock): ``fc`` has
+    2 * out_channels outputs, ``scale, shift = fc(SiLU(t_emb)).chunk(2, dim=1)``, and the embedding enters as a modulation of the second
+    GroupNorm, ``h = norm2(conv1(...)) * (1 + scale) + shift``, in the place of the bias added behind ``conv1``."""
 
-    def __init__(self, in_channels, out_channels, embed_dim, drop_rate=0.0):
+    def __init__(self, in_channels, out_channels, embed_dim, drop_rate=0.0, use_scale_shift_norm=False):
+        if not isinstance(use_scale_shift_norm, bool):
+            raise TypeError(f"use_scale_shift_norm must be a bool, got {use_scale_shift_norm!r}")
         super().__init__()
         self.in_channels, self.out_channels, self.drop_rate = in_channels, out_channels, drop_rate
+        self.use_scale_shift_norm = use_scale_shift_norm
         self.norm1 = _Norm(in_channels)
         self.conv1 = _Conv(in_channels, out_channels, 3)
-        self.fc = _Linear(embed_dim, out_channels)
+        self.fc = _Linear(embed_dim, 2 * out_channels if use_scale_shift_norm else out_channels)
         self.norm2 = _Norm(out_channels)
         self.conv2 = _Conv(out_channels, out_channels, 3, init_scale=0.0)
         self.has_skip = in_channels != out_channels     # the reference holds nn.Identity otherwise: no keys either way
@@ -117,8 +123,12 @@ class UNet(nn.Module):
     """Same constructor / forward contract as the reference (unet.py:96-107, :205)."""
 
     def __init__(self, in_channels, hid_channels, out_channels, ch_multipliers, num_res_blocks, apply_attn,
-                 time_embedding_dim=None, drop_rate=0., resample_with_conv=True, num_classes=None, num_heads=1, num_head_channels=None):
+                 time_embedding_dim=None, drop_rate=0., resample_with_conv=True, num_classes=None, num_heads=1, num_head_channels=None,
+                 use_scale_shift_norm=False):
+        if not isinstance(use_scale_shift_norm, bool):       # (refused before anything is drawn, like the checks below)
+            raise TypeError(f"use_scale_shift_norm must be a bool, got {use_scale_shift_norm!r}")
         super().__init__()
+        self.use_scale_shift_norm = use_scale_shift_norm
         for name, val in (("num_heads", num_heads), ("num_head_channels", num_head_channels)):
             if val is not None and (isinstance(val, bool) or int(val) != val or val < 1):
                 raise ValueError(f"{name} must be a positive integer, got {val!r}")
@@ -158,7 +168,7 @@ class UNet(nn.Module):
         heads_of(chs[-1], f"the middle block (level_{levels - 1})")
 
         def block(level, cin, cout):
-            res = ResidualBlock(cin, cout, E, drop_rate)
+            res = ResidualBlock(cin, cout, E, drop_rate, use_scale_shift_norm)
             return _seq(res, AttentionBlock(cout, heads_of(cout, f"level_{level}"))) if apply_attn[level] else res
 
         # construction order == the reference's, so seeded initialisation is bit-identical
@@ -172,7 +182,8 @@ class UNet(nn.Module):
                 mods.append(_seq(_Slot(), _Conv(chs[i], chs[i], 3)) if resample_with_conv else _Slot())
             self.downsamples[f"level_{i}"] = nn.ModuleList(mods)
         mid = chs[-1]
-        self.middle = _seq(ResidualBlock(mid, mid, E, drop_rate), AttentionBlock(mid, heads_of(mid, "the middle block")), ResidualBlock(mid, mid, E, drop_rate))
+        self.middle = _seq(ResidualBlock(mid, mid, E, drop_rate, use_scale_shift_norm), AttentionBlock(mid, heads_of(mid, "the middle block")),
+                           ResidualBlock(mid, mid, E, drop_rate, use_scale_shift_norm))
         self.upsamples = nn.ModuleDict()
         for i in range(levels):
             nxt = hid_channels if i == 0 else chs[i - 1]
@@ -192,6 +203,14 @@ class UNet(nn.Module):
 
         self.compute_dtype = _DTYPES[os.environ.get("DDPM_TORCH_AMD_COMPUTE", "fp32").lower()]
         self._eng = None
+
+    @staticmethod
+    def scale_shift_option(model_cfg, flag=False):
+        """For the command lines: a config's ``model.use_scale_shift_norm`` wins; a config that does not name it takes the flag.  Edits and
+        returns ``model_cfg``."""
+        if "use_scale_shift_norm" not in model_cfg and flag:
+            model_cfg["use_scale_shift_norm"] = True
+        return model_cfg
 
     @staticmethod
     def head_options(model_cfg, num_heads=1, num_head_channels=0):
@@ -342,10 +361,11 @@ class _Engine:
         self.res_blocks = []
         self.convs = {}
         self._collect()
+        # (a scale-shift block owns 2 Cout columns, [scale | shift]: _tbw)
         self.tb_off, o = {}, 0
         for rb in self.res_blocks:
             self.tb_off[id(rb)] = o
-            o += rb.out_channels
+            o += self._tbw(rb)
         self.tb_total = o
         half = self.hid // 2
         rate = math.log(10000) / (half - 1)
@@ -386,6 +406,11 @@ class _Engine:
             self._slab_tables.clear()
 
     # ---------------------------------------------------------------- topology helpers
+    @staticmethod
+    def _tbw(rb):
+        """Columns of the concatenated time projection that belong to ``rb``: its fc's outputs."""
+        return (2 if rb.use_scale_shift_norm else 1) * rb.out_channels
+
     def _split(self, blk):
         return (blk[0], blk[1]) if isinstance(blk, nn.Sequential) else (blk, None)
 
@@ -457,8 +482,9 @@ class _Engine:
 
     def _fc_all(self):
         """Concatenated time-bias projection: rows = all ResidualBlock.fc weights; bias = fc.bias + conv1.bias
-        (both are added at the same place, unet.py:85-86), so conv1's epilogue adds one per-sample vector.  The two
-        buffers are persistent and re-filled by ONE multi-tensor launch when a member parameter changed."""
+        (both are added at the same place, unet.py:85-86), so conv1's epilogue adds one per-sample vector.  A scale-shift block's
+        columns are its [scale | shift] and carry fc.bias alone: conv1.bias stays with conv1 (folded in, it would be added to the scale).
+        The two buffers are persistent and re-filled by ONE multi-tensor launch when a member parameter changed."""
         key = self._fc_versions()
         if self.fc_table is None or key[0][3] != self.fc_ptr0 or any(k[3] != q for k, q in zip(key, self.fc_ptrs)):
             E = self.E
@@ -467,9 +493,9 @@ class _Engine:
                 self.fc_b = self._f32(self.tb_total)
             rows = []
             for rb in self.res_blocks:
-                o, c = self.tb_off[id(rb)], rb.out_channels
+                o, c = self.tb_off[id(rb)], self._tbw(rb)
                 rows.append([rb.fc.weight.data_ptr(), 0, self.fc_w.data_ptr() + 4 * o * E, c * E])
-                rows.append([rb.fc.bias.data_ptr(), rb.conv1.bias.data_ptr(), self.fc_b.data_ptr() + 4 * o, c])
+                rows.append([rb.fc.bias.data_ptr(), 0 if rb.use_scale_shift_norm else rb.conv1.bias.data_ptr(), self.fc_b.data_ptr() + 4 * o, c])
             self.fc_table = torch.tensor(rows, dtype=torch.int64, device=self.device)
             self.fc_ptrs = tuple(k[3] for k in key)
             self.fc_ptr0 = key[0][3]
@@ -654,15 +680,15 @@ class _Engine:
                     blocks.append(rb_of_conv1[id(cw.mod)])
                 k = len(self.chunks)
                 limit = max(target // ramp[k], 1 << 16) if k < len(ramp) else target
-                pending_fc = sum(rb.out_channels for rb in blocks) * E
+                pending_fc = sum(self._tbw(rb) for rb in blocks) * E
                 if off + pending_fc - start >= limit or i + 1 == len(convs):
                     fc = None
                     if blocks:                                   # rows [o0, o0 + n) of the concatenated projection, stored at fbase
-                        o0, n = self.tb_off[id(blocks[0])], sum(rb.out_channels for rb in blocks)
-                        assert all(self.tb_off[id(rb)] == o0 + sum(q.out_channels for q in blocks[:j]) for j, rb in enumerate(blocks))
+                        o0, n = self.tb_off[id(blocks[0])], sum(self._tbw(rb) for rb in blocks)
+                        assert all(self.tb_off[id(rb)] == o0 + sum(self._tbw(q) for q in blocks[:j]) for j, rb in enumerate(blocks))
                         fbase = slot(("fc_w", k), n * E)
                         for rb in blocks:
-                            rows.append([fbase + (self.tb_off[id(rb)] - o0) * E, self.goff[id(rb.fc.weight)], 1, rb.out_channels * E, 1])
+                            rows.append([fbase + (self.tb_off[id(rb)] - o0) * E, self.goff[id(rb.fc.weight)], 1, self._tbw(rb) * E, 1])
                         fc = (o0, n, fbase)
                         members.append(("fc_w", k))
                     self.chunks.append((start, off, members))
@@ -672,8 +698,9 @@ class _Engine:
             fb = slot("fc_b", self.tb_total)
             for rb in self.res_blocks:
                 o, c = self.tb_off[id(rb)], rb.out_channels
-                rows.append([fb + o, self.goff[id(rb.fc.bias)], 1, c, 1])
-                rows.append([fb + o, self.goff[id(rb.conv1.bias)], 1, c, 1])
+                rows.append([fb + o, self.goff[id(rb.fc.bias)], 1, self._tbw(rb), 1])
+                if not rb.use_scale_shift_norm:              # (a scale-shift block's conv1.bias is no part of the projection's bias: a plain slot below)
+                    rows.append([fb + o, self.goff[id(rb.conv1.bias)], 1, c, 1])
                 if rb.has_skip:
                     t = slot(("b2", id(rb)), c)
                     rows.append([t, self.goff[id(rb.conv2.bias)], 1, c, 1])
@@ -755,14 +782,7 @@ class _Engine:
         up = bool(kw.get("upsample"))                    # Upsample block: x stored at half of dy's size, gathered in place by the kernel
         if (_WGRAD3 and self.T == torch.bfloat16 and R == 3 and S == 3 and (not up or (dy.H == 2 * x.H and dy.W == 2 * x.W))
                 and kw.get("stride", 1) == 1 and kw.get("pad_t") == 1 and kw.get("pad_l") == 1 and Creal == x.C):
-            boost = bool(boost_req)
-            pkey = ("w3", x.B, dy.H, dy.W, x.C, dy.C, boost)
-            patch = self._eff_splits.get(pkey)
-            if patch is None:
-                patch = ops.conv3x3_wgrad_splits(x.B, dy.H, dy.W, x.C, dy.C)
-                if boost and patch:                     # the whole chip instead of half of it (see _TAIL_BLOCKS)
-                    patch = ops.conv3x3_wgrad_splits(x.B, dy.H, dy.W, x.C, dy.C, 2 * patch)
-                self._eff_splits[pkey] = patch
+            patch = self._patch_copies(x.B, dy.H, dy.W, x.C, dy.C, bool(boost_req))
         point = 0
         if (not patch and self.T == torch.bfloat16 and R == 1 and S == 1 and not up and kw.get("stride", 1) == 1
                 and not kw.get("pad_t") and not kw.get("pad_l") and Creal == x.C and Nreal == dy.C):
@@ -830,6 +850,17 @@ class _Engine:
                     self._join_side(ctx)                     # ... and produced: the communicator orders itself after the main stream
                     self._comm(ctx, lambda works=works, chunk=chunk: works.append(self._all_reduce(chunk)))
         return did_bias
+
+    def _patch_copies(self, B, H, W, C, N, boost):
+        """Slab copies of the patch-stationary 3x3 weight gradient at this geometry (0: the kernel declines it), cached."""
+        pkey = ("w3", B, H, W, C, N, boost)
+        patch = self._eff_splits.get(pkey)
+        if patch is None:
+            patch = ops.conv3x3_wgrad_splits(B, H, W, C, N)
+            if boost and patch:                     # the whole chip instead of half of it (see _TAIL_BLOCKS)
+                patch = ops.conv3x3_wgrad_splits(B, H, W, C, N, 2 * patch)
+            self._eff_splits[pkey] = patch
+        return patch
 
     def _fc_wgrad(self, ctx, k):
         """d(fc.weight) of the residual blocks of chunk k: rows [o0, o0 + n) of dW = dtb^T s_t (all of them one product: the blocks'
@@ -1092,8 +1123,13 @@ class _Engine:
         a1 = self._new(B, x.H, x.W, Cin)
         stats1 = self._f32(B, ops.GN_GROUPS, 2) if save else None
         ops.gn_fwd(x, a1, rb.norm1.weight, rb.norm1.bias, stats1, ws, silu=True)
-        ops.conv2d(a1, c1.wf.data_ptr(), h1.ptr, h1.ld, Cout, 3, 3, x.H, x.W, pad_t=1, pad_l=1,
-                   rowbias=rowbias, rowbias_ld=self.tb_total, splitk=self.splitk)
+        ssn = rb.use_scale_shift_norm                # the block's columns of tb are [scale | shift] of norm2, not a bias behind conv1
+        if ssn:
+            ops.conv2d(a1, c1.wf.data_ptr(), h1.ptr, h1.ld, Cout, 3, 3, x.H, x.W, pad_t=1, pad_l=1,
+                       bias=rb.conv1.bias.data_ptr(), splitk=self.splitk)
+        else:
+            ops.conv2d(a1, c1.wf.data_ptr(), h1.ptr, h1.ld, Cout, 3, 3, x.H, x.W, pad_t=1, pad_l=1,
+                       rowbias=rowbias, rowbias_ld=self.tb_total, splitk=self.splitk)
         if rb.has_skip:
             cs = self._packed(rb.skip, save)
             ops.conv2d(x, cs.wf.data_ptr(), out.ptr, out.ld, Cout, 1, 1, x.H, x.W, bias=rb.skip.bias.data_ptr(), splitk=self.splitk)
@@ -1103,11 +1139,12 @@ class _Engine:
         a2 = self._new(B, x.H, x.W, Cout)
         stats2 = self._f32(B, ops.GN_GROUPS, 2) if save else None
         seed = (st["seed"] + 0x51ED27 * (self.tb_off[id(rb)] + 1)) & ((1 << 63) - 1) if st["drop_p"] > 0 else 0
-        ops.gn_fwd(h1, a2, rb.norm2.weight, rb.norm2.bias, stats2, ws, silu=True, drop_p=st["drop_p"], seed=seed, seed_dev=st["seed_dev"])
+        ops.gn_fwd(h1, a2, rb.norm2.weight, rb.norm2.bias, stats2, ws, silu=True, drop_p=st["drop_p"], seed=seed, seed_dev=st["seed_dev"],
+                   mod_ptr=rowbias if ssn else 0, mod_ld=self.tb_total)
         ops.conv2d(a2, c2.wf.data_ptr(), out.ptr, out.ld, Cout, 3, 3, x.H, x.W, pad_t=1, pad_l=1,
                    bias=rb.conv2.bias.data_ptr(), res_ptr=res_ptr, res_ld=res_ld, splitk=self.splitk)
         if save:
-            st["tape"].append(("res", rb, x, out, a1, stats1, h1, a2, stats2, seed, parts))
+            st["tape"].append(("res", rb, x, out, a1, stats1, h1, a2, stats2, seed, parts, rowbias))
 
     def _attn(self, st, ab, x, out):
         B, save, ws = st["B"], st["save"], st["ws"]
@@ -1392,7 +1429,7 @@ class _Engine:
                        dilate=1 if stride == 2 else 0, accumulate=acc, splitk=self.splitk)
 
     def _res_bwd(self, ctx, rec):
-        _, rb, x, out, a1, stats1, h1, a2, stats2, seed, parts = rec
+        _, rb, x, out, a1, stats1, h1, a2, stats2, seed, parts, mod_ptr = rec
         gflat, ws, B = ctx["gflat"], ctx["ws"], ctx["B"]
         Cin, Cout = rb.in_channels, rb.out_channels
         dout = out.grad
@@ -1413,13 +1450,31 @@ class _Engine:
         dh1 = self._new(B, x.H, x.W, Cout)
         # ... which also yields the gradient of the time bias (+ conv1 bias): the per-sample column sums of dh1 land in the
         # block's columns of the concatenated dtb
-        ops.gn_bwd(h1, da2, dh1, rb.norm2.weight, rb.norm2.bias, stats2, self._pptr(ctx, rb.norm2.weight), self._pptr(ctx, rb.norm2.bias),
-                   ws, silu=True, drop_p=drop_p, seed=seed, seed_dev=ctx["seed_dev"],
-                   colsum_ptr=ctx["dtb"].data_ptr() + 4 * self.tb_off[id(rb)], colsum_ld=self.tb_total)
+        dtb_ptr = ctx["dtb"].data_ptr() + 4 * self.tb_off[id(rb)]
+        if rb.use_scale_shift_norm:
+            # the modulated backward stores [dscale | dshift] into those columns.  conv1.bias is conv1's own here; its gradient, the column
+            # sum of dh1, comes from the weight-gradient kernel that reads dh1 anyway where that kernel takes this geometry (bf16), else
+            # from the per-sample column sums this launch can emit, summed over the batch by one [B][Cout] launch
+            fold = (_WGRAD3 and self.T == torch.bfloat16 and Cin == a1.C
+                    and self._patch_copies(B, x.H, x.W, a1.C, dh1.C, bool(boost)) > 0)
+            cb = None if fold else self._zeros(B, Cout)
+            ops.gn_bwd(h1, da2, dh1, rb.norm2.weight, rb.norm2.bias, stats2, self._pptr(ctx, rb.norm2.weight), self._pptr(ctx, rb.norm2.bias),
+                       ws, silu=True, drop_p=drop_p, seed=seed, seed_dev=ctx["seed_dev"],
+                       colsum_ptr=0 if fold else cb.data_ptr(), colsum_ld=Cout,
+                       mod_ptr=mod_ptr, mod_ld=self.tb_total, dmod_ptr=dtb_ptr, dmod_ld=self.tb_total)
+            if not fold:
+                with self._leaf(ctx, cb):
+                    ops.colsum(View(cb, 1, B, 1, Cout), 0, 0, self._pptr(ctx, rb.conv1.bias))
+        else:
+            ops.gn_bwd(h1, da2, dh1, rb.norm2.weight, rb.norm2.bias, stats2, self._pptr(ctx, rb.norm2.weight), self._pptr(ctx, rb.norm2.bias),
+                       ws, silu=True, drop_p=drop_p, seed=seed, seed_dev=ctx["seed_dev"], colsum_ptr=dtb_ptr, colsum_ld=self.tb_total)
+            fold = False
         # conv1
         da1 = self._new(B, x.H, x.W, Cin)
         ops.conv2d(dh1, c1.wd.data_ptr(), da1.ptr, da1.ld, Cin, 3, 3, x.H, x.W, pad_t=1, pad_l=1, splitk=self.splitk)
-        self._wgrad(ctx, rb.conv1.weight, dh1, a1, Cin, Cout, 3, 3, pad_t=1, pad_l=1, splits=self._splits(Cout, 9 * Cin, dh1.rows), boost=boost)
+        did = self._wgrad(ctx, rb.conv1.weight, dh1, a1, Cin, Cout, 3, 3, pad_t=1, pad_l=1, splits=self._splits(Cout, 9 * Cin, dh1.rows), boost=boost,
+                          bias=rb.conv1.bias if fold else None)
+        assert did == fold
         # GN1 + SiLU, then the skip path, into d(x)
         g, acc = self._grad_target(x)
         # (identity skip: the block's output gradient joins d(x) inside the same kernel)

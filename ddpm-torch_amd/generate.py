@@ -123,6 +123,9 @@ def build(args, rank=0):
     weights = weights_from(torch.load(chkpt_path, map_location=device), use_ema)
     table = next((v for k, v in weights.items() if k.endswith("class_embed.weight")), None)
     mk["num_classes"] = None if table is None else table.shape[0] - 1          # the checkpoint decides: one row per class + the null class
+    # ... and so it does for the scale-shift norm: a ResidualBlock's fc then has 2 * Cout rows, Cout being its conv1's
+    fc = next(((v, weights.get(k[:-len("fc.weight")] + "conv1.weight")) for k, v in weights.items() if k.endswith(".fc.weight")), None)
+    mk["use_scale_shift_norm"] = bool(fc is not None and fc[1] is not None and fc[0].shape[0] == 2 * fc[1].shape[0])
     # (the head count changes no parameter: no checkpoint can tell it, so the config — or, for a config without the keys, the flags — must)
     ddpm_torch.UNet.head_options(mk, getattr(args, "num_heads", 1), getattr(args, "num_head_channels", 0))
     model = ddpm_torch.UNet(out_channels=(2 if learned else 1) * info["channels"] * block ** 2, **mk).set_compute_dtype(args.compute)

@@ -87,6 +87,10 @@ def parse_args(argv=None):
                                                 "section wins when it names num_heads or num_head_channels")
     add("--num-head-channels", default=0, type=int, help="channels per attention head instead of a head count: a block over C channels gets "
                                                         "C / K heads.  0: use --num-heads")
+    add("--scale-shift-norm", action="store_true", help="the timestep (+ class) embedding modulates the second GroupNorm of every residual "
+                                                        "block, norm(h) * (1 + scale) + shift, instead of being added behind conv1 (not in the "
+                                                        "reference: use_scale_shift_norm of Improved DDPM / ADM); the config's "
+                                                        "model.use_scale_shift_norm wins")
     add("--label-drop", default=0.1, type=float, help="probability of training a sample on the null class (classifier-free guidance)")
     add("--device-data", action="store_true", help="hold the data set on the training GPU and assemble every batch there (not in the "
                                                    "reference); --num-workers then only serves a one-off decode of image files")
@@ -145,6 +149,7 @@ def run(rank=0, args=None, temp_dir=""):
     if num_classes:
         mcfg["num_classes"] = int(num_classes)
     ddpm_torch.UNet.head_options(mcfg, args.num_heads, args.num_head_channels)
+    ddpm_torch.UNet.scale_shift_option(mcfg, args.scale_shift_norm)
     unet = ddpm_torch.UNet(**mcfg).set_compute_dtype(args.compute)
     net = unet if block == 1 else ddpm_torch.ModelWrapper(unet, torch.nn.PixelUnshuffle(block), torch.nn.PixelShuffle(block))
 

@@ -186,6 +186,34 @@ int ddpm_groupnorm_silu_bwd(const void* x, long long x_ld, const void* dy, long 
                             const void* add, long long add_ld, int dtype, void* stream);
 long long ddpm_gn_workspace_floats(int B, int HW, int C, int G, int dtype);
 
+/* Scale-shift norm (AdaGN, `use_scale_shift_norm` of the Improved-DDPM / ADM residual block): the same kernels with a per-sample affine,
+ *   y = drop(silu(xhat * g_eff + b_eff)),   g_eff[b,c] = gamma[c] * (1 + s[b,c]),   b_eff[b,c] = beta[c] * (1 + s[b,c]) + h[b,c],
+ * xhat = (x - mean_g) * rstd_g.  mod: fp32, row b at mod + b*mod_ld, scale s in columns [0, C), shift h in [C, 2C); mod_ld >= 2C is
+ * otherwise arbitrary and the columns past 2C are never read.  Everything else (stats, workspace — sized by ddpm_gn_workspace_floats —,
+ * dropout, seed_dev, pitches) is ddpm_groupnorm_silu_fwd's; the products are formed in fp32 as written, so with mod == 0 the result,
+ * stats included, equals the plain entry point's bit for bit.  A sample's row of mod reaches that sample only.
+ * Validation on the host before any launch: everything the plain entry point checks, DDPM_ERR_NULL for a null mod, DDPM_ERR_SHAPE
+ * for mod_ld < 2C. */
+int ddpm_groupnorm_mod_silu_fwd(const void* x, long long x_ld, void* y, long long y_ld, const float* gamma, const float* beta,
+                                float* stats, float* workspace, int B, int HW, int C, int G, float eps, int silu,
+                                float drop_p, unsigned long long seed, const unsigned long long* seed_dev,
+                                const float* mod, long long mod_ld, int dtype, void* stream);
+/* backward of the above.  With t = g_eff*xhat + b_eff, dz = dy * keep/(1-p) * silu'(t), A[b,c] = sum_p dz*xhat, D[b,c] = sum_p dz:
+ *   dx = rstd * (dz*g_eff - xhat*c1 - c2)   (c1, c2: group means of dz*g_eff*xhat, dz*g_eff; accumulate / add / dx_colsum as in the plain
+ *   backward — dx_colsum here is the per-sample share of the gradient of a bias added in front of the norm, conv1.bias in the block),
+ *   dgamma[c] += sum_b A*(1 + s),  dbeta[c] += sum_b D*(1 + s)   (fp32 atomics, as in the plain backward),
+ *   dmod[b*dmod_ld + c] = gamma[c]*A + beta[c]*D,  dmod[b*dmod_ld + C + c] = D   (d/d scale, d/d shift).
+ * Each of the 2C gradient columns of a dmod row is OVERWRITTEN by one plain store from the one block that completes the sample's
+ * channel sums: no atomics, nothing accumulated, bit-identical from run to run; columns past 2C are not touched.  No pass over
+ * x, dy or dx beyond the plain backward's.  With mod == 0, dx equals the plain backward's bit for bit.
+ * Validation: as the forward, plus DDPM_ERR_NULL for a null dmod and DDPM_ERR_SHAPE for dmod_ld < 2C. */
+int ddpm_groupnorm_mod_silu_bwd(const void* x, long long x_ld, const void* dy, long long dy_ld, void* dx, long long dx_ld,
+                                const float* gamma, const float* beta, const float* stats, float* dgamma, float* dbeta,
+                                float* workspace, int B, int HW, int C, int G, int silu, float drop_p, unsigned long long seed,
+                                const unsigned long long* seed_dev, int accumulate, float* dx_colsum, long long colsum_ld,
+                                const void* add, long long add_ld, const float* mod, long long mod_ld, float* dmod, long long dmod_ld,
+                                int dtype, void* stream);
+
 /* get_timestep_embedding (ddpm_torch/functions.py:10-26): out[b] = cat(sin(t_b f), cos(t_b f)) (zero pad if dim odd);
  * freqs[dim/2] = exp(-i ln(1e4)/(dim/2 - 1)) is supplied by the host in fp32. */
 int ddpm_timestep_embedding(const long long* t, const float* freqs, float* out, int B, int dim, void* stream);

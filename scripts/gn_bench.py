@@ -1,4 +1,8 @@
-"""Isolated timing of the GroupNorm(+SiLU+dropout) forward / backward launches on the CIFAR UNet's tensor shapes (B = 128, bf16)."""
+"""Isolated timing of the GroupNorm(+SiLU+dropout) forward / backward launches on the CIFAR UNet's tensor shapes (B = 128, bf16).
+
+``--mod``: the scale-shift norm's entry points (ddpm_groupnorm_mod_silu_fwd / _bwd) next to the plain ones at the same shape in the same
+process — alternating (plain, modulated) pairs, the median of each and the spread (min .. max) of the pair ratios — on the B = 128
+shapes and on the CelebA-HQ streaming shapes at B = 2.  The yardstick is the plain entry point of the same run."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "ddpm-torch_amd")]
@@ -21,6 +25,41 @@ def timeit(fn, n=20):
     return a.elapsed_time(b) / n * 1e3
 
 
+def mod_column():
+    """plain vs modulated, alternating pairs (measuring-on-mi355x: one process, interleaved, spread reported)"""
+    import statistics
+    PAIRS = 7
+    hq = [(256, 128), (128, 128), (64, 256)]                       # CelebA-HQ at B = 2: the streaming family
+    print("shape                 fwd plain / mod us   ratio (min .. max)      bwd plain / mod us   ratio (min .. max)")
+    for Bq, H, C in [(B, h, c) for h, c, _ in SHAPES] + [(2, h, c) for h, c in hq]:
+        x = View(torch.randn(Bq, H, H, C, device="cuda").bfloat16(), Bq, H, H, C)
+        y, dy, dx = (View(torch.randn(Bq, H, H, C, device="cuda").bfloat16(), Bq, H, H, C) for _ in range(3))
+        g, bt = torch.ones(C, device="cuda"), torch.zeros(C, device="cuda")
+        dg, db = torch.zeros(C, device="cuda"), torch.zeros(C, device="cuda")
+        stats = torch.zeros(Bq, 32, 2, device="cuda")
+        ld = 2 * C + 12                                            # an engine-like pitch: the block's columns of a wider buffer
+        mod, dmod = 0.5 * torch.randn(Bq, ld, device="cuda"), torch.zeros(Bq, ld, device="cuda")
+        ws = torch.zeros(ops.gn_workspace_floats(Bq, H * H, C, x.dtype), device="cuda")
+        m = dict(mod_ptr=mod.data_ptr(), mod_ld=ld)
+        fw = {0: lambda: ops.gn_fwd(x, y, g, bt, stats, ws, silu=SILU, drop_p=DROP, seed=123),
+              1: lambda: ops.gn_fwd(x, y, g, bt, stats, ws, silu=SILU, drop_p=DROP, seed=123, **m)}
+        bw = {0: lambda: ops.gn_bwd(x, dy, dx, g, bt, stats, dg.data_ptr(), db.data_ptr(), ws, silu=SILU, drop_p=DROP, seed=123, accumulate=ACC),
+              1: lambda: ops.gn_bwd(x, dy, dx, g, bt, stats, dg.data_ptr(), db.data_ptr(), ws, silu=SILU, drop_p=DROP, seed=123, accumulate=ACC,
+                                    dmod_ptr=dmod.data_ptr(), dmod_ld=ld, **m)}
+        cols = []
+        for pair in (fw, bw):
+            t = {0: [], 1: []}
+            for _ in range(PAIRS):
+                for k in (0, 1):
+                    t[k].append(timeit(pair[k], n=10))
+            r = [b / a for a, b in zip(t[0], t[1])]
+            cols.append(f"{statistics.median(t[0]):7.1f} / {statistics.median(t[1]):7.1f}   {statistics.median(r):5.3f} ({min(r):5.3f} .. {max(r):5.3f})")
+        print(f"B{Bq:3d} {H:3d}^2 x {C:3d}:   {cols[0]}      {cols[1]}", flush=True)
+
+
+if "--mod" in sys.argv:
+    mod_column()
+    sys.exit(0)
 tot_f = tot_b = 0.0
 if os.environ.get('GN_ONLY'):
     SHAPES = SHAPES[:int(os.environ['GN_ONLY'])]
