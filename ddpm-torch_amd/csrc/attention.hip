@@ -19,29 +19,13 @@
 // every other token count — more than 256, or no multiple of 8 — goes through attention_stream.hip, which streams the other
 // side of the score matrix in tiles instead of holding a whole row block of it.
 #include "common.h"
+#include "attention_common.h"
 #include <string.h>
 
 namespace {
 
 constexpr int RB = 128;                        // rows of the score block owned by a workgroup
 constexpr int NT = 512;
-
-struct Opnd {                                   // [L rows][C] bf16, row pitch ld (elements); rsrc spans one image
-    __amdgpu_buffer_rsrc_t rsrc;
-    long long ld;
-};
-
-__device__ __forceinline__ Opnd make_opnd(const bf16_t* base, long long ld, int L, int C) {
-    Opnd o;
-    const UniformAddr u = uniform_addr(base);
-    o.rsrc = buffer_rsrc_at(u, (unsigned)(((long long)(L - 1) * ld + C) * 2));
-    o.ld = ld;
-    return o;
-}
-__device__ __forceinline__ u32x4 ldv(const Opnd& o, unsigned off) {
-    return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(o.rsrc, off, 0, 0));
-}
-__device__ __forceinline__ bf16x8 as_frag(const u32x4& v) { return __builtin_bit_cast(bf16x8, v); }
 
 struct AttnArgs {
     const bf16_t *q, *k, *v;  long long qkv_ld;   // packed projection buffer: q at +0, k at +C, v at +2C (pointers already offset)

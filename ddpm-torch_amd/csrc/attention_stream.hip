@@ -25,6 +25,7 @@
 // the element-wise step gives them probability 0 by index, never through exp.  Static LDS <= 64 KiB: no attribute call, nothing
 // that a stream capture would see.
 #include "common.h"
+#include "attention_common.h"
 #include <string.h>
 
 namespace {
@@ -32,21 +33,6 @@ namespace {
 constexpr int NT = 256;                         // 4 waves
 constexpr float NEG_BIG = -3.0e38f;             // "no key seen yet": finite, so the first rescale is exp(-huge) = 0, never exp(-inf + inf)
 
-struct Opnd {                                   // [L rows][C] bf16, row pitch ld (elements); rsrc spans one image
-    __amdgpu_buffer_rsrc_t rsrc;
-    long long ld;
-};
-__device__ __forceinline__ Opnd make_opnd(const bf16_t* base, long long ld, int L, int C) {
-    Opnd o;
-    const UniformAddr u = uniform_addr(base);
-    o.rsrc = buffer_rsrc_at(u, (unsigned)(((long long)(L - 1) * ld + C) * 2));
-    o.ld = ld;
-    return o;
-}
-__device__ __forceinline__ u32x4 ldv(const Opnd& o, unsigned off) {
-    return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(o.rsrc, off, 0, 0));
-}
-__device__ __forceinline__ bf16x8 as_frag(const u32x4& v) { return __builtin_bit_cast(bf16x8, v); }
 // 8-byte LDS write next to an LDS-DMA in flight (asm for the reason lds_rd16 is: hipcc would drain the ring in front of it)
 __device__ __forceinline__ void lds_wr8(unsigned addr, unsigned lo, unsigned hi) {
     uint2 v; v.x = lo; v.y = hi;

@@ -36,7 +36,7 @@ __device__ __forceinline__ UniformAddr uniform_addr(const void* p) {
     const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)ad), hi = __builtin_amdgcn_readfirstlane((unsigned)(ad >> 32));
     return UniformAddr{lo, hi};
 }
-// (the two steps are separate for attention.hip's make_opnd, which works out the extent between them; everyone else calls buffer_rsrc)
+// (the two steps are separate for attention_common.h's make_opnd, which works out the extent between them; everyone else calls buffer_rsrc)
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t buffer_rsrc_at(UniformAddr base, unsigned extent) {
     return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)base.hi << 32) | base.lo), 0,
                                              __builtin_amdgcn_readfirstlane((int)extent), 0x00020000);

@@ -164,6 +164,53 @@ def gemm(a_ptr, a_ld, a_bs, a_trans, b_ptr, b_ld, b_bs, b_trans, c_ptr, c_ld, c_
         lambda: _hip.lib().ddpm_gemm_variant(a_ld, a_trans, b_ld, b_trans, c_ld, M, N, K, batch, out_mode, splits, dtype))
 
 
+def attention_path(H, C, d, dtype, B, Lk, ld, save):
+    """The launch sequence of one attention block's core: H heads of d = C / H channels over Lk tokens, q | k | v rows of pitch ld.
+    "flash": the on-chip pair (ddpm_attention_fwd_lse / ddpm_attention_bwd); "fused": the inference-only single kernel
+    (ddpm_attention_fwd); "stream": the streaming pair (ddpm_attention_stream_*, with a head index ddpm_attention_mh_*);
+    "mat": gemm / softmax / gemm per head, the L x L logits and probabilities in memory.  The engine writes the answer on its tape:
+    the backward runs the partner of what the forward ran, whatever this rule becomes."""
+    bf16 = dtype == _hip.BF16
+    kernels = bf16 and d % 32 == 0 and d <= 512                                    # the head widths the flash and streaming kernels serve
+    streams = kernels and B * H <= 65535 and Lk * ld * 2 <= 0x7ffffff0             # one block row per (image, head); buffer-descriptor extent
+    if H == 1 and kernels and Lk <= 256 and Lk % 16 == 0:                          # (the on-chip pair has no head index)
+        return "flash"
+    if H == 1 and bf16 and not save and Lk % 128 == 0 and C in (128, 256):
+        return "fused"
+    if streams and (H > 1 or Lk > 256 or Lk % 8):                                  # a single head keeps the materialised path at L <= 256, L % 8 == 0
+        return "stream"
+    return "mat"
+
+
+# path -> (forward, backward) entry; "stream" with a head index runs the "mh" pair
+_ATTENTION = {"flash": ("ddpm_attention_fwd_lse", "ddpm_attention_bwd"), "stream": ("ddpm_attention_stream_fwd", "ddpm_attention_stream_bwd"),
+              "mh": ("ddpm_attention_mh_fwd", "ddpm_attention_mh_bwd")}
+
+
+# (the attention and softmax launches are not _timed: PROFILE holds the conv / gemm / GroupNorm launches)
+def attention_fwd(path, qkv, o, lse, Lk, C, H, scale):
+    """path: "flash" | "fused" | "stream" of attention_path.  qkv, o: Views; lse: fp32 [B][H][Lk] the backward needs, None at inference."""
+    if path == "fused":
+        return _hip.call("ddpm_attention_fwd", qkv.ptr, qkv.ld, o.ptr, o.ld, qkv.B, Lk, C, scale, qkv.dtype, _hip.stream())
+    heads = (H,) if H > 1 else ()
+    _hip.call(_ATTENTION["mh" if H > 1 else path][0], qkv.ptr, qkv.ld, o.ptr, o.ld, _hip.ptr(lse), qkv.B, Lk, C, *heads, scale, qkv.dtype, _hip.stream())
+
+
+def attention_bwd(path, qkv, o, do, lse, dvec, dqkv, Lk, C, H, scale):
+    """dq | dk | dv into dqkv: P is rebuilt from q, k and the saved log-sum-exp inside the kernels (dQ; then dK and dV).  path: "flash" | "stream"."""
+    heads = (H,) if H > 1 else ()
+    _hip.call(_ATTENTION["mh" if H > 1 else path][1], qkv.ptr, qkv.ld, o.ptr, o.ld, do.ptr, do.ld, lse.data_ptr(), dvec.data_ptr(), dqkv.ptr, dqkv.ld,
+              qkv.B, Lk, C, *heads, scale, qkv.dtype, _hip.stream())
+
+
+def softmax_fwd(logits_ptr, prob_ptr, rows, L, dtype):
+    _hip.call("ddpm_softmax_fwd", logits_ptr, prob_ptr, rows, L, dtype, _hip.stream())
+
+
+def softmax_bwd(prob_ptr, dp_ptr, ds_ptr, rows, L, dtype):
+    _hip.call("ddpm_softmax_bwd", prob_ptr, dp_ptr, ds_ptr, rows, L, dtype, _hip.stream())
+
+
 def gn_workspace_floats(B, HW, C, dtype):
     n = _hip.lib().ddpm_gn_workspace_floats(B, HW, C, GN_GROUPS, dtype)
     if n < 0:

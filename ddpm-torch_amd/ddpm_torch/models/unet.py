@@ -1148,50 +1148,34 @@ class _Engine:
 
     def _attn(self, st, ab, x, out):
         B, save, ws = st["B"], st["save"], st["ws"]
-        C, Lk = ab.in_channels, x.H * x.W
+        C, H, Lk = ab.in_channels, ab.num_heads, x.H * x.W
         hn = self._new(B, x.H, x.W, C)
         stats = self._f32(B, ops.GN_GROUPS, 2) if save else None
         ops.gn_fwd(x, hn, ab.norm.weight, ab.norm.bias, stats, ws, silu=False)
         qkv = self._new(B, x.H, x.W, 3 * C)
         ci = self._packed(ab.project_in, save)
         ops.conv2d(hn, ci.wf.data_ptr(), qkv.ptr, qkv.ld, 3 * C, 1, 1, x.H, x.W, bias=ab.project_in.bias.data_ptr(), splitk=self.splitk)
-        es, bs = self.es, Lk * 3 * C
         o = self._new(B, x.H, x.W, C)
         prob = lse = None
-        scale = 1.0 / math.sqrt(C)
-        flash = self.T == torch.bfloat16 and Lk <= 256 and Lk % 16 == 0 and C <= 512 and C % 32 == 0
-        fused = not save and not flash and self.T == torch.bfloat16 and Lk % 128 == 0 and C in (128, 256)
-        # any other token count in the bf16 mode — more than 256, or no multiple of 8 — streams the keys through LDS with an online softmax
-        # (csrc/attention_stream.hip): no L x L tensor, no L as a memory row.  (L <= 256 with L % 8 == 0 keeps the kernels it had.)
-        stream = (self.T == torch.bfloat16 and not flash and not fused and (Lk > 256 or Lk % 8) and C <= 512 and C % 32 == 0
-                  and Lk * qkv.ld * 2 <= 0x7ffffff0)
-        if ab.num_heads > 1:
-            prob, lse = self._attn_heads(ab, qkv, o, B, Lk, save)
-        elif fused:
-            # inference over more tokens than the kernel below serves: one kernel, the L x L logits / probabilities stay in LDS and
-            # registers (unet.py:41-52).  (Up to 256 tokens the training forward — DMA rings, one-butterfly softmax — is the faster
-            # one, 27 vs 32 us at B=128, L=256, C=256, and serves inference too.)
-            _hip.call("ddpm_attention_fwd", qkv.ptr, qkv.ld, o.ptr, o.ld, B, Lk, C, scale, self.dcode, _hip.stream())
-        elif flash or stream:
-            # training (and the geometries the kernel above does not serve): same, plus the row log-sum-exp the backward
-            # kernels rebuild the probabilities from — no L x L tensor exists in memory
-            lse = self._f32(B, Lk) if save else None
-            _hip.call("ddpm_attention_fwd_lse" if flash else "ddpm_attention_stream_fwd", qkv.ptr, qkv.ld, o.ptr, o.ld,
-                      lse.data_ptr() if save else 0, B, Lk, C, scale, self.dcode, _hip.stream())
+        # head h of q, k, v and o is channels [h d, (h + 1) d) of its third of the packed buffer / of o, every head with its own softmax
+        # at scale 1/sqrt(d)
+        scale = 1.0 / math.sqrt(C // H)
+        path = ops.attention_path(H, C, C // H, self.dcode, B, Lk, qkv.ld, save)
+        if path == "mat":
+            prob = self._attn_mat(qkv, o, B, Lk, C, H, scale)
         else:
-            self._need_vec_tokens(Lk)
-            q, kk, v = qkv.ptr, qkv.ptr + C * es, qkv.ptr + 2 * C * es
-            logits = self._f32(B, Lk, Lk)                       # S = Q K^T / sqrt(C)   (unet.py:46-48)
-            ops.gemm(q, 3 * C, bs, 0, kk, 3 * C, bs, 0, logits.data_ptr(), Lk, Lk * Lk, Lk, Lk, C, self.dcode, batch=B,
-                     alpha=scale, out_mode=1)
-            prob = _hip.retain(torch.empty((B, Lk, Lk), dtype=self.T, device=self.device))
-            _hip.call("ddpm_softmax_fwd", logits.data_ptr(), prob.data_ptr(), B * Lk, Lk, self.dcode, _hip.stream())
-            ops.gemm(prob.data_ptr(), Lk, Lk * Lk, 0, v, 3 * C, bs, 1, o.ptr, C, Lk * C, Lk, C, Lk, self.dcode, batch=B)   # O = P V (unet.py:50)
+            # one kernel: the L x L logits / probabilities stay in LDS and registers (unet.py:41-52), no L x L tensor exists in memory.
+            # Training saves the row log-sum-exp the backward kernels rebuild the probabilities from; "fused" has none to give.  (Up to
+            # 256 tokens the training forward — DMA rings, one-butterfly softmax — is the faster one, 27 vs 32 us at B=128, L=256, C=256,
+            # and serves inference too: attention_path asks for "flash" first.)
+            if save and path != "fused":
+                lse = self._f32(B, H, Lk) if H > 1 else self._f32(B, Lk)          # [B][L]; with a head index [B][H][L]
+            ops.attention_fwd(path, qkv, o, lse, Lk, C, H, scale)
         co = self._packed(ab.project_out, save)
         ops.conv2d(o, co.wf.data_ptr(), out.ptr, out.ld, C, 1, 1, x.H, x.W, bias=ab.project_out.bias.data_ptr(),
                    res_ptr=x.ptr, res_ld=x.ld, splitk=self.splitk)
         if save:
-            st["tape"].append(("attn", ab, x, out, hn, stats, qkv, prob, o, lse))
+            st["tape"].append(("attn", ab, x, out, hn, stats, qkv, prob, o, lse, path))   # the backward dispatches on `path` alone
 
     def _need_vec_tokens(self, Lk):
         """The materialised attention path's restriction on the token count."""
@@ -1202,26 +1186,12 @@ class _Engine:
                                       f"needs a token count that is a multiple of {self.vec} (the bf16 mode attends over any token count "
                                       f"when the channel count is a multiple of 32 up to 512)")
 
-    def _mh_streams(self, ab, qkv, B, Lk):
-        """Whether the head-indexed streaming kernels (ddpm_attention_mh_*) serve this block: bf16, a head width they have a bucket for."""
-        d = ab.in_channels // ab.num_heads
-        return (self.T == torch.bfloat16 and d % 32 == 0 and d <= 512 and B * ab.num_heads <= 65535
-                and Lk * qkv.ld * 2 <= 0x7ffffff0)
-
-    def _attn_heads(self, ab, qkv, o, B, Lk, save):
-        """The attention core of a block with num_heads > 1: head h of q, k, v and o is channels [h d, (h + 1) d) of its third of
-        the packed buffer / of o, every head with its own softmax at scale 1/sqrt(d).  Returns (prob, lse) for the tape."""
-        C, H = ab.in_channels, ab.num_heads
+    def _attn_mat(self, qkv, o, B, Lk, C, H, scale):
+        """The materialised attention core — the fp32 mode, a head width the kernels have no bucket for, a single bf16 head over
+        L <= 256, L % 8 == 0 tokens that the on-chip pair does not take: S = Q K^T / sqrt(d), P = softmax(S), O = P V (unet.py:46-50)
+        per head.  The operands are d-wide column slices of the same rows (pitch 3C, K = d); logits / probabilities [H][B][L][L], ONE
+        softmax launch.  Returns the probabilities for the tape."""
         d = C // H
-        scale = 1.0 / math.sqrt(d)
-        if self._mh_streams(ab, qkv, B, Lk):
-            # the streaming kernels with a head index, at every token count: one launch over B * H problems, lse [B][H][L]
-            lse = self._f32(B, H, Lk) if save else None
-            _hip.call("ddpm_attention_mh_fwd", qkv.ptr, qkv.ld, o.ptr, o.ld, lse.data_ptr() if save else 0, B, Lk, C, H, scale,
-                      self.dcode, _hip.stream())
-            return None, lse
-        # fp32 mode, or a head width the kernels have no bucket for: the materialised products of the single head, per head — the
-        # operands are d-wide column slices of the same rows (pitch 3C, K = d); logits / probabilities [H][B][L][L], ONE softmax launch
         self._need_vec_tokens(Lk)
         if d % self.vec:                              # (a head's column slice of every operand starts at h d elements: 16-byte multiples)
             raise NotImplementedError(f"attention with {H} heads of {d} channels in the {'bf16' if self.T == torch.bfloat16 else 'fp32'} mode: "
@@ -1233,22 +1203,15 @@ class _Engine:
             ops.gemm(q, 3 * C, bs, 0, kk, 3 * C, bs, 0, logits.data_ptr() + h * B * LL * 4, Lk, LL, Lk, Lk, d, self.dcode, batch=B,
                      alpha=scale, out_mode=1)
         prob = _hip.retain(torch.empty((H, B, Lk, Lk), dtype=self.T, device=self.device))
-        _hip.call("ddpm_softmax_fwd", logits.data_ptr(), prob.data_ptr(), H * B * Lk, Lk, self.dcode, _hip.stream())
+        ops.softmax_fwd(logits.data_ptr(), prob.data_ptr(), H * B * Lk, Lk, self.dcode)
         for h in range(H):
             v = qkv.ptr + (2 * C + h * d) * es
             ops.gemm(prob.data_ptr() + h * B * LL * es, Lk, LL, 0, v, 3 * C, bs, 1, o.ptr + h * d * es, C, Lk * C, Lk, d, Lk, self.dcode, batch=B)
-        return prob, None
+        return prob
 
-    def _attn_heads_bwd(self, ab, qkv, prob, o, lse, do, dqkv, B, Lk):
-        """Backward of _attn_heads: dq | dk | dv into dqkv, in the head layout of qkv."""
-        C, H = ab.in_channels, ab.num_heads
+    def _attn_mat_bwd(self, qkv, prob, do, dqkv, B, Lk, C, H, scale):
+        """Backward of _attn_mat: dq | dk | dv into dqkv, in the head layout of qkv."""
         d = C // H
-        scale = 1.0 / math.sqrt(d)
-        if lse is not None:
-            dvec = self._f32(B, H, Lk)
-            _hip.call("ddpm_attention_mh_bwd", qkv.ptr, qkv.ld, o.ptr, o.ld, do.ptr, do.ld, lse.data_ptr(), dvec.data_ptr(), dqkv.ptr, dqkv.ld,
-                      B, Lk, C, H, scale, self.dcode, _hip.stream())
-            return
         es, bs, LL = self.es, Lk * 3 * C, Lk * Lk
         dp = self._f32(H, B, Lk, Lk)
         for h in range(H):
@@ -1257,7 +1220,7 @@ class _Engine:
             ops.gemm(doh, C, Lk * C, 0, v, 3 * C, bs, 0, dp.data_ptr() + h * B * LL * 4, Lk, LL, Lk, Lk, d, self.dcode, batch=B, out_mode=1)   # dP = dO V^T
             ops.gemm(ph, Lk, LL, 1, doh, C, Lk * C, 1, dv, 3 * C, bs, Lk, d, Lk, self.dcode, batch=B)                                          # dV = P^T dO
         ds = _hip.retain(torch.empty((H, B, Lk, Lk), dtype=self.T, device=self.device))
-        _hip.call("ddpm_softmax_bwd", prob.data_ptr(), dp.data_ptr(), ds.data_ptr(), H * B * Lk, Lk, self.dcode, _hip.stream())
+        ops.softmax_bwd(prob.data_ptr(), dp.data_ptr(), ds.data_ptr(), H * B * Lk, Lk, self.dcode)
         for h in range(H):
             q, kk = qkv.ptr + h * d * es, qkv.ptr + (C + h * d) * es
             dq, dk = dqkv.ptr + h * d * es, dqkv.ptr + (C + h * d) * es
@@ -1490,40 +1453,24 @@ class _Engine:
                 pv.grad, pv.ginit = g.chan_slice(a, b), True
 
     def _attn_bwd(self, ctx, rec):
-        _, ab, x, out, hn, stats, qkv, prob, o, lse = rec
+        _, ab, x, out, hn, stats, qkv, prob, o, lse, path = rec
         gflat, ws, B = ctx["gflat"], ctx["ws"], ctx["B"]
-        C, Lk = ab.in_channels, x.H * x.W
+        C, H, Lk = ab.in_channels, ab.num_heads, x.H * x.W
         dout = out.grad
         assert dout is not None and out.ginit
         ci, co = self.convs[id(ab.project_in)], self.convs[id(ab.project_out)]
-        es, bs = self.es, Lk * 3 * C
         # project_out
         do = self._new(B, x.H, x.W, C)
         ops.conv2d(dout, co.wd.data_ptr(), do.ptr, do.ld, C, 1, 1, x.H, x.W, splitk=self.splitk)
         if not self._wgrad(ctx, ab.project_out.weight, dout, o, C, C, 1, 1, splits=self._splits(C, C, dout.rows), bias=ab.project_out.bias):
             self._bias_grad(ctx, dout, [ab.project_out.bias], C)
-        # attention core
-        q, kk, v = qkv.ptr, qkv.ptr + C * es, qkv.ptr + 2 * C * es
+        # attention core: the partner of what the forward ran
         dqkv = self._new(B, x.H, x.W, 3 * C)
-        dq, dk, dv = dqkv.ptr, dqkv.ptr + C * es, dqkv.ptr + 2 * C * es
-        scale = 1.0 / math.sqrt(C)
-        if ab.num_heads > 1:
-            self._attn_heads_bwd(ab, qkv, prob, o, lse, do, dqkv, B, Lk)
-        elif lse is not None:
-            # flash-style: P is rebuilt from q, k and the saved log-sum-exp inside the kernels (dQ; then dK and dV)
-            dvec = self._f32(B, Lk)
-            # (up to 256 tokens in multiples of 16 the forward was ddpm_attention_fwd_lse; every other record with an lse was streamed)
-            _hip.call("ddpm_attention_bwd" if Lk <= 256 and Lk % 16 == 0 else "ddpm_attention_stream_bwd", qkv.ptr, qkv.ld, o.ptr, o.ld,
-                      do.ptr, do.ld, lse.data_ptr(), dvec.data_ptr(), dqkv.ptr, dqkv.ld, B, Lk, C, scale, self.dcode, _hip.stream())
+        scale = 1.0 / math.sqrt(C // H)
+        if path == "mat":
+            self._attn_mat_bwd(qkv, prob, do, dqkv, B, Lk, C, H, scale)
         else:
-            dp = self._f32(B, Lk, Lk)                            # dP = dO V^T
-            ops.gemm(do.ptr, C, Lk * C, 0, v, 3 * C, bs, 0, dp.data_ptr(), Lk, Lk * Lk, Lk, Lk, C, self.dcode, batch=B, out_mode=1)
-            # dV = P^T dO
-            ops.gemm(prob.data_ptr(), Lk, Lk * Lk, 1, do.ptr, C, Lk * C, 1, dv, 3 * C, bs, Lk, C, Lk, self.dcode, batch=B)
-            ds = _hip.retain(torch.empty((B, Lk, Lk), dtype=self.T, device=self.device))
-            _hip.call("ddpm_softmax_bwd", prob.data_ptr(), dp.data_ptr(), ds.data_ptr(), B * Lk, Lk, self.dcode, _hip.stream())
-            ops.gemm(ds.data_ptr(), Lk, Lk * Lk, 0, kk, 3 * C, bs, 1, dq, 3 * C, bs, Lk, C, Lk, self.dcode, batch=B, alpha=scale)   # dQ = dS K
-            ops.gemm(ds.data_ptr(), Lk, Lk * Lk, 1, q, 3 * C, bs, 1, dk, 3 * C, bs, Lk, C, Lk, self.dcode, batch=B, alpha=scale)    # dK = dS^T Q
+            ops.attention_bwd(path, qkv, o, do, lse, self._f32(*lse.shape), dqkv, Lk, C, H, scale)      # (the second fp32 buffer: D = rowsum(dO o O))
         # project_in
         dhn = self._new(B, x.H, x.W, C)
         ops.conv2d(dqkv, ci.wd.data_ptr(), dhn.ptr, dhn.ld, C, 1, 1, x.H, x.W, splitk=self.splitk)

@@ -1,5 +1,6 @@
-"""TEST INFRASTRUCTURE for multi-head attention (csrc/attention_stream.hip: ``ddpm_attention_mh_fwd`` / ``ddpm_attention_mh_bwd``):
-numpy restatements of the two entry points as include/ddpm_hip.h states them, over the raw host pointers the product passes, for the host
+"""TEST INFRASTRUCTURE for multi-head attention (csrc/attention_stream.hip: ``ddpm_attention_mh_fwd`` / ``ddpm_attention_mh_bwd``, and
+the single-head streaming pair ``ddpm_attention_stream_fwd`` / ``ddpm_attention_stream_bwd`` as their one-head case):
+numpy restatements of the entry points as include/ddpm_hip.h states them, over the raw host pointers the product passes, for the host
 emulator (tests/abi_emulator.py; ``attach`` hangs them on the Emulator instance ``install`` returns).  Float64 arithmetic on the stored
 operands, rounded where the entry point stores.  They say nothing about the kernels themselves — tests/test_mha_gpu.py holds those to
 float64."""
@@ -52,8 +53,17 @@ def ddpm_attention_mh_bwd(qkv, ld, o, o_ld, d_o, do_ld, lse, dvec, dqkv, dqkv_ld
     Mat(dqkv, B * L, 3 * C, dqkv_ld, dt).set(g.astype(np.float32))
 
 
+def ddpm_attention_stream_fwd(qkv, ld, out, out_ld, lse, B, L, C, scale, dt, st):
+    """The single-head streaming forward: the heads = 1 case (the parameter list is the one above without ``heads``)."""
+    ddpm_attention_mh_fwd(qkv, ld, out, out_ld, lse, B, L, C, 1, scale, dt, st)
+
+
+def ddpm_attention_stream_bwd(qkv, ld, o, o_ld, d_o, do_ld, lse, dvec, dqkv, dqkv_ld, B, L, C, scale, dt, st):
+    ddpm_attention_mh_bwd(qkv, ld, o, o_ld, d_o, do_ld, lse, dvec, dqkv, dqkv_ld, B, L, C, 1, scale, dt, st)
+
+
 def attach(emu):
-    """Add the two entry points to an ``abi_emulator.Emulator`` instance (its ``call`` is ``getattr(self, name)``)."""
-    emu.ddpm_attention_mh_fwd = ddpm_attention_mh_fwd
-    emu.ddpm_attention_mh_bwd = ddpm_attention_mh_bwd
+    """Add the entry points to an ``abi_emulator.Emulator`` instance (its ``call`` is ``getattr(self, name)``)."""
+    for fn in (ddpm_attention_mh_fwd, ddpm_attention_mh_bwd, ddpm_attention_stream_fwd, ddpm_attention_stream_bwd):
+        setattr(emu, fn.__name__, fn)
     return emu
