@@ -376,6 +376,14 @@ class GaussianDiffusion:
                   _hip.ptr(pred), B, state[0].numel(), _MEAN_CODE[self.model_mean_type], int(bool(self.clip_sampling)), 1,
                   len(self.posterior_mean_coef1), _hip.stream())
 
+    def _mean_half(self, out2, state):
+        """What the guided step combines: the network output itself, or — a sampler on fixed tables (var_mode 0) over a 2C-channel model,
+        i.e. a DDIM built for a learned-variance one — its mean half as a plain copy, as ``DDIM.encode`` / ``decode`` take it."""
+        if not self.learned_var:
+            return out2
+        self._check_two_halves(out2, state)
+        return out2[:, :state.shape[1]].contiguous()
+
     @staticmethod
     def _null_class(denoise_fn):
         """Index of the null class of the class-conditional network behind ``denoise_fn`` (its ``num_classes``)."""
@@ -396,7 +404,7 @@ class GaussianDiffusion:
         scale = float(guidance_scale)
         if scale == 1.0:
             return ("cond",)
-        if self.learned_var:
+        if self._var_mode():                                        # (a DDIM on a 2C-channel model has var_mode 0: its own fixed table, the mean half)
             raise NotImplementedError("classifier-free guidance (guidance_scale != 1) of a learned-variance model: the guided step kernel "
                                       "combines the mean output on a fixed variance table; sample such a model at guidance_scale = 1")
         return ("cfg", scale, self._null_class(denoise_fn))
@@ -488,7 +496,7 @@ class GaussianDiffusion:
         pred = torch.empty_like(x_T) if on_step is not None else None
         for ti in range(steps - 1, -1, -1):
             t.fill_(ti)
-            out2 = denoise_fn(state, self._model_t(t), y2).contiguous().float()
+            out2 = self._mean_half(denoise_fn(state, self._model_t(t), y2).contiguous().float(), state)
             z = torch.empty_like(x_T).normal_(generator=rng) if z_stream is None else next(z_stream).to(x_T).contiguous()
             self._step_cfg_call(state, out2, z, t, scale, pred, B)
             if on_step is not None:
@@ -619,7 +627,7 @@ class GaussianDiffusion:
             if not external_z:
                 z.normal_(generator=rng)
             if guided:
-                self._step_cfg_call(state, out, z, t, form[1], None, B)
+                self._step_cfg_call(state, self._mean_half(out, state), z, t, form[1], None, B)
             else:
                 self._step_call(x_t, out, z, t, x_t, None, self.clip_sampling)         # in place
             _hip.call("ddpm_add_i64", t.data_ptr(), rows, -1, _hip.stream())
@@ -662,7 +670,8 @@ class GaussianDiffusion:
         """diffusion.py:160-174.  Not in the reference: ``y`` (int64 [B] class labels of a class-conditional network) and
         ``guidance_scale`` (classifier-free guidance, Ho & Salimans 2022: the step runs on scale * out(x, y) + (1 - scale) * out(x, null);
         1 = plain conditional sampling, any other value evaluates both branches as one 2B-row network call).  Learned-variance models
-        are sampled at scale 1 only (NotImplementedError otherwise).  RNG consumption is that of the unconditional loop."""
+        are sampled at scale 1 only (NotImplementedError otherwise; a DDIM built for one runs on fixed tables and guides the mean half).
+        RNG consumption is that of the unconditional loop."""
         return self._sample_loop(denoise_fn, shape, device, noise, seed, y=y, guidance_scale=guidance_scale)
 
     @torch.inference_mode()
