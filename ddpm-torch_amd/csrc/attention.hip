@@ -640,6 +640,9 @@ extern "C" int ddpm_attention_bwd(const void* qkv, long long ld, const void* o, 
     if (rc) return rc;
     if (!o || !d_o || !lse || !dvec || !dqkv) return DDPM_ERR_NULL;
     if (!aligned16(o) || !aligned16(d_o) || !aligned16(dqkv) || o_ld % 8 || do_ld % 8 || dqkv_ld % 8 || dqkv_ld < 3 * C) return DDPM_ERR_ALIGN;
+    // d_o is read through a buffer descriptor like q, k, v (make_opnd in both kernels): one sample within the 32-bit offsets;
+    // o and dqkv go through 64-bit pointers
+    if (do_ld < C || (long long)L * do_ld * 2 > BUF_OOB) return DDPM_ERR_SHAPE;
     AttnArgs a; memset(&a, 0, sizeof(a));
     a.q = (const bf16_t*)qkv; a.k = a.q + C; a.v = a.q + 2 * C; a.qkv_ld = ld;
     a.o = (const bf16_t*)o; a.o_ld = o_ld; a.d_o = (const bf16_t*)d_o; a.do_ld = do_ld;

@@ -135,7 +135,7 @@ void conv3x3_stream_kernel(CsArgs a) {
             const int lc = (v & 7) ^ (PATCH == 16 ? (hx >> 1) & 7 : ((hx >> 1) ^ ((hy & 1) << 2)) & 7);
             // nearest-neighbour 2x up-sampling folded into the gather: virtual pixel (iy, ix) is stored pixel (iy >> 1, ix >> 1)
             const int sy = iy >> a.ups, sx = ix >> a.ups;
-            ho[i] = ok ? ((unsigned)((t.img * (a.H >> a.ups) + sy) * (a.W >> a.ups) + sx) * (unsigned)a.x_ld + (unsigned)(lc * 8)) * 2u : BUF_OOB;     // < 2^31: checked by the launcher
+            ho[i] = ok ? ((unsigned)((t.img * (a.H >> a.ups) + sy) * (a.W >> a.ups) + sx) * (unsigned)a.x_ld + (unsigned)(lc * 8)) * 2u : BUF_OOB;     // < 2^31: ddpm_conv3x3_stream_launch below returns -1 when xbytes > BUF_OOB
         }
     };
     // one part of a tile's plan (the main loop rebuilds the plan for the NEXT tile part by part, each in the step that requests it —

@@ -249,7 +249,7 @@ __global__ __launch_bounds__(256) void wgrad_unpack_kernel(const float* __restri
     const float* src = gpack + d[0];
     float* dst = gflat + d[1];
     const unsigned C = (unsigned)d[3], RS = (unsigned)d[4];
-    const unsigned total = (unsigned)(d[2] * C * RS);                       // < 2^31 per tensor (checked by the host: the flat buffer is indexed with ints elsewhere too)
+    const unsigned total = (unsigned)(d[2] * C * RS);                       // < 2^31 per tensor (checked where the table is built: ddpm_torch/models/unet.py _Engine._wgrad_table raises on a larger row)
     float acc = 0.f;
     if (RS == 1) {                                                          // plain copies (everything but the conv weights)
         for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {

@@ -806,7 +806,7 @@ void gn_lds_bwd8_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __
     }
     const float keep_scale = a.drop_p > 0.f ? 1.0f / (1.0f - a.drop_p) : 1.0f;
     const unsigned h0 = dropout_h0(gn_seed(a));
-    const unsigned idx0 = (unsigned)(((unsigned)b * (unsigned)s.HW) * (unsigned)s.C + (unsigned)(c0 + j * VEC));   // < 2^32: checked by the host
+    const unsigned idx0 = (unsigned)(((unsigned)b * (unsigned)s.HW) * (unsigned)s.C + (unsigned)(c0 + j * VEC));   // < 2^32: gn_lds_addressable (the dispatchers below)
     // dz = dy * dropout mask * silu'(z) for one vector: one hash word per pair of channels
     auto dz_vec = [&](int p, const float (&xh)[VEC], float (&d)[VEC]) {
         if (a.drop_p > 0.f) {
@@ -1006,7 +1006,7 @@ void gn_lds_bwd_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __r
     const __amdgpu_buffer_rsrc_t rdx = gn_slice_rsrc(dx + ((long long)b * s.HW) * dx_ld + c0, ((long long)(s.HW - 1) * dx_ld + f.seg_ch) * ES);
     const __amdgpu_buffer_rsrc_t rad = gn_slice_rsrc(addp ? addp + ((long long)b * s.HW) * add_ld + c0 : x, addp ? ((long long)(s.HW - 1) * add_ld + f.seg_ch) * ES : 0);
     const unsigned h0 = dropout_h0(gn_seed(a));            // (its load, if any, also goes out before the DMA)
-    // slice offsets of pixel row prow + i * R: base + i * step (the slices are < 2^31 bytes: checked by the host)
+    // slice offsets of pixel row prow + i * R: base + i * step (the slices are < 2^31 bytes: gn_lds_addressable in the dispatchers below)
     const unsigned x_o = (unsigned)((prow * s.x_ld + j * VEC) * ES), x_st = (unsigned)(f.rows_per_iter * s.x_ld * ES);
     const unsigned dy_o = (unsigned)((prow * dy_ld + j * VEC) * ES), dy_st = (unsigned)(f.rows_per_iter * dy_ld * ES);
     const unsigned dx_o = (unsigned)((prow * dx_ld + j * VEC) * ES), dx_st = (unsigned)(f.rows_per_iter * dx_ld * ES);
@@ -1042,7 +1042,7 @@ void gn_lds_bwd_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __r
         gn_lds_rd_consts<VEC>(kcol + K_MEAN * kstride, mean);
     }
     const float keep_scale = do_drop ? 1.0f / (1.0f - a.drop_p) : 1.0f;
-    const unsigned idx0 = (unsigned)(((unsigned)b * (unsigned)s.HW) * (unsigned)s.C + (unsigned)(c0 + j * VEC));   // < 2^32: checked by the host
+    const unsigned idx0 = (unsigned)(((unsigned)b * (unsigned)s.HW) * (unsigned)s.C + (unsigned)(c0 + j * VEC));   // < 2^32: gn_lds_addressable (the dispatchers below)
     float a1[VEC], a2[VEC];
 #pragma unroll
     for (int e = 0; e < VEC; ++e) a1[e] = a2[e] = 0.f;
@@ -1742,6 +1742,20 @@ static int gn_geometry(int B, int HW, int C, int G, long long x_ld, long long y_
     return DDPM_OK;
 }
 
+// Operand limit of the GroupNorm entries: an operand of 2^31 elements or more ((B*HW - 1) * ld + C) is refused.  The two-launch and
+// register-resident kernels index pixels in 64 bits, but no form has run beyond that size, and the LDS-staged forms draw the dropout
+// index of an element in `unsigned` (gn_lds_addressable below): the limit keeps every form inside what has been read and tested.
+static bool gn_operand_ok(int B, int HW, int C, long long ld) {
+    return ((long long)B * HW - 1) * ld + C < (1ll << 31);
+}
+
+// The LDS-staged kernels (gn_lds_fwd_kernel, gn_lds_bwd_kernel, gn_lds_bwd8_kernel) address one (sample, group chunk) slice of every
+// operand with 32-bit byte offsets behind a buffer descriptor (gn_slice_rsrc) and form the dropout index b*HW*C + .. in `unsigned`:
+// a slice of pitch ld must end within BUF_OOB and the tensor must hold fewer than 2^32 elements, else the caller takes another form.
+static bool gn_lds_addressable(const GnShape& s, int esize, int seg_ch, long long ld_max) {
+    return ((long long)(s.HW - 1) * ld_max + seg_ch) * esize <= (long long)BUF_OOB && (long long)s.B * s.HW * s.C < (1ll << 32);
+}
+
 static GnApply make_apply(const float* gamma, const float* beta, float eps, int silu, float drop_p, unsigned long long seed, float* stats,
                           const unsigned long long* seed_dev = nullptr) {
     GnApply a; a.seed_dev = seed_dev; a.gamma = gamma; a.beta = beta; a.eps = eps; a.silu = silu; a.drop_p = drop_p; a.seed = seed; a.stats = stats;
@@ -1770,6 +1784,7 @@ static int gn_fwd_dispatch(const void* x, long long x_ld, void* y, long long y_l
     int rc = gn_geometry(B, HW, C, G, x_ld, y_ld, es, s, block, grid);
     if (rc) return rc;
     if (MOD && mod_ld < 2ll * C) return DDPM_ERR_SHAPE;
+    if (!gn_operand_ok(B, HW, C, x_ld) || !gn_operand_ok(B, HW, C, y_ld)) return DDPM_ERR_SHAPE;
     typename GnArgs<MOD>::type a;
     static_cast<GnApply&>(a) = make_apply(gamma, beta, eps, silu, drop_p, seed, stats, seed_dev);
     if constexpr (MOD) { a.mod = mod; a.mod_ld = mod_ld; a.dmod = nullptr; a.dmod_ld = 0; }
@@ -1778,9 +1793,10 @@ static int gn_fwd_dispatch(const void* x, long long x_ld, void* y, long long y_l
     GnFused fl; size_t lds_l = 0;
     const bool reg_ok = gn_fused_plan(s, es, f, lds);
     // small slices (<= 2 vectors per thread of a 256-thread block): the staged kernel in its 256-thread form
-    const bool small = reg_ok && f.nv <= 2 && f.seg_vecs <= 32;
+    const long long ld_max = x_ld > y_ld ? x_ld : y_ld;
+    const bool small = reg_ok && f.nv <= 2 && f.seg_vecs <= 32 && gn_lds_addressable(s, es, f.seg_ch, ld_max);
     if (small) { fl = f; fl.xcd_remap = 0; lds_l = gn_lds_bytes(f.nv <= 1 ? 1 : 2, 256, f.seg_ch); }
-    if (small || (!(reg_ok && f.nv <= 2) && gn_lds_plan(s, es, fl, lds_l))) {        // x staged in LDS: single launch, 1 read + 1 write of HBM
+    if (small || (!(reg_ok && f.nv <= 2) && gn_lds_plan(s, es, fl, lds_l) && gn_lds_addressable(s, es, fl.seg_ch, ld_max))) {        // x staged in LDS: single launch, 1 read + 1 write of HBM
         const dim3 fgrid(G / fl.GPB, B);
 #define GN_LF(T, NV, NT, FLV) do { static DevOnce attr; if (!attr) { if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gn_lds_fwd_kernel<T, NV, NT, FLV, MOD>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return DDPM_ERR_LAUNCH; attr = true; } \
         hipLaunchKernelGGL((gn_lds_fwd_kernel<T, NV, NT, FLV, MOD>), fgrid, dim3(NT), lds_l, st, (const T*)x, (T*)y, s, fl, a); } while (0)
@@ -1846,6 +1862,8 @@ static int gn_bwd_dispatch(const void* x, long long x_ld, const void* dy, long l
     if (rc) return rc;
     if (dy_ld % (16 / es) || dx_ld % (16 / es) || (add && (add_ld % (16 / es) || !aligned16(add)))) return DDPM_ERR_ALIGN;
     if (MOD && (mod_ld < 2ll * C || dmod_ld < 2ll * C)) return DDPM_ERR_SHAPE;
+    if (!gn_operand_ok(B, HW, C, x_ld) || !gn_operand_ok(B, HW, C, dy_ld) || !gn_operand_ok(B, HW, C, dx_ld) || (add && !gn_operand_ok(B, HW, C, add_ld)))
+        return DDPM_ERR_SHAPE;
     typename GnArgs<MOD>::type a;
     static_cast<GnApply&>(a) = make_apply(gamma, beta, 0.f, silu, drop_p, seed, nullptr, seed_dev);
     if constexpr (MOD) { a.mod = mod; a.mod_ld = mod_ld; a.dmod = dmod; a.dmod_ld = dmod_ld; }
@@ -1858,9 +1876,12 @@ static int gn_bwd_dispatch(const void* x, long long x_ld, const void* dy, long l
     // 1) slices too big for two register vectors per thread: (x, dy) staged in LDS, one launch, one HBM read of each input
     GnFused fl; size_t lds_l = 0;
     const bool small = gn_fused_plan(s, es, f, lds) && f.nv <= 2;
-    const bool small_lds = small && f.seg_vecs <= 32;
+    long long ld_max = x_ld > dy_ld ? x_ld : dy_ld;
+    if (dx_ld > ld_max) ld_max = dx_ld;
+    if (add && add_ld > ld_max) ld_max = add_ld;
+    const bool small_lds = small && f.seg_vecs <= 32 && gn_lds_addressable(s, es, f.seg_ch, ld_max);
     if (small_lds) { fl = f; fl.xcd_remap = 0; lds_l = gn_lds_bytes(f.nv <= 1 ? 1 : 2, 256, f.seg_ch); }
-    if (small_lds || (!small && gn_lds_plan(s, es, fl, lds_l))) {
+    if (small_lds || (!small && gn_lds_plan(s, es, fl, lds_l) && gn_lds_addressable(s, es, fl.seg_ch, ld_max))) {
         const dim3 fgrid(G / fl.GPB, B);
 #define GN_LDS(K, NT, ...) do { static DevOnce attr; if (!attr) { if (hipFuncSetAttribute(reinterpret_cast<const void*>(&K<__VA_ARGS__>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return DDPM_ERR_LAUNCH; attr = true; } \
         hipLaunchKernelGGL((K<__VA_ARGS__>), fgrid, dim3(NT), lds_l, st, (const T_*)x, (const T_*)dy, (T_*)dx, s, fl, dy_ld, dx_ld, stats, dgamma, dbeta, a, accumulate, dx_colsum, colsum_ld, (const T_*)add, add_ld); } while (0)

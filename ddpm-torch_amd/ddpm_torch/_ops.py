@@ -12,6 +12,9 @@ from . import _hip
 
 GN_GROUPS = 32
 GN_EPS = 1e-6
+# The GEMM-shaped kernels address an operand through a buffer descriptor with 32-bit byte offsets: their launchers refuse an operand
+# whose extent exceeds this many bytes (csrc/gfx950.h BUF_OOB; DESIGN.md "Size limits").
+BUF_OOB = 0x7FFFFFF0
 
 # Optional per-launch timing (bench.py's roofline leg): when a list, every MFMA launch appends
 # (kind, algorithmic flops, start event, end event, shape, kernel id) recorded on the launch stream; kinds starting with "hbm_" are the
@@ -172,7 +175,7 @@ def attention_path(H, C, d, dtype, B, Lk, ld, save):
     the backward runs the partner of what the forward ran, whatever this rule becomes."""
     bf16 = dtype == _hip.BF16
     kernels = bf16 and d % 32 == 0 and d <= 512                                    # the head widths the flash and streaming kernels serve
-    streams = kernels and B * H <= 65535 and Lk * ld * 2 <= 0x7ffffff0             # one block row per (image, head); buffer-descriptor extent
+    streams = kernels and B * H <= 65535 and Lk * ld * 2 <= BUF_OOB                # one block row per (image, head); buffer-descriptor extent
     if H == 1 and kernels and Lk <= 256 and Lk % 16 == 0:                          # (the on-chip pair has no head index)
         return "flash"
     if H == 1 and bf16 and not save and Lk % 128 == 0 and C in (128, 256):

@@ -379,6 +379,7 @@ class _Engine:
         self._ws = None
         self._ws_need, self._ws_retired = {}, []
         self.drop_calls = 0
+        self._admitted = set()                     # (B, H, W, backward) keys admit() has passed
         self.last_tape = None
         self.debug_keep_tape = False               # tests set it to look at the tape after a step; costs the activations' lifetime
         self.splitk = ops.SplitK(self.device)
@@ -714,6 +715,10 @@ class _Engine:
                 if self.goff[id(prm)] not in covered:
                     rows.append([slot(id(prm), prm.numel()), self.goff[id(prm)], 1, prm.numel(), 1])
             self.ptotal = off
+            # wgrad_unpack_kernel (csrc/elementwise.hip) counts the elements of one row in `unsigned`
+            big = [r for r in rows if r[2] * r[3] * r[4] >= 1 << 31]
+            if big:
+                raise ValueError(f"a parameter tensor of {big[0][2] * big[0][3] * big[0][4]} elements: the gradient unpack indexes one tensor with 32 bits (< 2^31 elements)")
             self.wdesc = torch.tensor(rows, dtype=torch.int64, device=self.device)
             self.tail = (conv_end, self.ptotal)
         return self.wdesc
@@ -934,6 +939,99 @@ class _Engine:
         ops.gemm(a.data_ptr(), K, 0, 0, w.data_ptr(), K, 0, 0, out.data_ptr(), N, 0, M, N, K, _hip.F32, bias=_hip.ptr(bias), out_mode=1)
         return out
 
+    # ================================================================ admission (the 2 GiB operand limit)
+    def operand_plan(self, H, W, backward=True):
+        """[(layer, operand, pixel rows per image, channels, pitch)] of every activation a conv, weight-gradient or GEMM kernel reads
+        through a buffer descriptor in forward (and, with ``backward``, in the backward) on H x W images: the buffer geometry of
+        ``forward`` below, walked without allocating.  An operand of B images spans ((B * rows - 1) * pitch + channels) * es bytes,
+        which the launchers hold to ops.BUF_OOB.  Gradients are dense buffers of their view's width (_grad_target), so the backward
+        adds the dense twin of every conv's input and output.  Attention reads q | k | v per sample: no batch limit comes from it."""
+        m, n, L = self.m, self.n, self.L
+        names = {id(mod): name for name, mod in m.named_modules()}
+        plan = []
+
+        def op(mod, what, hw, C, ld=None):
+            plan.append((names.get(id(mod), "?"), what, hw, C, C if ld is None else ld))
+
+        def conv(mod, hw, xC, x_ld, N, hw_out=None):
+            op(mod, "input", hw, xC, x_ld)
+            if backward:                            # dy of the weight gradient = x of the data gradient; dx is written dense
+                op(mod, "output gradient", hw if hw_out is None else hw_out, N)
+                op(mod, "input gradient", hw, xC)
+
+        def res(rb, hw, xC, x_ld):
+            conv(rb.conv1, hw, rb.in_channels, rb.in_channels, rb.out_channels)            # a1: GN + SiLU of x, dense
+            if rb.has_skip:
+                conv(rb.skip, hw, xC, x_ld, rb.out_channels)
+            conv(rb.conv2, hw, rb.out_channels, rb.out_channels, rb.out_channels)          # a2
+
+        def attn(ab, hw):
+            C = ab.in_channels
+            conv(ab.project_in, hw, C, C, 3 * C)                                           # (backward: the dense [3C] gradient of q | k | v)
+            conv(ab.project_out, hw, C, C, C)
+
+        def block(blk, hw, xC, x_ld):
+            r, a = self._split(blk)
+            res(r, hw, xC, x_ld)
+            if a is not None:
+                attn(a, hw)
+
+        enc = [(self.hid, 0)]
+        for i in range(L):
+            enc += [(self.chs[i], i)] * n
+            if i != L - 1:
+                enc.append((self.chs[i], i + 1))
+        hw = [(H >> i) * (W >> i) for i in range(L)]
+        width, h_ch, k = [], self.chs[-1], 0        # pitch of the concat buffer every encoder output is written into
+        for i in range(L - 1, -1, -1):
+            for j in range(n + 1):
+                width.append(h_ch + enc[len(enc) - 1 - k][0])
+                h_ch = self.chs[i]
+                k += 1
+        slot_ld = lambda e: width[len(enc) - 1 - e]
+        cin = self.convs[id(m.in_conv)].Cp
+        conv(m.in_conv, hw[0], cin, cin, self.hid)
+        e = 0
+        for i in range(L):
+            mods = m.downsamples[f"level_{i}"]
+            for j in range(n):
+                block(mods[j], hw[i], enc[e][0], slot_ld(e))
+                e += 1
+            if i != L - 1:
+                if m.resample_with_conv:
+                    conv(mods[n][1], hw[i], enc[e][0], slot_ld(e), self.chs[i], hw_out=hw[i + 1])
+                e += 1
+        res(m.middle[0], hw[-1], enc[e][0], slot_ld(e))
+        attn(m.middle[1], hw[-1])
+        res(m.middle[2], hw[-1], self.chs[-1], self.chs[-1])
+        k = 0
+        for i in range(L - 1, -1, -1):
+            mods = m.upsamples[f"level_{i}"]
+            for j in range(n + 1):
+                block(mods[j], hw[i], width[k], width[k])                                  # the whole concat buffer
+                k += 1
+            if i != 0 and m.resample_with_conv:
+                conv(mods[n + 1][1], hw[i], self.chs[i], self.chs[i], self.chs[i], hw_out=hw[i - 1])
+        conv(m.out_conv[2], hw[0], self.hid, self.hid, self.convs[id(m.out_conv[2])].Np)
+        return plan
+
+    def max_batch(self, H, W, backward=True):
+        """Largest batch of H x W images at which every operand of operand_plan stays within ops.BUF_OOB (in this compute mode)."""
+        return min(((ops.BUF_OOB // self.es - C) // ld + 1) // hw for _, _, hw, C, ld in self.operand_plan(H, W, backward))
+
+    def admit(self, B, H, W, backward=True):
+        """Raise before the first launch when a batch would meet DDPM_ERR_SHAPE in the middle of the network."""
+        key = (B, H, W, backward)
+        if key in self._admitted:
+            return
+        over = [(((B * hw - 1) * ld + C) * self.es, layer, what) for layer, what, hw, C, ld in self.operand_plan(H, W, backward)]
+        nbytes, layer, what = max(over)
+        if nbytes > ops.BUF_OOB:
+            raise ValueError(f"batch {B} of {H} x {W} images: the {what} of {layer} spans {nbytes} bytes in the "
+                             f"{'bf16' if self.es == 2 else 'fp32'} mode, beyond the {ops.BUF_OOB} bytes a kernel operand may span; "
+                             f"the largest admissible batch is {self.max_batch(H, W, backward)}")
+        self._admitted.add(key)
+
     # ================================================================ forward
     def forward(self, x, t, training, tape, seed_dev=0, y=None):
         """``seed_dev``: address of a device uint64 holding the per-step part of the dropout seed (captured training step:
@@ -958,6 +1056,7 @@ class _Engine:
         elif y is not None:
             raise ValueError("this UNet is unconditional (num_classes=None): it takes no class labels y")
         save = tape is not None
+        self.admit(B, H, W, backward=save)                      # before the first launch (and before anything is recorded)
         self._refresh_packs(save)
         ws = self._workspace(B, H, W)
         st = dict(B=B, ws=ws, save=save, training=training, tape=tape)

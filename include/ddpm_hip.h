@@ -13,6 +13,15 @@
  *     pitch ld >= C (in elements), so channel slices of a wider buffer are valid operands (zero-copy concat).
  *     Pointers and pitches must be 16-byte aligned; channel counts are multiples of 16/sizeof(dtype).
  *   - Return value: 0 OK, 1 bad shape, 2 bad dtype, 3 misaligned, 4 launch failure, 5 null pointer.
+ *   - OPERAND LIMIT.  The GEMM-shaped kernels (convolutions, weight gradients, ddpm_gemm, attention) read their operands through
+ *     buffer descriptors with 32-bit byte offsets.  Their launchers return 1 (bad shape), before anything is launched, when the
+ *     extent of such an operand exceeds 0x7ffffff0 bytes (2 GiB - 16).  The extent of a pitched [rows][cols] operand is
+ *     ((rows - 1) * ld + cols) * sizeof(dtype), of an NHWC activation (B*H*W*ld - (ld - C)) * sizeof(dtype).  Each such entry below
+ *     names the operands its limit covers; outputs, residuals and fp32 side operands are addressed with 64-bit pointers and have
+ *     none.  The GroupNorm entries refuse an operand of 2^31 elements or more (see there).  ddpm_add_rows, ddpm_colsum,
+ *     ddpm_upsample2x_bwd and ddpm_nchw_to_nhwc index with 64-bit arithmetic: no operand limit
+ *     (tests/test_large_operands_gpu.py runs them on operands of more than 2^31 elements).  ddpm_torch's UNet checks a batch against
+ *     the limit before its first launch (a ValueError naming the layer; engine.max_batch(H, W)).
  */
 #ifndef DDPM_HIP_H
 #define DDPM_HIP_H
@@ -32,7 +41,10 @@ extern "C" {
  * max(ceil(M/128)*ceil(N/128)*16384, ceil(M/64)*ceil(N/64)*4096)*splits floats and splitk_cnt one zero-initialised counter
  * per 64x64 output tile (left zero) — the library picks the tile size.  splits == 2 is an OFFER to the small-grid kernel (at most
  * 128 tiles of 64x64): it takes 2, 4 or 8 K runs per tile with tiles x runs <= 256, so for splits == 2 splitk_ws must hold at
- * least 256*4096 floats (4 MiB) as well. */
+ * least 256*4096 floats (4 MiB) as well.
+ * Operand limit: x (B*H*W stored pixels of pitch x_ld) and w; beyond it the call returns 1.  One form has none: 3x3 / stride 1 /
+ * pad 1 on bf16 with C == 8, N % 16 == 0, N <= 128, H and W multiples of 16, at least 16384 output pixels and neither row bias,
+ * residual nor accumulate (the few-input-channel edge kernel) reads x through 64-bit pointers. */
 int ddpm_conv2d_nhwc(const void* x, long long x_ld, const void* w, void* y, long long y_ld,
                      const float* bias, const float* rowbias, long long rowbias_ld,
                      const void* residual, long long res_ld,
@@ -52,7 +64,8 @@ int ddpm_conv2d_nhwc(const void* x, long long x_ld, const void* w, void* y, long
  *                     table[i] = {src address of copy 0, dst address, floats, copies, stride}.
  * ddpm_wgrad_unpack rewrites all layers' packed gradients into the parameter layout [n][c][r][s] in one launch:
  * descs[i] = {src offset in gpack, dst offset in gflat (floats), N, C, R*S} as int64 (R*S = 1: plain segment copy);
- * every value is multiplied by `scale` (1/world_size after the data-parallel sum all-reduce of gpack). */
+ * every value is multiplied by `scale` (1/world_size after the data-parallel sum all-reduce of gpack).
+ * Operand limit (ddpm_conv2d_wgrad_nhwc): dy ([B*Ho*Wo][N], pitch dy_ld) and x (B*H*W stored pixels of pitch x_ld). */
 int ddpm_conv2d_wgrad_nhwc(const void* dy, long long dy_ld, const void* x, long long x_ld, float* dw, long long slab_stride,
                            int B, int H, int W, int C, int Creal, int Ho, int Wo, int N, int Nreal, int R, int S,
                            int stride, int pad_t, int pad_l, int upsample, int splits, int dtype, void* stream);
@@ -67,7 +80,8 @@ int ddpm_wgrad_effective_splits(int K, int splits, int dtype);
  *   slab_stride  > 0: slice s stores at dw + s*slab_stride (and dbias + s*bias_stride); all ddpm_conv3x3_wgrad_splits(...)
  *                     copies are written in full and ddpm_wgrad_reduce sums them in a fixed order (deterministic).
  * C % 32 == 0, N % 8 == 0 and H = W in {4, 8} or H, W multiples of 16; otherwise DDPM_ERR_SHAPE (use ddpm_conv2d_wgrad_nhwc).
- * splits <= 0: chosen by the library. */
+ * splits <= 0: chosen by the library.
+ * Operand limit: dy (B*H*W pixels of pitch dy_ld) and x (B*H*W pixels of pitch x_ld; the _up_ entry: B*(H/2)*(W/2)). */
 int ddpm_conv3x3_wgrad_splits(int B, int H, int W, int C, int N, int splits);
 int ddpm_conv3x3_wgrad_nhwc(const void* dy, long long dy_ld, const void* x, long long x_ld, float* dw, long long slab_stride,
                             float* dbias, long long bias_stride, int B, int H, int W, int C, int N, int Nreal, int splits,
@@ -84,7 +98,8 @@ int ddpm_conv3x3_wgrad_up_nhwc(const void* dy, long long dy_ld, const void* x, l
  *     dW[n][c] = sum_p dy[p][n] * x[p][c]      db[n] = sum_p dy[p][n]      p over the P = B*H*W pixels
  * ddpm_conv1x1_wgrad_splits returns the number of slab copies the kernel writes for this geometry (0: not covered, use
  * ddpm_conv2d_wgrad_nhwc); slice s STORES its partials at dw + s*slab_stride ([N][C] fp32) and dbias + s*bias_stride (dbias may be
- * NULL); ddpm_wgrad_reduce sums the copies in a fixed order. */
+ * NULL); ddpm_wgrad_reduce sums the copies in a fixed order.
+ * Operand limit: dy ([P][N], pitch dy_ld) and x ([P][C], pitch x_ld). */
 int ddpm_conv1x1_wgrad_splits(int P, int C, int N);
 int ddpm_conv1x1_wgrad_nhwc(const void* dy, long long dy_ld, const void* x, long long x_ld, float* dw, long long slab_stride,
                             float* dbias, long long bias_stride, int P, int C, int N, int splits, int dtype, void* stream);
@@ -104,7 +119,9 @@ int ddpm_wgrad_unpack_sumsq(const float* gpack, float* gflat, const long long* d
 
 /* F.linear (modules.py:58-59; unet.py:77,123,125) and torch.einsum in AttentionBlock.qkv (unet.py:46,50):
  *   C[b][m][n] = alpha * sum_k A[b][m][k] * B[b][n][k] + bias[n] + residual[b][m][n]   (+ C when accumulate)
- * a_trans/b_trans = 1: the operand is stored [k][m] / [k][n].  out_mode: 0 dtype | 1 fp32 | 2 fp32 atomic add. */
+ * a_trans/b_trans = 1: the operand is stored [k][m] / [k][n].  out_mode: 0 dtype | 1 fp32 | 2 fp32 atomic add.
+ * Operand limit: A and B PER BATCH (one [rows][cols] matrix of pitch a_ld / b_ld); the batch strides are 64-bit, so the batches
+ * together may span any size. */
 int ddpm_gemm(const void* a, long long a_ld, long long a_bs, int a_trans,
               const void* b, long long b_ld, long long b_bs, int b_trans,
               void* c, long long c_ld, long long c_bs,
@@ -117,7 +134,8 @@ int ddpm_gemm(const void* a, long long a_ld, long long a_bs, int a_trans,
  * for a packed projection buffer qkv[B][L][ld] with q at channel 0, k at channel C and v at channel 2C:
  *     out[b][i][:] = sum_j softmax_j(q[b][i] . k[b][j] * scale) v[b][j]        (out pitch out_ld, bf16)
  * The L x L logits stay on chip (LDS / registers).  bf16 only, C in {128, 256}, L a multiple of 128; anything else returns
- * DDPM_ERR_SHAPE and the caller keeps ddpm_gemm + ddpm_softmax_fwd + ddpm_gemm. */
+ * DDPM_ERR_SHAPE and the caller keeps ddpm_gemm + ddpm_softmax_fwd + ddpm_gemm.
+ * Operand limit: q, k and v of one sample ((L - 1) * ld + C elements each); the samples' bases are 64-bit. */
 int ddpm_attention_fwd(const void* qkv, long long ld, void* out, long long out_ld, int B, int L, int C, float scale,
                        int dtype, void* stream);
 
@@ -126,7 +144,9 @@ int ddpm_attention_fwd(const void* qkv, long long ld, void* out, long long out_l
  * for inference); the backward rebuilds the probabilities from q, k and lse on chip — no L x L tensor is ever written — and produces
  *     dV = P^T dO      dS = P o (dO V^T - D),  D[i] = sum_c dO[i][c] O[i][c]      dQ = dS K * scale      dK = dS^T Q * scale
  * into the packed gradient buffer dqkv[B][L][dqkv_ld] (dq at channel 0, dk at C, dv at 2C).  dvec: [B][L] fp32 workspace (receives D).
- * bf16 only; L <= 256 with L % 16 == 0 (the reference attends at 16x16 and below); C <= 512 with C % 32 == 0; else DDPM_ERR_SHAPE. */
+ * bf16 only; L <= 256 with L % 16 == 0 (the reference attends at 16x16 and below); C <= 512 with C % 32 == 0; else DDPM_ERR_SHAPE.
+ * Operand limit: qkv of ONE sample, L * ld * 2 <= 0x7ffffff0 bytes, and in the backward d_o likewise, L * do_ld * 2 (do_ld >= C); the
+ * samples' bases are 64-bit, and o, out and dqkv are addressed with 64-bit pointers. */
 int ddpm_attention_fwd_lse(const void* qkv, long long ld, void* out, long long out_ld, float* lse, int B, int L, int C, float scale,
                            int dtype, void* stream);
 int ddpm_attention_bwd(const void* qkv, long long ld, const void* o, long long o_ld, const void* d_o, long long do_ld,
@@ -155,14 +175,19 @@ int ddpm_attention_stream_bwd(const void* qkv, long long ld, const void* o, long
  * C % heads == 0, d % 32 == 0, d <= 512 and B * heads <= 65535; bf16 only.  C itself is not bounded by 512.  The kernel bucket
  * follows d as the streaming pair's follows C (d = 32 runs in the 64-channel bucket).  No allocation, synchronisation or attribute
  * call; no atomics or split accumulation (a repeated backward is bit-identical); a head reads only its own [L][d] of each operand and
- * writes only its own [L][d] of each output. */
+ * writes only its own [L][d] of each output.
+ * Operand limit (this pair and the streaming pair above), per sample: L * ld * 2 <= 0x7ffffff0 bytes for qkv, and in the backward
+ * also L * o_ld * 2 and L * do_ld * 2 for o and d_o; the samples' bases are 64-bit. */
 int ddpm_attention_mh_fwd(const void* qkv, long long ld, void* out, long long out_ld, float* lse, int B, int L, int C, int heads,
                           float scale, int dtype, void* stream);
 int ddpm_attention_mh_bwd(const void* qkv, long long ld, const void* o, long long o_ld, const void* d_o, long long do_ld,
                           const float* lse, float* dvec, void* dqkv, long long dqkv_ld, int B, int L, int C, int heads, float scale,
                           int dtype, void* stream);
 
-/* nn.GroupNorm(32, C, eps=1e-6) -> SiLU -> Dropout(p) (unet.py:18-20,15,81,85-87,139-140; :57 without SiLU):
+/* Operand limit of the four GroupNorm entries below: every activation operand (x, y; dy, dx, add) must hold fewer than 2^31 elements,
+ * (B*HW - 1) * ld + C < 2^31, else 1 (bad shape) before any launch.  Up to that size the library picks a form whose indexing reaches
+ * the operand (the LDS-staged forms are used only while one sample's slice of every operand ends within 0x7ffffff0 bytes).
+ * nn.GroupNorm(32, C, eps=1e-6) -> SiLU -> Dropout(p) (unet.py:18-20,15,81,85-87,139-140; :57 without SiLU):
  *   y = drop(silu((x - mean_g) * rstd_g * gamma_c + beta_c)),  biased variance over (C/G)*HW elements.
  * stats (optional) receives [B][G][2] = (mean, rstd) for the backward.  workspace: ddpm_gn_workspace_floats().
  * Dropout keep-mask = hash(seed, linear NHWC index) (see ddpm_dropout_mask); scale 1/(1-p).  seed_dev (optional device
@@ -218,7 +243,8 @@ int ddpm_groupnorm_mod_silu_bwd(const void* x, long long x_ld, const void* dy, l
  * freqs[dim/2] = exp(-i ln(1e4)/(dim/2 - 1)) is supplied by the host in fp32. */
 int ddpm_timestep_embedding(const long long* t, const float* freqs, float* out, int B, int dim, void* stream);
 
-/* layout / packing helpers (no reference counterpart: the NHWC + packed-weight layout is this library's) */
+/* layout / packing helpers (no reference counterpart: the NHWC + packed-weight layout is this library's).
+ * ddpm_nchw_to_nhwc: y[b][p][c] = x[b][c][p] for c < C, 0 for C <= c < Cp.  No operand limit (64-bit element indices). */
 int ddpm_nchw_to_nhwc(const float* x, void* y, int B, int C, int HW, int Cp, int dtype, void* stream);
 int ddpm_pack_weight(const float* w, void* w_fwd /*[N][R][S][Cp]*/, void* w_dgrad /*[C][R][S][Np], taps flipped*/,
                      int N, int C, int R, int S, int Cp, int Np, int dtype, void* stream);
@@ -391,9 +417,10 @@ int ddpm_silu_fwd(const float* x, float* y, long long n, void* stream);
 int ddpm_silu_bwd(const float* x, const float* dy, float* dx, long long n, int accumulate, void* stream);
 
 /* bias / time-bias gradients: per_sample[b][c] += sum_pixels dy, total[c] += sum_{b,pixels} dy (fp32 atomics into
- * zero-initialised buffers); C <= 64 x 256 16-byte vectors per launch (groups of 256 on blockIdx.z) */
+ * zero-initialised buffers); C <= 64 x 256 16-byte vectors per launch (groups of 256 on blockIdx.z).  No operand limit (64-bit
+ * element offsets); B <= 65535 (blockIdx.y). */
 int ddpm_colsum(const void* dy, long long ld, float* per_sample, long long ps_ld, float* total, int B, int HW, int C, int dtype, void* stream);
-/* backward of nn.Upsample(2,"nearest"): dx[b,y,x,c] (+)= sum of the 2x2 block of dy_up */
+/* backward of nn.Upsample(2,"nearest"): dx[b,y,x,c] (+)= sum of the 2x2 block of dy_up.  No operand limit (64-bit element offsets). */
 int ddpm_upsample2x_bwd(const void* dy_up, void* dx, long long dx_ld, int B, int H, int W, int C, int accumulate, int dtype, void* stream);
 /* 2x resampling WITHOUT a convolution — UNet(resample_with_conv=False): ddpm_torch/models/unet.py:169 `nn.AvgPool2d(2)`, :196
  * `nn.Upsample(scale_factor=2, mode="nearest")` on its own — and their autograd.  NHWC with pixel pitches; H, W = the SMALL grid.
@@ -401,7 +428,8 @@ int ddpm_upsample2x_bwd(const void* dy_up, void* dx, long long dx_ld, int B, int
  *   up = 1: y[b,2h+a,2w+b,:] (+)= scale * x[b,h,w,:], a, b in {0, 1}                                       (Upsample forward: 1; AvgPool backward: 0.25) */
 int ddpm_resample2x_nhwc(const void* x, long long x_ld, void* y, long long y_ld, int B, int H, int W, int C, int up, float scale,
                          int accumulate, int dtype, void* stream);
-/* y (+)= x over [rows][C] slices with pitches (gradient fan-in of the residual / skip connections) */
+/* y (+)= x over [rows][C] slices with pitches (gradient fan-in of the residual / skip connections).  No operand limit (64-bit
+ * element offsets). */
 int ddpm_add_rows(const void* x, long long x_ld, void* y, long long y_ld, long long rows, int C, int accumulate, int dtype, void* stream);
 
 /* torch.softmax over the keys (unet.py:47-49) and its backward dS = P*(dP - sum(dP*P)); rows of length L */

@@ -113,6 +113,7 @@ class Arena:
         self.dgen = torch.Generator(device=device).manual_seed(seed)    # buffer contents, drawn where they live
         self.pgen = torch.Generator(device=device).manual_seed(seed + 7919)   # draws of a profile (masks): never the buffers' stream
         self.poison, self.profile, self.yardstick = poison, profile, yardstick
+        self.amplify, self.rows_per_image = None, None      # replay(amplify=): see amplify_images
         assert profile is None or profile in PROFILES, profile
         self.bufs = []
 
@@ -236,6 +237,7 @@ class Result:
         self.outputs = {}                   # buffer name -> the stored output elements (replay() fills it)
         self.tensors = {}                   # table-driven entries: (row, column name) -> that row's output, whatever the packing
         self.depth, self.clip = None, None  # reductions: the chain length of the bound; the update: the float64 clip coefficient
+        self.sensitivity = {}               # (output, image) -> fraction of elements the loss of that image moves by > 8 bars (amplify=)
 
     def cmp(self, what, got, ref, bar, yard=None):
         """yard (optional): the yardstick's value of the same output, put through the same bar; it never decides a replay."""
@@ -308,8 +310,17 @@ def conv_fp64(can, w, Ho, Wo, stride):
 def wgrad_fp64(can, dy, R, S, Ho, Wo, stride):
     """dw[n,r,s,c] = sum_{b,oy,ox} dy[b,oy,ox,n] * can[b, oy*stride+r, ox*stride+s, c]  ->  [N,R,S,C]."""
     N, C = dy.shape[-1], can.shape[-1]
-    g = dy.reshape(-1, N).T
+    P = dy.numel() // N
     out = can.new_zeros(N, R, S, C)
+    if P >= 1 << 18 and P % 1024 == 0:
+        # millions of pixels into one N x C tile: a single matmul keeps a few compute units busy for tens of seconds; partial sums over
+        # runs of 1024 pixels as one batched product, added up afterwards (float64 either way)
+        g = dy.reshape(-1, 1024, N).transpose(1, 2)
+        for r in range(R):
+            for s in range(S):
+                out[:, r, s] = torch.bmm(g, _tap(can, r, s, Ho, Wo, stride).reshape(-1, 1024, C)).sum(0)
+        return out
+    g = dy.reshape(-1, N).T
     for r in range(R):
         for s in range(S):
             out[:, r, s] = g @ _tap(can, r, s, Ho, Wo, stride).reshape(-1, C)
@@ -444,23 +455,58 @@ def _reduce_slabs(A, slab, n_one, copies, stride):
     return dst.t
 
 
-def _wgrad_common(A, res, dy_b, x_b, can, dy, R, S, Ho, Wo, stride, Nreal, Creal, dw, slab_stride, copies, prior, dbias=None,
-                  bias_stride=0, bprior=None):
+def amplify_images(A, view, rows_per_image, ld, es):
+    """Reductions over millions of pixels (LARGE_OPERANDS): one lost image would move the sum by a few bars only, so the rows of three
+    images of `view` ([rows][cols], pitch ld, elements of es bytes) — the first, the last and the one whose bytes straddle offset 2^30
+    of the operand — are multiplied by A.amplify (a power of two: exact in either type).  Returns the three image indices; nothing
+    happens (and () comes back) when the replay was not asked to amplify."""
+    if not A.amplify:
+        return ()
+    B = view.shape[0] // rows_per_image
+    picked = sorted({0, min(B - 1, (1 << 30) // (rows_per_image * ld * es)), B - 1})
+    for b in picked:
+        view[b * rows_per_image:(b + 1) * rows_per_image] *= A.amplify
+    return tuple(picked)
+
+
+def _sensitivity(res, what, contributions, bar):
+    """Result.sensitivity[(what, image)]: the fraction of the output elements that dropping that image alone would move by more than
+    8 bars, measured on the float64 reference (contributions: image -> its float64 share of the sum)."""
+    for b, c in contributions.items():
+        res.sensitivity[(what, b)] = float((c.abs() > 8 * bar).double().mean())
+
+
+def _wgrad_common(A, res, dy_b, x_b, pieces, R, S, Ho, Wo, stride, Nreal, Creal, dw, slab_stride, copies, prior, dbias=None,
+                  bias_stride=0, bprior=None, amplified=()):
+    """pieces: iterable of (can, dy, b0) — the float64 canvas and output gradient of the images b0 .. of one slice (image_slices):
+    the sums over all slices are the reference, so that operands of 2 GiB never need their float64 copy whole."""
     n_one = Nreal * R * S * Creal
-    full = wgrad_fp64(can, dy, R, S, Ho, Wo, stride)[:Nreal, :, :, :Creal].reshape(-1)
-    mag = full.abs()
-    sq = wgrad_fp64(can * can, dy * dy, R, S, Ho, Wo, stride)[:Nreal, :, :, :Creal].reshape(-1).sqrt()
-    K = dy.shape[0] * Ho * Wo
+    full = sq = g1 = g2 = None
+    K, share = 0, {}
+    cut = lambda t: t[:Nreal, :, :, :Creal].reshape(-1)
+    for can, dy, b0 in pieces:
+        f = cut(wgrad_fp64(can, dy, R, S, Ho, Wo, stride))
+        q = cut(wgrad_fp64(can * can, dy * dy, R, S, Ho, Wo, stride))
+        g = dy.reshape(-1, dy.shape[-1])[:, :Nreal]
+        full, sq = (f, q) if full is None else (full + f, sq + q)
+        g1, g2 = (g.sum(0), (g * g).sum(0)) if g1 is None else (g1 + g.sum(0), g2 + (g * g).sum(0))
+        K += dy.shape[0] * Ho * Wo
+        for b in amplified:
+            if b0 <= b < b0 + dy.shape[0]:
+                share[b] = cut(wgrad_fp64(can[b - b0:b - b0 + 1], dy[b - b0:b - b0 + 1], R, S, Ho, Wo, stride))
+        del can, dy, f, q, g
+    mag, sq = full.abs(), sq.sqrt()
     ua = U_ACC_MFMA_F32 if dy_b.t.dtype == torch.float32 else U_ACC
     if slab_stride == 0:
         got = dw.t[:n_one]
         full, mag = full + prior, mag + prior.abs()
     else:
         got = _reduce_slabs(A, dw, n_one, copies, slab_stride)
-    res.cmp("dw", got, full, C_GEMM * (U_F32 * mag + ua * math.sqrt(K) * sq))
+    bar = C_GEMM * (U_F32 * mag + ua * math.sqrt(K) * sq)
+    res.cmp("dw", got, full, bar)
+    _sensitivity(res, "dw", share, bar)
     if dbias is not None:
-        g = dy.reshape(-1, dy.shape[-1])[:, :Nreal]
-        ref, sq = g.sum(0), (g * g).sum(0).sqrt()
+        ref, sq = g1, g2.sqrt()
         mag = ref.abs()
         if bias_stride == 0 and slab_stride == 0:
             got = dbias.t[:Nreal]
@@ -485,6 +531,7 @@ def rep_conv3x3_wgrad(A, sig, res, up=False):
     dy = A.buf("dy", pitched(B * H * W, N, dy_ld), dt, _mod(pdy)).fill(A.randn(pitched(B * H * W, N, dy_ld)))
     x = A.buf("x", pitched(B * Hs * Ws, C, x_ld), dt, _mod(px)).fill(A.randn(pitched(B * Hs * Ws, C, x_ld)))
     A.shape("data", dy.inp(B * H * W, N, dy_ld).mat(B * H * W, N, dy_ld))
+    amplified = amplify_images(A, dy.mat(B * H * W, N, dy_ld), H * W, dy_ld, 2)
     x.inp(B * Hs * Ws, C, x_ld)
     n_one = Nreal * 9 * C
     if slab_stride:
@@ -505,10 +552,12 @@ def rep_conv3x3_wgrad(A, sig, res, up=False):
         bprior = None if db is None else _d(db.t).clone()
     _wgrad_launch(A, "ddpm_conv3x3_wgrad_up_nhwc" if up else "ddpm_conv3x3_wgrad_nhwc",
                   [dy.ptr, dy_ld, x.ptr, x_ld, dw.ptr, slab_stride, _ptr(db), bias_stride, B, H, W, C, N, Nreal, splits, dt])
-    xs = _d(x.mat(B * Hs * Ws, C, x_ld)).reshape(B, Hs, Ws, C)
-    g = _d(dy.mat(B * H * W, N, dy_ld)).reshape(B, H, W, N)
-    can = canvas(xs, H, W, 3, 3, 1, 1, 1, int(up), 0)
-    _wgrad_common(A, res, dy, x, can, g, 3, 3, H, W, 1, Nreal, C, dw, slab_stride, copies, prior, db, bias_stride, bprior)
+    def pieces():
+        for b0, b1 in image_slices(B, 5 * (H + 2) * (W + 2) * C + 4 * H * W * N):
+            xs = _d(x.mat(B * Hs * Ws, C, x_ld)[b0 * Hs * Ws:b1 * Hs * Ws]).reshape(b1 - b0, Hs, Ws, C)
+            g = _d(dy.mat(B * H * W, N, dy_ld)[b0 * H * W:b1 * H * W]).reshape(b1 - b0, H, W, N)
+            yield canvas(xs, H, W, 3, 3, 1, 1, 1, int(up), 0), g, b0
+    _wgrad_common(A, res, dy, x, pieces(), 3, 3, H, W, 1, Nreal, C, dw, slab_stride, copies, prior, db, bias_stride, bprior, amplified)
 
 
 def rep_conv3x3_wgrad_up(A, sig, res):
@@ -523,13 +572,17 @@ def rep_conv1x1_wgrad(A, sig, res):
     dy = A.buf("dy", pitched(P, N, dy_ld), dt, _mod(pdy)).fill(A.randn(pitched(P, N, dy_ld)))
     x = A.buf("x", pitched(P, C, x_ld), dt, _mod(px)).fill(A.randn(pitched(P, C, x_ld)))
     A.shape("data", dy.inp(P, N, dy_ld).mat(P, N, dy_ld))
+    rpi = A.rows_per_image or P                           # a 1x1 weight gradient has no images of its own: the table row names them
+    amplified = amplify_images(A, dy.mat(P, N, dy_ld), rpi, dy_ld, 2)
     x.inp(P, C, x_ld)
     dw = _slab_setup(A, "dw", N * C, splits, slab_stride, _mod(pdw))
     db = _slab_setup(A, "dbias", N, splits, bias_stride, _mod(pdb)) if _opt(pdb) else None
     _wgrad_launch(A, "ddpm_conv1x1_wgrad_nhwc", [dy.ptr, dy_ld, x.ptr, x_ld, dw.ptr, slab_stride, _ptr(db), bias_stride, P, C, N, splits, dt])
-    g = _d(dy.mat(P, N, dy_ld)).reshape(1, P, 1, N)
-    can = _d(x.mat(P, C, x_ld)).reshape(1, P, 1, C)
-    _wgrad_common(A, res, dy, x, can, g, 1, 1, P, 1, 1, N, C, dw, slab_stride, splits, None, db, bias_stride, None)
+    def pieces():
+        for b0, b1 in image_slices(P // rpi, 3 * rpi * (C + N)):
+            yield (_d(x.mat(P, C, x_ld)[b0 * rpi:b1 * rpi]).reshape(b1 - b0, rpi, 1, C),
+                   _d(dy.mat(P, N, dy_ld)[b0 * rpi:b1 * rpi]).reshape(b1 - b0, rpi, 1, N), b0)
+    _wgrad_common(A, res, dy, x, pieces(), 1, 1, rpi, 1, 1, N, C, dw, slab_stride, splits, None, db, bias_stride, None, amplified)
 
 
 def rep_conv2d_wgrad(A, sig, res):
@@ -537,6 +590,7 @@ def rep_conv2d_wgrad(A, sig, res):
     dy = A.buf("dy", pitched(B * Ho * Wo, N, dy_ld), dt, _mod(pdy)).fill(A.randn(pitched(B * Ho * Wo, N, dy_ld)))
     x = A.buf("x", pitched(B * H * W, C, x_ld), dt, _mod(px)).fill(A.randn(pitched(B * H * W, C, x_ld)))
     A.shape("data", dy.inp(B * Ho * Wo, N, dy_ld).mat(B * Ho * Wo, N, dy_ld))
+    amplified = amplify_images(A, dy.mat(B * Ho * Wo, N, dy_ld), Ho * Wo, dy_ld, 2 if dt == BF16 else 4)
     x.inp(B * H * W, C, x_ld)
     n_one = Nreal * R * S * Creal
     if slab_stride:
@@ -552,10 +606,13 @@ def rep_conv2d_wgrad(A, sig, res):
         prior = _d(dw.t).clone()
     _wgrad_launch(A, "ddpm_conv2d_wgrad_nhwc", [dy.ptr, dy_ld, x.ptr, x_ld, dw.ptr, slab_stride, B, H, W, C, Creal, Ho, Wo, N, Nreal,
                                                R, S, stride, pad_t, pad_l, ups, splits, dt])
-    xs = _d(x.mat(B * H * W, C, x_ld)).reshape(B, H, W, C)
-    g = _d(dy.mat(B * Ho * Wo, N, dy_ld)).reshape(B, Ho, Wo, N)
-    can = canvas(xs, Ho, Wo, R, S, stride, pad_t, pad_l, ups, 0)
-    _wgrad_common(A, res, dy, x, can, g, R, S, Ho, Wo, stride, Nreal, Creal, dw, slab_stride, copies, prior)
+    def pieces():
+        nh, nw = (Ho - 1) * stride + R, (Wo - 1) * stride + S
+        for b0, b1 in image_slices(B, 5 * nh * nw * C + 4 * Ho * Wo * N):
+            xs = _d(x.mat(B * H * W, C, x_ld)[b0 * H * W:b1 * H * W]).reshape(b1 - b0, H, W, C)
+            g = _d(dy.mat(B * Ho * Wo, N, dy_ld)[b0 * Ho * Wo:b1 * Ho * Wo]).reshape(b1 - b0, Ho, Wo, N)
+            yield canvas(xs, Ho, Wo, R, S, stride, pad_t, pad_l, ups, 0), g, b0
+    _wgrad_common(A, res, dy, x, pieces(), R, S, Ho, Wo, stride, Nreal, Creal, dw, slab_stride, copies, prior, amplified=amplified)
 
 
 def rep_wgrad_reduce(A, sig, res):
@@ -912,22 +969,40 @@ def _logit_err(q, k, scale):
     return U_ACC * math.sqrt(C) * ((q * q) @ (k * k).transpose(1, 2)).sqrt() * scale
 
 
-def rep_attn_fwd(A, sig, res, lse_entry=False):
+def _heads(t, heads):
+    """[B, L, heads * d] -> [B * heads, L, d]: head h of a packed third is its channels [h d, (h + 1) d) (include/ddpm_hip.h)."""
+    B, L, C = t.shape
+    return t if heads == 1 else t.reshape(B, L, heads, C // heads).permute(0, 2, 1, 3).reshape(B * heads, L, C // heads)
+
+
+def _unheads(t, B, heads):
+    """inverse of _heads"""
+    _, L, d = t.shape
+    return t if heads == 1 else t.reshape(B, heads, L, d).permute(0, 2, 1, 3).reshape(B, L, heads * d)
+
+
+def rep_attn_fwd(A, sig, res, lse_entry=False, mh=False):
     """out = softmax(q k^T * scale) v, lse = log sum exp.  Model (csrc/attention.hip rounds P to bf16 in front of the PV product):
     M_ic = |out_ic| + sum_j P_ij |v_jc| (the bf16 store, and the rounding of P: 2^-8 sum_j P_ij |v_jc|), plus the logit error e_ij
     carried through exp: 2 max_j e_ij * sum_j P_ij |v_jc|, and the fp32 PV sum u_acc sqrt(L) S.  lse: u_acc (|lse| + log L) + max_j e_ij."""
-    if lse_entry:
+    heads = 1
+    if mh:                              # ddpm_attention_mh_fwd: the same product per head of width C / heads, lse [B][heads][L]
+        pq, ld, po, o_ld, plse, B, L, C, heads, scale, dt = sig
+    elif lse_entry:
         pq, ld, po, o_ld, plse, B, L, C, scale, dt = sig
     else:
         pq, ld, po, o_ld, B, L, C, scale, dt = sig
         plse = ("p", True, 0)
     qkv, q, k, v = _qkv(A, pq, ld, B, L, C, dt)
+    q, k, v = (_heads(t, heads) for t in (q, k, v))
     o = A.buf("out", pitched(B * L, C, o_ld), dt, _mod(po)).fill(A.randn(pitched(B * L, C, o_ld)))
-    lse = A.buf("lse", B * L, F32, _mod(plse)) if _opt(plse) else None
+    lse = A.buf("lse", B * heads * L, F32, _mod(plse)) if _opt(plse) else None
     if lse is not None:
         lse.all_out()
     A.snapshot()
-    if lse_entry:
+    if mh:
+        _launch("ddpm_attention_mh_fwd", [qkv.ptr, ld, o.ptr, o_ld, _ptr(lse), B, L, C, heads, scale, dt])
+    elif lse_entry:
         _launch("ddpm_attention_fwd_lse", [qkv.ptr, ld, o.ptr, o_ld, _ptr(lse), B, L, C, scale, dt])
     else:
         _launch("ddpm_attention_fwd", [qkv.ptr, ld, o.ptr, o_ld, B, L, C, scale, dt])
@@ -946,40 +1021,58 @@ def rep_attn_fwd(A, sig, res, lse_entry=False):
     if A.yardstick:                                       # matmul -> softmax -> matmul in fp32
         s32 = q.float() @ k.float().transpose(1, 2) * scale
         yard, ylse = (torch.softmax(s32, -1) @ v.float()).to(_TD[dt]), torch.logsumexp(s32, -1)
-    res.cmp("out", got.reshape(B, L, C), ref, bar, yard)
+    res.cmp("out", _heads(got.reshape(B, L, C), heads), ref, bar, yard)
     if lse is not None:
-        res.cmp("lse", lse.t.reshape(B, L), ls, C_ATTN * (U_ACC * (ls.abs() + math.log(L)) + e[..., 0]), ylse)
+        res.cmp("lse", lse.t.reshape(B * heads, L), ls, C_ATTN * (U_ACC * (ls.abs() + math.log(L)) + e[..., 0]), ylse)
 
 
 def rep_attn_fwd_lse(A, sig, res):
     rep_attn_fwd(A, sig, res, lse_entry=True)
 
 
-def rep_attn_bwd(A, sig, res):
+def rep_attn_mh_fwd(A, sig, res):
+    rep_attn_fwd(A, sig, res, mh=True)
+
+
+def rep_attn_mh_bwd(A, sig, res):
+    rep_attn_bwd(A, sig, res, mh=True)
+
+
+def rep_attn_bwd(A, sig, res, mh=False):
     """dV = P^T dO, dS = P o (dO V^T - D), D_i = dO_i . O_i, dQ = dS K scale, dK = dS^T Q scale, with P from q, k and the given lse and
     O the given (bf16) forward output.  Model: the bf16 store (2^-8 |ref|); P rounded to bf16 before dV (2^-8 sum_i P_ij |dO_ic|); dS
     rounded to bf16 before dQ / dK — independent roundings of the L terms, so 2^-8 sqrt(sum_j (dS_ij k_jc)^2); the fp32 error of
     dP - D (u_acc sqrt(C) (root of the squared dO V^T terms) + u_acc |D|) and of the logits carried through P and dS; the fp32 sums
     u_acc sqrt(L) S.  D: GEMM-shaped over C."""
-    pq, ld, po, o_ld, pdo, do_ld, plse, pdv, pdq, dq_ld, B, L, C, scale, dt = sig
+    heads = 1
+    if mh:                              # ddpm_attention_mh_bwd: per head of width C / heads; lse, dvec [B][heads][L]
+        pq, ld, po, o_ld, pdo, do_ld, plse, pdv, pdq, dq_ld, B, L, C, heads, scale, dt = sig
+    else:
+        pq, ld, po, o_ld, pdo, do_ld, plse, pdv, pdq, dq_ld, B, L, C, scale, dt = sig
     qkv, q, k, v = _qkv(A, pq, ld, B, L, C, dt)
+    q, k, v = (_heads(t, heads) for t in (q, k, v))
+    BH, Cf, C = B * heads, C, C // heads           # from here on C is the head's width, Cf a third of the packed row
     s = q @ k.transpose(1, 2) * scale
     ls = torch.logsumexp(s, -1)
-    o = A.buf("o", pitched(B * L, C, o_ld), dt, _mod(po)).fill(A.randn(pitched(B * L, C, o_ld)))
-    o.inp(B * L, C, o_ld).mat(B * L, C, o_ld).copy_((torch.exp(s - ls[..., None]) @ v).reshape(B * L, C))
-    d_o = A.buf("d_o", pitched(B * L, C, do_ld), dt, _mod(pdo)).fill(A.randn(pitched(B * L, C, do_ld)))
-    A.shape("attn_do", d_o.inp(B * L, C, do_ld).mat(B * L, C, do_ld))
-    lse = A.buf("lse", B * L, F32, _mod(plse)).fill(ls).all_in()
-    dvec = A.buf("dvec", B * L, F32, _mod(pdv)).fill(torch.full((B * L,), float("nan")))
+    o = A.buf("o", pitched(B * L, Cf, o_ld), dt, _mod(po)).fill(A.randn(pitched(B * L, Cf, o_ld)))
+    o.inp(B * L, Cf, o_ld).mat(B * L, Cf, o_ld).copy_(_unheads(torch.exp(s - ls[..., None]) @ v, B, heads).reshape(B * L, Cf))
+    d_o = A.buf("d_o", pitched(B * L, Cf, do_ld), dt, _mod(pdo)).fill(A.randn(pitched(B * L, Cf, do_ld)))
+    A.shape("attn_do", d_o.inp(B * L, Cf, do_ld).mat(B * L, Cf, do_ld))
+    lse = A.buf("lse", BH * L, F32, _mod(plse)).fill(ls).all_in()
+    dvec = A.buf("dvec", BH * L, F32, _mod(pdv)).fill(torch.full((BH * L,), float("nan")))
     dvec.all_out()
-    dq = A.buf("dqkv", pitched(B * L, 3 * C, dq_ld), dt, _mod(pdq)).fill(A.randn(pitched(B * L, 3 * C, dq_ld)))
+    dq = A.buf("dqkv", pitched(B * L, 3 * Cf, dq_ld), dt, _mod(pdq)).fill(A.randn(pitched(B * L, 3 * Cf, dq_ld)))
     A.snapshot()
-    _launch("ddpm_attention_bwd", [qkv.ptr, ld, o.ptr, o_ld, d_o.ptr, do_ld, lse.ptr, dvec.ptr, dq.ptr, dq_ld, B, L, C, scale, dt])
+    if mh:
+        _launch("ddpm_attention_mh_bwd", [qkv.ptr, ld, o.ptr, o_ld, d_o.ptr, do_ld, lse.ptr, dvec.ptr, dq.ptr, dq_ld, B, L, Cf, heads, scale, dt])
+    else:
+        _launch("ddpm_attention_bwd", [qkv.ptr, ld, o.ptr, o_ld, d_o.ptr, do_ld, lse.ptr, dvec.ptr, dq.ptr, dq_ld, B, L, Cf, scale, dt])
     sync()
-    got = _d(dq.out(B * L, 3 * C, dq_ld)).reshape(B, L, 3 * C)
+    got = _d(dq.out(B * L, 3 * Cf, dq_ld)).reshape(B, L, 3 * Cf)
     A.check()
-    O = _d(o.mat(B * L, C, o_ld)).reshape(B, L, C)
-    dO = _d(d_o.mat(B * L, C, do_ld)).reshape(B, L, C)
+    O = _heads(_d(o.mat(B * L, Cf, o_ld)).reshape(B, L, Cf), heads)
+    dO = _heads(_d(d_o.mat(B * L, Cf, do_ld)).reshape(B, L, Cf), heads)
+    B = BH                                          # one problem per (image, head)
     P = torch.exp(s - _d(lse.t).reshape(B, L, 1))
     D = (dO * O).sum(-1)
     dP = dO @ v.transpose(1, 2)
@@ -991,8 +1084,8 @@ def rep_attn_bwd(A, sig, res):
     res.cmp("dvec", dvec.t.reshape(B, L), D, C_ATTN * (U_F32 * (dO * O).abs().sum(-1) + U_ACC * math.sqrt(C) * ((dO * O) ** 2).sum(-1).sqrt()))
     outs = (
         ("dq", dS @ k * scale, (dS * dS) @ (k * k), dS_err @ k.abs() * scale, 0),
-        ("dk", kT(dS) @ q * scale, kT(dS * dS) @ (q * q), kT(dS_err) @ q.abs() * scale, C),
-        ("dv", kT(P) @ dO, kT(P * P) @ (dO * dO), kT(e_s * P) @ dO.abs(), 2 * C),
+        ("dk", kT(dS) @ q * scale, kT(dS * dS) @ (q * q), kT(dS_err) @ q.abs() * scale, Cf),
+        ("dv", kT(P) @ dO, kT(P * P) @ (dO * dO), kT(e_s * P) @ dO.abs(), 2 * Cf),
     )
     yard = {}
     if A.yardstick:                                       # the same products on the given o and lse, every step in fp32, stores in bf16
@@ -1004,7 +1097,7 @@ def rep_attn_bwd(A, sig, res):
         sq = sq.sqrt() * (scale if nm != "dv" else 1.0)
         rounding = (U_BF16 * (kT(P) @ dO.abs())) if nm == "dv" else U_BF16 * sq
         bar = C_ATTN * (U_BF16 * ref.abs() + rounding + prop + U_ACC * math.sqrt(L) * sq)
-        res.cmp(nm, got[..., c0:c0 + C], ref, bar, yard.get(nm))
+        res.cmp(nm, _heads(got[..., c0:c0 + Cf], heads), ref, bar, yard.get(nm))
 
 
 # elementwise, reductions and diffusion -----------------------------------------------------------------------------------------------
@@ -1014,6 +1107,7 @@ def rep_colsum(A, sig, res):
     ps = A.buf("per_sample", pitched(B, C, ps_ld), F32, _mod(pps)).fill(A.randn(pitched(B, C, ps_ld))) if _opt(pps) else None
     tot = A.buf("total", C, F32, _mod(ptot)).fill(A.randn(C)) if _opt(ptot) else None
     A.shape("data", dy.inp(B * HW, C, ld).mat(B * HW, C, ld))
+    amplified = amplify_images(A, dy.mat(B * HW, C, ld), HW, ld, 2 if dt == BF16 else 4)
     if ps is not None:
         A.shape("additive", ps.inp(B, C, ps_ld).mat(B, C, ps_ld))
         ps.atomic = True
@@ -1036,8 +1130,9 @@ def rep_colsum(A, sig, res):
                 C_GEMM * (U_F32 * (g.sum(1).abs() + p_ps.abs()) + U_ACC * math.sqrt(HW) * (g * g).sum(1).sqrt()))
     if tot is not None:
         gg = g.reshape(-1, C)
-        res.cmp("total", tot.t, gg.sum(0) + p_tot,
-                C_GEMM * (U_F32 * (gg.sum(0).abs() + p_tot.abs()) + U_ACC * math.sqrt(B * HW) * (gg * gg).sum(0).sqrt()))
+        bar = C_GEMM * (U_F32 * (gg.sum(0).abs() + p_tot.abs()) + U_ACC * math.sqrt(B * HW) * (gg * gg).sum(0).sqrt())
+        res.cmp("total", tot.t, gg.sum(0) + p_tot, bar)
+        _sensitivity(res, "total", {b: g[b].sum(0) for b in amplified}, bar)
 
 
 def rep_upsample2x_bwd(A, sig, res):
@@ -1309,6 +1404,25 @@ def rep_add_rows(A, sig, res):
         res.cmp("y", got, X + prior, C_GEMM * u * (X.abs() + prior.abs()))
     else:
         res.cmp("y", got, X, torch.zeros_like(X))
+
+
+def rep_nchw_to_nhwc(A, sig, res):
+    """y[b][p][c] = x[b][c][p] for c < C, zero for C <= c < Cp (x fp32 NCHW, y the compute type, NHWC with Cp channels).  A copy: exact
+    in fp32 (bar 0); a bf16 store rounds once, u_out |x|; a pad channel must be exactly zero."""
+    px, py, B, C, HW, Cp, dt = sig
+    x = A.buf("x", B * C * HW, F32, _mod(px)).fill(A.randn(B * C * HW)).all_in()
+    y = A.buf("y", B * HW * Cp, dt, _mod(py)).fill(A.randn(B * HW * Cp))
+    A.shape("data", x.t)
+    y.all_out()
+    A.snapshot()
+    _launch("ddpm_nchw_to_nhwc", [x.ptr, y.ptr, B, C, HW, Cp, dt])
+    sync()
+    A.check()
+    u = U_BF16 if dt == BF16 else 0.0
+    for b0, b1 in image_slices(B, 6 * HW * Cp):
+        ref = torch.zeros(b1 - b0, HW, Cp, dtype=torch.float64, device=A.device)
+        ref[..., :C] = _d(x.t[b0 * C * HW:b1 * C * HW]).reshape(b1 - b0, C, HW).transpose(1, 2)
+        res.cmp("y", y.t[b0 * HW * Cp:b1 * HW * Cp].reshape(b1 - b0, HW, Cp), ref, u * ref.abs())
 
 
 def rep_timestep_embedding(A, sig, res):
@@ -2040,6 +2154,8 @@ REPLAY = {
     "ddpm_attention_fwd": rep_attn_fwd,
     "ddpm_attention_fwd_lse": rep_attn_fwd_lse,
     "ddpm_attention_bwd": rep_attn_bwd,
+    "ddpm_attention_mh_fwd": rep_attn_mh_fwd,
+    "ddpm_attention_mh_bwd": rep_attn_mh_bwd,
     "ddpm_colsum": rep_colsum,
     "ddpm_upsample2x_bwd": rep_upsample2x_bwd,
     "ddpm_q_sample": rep_q_sample,
@@ -2051,6 +2167,7 @@ REPLAY = {
     "ddpm_silu_fwd": rep_silu_fwd,
     "ddpm_silu_bwd": rep_silu_bwd,
     "ddpm_add_rows": rep_add_rows,
+    "ddpm_nchw_to_nhwc": rep_nchw_to_nhwc,
     "ddpm_timestep_embedding": rep_timestep_embedding,
     "ddpm_gather_rows_f32": rep_gather_rows,
     "ddpm_weighted_sum_f32": rep_weighted_sum,
@@ -2094,11 +2211,12 @@ SYNTHETIC = [
 # pitched as tests/test_kernels_gpu.py pitches them (x_ld = C + 16, y_ld = N + 32, row bias N + 8), every pointer 16-byte aligned.
 # Each row is (signature, kernel id variant_of must name, or None for the entries without a dispatch query).
 def _conv_sig(B, H, W, C, N, Ho=None, Wo=None, R=3, S=3, stride=1, pad=(1, 1), ups=0, dil=0, bias=0, rowbias=0, res=0, acc=0, mode=0,
-              splits=1, dt=BF16, x_ld=None):
+              splits=1, dt=BF16, x_ld=None, y_ld=None):
     Ho, Wo = (H << ups if Ho is None else Ho), (W << ups if Wo is None else Wo)
     ws = splits > 1
-    return ("ddpm_conv2d_nhwc", (_p(), C + 16 if x_ld is None else x_ld, _p(), _p(), N + 32, _p(null=not bias), _p(null=not rowbias),
-                                 N + 8 if rowbias else 0, _p(null=not res), N + 32 if res else 0, B, H, W, C, Ho, Wo, N, R, S, stride,
+    y_ld = N + 32 if y_ld is None else y_ld
+    return ("ddpm_conv2d_nhwc", (_p(), C + 16 if x_ld is None else x_ld, _p(), _p(), y_ld, _p(null=not bias), _p(null=not rowbias),
+                                 N + 8 if rowbias else 0, _p(null=not res), y_ld if res else 0, B, H, W, C, Ho, Wo, N, R, S, stride,
                                  pad[0], pad[1], ups, dil, acc, mode, splits, _p(null=not ws), _p(null=not ws), dt))
 
 
@@ -2292,6 +2410,216 @@ EDGE_CHANNELS = [
     (("ddpm_colsum", (_p(), 16, _p(null=True), 0, _p(), 64, 256, 16, BF16)), None),
     (("ddpm_colsum", (_p(), 4, _p(null=True), 0, _p(), 16, 1024, 4, F32)), None),
     (("ddpm_colsum", (_p(), 12, _p(null=True), 0, _p(), 64, 256, 12, F32)), None),
+]
+
+
+# ----------------------------------------------------------------------------------------------------------------- the 2 GiB operand limit
+# Every GEMM-shaped kernel addresses its operands through buffer descriptors with 32-bit byte offsets; its launcher refuses an operand
+# whose extent exceeds BUF_OOB bytes (csrc/gfx950.h).  LARGE_OPERANDS holds, for every entry behind such a guard, signatures whose largest
+# guarded operand has an extent E in the window  BUF_OOB - unit < E <= BUF_OOB  (unit: the bytes of one image of that operand for the
+# image-shaped entries, of one row for the others), E computed as the launcher computes it (guarded_extents), and next to each the
+# NEIGHBOUR one image (dense rows) or one pitch step (stretched rows) larger, which the launcher must refuse with DDPM_ERR_SHAPE.
+#   dense      natural pitch, B chosen to land in the window, the fewest channels at which the dispatch still names the kernel: the tile
+#              counts, grid sizes and FastDiv inputs of the largest pixel count;
+#   stretched  few pixels, the guarded operand's pitch raised until (rows - 1) * ld + cols lands in the window: the same byte offsets
+#              with almost no arithmetic.  Only operands a kernel reads through a buffer descriptor are stretched (a descriptor
+#              range-checks every load); every output keeps its natural pitch.
+# Row: (signature, kernel id variant_of must name or None, neighbour signature, what the neighbour must be: "refused", or the kernel id
+# that admits it, amplification (power of two, rows of one image) for the reductions or None).
+BUF_OOB = 0x7FFFFFF0
+ERR_SHAPE = 1                       # DDPM_ERR_SHAPE
+
+
+def stretch_ld(rows, cols, es=2):
+    """largest pitch (in whole 16-byte vectors) at which a [rows][cols] operand of es-byte elements still ends within BUF_OOB"""
+    vec = 16 // es
+    return (BUF_OOB // es - cols) // (rows - 1) // vec * vec
+
+
+def guarded_extents(sig):
+    """{operand: (extent in bytes as the launcher of that entry computes it, bytes of one window unit)} of the operands the entry's
+    BUF_OOB guard covers."""
+    name, w = sig
+    conv = lambda pix, hw, ld, C, es: ((pix * ld - (ld - C)) * es, hw * ld * es)
+    rows = lambda n, cols, ld, es: (pitched(n, cols, ld) * es, ld * es)
+    if name == "ddpm_conv2d_nhwc":
+        x_ld, B, H, W, C, N, R, S, dt = w[1], w[10], w[11], w[12], w[13], w[16], w[17], w[18], w[29]
+        es = 2 if dt == BF16 else 4
+        return {"x": conv(B * H * W, H * W, x_ld, C, es), "w": rows(N, R * S * C, R * S * C, es)}
+    if name in ("ddpm_conv3x3_wgrad_nhwc", "ddpm_conv3x3_wgrad_up_nhwc"):
+        dy_ld, x_ld, (B, H, W, C, N) = w[1], w[3], w[8:13]
+        Hs, Ws = (H // 2, W // 2) if name.endswith("_up_nhwc") else (H, W)
+        return {"dy": conv(B * H * W, H * W, dy_ld, N, 2), "x": conv(B * Hs * Ws, Hs * Ws, x_ld, C, 2)}
+    if name == "ddpm_conv1x1_wgrad_nhwc":
+        dy_ld, x_ld, P, C, N = w[1], w[3], w[8], w[9], w[10]
+        return {"dy": rows(P, N, dy_ld, 2), "x": rows(P, C, x_ld, 2)}
+    if name == "ddpm_conv2d_wgrad_nhwc":
+        dy_ld, x_ld, B, H, W, C, Ho, Wo, N, dt = w[1], w[3], w[6], w[7], w[8], w[9], w[11], w[12], w[13], w[22]
+        es = 2 if dt == BF16 else 4
+        return {"dy": rows(B * Ho * Wo, N, dy_ld, es), "x": conv(B * H * W, H * W, x_ld, C, es)}
+    if name == "ddpm_gemm":
+        a_ld, a_tr, b_ld, b_tr, M, N, K, dt = w[1], w[3], w[5], w[7], w[15], w[16], w[17], w[23]
+        es = 2 if dt == BF16 else 4
+        return {"a": rows(*((K, M) if a_tr else (M, K)), a_ld, es), "b": rows(*((K, N) if b_tr else (N, K)), b_ld, es)}
+    if name in ("ddpm_attention_fwd_lse", "ddpm_attention_mh_fwd"):
+        return {"qkv": (w[6] * w[1] * 2, w[1] * 2)}                                                # L * ld * 2 per sample
+    if name == "ddpm_attention_fwd":                  # finish_desc on q, k, v of one sample: [L][C] of pitch ld each
+        return {"qkv": rows(w[5], w[6], w[1], 2)}
+    if name == "ddpm_attention_bwd":                  # d_o goes through a descriptor as q, k, v do; o and dqkv through 64-bit pointers
+        L = w[11]
+        return {"qkv": (L * w[1] * 2, w[1] * 2), "d_o": (L * w[5] * 2, w[5] * 2)}
+    if name == "ddpm_attention_mh_bwd":
+        L = w[11]
+        return {"qkv": (L * w[1] * 2, w[1] * 2), "o": (L * w[3] * 2, w[3] * 2), "d_o": (L * w[5] * 2, w[5] * 2)}
+    raise KeyError(name)
+
+
+def largest_extent(sig, rows_per_image=None):
+    """(operand, extent bytes, unit bytes) of the largest guarded operand.  rows_per_image: the pixel rows a dense row of the table
+    calls one image of ddpm_conv1x1_wgrad_nhwc, which takes a pixel count and knows no images."""
+    k, (e, u) = max(guarded_extents(sig).items(), key=lambda kv: kv[1][0])
+    return k, e, u * (rows_per_image if rows_per_image and sig[0] == "ddpm_conv1x1_wgrad_nhwc" else 1)
+
+
+def refusal_status(sig):
+    """Status of the LAUNCHING entry on made-up pointers.  Only for a signature guarded_extents puts beyond BUF_OOB: the launcher
+    returns before any launch (tests/test_abi_surface.py relies on the same); an admitted size must never get here."""
+    assert largest_extent(sig)[1] > BUF_OOB, f"{short(sig)} is within the limit: it would launch on made-up pointers"
+    name, words = sig
+    args = [(0 if w[1] else 0x10000 + w[2]) if isinstance(w, tuple) else w for w in words]
+    if name == "ddpm_conv1x1_wgrad_nhwc" and args[11] <= 0:      # the slab count the library plans: a mismatch is refused on its own
+        args[11] = int(_hip.lib().ddpm_conv1x1_wgrad_splits(args[8], args[9], args[10]))
+        assert args[11] > 0
+    return int(getattr(_hip.lib(), name)(*args, 0))
+
+
+def _wider(sig, index, step=8):
+    """the signature with the pitch word at `index` one vector wider"""
+    name, w = sig
+    return (name, w[:index] + (w[index] + step,) + w[index + 1:])
+
+
+def _wg3_dense(B, H, W, C, N, up=False):
+    return ("ddpm_conv3x3_wgrad_up_nhwc" if up else "ddpm_conv3x3_wgrad_nhwc",
+            (_p(), N, _p(), C, _p(), N * 9 * C, _p(), N, B, H, W, C, N, N, 0, BF16))
+
+
+def _wg1_sig(P, C, N, dy_ld=None, x_ld=None):
+    return ("ddpm_conv1x1_wgrad_nhwc", (_p(), dy_ld or N, _p(), x_ld or C, _p(), N * C + 64, _p(), N + 4, P, C, N, 0, BF16))
+
+
+def _with(sig, **kw):
+    """a hand-written signature with words replaced by position: _with(sig, i3=ld) sets word 3"""
+    name, w = sig
+    w = list(w)
+    for k, v in kw.items():
+        w[int(k[1:])] = v
+    return (name, tuple(w))
+
+
+def _mh_sigs(B, L, C, heads, ld=None, o_ld=None, do_ld=None):
+    scale = float(C // heads) ** -0.5
+    ld = 3 * C + 16 if ld is None else ld
+    return (("ddpm_attention_mh_fwd", (_p(), ld, _p(), C + 8, _p(), B, L, C, heads, scale, BF16)),
+            ("ddpm_attention_mh_bwd", (_p(), ld, _p(), o_ld or C + 8, _p(), do_ld or C + 8, _p(), _p(), _p(), 3 * C + 24, B, L, C, heads, scale, BF16)))
+
+
+def _large_rows():
+    rows = []
+
+    def dense(sig_of, B, variant, amp=None):
+        rows.append((sig_of(B), variant, sig_of(B + 1), "refused", amp))
+
+    def stretched(sig, index, variant, amp=None, neighbour="refused", step=8):
+        rows.append((sig, variant, _wider(sig, index, step), neighbour, amp))
+
+    S = stretch_ld
+    # ---- ddpm_conv2d_nhwc.  Dense: 32 x 32 images of 64 channels, B = 16383 (16.8 M pixels, 65 532 tiles).
+    dense(lambda B: _conv_sig(B, 32, 32, 64, 64, bias=1, x_ld=64, y_ld=64), 16383, 13)                                  # conv3x3_pc
+    dense(lambda B: _conv_sig(B, 32, 32, 64, 64, R=1, S=1, pad=(0, 0), bias=1, res=1, x_ld=64, y_ld=64), 16383, 7)      # pw_conv
+    stretched(_conv_sig(16, 32, 32, 64, 64, bias=1, rowbias=1, res=1, x_ld=S(16384, 64)), 1, 8)                         # conv3x3_stream<16>
+    stretched(_conv_sig(16, 32, 32, 64, 64, acc=1, x_ld=S(16384, 64)), 1, 8)                                            # ... "+="
+    stretched(_conv_sig(64, 8, 8, 64, 64, bias=1, rowbias=1, x_ld=S(4096, 64)), 1, 10)                                  # conv3x3_stream<8>
+    stretched(_conv_sig(16, 32, 32, 64, 64, bias=1, x_ld=S(16384, 64)), 1, 13)                                          # conv3x3_pc
+    stretched(_conv_sig(16, 32, 32, 64, 96, bias=1, res=1, x_ld=S(16384, 64)), 1, 5)                                    # conv3x3_halo
+    stretched(_conv_sig(3, 12, 20, 64, 96, bias=1, rowbias=1, res=1, acc=1, x_ld=S(720, 64)), 1, 4)                     # gemm64
+    stretched(_conv_sig(16, 32, 32, 64, 3, bias=1, mode=3, x_ld=S(16384, 64)), 1, 11)                                   # edge conv, few outputs
+    # edge conv, few inputs: csrc/edgeconv.hip conv3x3_few_in_kernel reads x through 64-bit pointers and its launcher has no extent
+    # guard, so the neighbour is ADMITTED (and names the same kernel): no operand limit applies to this form
+    stretched(_conv_sig(16, 32, 32, 8, 64, bias=1, x_ld=S(16384, 8)), 1, 12, neighbour=12)
+    stretched(_conv_sig(2, 8, 12, 64, 64, Ho=4, Wo=6, stride=2, pad=(0, 0), bias=1, x_ld=S(192, 64)), 1, 4)             # stride 2 (Downsample)
+    stretched(_conv_sig(22, 8, 24, 64, 64, ups=1, bias=1, x_ld=S(22 * 192, 64)), 1, 13)                                 # Upsample: x stored at 8 x 24
+    stretched(_conv_sig(4, 4, 8, 64, 64, Ho=8, Wo=16, pad=(2, 2), dil=1, acc=1, x_ld=S(128, 64)), 1, 3)                 # parity-phase data gradient
+    stretched(_conv_sig(3, 6, 10, 32, 64, bias=1, dt=F32, x_ld=S(180, 32, 4)), 1, 4, step=4)                            # fp32
+    stretched(_conv_sig(64, 16, 16, 64, 12, bias=1, mode=3, dt=F32, x_ld=S(16384, 64, 4)), 1, 3, step=4)                # fp32, tile GEMM
+    # ---- weight gradients: dy amplified by 16 on three images (amplify_images)
+    dense(lambda B: _wg3_dense(B, 32, 32, 64, 64), 16383, 14, amp=(16, 1024))                                            # wgrad3x3_ws, slabs
+    stretched(_with(_wg3_sig(4, 16, 48, 64, 64), i1=S(4 * 768, 64)), 1, 14, amp=(16, 768))                              # ... atomics, dy stretched
+    stretched(_with(_wg3_edge_sig(16, 32, 32, 64, 8, 1), i3=S(16384, 64)), 3, 6, amp=(16, 1024))                        # wgrad3x3, x stretched
+    stretched(_with(_wg3_sig(3, 48, 16, 64, 128, up=True, slab=True), i1=S(3 * 768, 128)), 1, 14, amp=(16, 768))        # _up_, dy stretched
+    stretched(_with(_wg3_sig(3, 48, 16, 64, 128, up=True), i3=S(3 * 192, 64)), 3, 14, amp=(16, 768))                    # _up_, x (24 x 8) stretched
+    dense(lambda B: _wg1_sig(B * 1024, 64, 64), 16383, 9, amp=(16, 1024))                                                # wgrad1x1
+    stretched(_wg1_sig(4224, 64, 64, dy_ld=S(4224, 64)), 1, 9, amp=(16, 192))
+    stretched(_wg1_sig(4224, 64, 64, x_ld=S(4224, 64)), 3, 9, amp=(16, 192))
+    stretched(_with(_wg_sig(3, 12, 20, 64, 64, splits=4), i3=S(720, 64)), 3, 2, amp=(16, 240))                          # generic, x (gathered)
+    stretched(_with(_wg_sig(3, 12, 20, 64, 64, splits=4, slab=True), i1=S(720, 64)), 1, 2, amp=(16, 240))               # generic, dy
+    # ---- ddpm_gemm: the limit is per batch; batch = 2 puts the second batch's base beyond 2^31 bytes
+    g = _gemm_sig(304, 136, 200, 2, bias=1, res=1)
+    a_ld, b_ld = S(304, 200), S(136, 200)
+    stretched(_with(g, i1=a_ld, i2=304 * a_ld), 1, 4)
+    stretched(_with(g, i5=b_ld, i6=136 * b_ld), 5, 4)
+    gt = _gemm_sig(304, 136, 200, 2, a_tr=1, mode=1)
+    stretched(_with(gt, i1=S(200, 304), i2=200 * S(200, 304)), 1, 2)
+    # ---- attention: B = 2, the per-sample extent L * ld * 2 in the window, the second sample's base beyond 2^31 bytes
+    for sg in _attn_sigs(2, 256, 64) + _attn_sigs(2, 144, 128):
+        L = sg[0][1][6 if sg[0][0] == "ddpm_attention_fwd_lse" else 11]
+        stretched(_with(sg[0], i1=BUF_OOB // 2 // L // 8 * 8), 1, None)
+    for sg in (_attn_sigs(2, 256, 64)[1], _attn_sigs(2, 144, 128)[1]):                                                     # the flash backward's d_o
+        stretched(_with(sg[0], i5=BUF_OOB // 2 // sg[0][1][11] // 8 * 8), 5, None)
+    # ddpm_attention_stream_fwd / _bwd are the heads = 1 case of the mh entries (the same launcher and kernels, csrc/attention_stream.hip
+    # stream_fwd / stream_bwd): the last two mh rows below run exactly that case.
+    stretched(("ddpm_attention_fwd", (_p(), stretch_ld(128, 128), _p(), 128 + 8, 2, 128, 128, 128.0 ** -0.5, BF16)), 1, None)   # inference kernel
+    ld = BUF_OOB // 2 // 200 // 8 * 8
+    f, b = _mh_sigs(2, 200, 128, 2, ld=ld)
+    stretched(f, 1, None)
+    stretched(b, 1, None)
+    stretched(_mh_sigs(2, 200, 128, 2, o_ld=ld)[1], 3, None)
+    stretched(_mh_sigs(2, 200, 128, 2, do_ld=ld)[1], 5, None)
+    f, b = _mh_sigs(2, 520, 512, 1, ld=BUF_OOB // 2 // 520 // 8 * 8)                                                       # d = 512, L > 256
+    stretched(f, 1, None)
+    stretched(b, 1, None)
+    return rows
+
+
+LARGE_OPERANDS = _large_rows()
+
+# Entries with no guard: the activation-space kernels that index with 64-bit arithmetic.  One bf16 signature each whose operand holds
+# just over 2^31 elements (just over 2^32 bytes), reached the stretched way where the entry takes a pitch: a few rows whose element
+# offsets pass 2^31 while the float64 reference stays small.  The comment of a row quotes the lines of csrc/elementwise.hip that make
+# its indexing 64-bit.  Row: (signature, amplification or None).
+_E31 = 1 << 31
+
+
+def _past(rows, vec=8):
+    """smallest pitch (whole vectors) at which the last of `rows` rows starts beyond element offset 2^31"""
+    return -(-(_E31 // (rows - 1) + 1) // vec) * vec
+
+
+ACROSS_2_31 = [
+    # add_kernel: `const long long r = i / cv;` ... `x + r * x_ld + c`, `y + r * y_ld + c` (x_ld, y_ld, rows are long long)
+    (("ddpm_add_rows", (_p(), _past(1000), _p(), 256, 1000, 256, 1, BF16)), None),
+    (("ddpm_add_rows", (_p(16), 384, _p(), _past(777), 777, 128, 0, BF16)), None),
+    # colsum_kernel: `const T* base = dy + (long long)b * HW * ld + cx * VEC;` ... `base + (long long)p * ld`,
+    # `per_sample + (long long)b * ps_ld + c` (ld, ps_ld are long long)
+    (("ddpm_colsum", (_p(), _past(3 * 192), _p(), 64 + 4, _p(), 3, 192, 64, BF16)), (16, 192)),
+    # upsample_bwd_kernel: `const long long b = r / H;` ... `dx + ((b * H + y) * W + x) * dx_ld + c` (dx_ld is long long); the dense
+    # input `dyu + (((b * 2 * H + 2 * y + dy) * 2 * W) + 2 * x + dxx) * C + c` is formed in long long through b as well, but this
+    # row stretches dx only: the dense dy_up stays small, its index is not taken past 2^31 here.  No amplification: every output
+    # pixel is the sum of its own 2 x 2 block, no image enters another image's output, and every image of dx is compared.
+    (("ddpm_upsample2x_bwd", (_p(), _p(), _past(3 * 24), 3, 4, 6, 64, 1, BF16)), None),
+    # nchw_to_nhwc_kernel: `const long long n = (long long)B * HW * Cp;` the loop index i, `bp = i / Cp`, `b = bp / HW` are long long
+    # and x is read at `(b * C + c) * HW + p`.  Dense (the entry takes no pitch): 2^28 + 4096 pixels of 8 stored channels.
+    (("ddpm_nchw_to_nhwc", (_p(), _p(), 65537, 3, 4096, 8, BF16)), None),
 ]
 
 
@@ -2645,7 +2973,6 @@ def hostile_rows():
 # holds it to: [exact] a bit-exact copy or integer comparison.
 COVERED_ELSEWHERE = {
     "ddpm_pack_weight": "test_timestep_embedding_and_layout_kernels [exact]",
-    "ddpm_nchw_to_nhwc": "test_timestep_embedding_and_layout_kernels [exact]",
     "ddpm_gather_i64": "test_diffusion_algebra_kernels [exact]",
     "ddpm_add_i64": "test_diffusion_algebra_kernels [exact]",
     "ddpm_stream_order": "not a kernel of arithmetic (stream ordering edge)",
@@ -2658,7 +2985,7 @@ def sync():
         torch.cuda.synchronize()
 
 
-def replay(sig, device, seed=0, poison=False, profile=None, yardstick=False):
+def replay(sig, device, seed=0, poison=False, profile=None, yardstick=False, amplify=None, keep_outputs=True):
     """Replay one signature on `device`; returns a Result (worst err/bar and where).  Without keywords: the draws and checks the
     recorded and odd-geometry tests have always had.  poison: everything the contract does not let the call read holds POISON bytes
     (Buf.poison).  profile: a key of PROFILES.  yardstick: the non-linear families also put a plain fp32 torch composition through cmp."""
@@ -2666,9 +2993,13 @@ def replay(sig, device, seed=0, poison=False, profile=None, yardstick=False):
     name, words = sig
     res = Result(sig, nonfinite=bool(profile) and profile.startswith("nonfinite"))
     A = Arena(device, seed, poison=poison, profile=profile, yardstick=yardstick)
+    if amplify is not None:             # (power of two, rows of one image): the reduction replays scale three images (amplify_images)
+        A.amplify, A.rows_per_image = amplify
     REPLAY[name](A, words, res)
     res.max_bytes = max((b.nbytes for b in A.bufs), default=0)
     for b in A.bufs:
+        if not keep_outputs:            # the 2 GiB rows: no second copy of every output
+            break
         if bool(b.written.any()) and not b.scratch:
             res.outputs[b.name] = (b.t[b.written if b.result is None else b.result].clone(), b.atomic)
     return res
