@@ -18,6 +18,7 @@ through the C-ABI in ``csrc/`` (see ``include/ddpm_hip.h``):
 
 There is no CPU path: CPU tensors raise (the CPU restatement used for checking lives in ``oracle/``).
 """
+import collections
 import contextlib
 import itertools
 import math
@@ -331,6 +332,16 @@ _TAIL_BLOCKS = 4
 _DP_ISSUE_ON_SIDE = os.environ.get("DDPM_DP_ISSUE_ON_SIDE", "0") != "0"
 
 
+# The network's layout (_Engine._layout).  _Buf: a symbolic activation buffer, images of (H >> level) x (W >> level) pixels with C
+# channels; a part of a decoder concat buffer names that buffer (``parent``, an index into _Engine.bufs) and its channel offset there, and
+# its pitch is the parent's width.  _Step: what runs between two buffers (indices ``src``, ``dst``) — ``kind`` "conv" (``mod`` a 3x3 conv;
+# ``up`` None: same size, 0: stride 2 to the next level, 1: behind a nearest-2x upsample from it), "resample" (the same moves without a
+# conv: AvgPool2d(2) / Upsample), "block" (``mod`` a ResidualBlock, or Sequential(ResidualBlock, AttentionBlock); a decoder block reads a
+# whole concat buffer and names its two ``parts``), "middle" (res, attn, res) and "head" (out_conv; no ``dst``: it writes the NCHW output).
+_Buf = collections.namedtuple("_Buf", "level C parent off")
+_Step = collections.namedtuple("_Step", "kind mod src dst parts up")
+
+
 class _Engine:
     _serials = itertools.count(1)
 
@@ -360,6 +371,7 @@ class _Engine:
         # ordered residual blocks (execution order) -> slice of the concatenated time-bias GEMM
         self.res_blocks = []
         self.convs = {}
+        self._layout()
         self._collect()
         # (a scale-shift block owns 2 Cout columns, [scale | shift]: _tbw)
         self.tb_off, o = {}, 0
@@ -415,39 +427,104 @@ class _Engine:
     def _split(self, blk):
         return (blk[0], blk[1]) if isinstance(blk, nn.Sequential) else (blk, None)
 
-    def _collect(self):
-        m = self.m
+    def _layout(self):
+        """The one statement of the network's order and concat geometry (the reference's unet.py:205-233): ``self.bufs`` and ``self.steps``
+        (_Buf, _Step above), in execution order.  It depends on the model alone — not on the batch, the image size or the compute mode —
+        and _collect, forward, operand_plan and _workspace all read it, through _sites where they ask what a step runs."""
+        m, n, L, chs = self.m, self.n, self.L, self.chs
+        self.bufs, self.steps = bufs, steps = [], []
 
-        def reg(conv):
-            self.convs[id(conv)] = _ConvW(conv, self.vec)
+        def buf(level, C, parent=None, off=0):
+            bufs.append(_Buf(level, C, parent, off))
+            return len(bufs) - 1
 
-        def regblock(blk):
-            res, att = self._split(blk)
-            self.res_blocks.append(res)
-            reg(res.conv1); reg(res.conv2)
-            if res.has_skip:
-                reg(res.skip)
-            if att is not None:
-                reg(att.project_in); reg(att.project_out)
+        enc = [self.hid]                                        # channels of every encoder output (the reference's hs)
+        for i in range(L):
+            enc += [chs[i]] * (n + (i != L - 1))
+        # decoder concat buffers [h | skip] in the decoder's order: it pops the encoder outputs last first.  Nothing is ever copied
+        # into them: the step that produces h or an encoder output has its slice as its destination.
+        cats, h_ch = [], chs[-1]
+        for i in range(L - 1, -1, -1):
+            for j in range(n + 1):
+                cs = enc[-1 - len(cats)]
+                full = buf(i, h_ch + cs)
+                cats.append((buf(i, h_ch, full, 0), buf(i, cs, full, h_ch)))
+                h_ch = chs[i]
+        skips = iter([skip for _, skip in reversed(cats)])      # ... so encoder output e lands in the last concat buffer but e
+        cur = buf(0, m.in_channels)                             # the NHWC copy of the input image (its channels padded: _sites)
 
-        reg(m.in_conv)
-        for i in range(self.L):
+        def step(kind, mod, dst, parts=None, up=None):
+            nonlocal cur
+            steps.append(_Step(kind, mod, bufs[parts[0]].parent if parts else cur, dst, parts, up))
+            cur = dst
+
+        def move(conv, dst, up):                                # between two levels (unet.py:163-170, :196-199)
+            step("conv", conv[1], dst, up=up) if m.resample_with_conv else step("resample", None, dst, up=up)
+
+        step("conv", m.in_conv, next(skips))
+        for i in range(L):
             mods = m.downsamples[f"level_{i}"]
-            for j in range(self.n):
-                regblock(mods[j])
-            if i != self.L - 1 and m.resample_with_conv:
-                reg(mods[self.n][1])
-        self.res_blocks.append(m.middle[0]); reg(m.middle[0].conv1); reg(m.middle[0].conv2)
-        reg(m.middle[1].project_in); reg(m.middle[1].project_out)
-        self.res_blocks.append(m.middle[2]); reg(m.middle[2].conv1); reg(m.middle[2].conv2)
-        for i in range(self.L - 1, -1, -1):
+            for j in range(n):
+                step("block", mods[j], next(skips))
+            if i != L - 1:
+                move(mods[n], next(skips), 0)
+        step("middle", m.middle, cats[0][0])
+        k = 0
+        for i in range(L - 1, -1, -1):
             mods = m.upsamples[f"level_{i}"]
-            for j in range(self.n + 1):
-                regblock(mods[j])
-            if i != 0 and m.resample_with_conv:
-                reg(mods[self.n + 1][1])
-                self.convs[id(mods[self.n + 1][1])].up = True
-        reg(m.out_conv[2])
+            for j in range(n + 1):                              # the level's last block writes a buffer of its own
+                step("block", mods[j], cats[k + 1][0] if j < n else buf(i, chs[i]), parts=cats[k])
+                k += 1
+            if i != 0:
+                move(mods[n + 1], cats[k][0], 1)
+        step("head", m.out_conv, None)
+
+    def _sites(self, s):
+        """What step ``s`` of the layout runs: ([(conv, input channels, input pitch, output channels, input level, output level)], in the
+        order of the engine's conv table, and [(channels, level)] of its GroupNorms)."""
+        x = self.bufs[s.src]
+        lvl, ld = x.level, x.C if x.parent is None else self.bufs[x.parent].C
+        pad = lambda c: -(-c // self.vec) * self.vec            # packed width: in_conv's input and the head's output; every other is a multiple of 32
+        convs, norms = [], []
+
+        def res(rb):
+            # conv1 and conv2 read the dense GroupNorm outputs a1 and a2; the 1x1 skip reads the block's own input at that input's pitch
+            convs.append((rb.conv1, rb.in_channels, rb.in_channels, rb.out_channels, lvl, lvl))
+            convs.append((rb.conv2, rb.out_channels, rb.out_channels, rb.out_channels, lvl, lvl))
+            if rb.has_skip:
+                convs.append((rb.skip, x.C, ld, rb.out_channels, lvl, lvl))
+            norms.extend([(rb.in_channels, lvl), (rb.out_channels, lvl)])
+
+        def attn(ab):
+            C = ab.in_channels
+            convs.append((ab.project_in, C, C, 3 * C, lvl, lvl))                  # (backward: the dense [3C] gradient of q | k | v)
+            convs.append((ab.project_out, C, C, C, lvl, lvl))
+            norms.append((C, lvl))
+
+        if s.kind == "conv":
+            convs.append((s.mod, pad(x.C), pad(ld), s.mod.weight.shape[0], lvl, self.bufs[s.dst].level))
+        elif s.kind == "block":
+            rb, ab = self._split(s.mod)
+            res(rb)
+            if ab is not None:
+                attn(ab)
+        elif s.kind == "middle":                                # (its second block has no skip projection: x stands for nothing there)
+            res(s.mod[0]); attn(s.mod[1]); res(s.mod[2])
+        elif s.kind == "head":
+            norms.append((self.hid, lvl))
+            convs.append((s.mod[2], self.hid, self.hid, pad(s.mod[2].weight.shape[0]), lvl, lvl))
+        return convs, norms
+
+    def _collect(self):
+        """The conv table and the residual blocks in execution order — per block conv1, conv2, the skip if present, then project_in,
+        project_out: _wgrad_table's all-reduce chunks, the pack table, tb_off and the _TAIL_BLOCKS boost all go by that order."""
+        rb_of_conv1 = {id(rb.conv1): rb for rb in self.m.modules() if isinstance(rb, ResidualBlock)}
+        for s in self.steps:
+            for conv, *_ in self._sites(s)[0]:
+                cw = self.convs[id(conv)] = _ConvW(conv, self.vec)
+                cw.up = s.kind == "conv" and s.up == 1
+                if id(conv) in rb_of_conv1:
+                    self.res_blocks.append(rb_of_conv1[id(conv)])
 
     # ---------------------------------------------------------------- derived weight caches
     def _refresh_packs(self, need_dgrad):
@@ -611,14 +688,8 @@ class _Engine:
         key = (B, H, W)
         need = self._ws_need.get(key)
         if need is None:
-            need = 0
-            for i in range(self.L):                      # every GroupNorm width that occurs at level i
-                hw = (H >> i) * (W >> i)
-                below = self.chs[i + 1] if i + 1 < self.L else self.chs[-1]
-                above = self.chs[i - 1] if i else self.hid
-                for c in {self.chs[i], above, self.chs[i] + below, 2 * self.chs[i], self.chs[i] + above}:
-                    need = max(need, ops.gn_workspace_floats(B, hw, c, self.dcode))
-            self._ws_need[key] = need
+            norms = {site for s in self.steps for site in self._sites(s)[1]}
+            need = self._ws_need[key] = max(ops.gn_workspace_floats(B, (H >> lvl) * (W >> lvl), c, self.dcode) for c, lvl in norms)
         if self._ws is None or self._ws.numel() < need:
             self._ws_retired.append(self._ws)
             self._ws = torch.empty(need, dtype=torch.float32, device=self.device)
@@ -942,77 +1013,19 @@ class _Engine:
     # ================================================================ admission (the 2 GiB operand limit)
     def operand_plan(self, H, W, backward=True):
         """[(layer, operand, pixel rows per image, channels, pitch)] of every activation a conv, weight-gradient or GEMM kernel reads
-        through a buffer descriptor in forward (and, with ``backward``, in the backward) on H x W images: the buffer geometry of
-        ``forward`` below, walked without allocating.  An operand of B images spans ((B * rows - 1) * pitch + channels) * es bytes,
+        through a buffer descriptor in forward (and, with ``backward``, in the backward) on H x W images: the layout ``forward`` below
+        runs, read without allocating.  An operand of B images spans ((B * rows - 1) * pitch + channels) * es bytes,
         which the launchers hold to ops.BUF_OOB.  Gradients are dense buffers of their view's width (_grad_target), so the backward
         adds the dense twin of every conv's input and output.  Attention reads q | k | v per sample: no batch limit comes from it."""
-        m, n, L = self.m, self.n, self.L
-        names = {id(mod): name for name, mod in m.named_modules()}
+        names = {id(mod): name for name, mod in self.m.named_modules()}
         plan = []
-
-        def op(mod, what, hw, C, ld=None):
-            plan.append((names.get(id(mod), "?"), what, hw, C, C if ld is None else ld))
-
-        def conv(mod, hw, xC, x_ld, N, hw_out=None):
-            op(mod, "input", hw, xC, x_ld)
-            if backward:                            # dy of the weight gradient = x of the data gradient; dx is written dense
-                op(mod, "output gradient", hw if hw_out is None else hw_out, N)
-                op(mod, "input gradient", hw, xC)
-
-        def res(rb, hw, xC, x_ld):
-            conv(rb.conv1, hw, rb.in_channels, rb.in_channels, rb.out_channels)            # a1: GN + SiLU of x, dense
-            if rb.has_skip:
-                conv(rb.skip, hw, xC, x_ld, rb.out_channels)
-            conv(rb.conv2, hw, rb.out_channels, rb.out_channels, rb.out_channels)          # a2
-
-        def attn(ab, hw):
-            C = ab.in_channels
-            conv(ab.project_in, hw, C, C, 3 * C)                                           # (backward: the dense [3C] gradient of q | k | v)
-            conv(ab.project_out, hw, C, C, C)
-
-        def block(blk, hw, xC, x_ld):
-            r, a = self._split(blk)
-            res(r, hw, xC, x_ld)
-            if a is not None:
-                attn(a, hw)
-
-        enc = [(self.hid, 0)]
-        for i in range(L):
-            enc += [(self.chs[i], i)] * n
-            if i != L - 1:
-                enc.append((self.chs[i], i + 1))
-        hw = [(H >> i) * (W >> i) for i in range(L)]
-        width, h_ch, k = [], self.chs[-1], 0        # pitch of the concat buffer every encoder output is written into
-        for i in range(L - 1, -1, -1):
-            for j in range(n + 1):
-                width.append(h_ch + enc[len(enc) - 1 - k][0])
-                h_ch = self.chs[i]
-                k += 1
-        slot_ld = lambda e: width[len(enc) - 1 - e]
-        cin = self.convs[id(m.in_conv)].Cp
-        conv(m.in_conv, hw[0], cin, cin, self.hid)
-        e = 0
-        for i in range(L):
-            mods = m.downsamples[f"level_{i}"]
-            for j in range(n):
-                block(mods[j], hw[i], enc[e][0], slot_ld(e))
-                e += 1
-            if i != L - 1:
-                if m.resample_with_conv:
-                    conv(mods[n][1], hw[i], enc[e][0], slot_ld(e), self.chs[i], hw_out=hw[i + 1])
-                e += 1
-        res(m.middle[0], hw[-1], enc[e][0], slot_ld(e))
-        attn(m.middle[1], hw[-1])
-        res(m.middle[2], hw[-1], self.chs[-1], self.chs[-1])
-        k = 0
-        for i in range(L - 1, -1, -1):
-            mods = m.upsamples[f"level_{i}"]
-            for j in range(n + 1):
-                block(mods[j], hw[i], width[k], width[k])                                  # the whole concat buffer
-                k += 1
-            if i != 0 and m.resample_with_conv:
-                conv(mods[n + 1][1], hw[i], self.chs[i], self.chs[i], self.chs[i], hw_out=hw[i - 1])
-        conv(m.out_conv[2], hw[0], self.hid, self.hid, self.convs[id(m.out_conv[2])].Np)
+        for s in self.steps:
+            for mod, xC, x_ld, N, lvl, out_lvl in self._sites(s)[0]:
+                layer, hw = names.get(id(mod), "?"), (H >> lvl) * (W >> lvl)
+                plan.append((layer, "input", hw, xC, x_ld))
+                if backward:                        # dy of the weight gradient = x of the data gradient; dx is written dense
+                    plan.append((layer, "output gradient", (H >> out_lvl) * (W >> out_lvl), N, N))
+                    plan.append((layer, "input gradient", hw, xC, xC))
         return plan
 
     def max_batch(self, H, W, backward=True):
@@ -1079,80 +1092,37 @@ class _Engine:
                 st["y"] = y
         st["tb"] = tb
 
-        # ---- decoder concat buffers: encoder outputs are written straight into their slice
-        n, L = self.n, self.L
-        enc = [(self.hid, 0)]                                   # (channels, level) of every hs entry
-        for i in range(L):
-            enc += [(self.chs[i], i)] * n
-            if i != L - 1:
-                enc.append((self.chs[i], i + 1))
-        sizes = [(H >> i, W >> i) for i in range(L)]
-        cats, k = [], 0
-        h_ch = self.chs[-1]
-        for i in range(L - 1, -1, -1):
-            for j in range(n + 1):
-                cs, lvl = enc[len(enc) - 1 - k]
-                assert lvl == i
-                full = self._new(B, sizes[i][0], sizes[i][1], h_ch + cs)
-                full_parts = (full.chan_slice(0, h_ch), full.chan_slice(h_ch, h_ch + cs))
-                cats.append((full, full_parts))
-                h_ch = self.chs[i]
-                k += 1
-        assert k == len(enc)
-
-        def skip_slot(e):
-            return cats[len(enc) - 1 - e][1][1]
-
-        # ---- encoder
+        # ---- the layout's buffers at this geometry.  The decoder's concat buffers and their slices are made here, ahead of the encoder that
+        # writes into them; every other buffer is made by the step that writes it and lives no longer than something refers to it.
+        bufs = self.bufs
+        views = [None] * len(bufs)
+        for k, b in enumerate(bufs):
+            if b.parent is not None:
+                if views[b.parent] is None:
+                    views[b.parent] = self._new(B, H >> b.level, W >> b.level, bufs[b.parent].C)
+                views[k] = views[b.parent].chan_slice(b.off, b.off + b.C)
         cin = self.convs[id(m.in_conv)].Cp                      # in_conv's packed width: one vector for RGB, more from 9 (bf16) / 5 (fp32) channels on
         xin = self._new(B, H, W, cin)                           # channel-padded NHWC copy of x
         _hip.call("ddpm_nchw_to_nhwc", x.data_ptr(), xin.ptr, B, m.in_channels, H * W, cin, self.dcode, _hip.stream())
-        e = 0
-        cur = skip_slot(e)
-        self._conv(st, m.in_conv, xin, cur, 3)
-        for i in range(L):
-            mods = m.downsamples[f"level_{i}"]
-            for j in range(n):
-                e += 1
-                nxt = skip_slot(e)
-                self._block(st, mods[j], cur, nxt)
-                cur = nxt
-            if i != L - 1:
-                e += 1
-                nxt = skip_slot(e)
-                if m.resample_with_conv:
-                    self._conv(st, mods[n][1], cur, nxt, 3, stride=2)
-                else:
-                    self._resample(st, cur, nxt, up=0)           # nn.AvgPool2d(2)
-                cur = nxt
-        # ---- middle
-        hh, ww = sizes[-1]
-        a = self._new(B, hh, ww, self.chs[-1])
-        self._res(st, m.middle[0], cur, a)
-        b = self._new(B, hh, ww, self.chs[-1])
-        self._attn(st, m.middle[1], a, b)
-        self._res(st, m.middle[2], b, cats[0][1][0])
-        # ---- decoder
-        k = 0
-        for i in range(L - 1, -1, -1):
-            mods = m.upsamples[f"level_{i}"]
-            for j in range(n + 1):
-                full, parts = cats[k]
-                last_of_level = j == n
-                if not last_of_level:
-                    dst = cats[k + 1][1][0]
-                else:
-                    dst = self._new(B, sizes[i][0], sizes[i][1], self.chs[i])
-                self._block(st, mods[j], full, dst, parts=parts)
-                k += 1
-                cur = dst
-            if i != 0:
-                dst = cats[k][1][0]
-                if m.resample_with_conv:
-                    self._conv(st, mods[n + 1][1], cur, dst, 3, upsample=1)
-                else:
-                    self._resample(st, cur, dst, up=1)           # nn.Upsample(2, "nearest") alone
-                cur = dst
+        # ---- encoder, middle, decoder (the last step, the head, is below)
+        cur = xin
+        for s in self.steps[:-1]:
+            src = cur if s.parts is None else views[s.src]      # (rebound before `out` is made: the buffer a level's last block wrote dies here)
+            b = bufs[s.dst]
+            out = views[s.dst] if b.parent is not None else self._new(B, H >> b.level, W >> b.level, b.C)
+            if s.kind == "conv":
+                self._conv(st, s.mod, src, out, 3, stride=2 if s.up == 0 else 1, upsample=1 if s.up == 1 else 0)
+            elif s.kind == "resample":
+                self._resample(st, src, out, up=s.up)
+            elif s.kind == "block":
+                self._block(st, s.mod, src, out, parts=s.parts and (views[s.parts[0]], views[s.parts[1]]))
+            else:
+                mid1 = self._new(B, out.H, out.W, out.C)
+                self._res(st, s.mod[0], src, mid1)
+                mid2 = self._new(B, out.H, out.W, out.C)
+                self._attn(st, s.mod[1], mid1, mid2)
+                self._res(st, s.mod[2], mid2, out)
+            cur = out
         # ---- head: GN + SiLU + conv -> NCHW fp32
         out = self._f32(B, m.out_channels, H, W)
         act = self._new(B, H, W, self.hid)
@@ -1178,10 +1148,9 @@ class _Engine:
             pl = 0 if x.W % 2 == 0 else 1
         else:
             pt = pl = k // 2
-        xin = x
         if cw.Cp != x.C:
             raise RuntimeError("channel padding mismatch")
-        ops.conv2d(xin, cw.wf.data_ptr(), out.ptr, out.ld, cw.N, k, k, out.H, out.W, stride=stride, pad_t=pt, pad_l=pl,
+        ops.conv2d(x, cw.wf.data_ptr(), out.ptr, out.ld, cw.N, k, k, out.H, out.W, stride=stride, pad_t=pt, pad_l=pl,
                    upsample=upsample, bias=conv.bias.data_ptr(), splitk=self.splitk)
         if st["save"]:
             st["tape"].append(("conv", conv, x, out, k, stride, pt, pl, upsample))
@@ -1216,8 +1185,6 @@ class _Engine:
         rowbias = tb.data_ptr() + 4 * self.tb_off[id(rb)]
         c1 = self._packed(rb.conv1, save)
         c2 = self._packed(rb.conv2, save)
-        a1 = stats1 = a2 = stats2 = None
-        seed = 0
         h1 = self._new(B, x.H, x.W, Cout)
         a1 = self._new(B, x.H, x.W, Cin)
         stats1 = self._f32(B, ops.GN_GROUPS, 2) if save else None

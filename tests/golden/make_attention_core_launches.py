@@ -59,13 +59,13 @@ def make(cfg, dtype, H, W, heads):
     return m, rnd(B, 3, H, W, seed=1), torch.tensor([3, 977]), rnd(B, 3, H, W, seed=2)
 
 
-def spy(monkeypatch):
-    """Install the emulator; returns (emulator, list that receives one record per launch)."""
+def spy(monkeypatch, pointer=lambda a: "ptr" if a else "null"):
+    """Install the emulator; returns (emulator, list that receives one record per launch).  ``pointer``: what a record keeps of an address."""
     emu = mha_emulator.attach(abi_emulator.install(monkeypatch, _hip))
     launches, inner = [], _hip._invoke
 
     def invoke(name, args):
-        launches.append([name] + [("ptr" if a else "null") if T in (ctypes.c_void_p, ctypes.c_char_p) else a
+        launches.append([name] + [pointer(a) if T in (ctypes.c_void_p, ctypes.c_char_p) else a
                                   for T, a in zip(_hip.PROTOTYPES[name], args)])
         inner(name, args)
     monkeypatch.setattr(_hip, "_invoke", invoke)
@@ -92,14 +92,14 @@ def run(case, launches):
     return m, dict(train_fwd=fwd, train_bwd=bwd, eval=list(launches)), out
 
 
-def pack(res):
-    """{case: {leg: launches}} -> the fixture's form (see the module docstring)."""
+def pack(res, full=CORE):
+    """{case: {leg: launches}} -> the fixture's form (see the module docstring).  ``full``: how the JSON text of a launch kept in full begins."""
     table, legs = {}, {}
     for case, by in res.items():
         legs[case] = {}
         for leg, launches in by.items():
             text = [json.dumps(r, separators=(",", ":")) for r in launches]
-            core = [table.setdefault(t, len(table)) for t in text if t.startswith(CORE)]
+            core = [table.setdefault(t, len(table)) for t in text if t.startswith(full)]
             legs[case][leg] = dict(n=len(text), sha256=hashlib.sha256("\n".join(text).encode()).hexdigest(), core=core)
     return dict(launches=[json.loads(t) for t in table], legs=legs)
 

@@ -20,6 +20,12 @@ TINY = dict(in_channels=3, hid_channels=32, out_channels=3, ch_multipliers=[1, 2
 TINY3 = dict(in_channels=3, hid_channels=32, out_channels=3, ch_multipliers=[1, 2, 2], num_res_blocks=2, apply_attn=[False, True, False], drop_rate=0.1)
 
 TINY3_POOL = dict(TINY3, resample_with_conv=False)        # AvgPool2d(2) / bare nearest Upsample between the levels (unet.py:169, :196)
+ONE_LEVEL = dict(TINY, ch_multipliers=[1], apply_attn=[True])                             # no resampling at all
+# identity skips in the encoder, equal widths across levels, attention on the two deepest levels (4 x 4 and 2 x 2 tokens at 16 x 16)
+FOUR_EQUAL = dict(TINY3, ch_multipliers=[1, 1, 2, 2], num_res_blocks=3, apply_attn=[False, False, True, True])
+FOUR_EQUAL_POOL = dict(FOUR_EQUAL, resample_with_conv=False)
+TOPOLOGIES = [TINY, TINY3, TINY3_POOL, ONE_LEVEL, FOUR_EQUAL, FOUR_EQUAL_POOL]
+TOPOLOGY_IDS = ["tiny", "tiny3", "tiny3_pool_resample", "one_level", "four_equal_n3", "four_equal_n3_pool_resample"]
 
 pytestmark = pytest.mark.skipif(not os.path.exists(_hip.LIB_PATH), reason="libddpm_hip.so not built")
 
@@ -38,7 +44,7 @@ def make(cfg, seed=5, dtype=torch.float32):
     return m, sd
 
 
-@pytest.mark.parametrize("cfg", [TINY, TINY3, TINY3_POOL], ids=["tiny", "tiny3", "tiny3_pool_resample"])
+@pytest.mark.parametrize("cfg", TOPOLOGIES, ids=TOPOLOGY_IDS)
 def test_forward_fp32_matches_oracle(emu, cfg):
     m, sd = make(cfg)
     m.eval()
@@ -60,7 +66,7 @@ def test_forward_bf16_close(emu):
     check(y, ref, 5e-2, name="fwd_bf16")      # bf16 storage of every activation: loose, documented tolerance
 
 
-@pytest.mark.parametrize("cfg", [TINY, TINY3, TINY3_POOL], ids=["tiny", "tiny3", "tiny3_pool_resample"])
+@pytest.mark.parametrize("cfg", TOPOLOGIES, ids=TOPOLOGY_IDS)
 def test_backward_fp32_matches_oracle(emu, cfg):
     m, sd = make(cfg)
     m.train()

@@ -20,6 +20,7 @@ import ddpm_torch
 from ddpm_torch import _hip, _ops
 from tests import abi_emulator
 from tests import launch_replay as LR
+from tests.golden import make_engine_layout as EL
 from tests.golden.recipes import rnd
 from tests.test_host_emulated import TINY, make
 
@@ -129,7 +130,7 @@ def test_max_batch_of_the_shipped_configurations(monkeypatch, name, size, bf16, 
 GUARDED = ("ddpm_conv2d_nhwc", "ddpm_conv2d_wgrad_nhwc", "ddpm_conv3x3_wgrad_nhwc", "ddpm_conv3x3_wgrad_up_nhwc", "ddpm_conv1x1_wgrad_nhwc", "ddpm_gemm")
 
 
-def _recorded(monkeypatch, m, B, size):
+def _recorded(monkeypatch, m, B, size, labels=None):
     """Every distinct launch signature of one training forward + backward at batch B, with nothing launched and nothing computed: the
     C-ABI calls are recorded and dropped, and every activation view stands on one small buffer (a signature keeps pitches, shapes and
     pointer alignment, which is all the launchers' validation and the dispatch queries read)."""
@@ -140,8 +141,9 @@ def _recorded(monkeypatch, m, B, size):
     def new(B_, H, W, C, dtype, device):
         return _ops.View(bases.setdefault(dtype, torch.zeros(64, dtype=dtype)), B_, H, W, C)
     monkeypatch.setattr(_ops.View, "new", staticmethod(new))
-    x = torch.zeros(B, m.in_channels, size, size)
-    y = m(x, torch.arange(B) % 1000)
+    H, W = size
+    x = torch.zeros(B, m.in_channels, H, W)
+    y = m(x, torch.arange(B) % 1000, *(() if labels is None else (torch.arange(B) % (m.num_classes + 1),)))
     y.sum().backward()
     return [s for s in rec.sigs if s[0] in GUARDED]
 
@@ -151,6 +153,22 @@ def _dry(sig):
     if sig[0] in ("ddpm_conv2d_nhwc", "ddpm_conv2d_wgrad_nhwc", "ddpm_gemm"):
         return LR.variant_of(LR.geometry(sig, offsets=False))
     return None
+
+
+def _plan_against_signatures(monkeypatch, m, eng, H, W, label, labels=None):
+    B = eng.max_batch(H, W)
+    sigs = _recorded(monkeypatch, m, B, (H, W), labels)
+    assert len(sigs) > 50
+    worst = max(LR.largest_extent(s)[1] for s in sigs)
+    assert worst <= LR.BUF_OOB and worst == _bytes(eng, B, H, W, True), (worst, _bytes(eng, B, H, W, True))
+    refused = [s for s in sigs if (_dry(s) or 0) < 0]
+    assert not refused, [LR.short(s) for s in refused[:3]]
+    monkeypatch.setattr(eng, "admit", lambda *a, **k: None)
+    over = _recorded(monkeypatch, m, B + 1, (H, W), labels)
+    beyond = [s for s in over if LR.largest_extent(s)[1] > LR.BUF_OOB]
+    assert beyond and max(LR.largest_extent(s)[1] for s in over) == _bytes(eng, B + 1, H, W, True)
+    assert all(_dry(s) in (None, -LR.ERR_SHAPE) for s in beyond) and any(_dry(s) == -LR.ERR_SHAPE for s in beyond)
+    print(f"\n{label} {H} x {W}: max_batch {B}, {len(sigs)} guarded signatures, largest operand {worst} B; at {B + 1}: {len(beyond)} refused")
 
 
 @pytest.mark.parametrize("name,size", [("celebahq.json", 256), ("celeba.json", 64)])
@@ -165,20 +183,30 @@ def test_plan_matches_the_signatures_the_engine_emits(monkeypatch, name, size):
     m.train()
     for dtype in ((torch.bfloat16, torch.float32) if size == 256 else (torch.bfloat16,)):
         m.set_compute_dtype(dtype)
-        eng = m.engine()
-        B = eng.max_batch(size, size)
-        sigs = _recorded(monkeypatch, m, B, size)
-        assert len(sigs) > 50
-        worst = max(LR.largest_extent(s)[1] for s in sigs)
-        assert worst <= LR.BUF_OOB and worst == _bytes(eng, B, size, size, True), (worst, _bytes(eng, B, size, size, True))
-        refused = [s for s in sigs if (_dry(s) or 0) < 0]
-        assert not refused, [LR.short(s) for s in refused[:3]]
-        monkeypatch.setattr(eng, "admit", lambda *a, **k: None)
-        over = _recorded(monkeypatch, m, B + 1, size)
-        beyond = [s for s in over if LR.largest_extent(s)[1] > LR.BUF_OOB]
-        assert beyond and max(LR.largest_extent(s)[1] for s in over) == _bytes(eng, B + 1, size, size, True)
-        assert all(_dry(s) in (None, -LR.ERR_SHAPE) for s in beyond) and any(_dry(s) == -LR.ERR_SHAPE for s in beyond)
-        print(f"\n{name} {size} x {size} {dtype}: max_batch {B}, {len(sigs)} guarded signatures, largest operand {worst} B; at {B + 1}: {len(beyond)} refused")
+        _plan_against_signatures(monkeypatch, m, m.engine(), size, size, f"{name} {dtype}")
+
+
+# the topologies of tests/golden/make_engine_layout.py.  Two of them on a larger image than there, because at max_batch the path chooser
+# (batch x heads > 65535) sends their attention to the materialised path, which refuses token counts that are no multiple of 8:
+# four_equal_n3 at 32 x 16, not 16 x 8 (max_batch 131071, 2 tokens on level 3); two_all_options at 16 x 12, not 12 x 10 (max_batch 46603
+# of two heads, 30 tokens on level 1; at 16 x 12 max_batch x 2 stays below 65536 and the head-indexed streaming kernels serve it).
+SIZES = {"four_equal_n3": (32, 16), "two_all_options": (16, 12)}
+TOPOLOGIES = [(case, dtype) for case in EL.CASES for dtype in (torch.bfloat16, torch.float32)
+              if dtype == torch.bfloat16 or case in ("three_n2_rwc", "one_level")]
+
+
+@pytest.mark.parametrize("case,dtype", TOPOLOGIES, ids=[f"{c}-{'bf16' if d == torch.bfloat16 else 'fp32'}" for c, d in TOPOLOGIES])
+def test_plan_matches_the_signatures_on_other_topologies(monkeypatch, case, dtype):
+    """The same on networks that are not the shipped ones: one level, four levels of three blocks with equal widths, conv-free
+    resampling, every option on — at B = max_batch and max_batch + 1, where the activations decide (at a small B the weight operands
+    are the largest, and the plan does not list them)."""
+    abi_emulator.install(monkeypatch, _hip)
+    cfg, _, H, W, labels = EL.CASES[case]
+    H, W = SIZES.get(case, (H, W))
+    m = ddpm_torch.UNet(**cfg)
+    m.train()
+    m.set_compute_dtype(dtype)
+    _plan_against_signatures(monkeypatch, m, m.engine(), H, W, f"{case} {dtype}", labels=labels)
 
 
 # ------------------------------------------------------------------------------------------- GroupNorm: the new refusal
