@@ -11,7 +11,7 @@ import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = ["gemm.hip", "wgrad.hip", "wgrad1x1.hip", "attention.hip", "attention_stream.hip", "pointwise.hip", "conv3x3.hip", "edgeconv.hip", "norm.hip", "elementwise.hip", "optim.hip", "probe.hip", "plan.hip", "toymlp.hip", "manifold.hip", "batch.hip", "ddim.hip", "guidance.hip"]
+SOURCES = ["gemm.hip", "wgrad.hip", "wgrad1x1.hip", "attention.hip", "attention_stream.hip", "pointwise.hip", "conv3x3.hip", "edgeconv.hip", "norm.hip", "elementwise.hip", "optim.hip", "probe.hip", "plan.hip", "toymlp.hip", "manifold.hip", "batch.hip", "ddim.hip", "guidance.hip", "inpaint.hip"]
 OUT = os.path.join(HERE, "libddpm_hip.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-munsafe-fp-atomics", "-fPIC"]
 

@@ -162,6 +162,16 @@ __device__ __forceinline__ void step_elem(const VlbCoef& k, int mean_type, int c
     x_prev = __builtin_fmaf(z, mask_sd, mean);
 }
 
+// The model log-variance of one element of a learned-variance model (var_mode 1: v itself; 2: the interpolation of Nichol & Dhariwal 2021
+// eq. 15, f not clamped, each product and sum rounded on its own) — the definition for every kernel that reads a v half
+// (elementwise.hip, inpaint.hip; the modes are described in front of the bound kernels of elementwise.hip).
+__device__ __forceinline__ float lv_logvar(int var_mode, float v, float lv_min, float lv_max) {
+#pragma clang fp contract(off)
+    if (var_mode == 1) return v;
+    const float f = 0.5f * (v + 1.0f);
+    return f * lv_max + (1.0f - f) * lv_min;
+}
+
 // "Done once per DEVICE" flag for the launchers' hipFuncSetAttribute(MaxDynamicSharedMemorySize) opt-ins: the attribute belongs to the
 // (function, device) pair, so a process that drives a second GPU has to set it there too.  Reads like the bool it replaces
 // (`static DevOnce set; if (!set) { ...; set = true; }`); devices are folded modulo 64, setting an attribute twice is harmless.

@@ -540,12 +540,7 @@ __device__ __forceinline__ void bpd_elem(const BpdConst& c, long long tt, int me
 //   var_mode 0 : (step only) the table entry, v ignored — what DDIM does with a 2C-channel model.
 // (`#pragma clang fp contract(off)`: the __f*_rn spellings are plain operators in this toolchain and do not keep the compiler from fusing a
 // product into a following sum; the pragma does.)
-__device__ __forceinline__ float lv_logvar(int var_mode, float v, float lv_min, float lv_max) {
-#pragma clang fp contract(off)
-    if (var_mode == 1) return v;
-    const float f = 0.5f * (v + 1.0f);
-    return f * lv_max + (1.0f - f) * lv_min;
-}
+// (lv_logvar itself lives in common.h, beside step_elem: csrc/inpaint.hip evaluates the same expression.)
 // The variance policy the bound kernels below are compiled for: where an element's BpdConst comes from, whether the network's rows carry
 // a v half (HAS_V: rows of PITCH * n floats, v at +n), and which t = 0 decoders exist.  `opt` is the policy's one launch option.
 struct FixedVar {                       // both log-variances are table entries: the constants are formed once per row; opt = decoder

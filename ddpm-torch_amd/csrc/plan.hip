@@ -85,6 +85,7 @@ const EntryPoint kEntryPoints[] = {
     EP(ddpm_p_sample_step_lv), EP(ddpm_vlb_terms_lv), EP(ddpm_bpd_terms_lv), EP(ddpm_learned_loss),
     EP(ddpm_class_embed_fwd), EP(ddpm_class_embed_bwd), EP(ddpm_p_sample_step_cfg),
     EP(ddpm_groupnorm_mod_silu_fwd), EP(ddpm_groupnorm_mod_silu_bwd),
+    EP(ddpm_p_sample_step_masked), EP(ddpm_q_jump),
 };
 constexpr int kNumEntryPoints = (int)(sizeof(kEntryPoints) / sizeof(kEntryPoints[0]));
 

@@ -69,8 +69,7 @@ class DDIM(ddpm_torch.GaussianDiffusion):
         ab_prev = torch.cat([torch.ones(1, dtype=torch.float64), ab[:-1]], dim=0)
         self.alphas = ab / ab_prev
         self.betas = 1.0 - self.alphas
-        self.alphas_bar_prev = self._build_tables(self.betas, ab, eta2=eta2)
-        self.sqrt_alphas_bar_prev = torch.sqrt(self.alphas_bar_prev)
+        self._build_tables(self.betas, ab, eta2=eta2)             # (also alphas_bar_prev and sqrt_alphas_bar_prev, ddim.py:66-67)
         self.subsequence = torch.as_tensor(subsequence)
         self._sub_dev = {}
         # the encoder's tables (fp64 like every other one; _tab casts them to fp32 once per device)

@@ -114,6 +114,9 @@ PROTOTYPES = {
     "ddpm_class_embed_fwd": [P, P, P, P, P, I, I, I, P],
     "ddpm_class_embed_bwd": [P, P, P, I, I, I, P],
     "ddpm_p_sample_step_cfg": [P] * 9 + [F, P, P] + [I] * 6 + [P],
+    # inpainting and image editing (csrc/inpaint.hip; driven by GaussianDiffusion.inpaint)
+    "ddpm_p_sample_step_masked": [P] * 16 + [I] * 9 + [P],
+    "ddpm_q_jump": [P] * 6 + [I, I, I, P],
     # launch plans (csrc/plan.hip; driven by _plan.LaunchPlan)
     "ddpm_stream_order": [P, P],
     "ddpm_fill_zero": [P, L, P],

@@ -22,7 +22,7 @@ import torch
 from . import _hip
 from ._graphs import SegmentedGraph
 
-__all__ = ["get_beta_schedule", "GaussianDiffusion"]
+__all__ = ["get_beta_schedule", "GaussianDiffusion", "repaint_schedule"]
 
 _F64 = torch.float64
 
@@ -48,6 +48,32 @@ def get_beta_schedule(beta_schedule, beta_start, beta_end, timesteps, dtype=_F64
     betas = table[beta_schedule]()
     assert betas.shape == (timesteps,)
     return betas
+
+
+def repaint_schedule(S, jump_length=1, resamples=1, start=None):
+    """The order of operations of a RePaint chain (Lugmayr et al. 2022, Algorithm 1 with the jumps of its §4.2) on S levels: a list of
+    ``"down"`` (one reverse step: a network call, the state goes from index i to i - 1) and ``"up"`` (one forward jump from i to
+    i + jump_length).  The chain begins at index ``top`` = S - 1, or ``start``, and ends at -1 (the clean image).  After a reverse step
+    arrives at index i it jumps when 0 <= i <= top - j, (top - i) % j == 0 and fewer than ``resamples`` - 1 jumps have been taken from i,
+    so every stretch of j levels below ``top`` is walked ``resamples`` times: (top + 1) + (resamples - 1) * j * (top // j) network calls.
+    ``resamples`` = 1 is the plain replacement method (no jump)."""
+    S, j, r = int(S), int(jump_length), int(resamples)
+    top = S - 1 if start is None else int(start)
+    if S < 1 or not 0 <= top <= S - 1:
+        raise ValueError(f"the chain starts at an index in [0, {S - 1}], got {top}")
+    if r < 1 or j < 1:
+        raise ValueError(f"resamples and jump_length are at least 1, got resamples={r}, jump_length={j}")
+    if r > 1 and j > top:
+        raise ValueError(f"a jump of {j} levels does not fit below the starting index {top}")
+    ops, taken, i = [], {}, top
+    while i >= 0:
+        ops.append("down")
+        i -= 1
+        if r > 1 and 0 <= i <= top - j and (top - i) % j == 0 and taken.get(i, 0) < r - 1:
+            taken[i] = taken.get(i, 0) + 1
+            ops.append("up")
+            i += j
+    return ops
 
 
 _MEAN_CODE = {"eps": 0, "x_0": 1, "mean": 2}
@@ -172,6 +198,10 @@ class GaussianDiffusion:
         self.alphas_bar = ab
         self.sqrt_alphas_bar = ab.sqrt()
         self.sqrt_one_minus_alphas_bar = (1.0 - ab).sqrt()
+        # the level a reverse step arrives at (ab[-1] = 1: the clean image): the masked step re-noises the known region to it
+        self.alphas_bar_prev = ab_prev
+        self.sqrt_alphas_bar_prev = ab_prev.sqrt()
+        self.sqrt_one_minus_alphas_bar_prev = (1.0 - ab_prev).sqrt()
         self.sqrt_recip_alphas_bar = (1.0 / ab).sqrt()
         self.sqrt_recip_m1_alphas_bar = (1.0 / ab - 1.0).sqrt()
         self.posterior_var = betas * (1.0 - ab_prev) / (1.0 - ab) * (eta2 if ddim else 1.0)
@@ -439,15 +469,17 @@ class GaussianDiffusion:
     def _model_t(self, t):
         return t
 
-    def _sample_loop(self, denoise_fn, shape, device, noise, seed, on_step=None, z_stream=None, y=None, guidance_scale=1.0):
+    def _sample_loop(self, denoise_fn, shape, device, noise, seed, on_step=None, z_stream=None, y=None, guidance_scale=1.0, edit=None):
         form = self._guidance_form(denoise_fn, y, guidance_scale)
         with self._time_tables(denoise_fn):
-            return self._sample_loop_impl(denoise_fn, shape, device, noise, seed, on_step, z_stream, y, form)
+            return self._sample_loop_impl(denoise_fn, shape, device, noise, seed, on_step, z_stream, y, form, edit)
 
-    def _sample_loop_impl(self, denoise_fn, shape, device, noise, seed, on_step=None, z_stream=None, y=None, form=None):
+    def _sample_loop_impl(self, denoise_fn, shape, device, noise, seed, on_step=None, z_stream=None, y=None, form=None, edit=None):
         """The T-step (or S-step) loop.  ``z_stream`` (parity tests only) is an iterator of per-step noise tensors
         that replaces the generator draws, so an identical (x_T, z_1..z_T) stream can be injected.  ``y`` / ``form``: class labels and
         the way they are used (``_guidance_form``); the RNG consumption of every form is that of the unconditional loop.
+        ``edit`` = (x_0, start) (``GaussianDiffusion.edit``): the chain begins at index ``start`` from ``q_sample(x_0, start)``, whose
+        draw takes the place of the x_T draw, and runs ``start + 1`` steps.
 
         The step body (model call, noise draw, fused update, t -= 1) has static shapes, so it is captured ONCE into a
         hipGraph and replayed: at 32x32 the eager loop is bound by ~250 kernel launches per step, not by the GPU.
@@ -457,18 +489,20 @@ class GaussianDiffusion:
         device = torch.device(device)
         _hip.require_cuda(torch.empty(0, device=device))        # no CPU fallback: sampling runs on the GPU only
         B = (shape or noise.shape)[0]
-        steps = self._num_steps()
+        steps = self._num_steps() if edit is None else edit[1] + 1
         if form is not None:
             y = torch.as_tensor(y).to(device=device, dtype=torch.int64).contiguous()
             if y.shape != (B,):
                 raise ValueError(f"expected class labels y of shape [{B}], got {tuple(y.shape)}")
         if (on_step is None and steps >= 4 and device.type == "cuda"
                 and os.environ.get("DDPM_TORCH_AMD_GRAPH", "1") != "0" and not torch.cuda.is_current_stream_capturing()):
-            done = self._graph_loop(denoise_fn, tuple(shape or noise.shape), device, noise, seed, steps, z_stream, y, form)
+            done = self._graph_loop(denoise_fn, tuple(shape or noise.shape), device, noise, seed, steps, z_stream, y, form, edit)
             if done is not None:
                 return done
         rng = torch.Generator(device).manual_seed(seed) if seed is not None else None       # diffusion.py:164-166
-        if noise is None:
+        if edit is not None:
+            x_t = self._edit_state(edit, rng)
+        elif noise is None:
             x_t = torch.empty(shape, device=device).normal_(generator=rng)                  # x_T first, then one z per step
         else:
             x_t = noise.to(device)
@@ -562,7 +596,13 @@ class GaussianDiffusion:
                 cache[key] = ent
         return ent
 
-    def _graph_loop(self, denoise_fn, shape, device, noise, seed, steps, z_stream=None, y=None, form=None):
+    def _edit_state(self, edit, rng):
+        """q_sample(x_0, start) on one draw from ``rng``: where an edited chain begins (``edit`` = (x_0, start))."""
+        x_0, start = edit
+        t = torch.full((x_0.shape[0],), start, dtype=torch.int64, device=x_0.device)
+        return self.q_sample(x_0, t, noise=torch.empty_like(x_0).normal_(generator=rng))
+
+    def _graph_loop(self, denoise_fn, shape, device, noise, seed, steps, z_stream=None, y=None, form=None, edit=None):
         """Replay the captured sampling step ``steps`` times; returns None if capture is not possible (the caller then
         runs the eager loop; no RNG state has been consumed).  ``z_stream`` (parity tests only): per-step noise tensors that are copied
         into the captured step's noise buffer instead of being drawn inside it.  ``form`` (``_guidance_form``) extends the cache key: a
@@ -578,7 +618,9 @@ class GaussianDiffusion:
             e.ensure_fresh()
         if rng is not None:
             rng.manual_seed(seed)
-        if noise is None:
+        if edit is not None:
+            x_t.copy_(self._edit_state(edit, rng))                # the draw of q_sample in the place of the x_T draw
+        elif noise is None:
             x_t.normal_(generator=rng)                            # x_T first, then one z per step (diffusion.py:166-171)
         else:
             x_t.copy_(noise)
@@ -595,6 +637,8 @@ class GaussianDiffusion:
         """Capture a step the cache knows under an extended key: here the conditional and the guided sampling step (``_guidance_form``)."""
         if kind[0] in ("cond", "cfg"):
             return self._capture_sample_step(denoise_fn, shape, device, default_rng, external_z, form=kind)
+        if kind[0] == "inpaint":
+            return self._capture_inpaint_steps(denoise_fn, shape, device, default_rng, external_z, kind)
         raise NotImplementedError(kind)
 
     def prepare_sampler(self, denoise_fn, shape, device, seeded=True):
@@ -694,6 +738,176 @@ class GaussianDiffusion:
 
         x = self._sample_loop(denoise_fn, shape, device, noise, seed, on_step=keep, z_stream=z_stream, y=y, guidance_scale=guidance_scale)
         return x.cpu(), preds
+
+    # ------------------------------------------------------------------ inpainting and image editing (not in the reference)
+    # RePaint (Lugmayr et al., CVPR 2022, Algorithm 1) as a sampling-loop feature.  Index convention of every loop here: the device ``t``
+    # buffer is the index of the current state (S - 1 at the start, -1 when clean); a reverse step at t = i takes the state from i to i - 1
+    # and re-noises the known region to i - 1; a jump adds j to t, then applies `ddpm_q_jump` at the new index.
+    def _jump_tables(self, j, device):
+        """(ja, jb) of `ddpm_q_jump` for jumps of ``j`` levels, indexed by the arrival index i: ja[i] = sqrt(ab[i] / ab[i-j]),
+        jb[i] = sqrt(1 - ab[i] / ab[i-j]) with ab[-1] = 1, NaN where i - j < -1.  Formed in fp64 (the ratio of two fp32 table entries
+        would lose about three digits of 1 - a at small betas); the fp32 device copies are cached per (j, device) by ``_tab``."""
+        names = (f"repaint_jump_a_{j}", f"repaint_jump_b_{j}")
+        if not hasattr(self, names[0]):
+            ab = torch.cat([torch.ones(1, dtype=_F64), self.alphas_bar.to(_F64)])           # ab[i] sits at i + 1
+            i = torch.arange(len(self.alphas_bar))
+            src = i - j + 1
+            ratio = torch.where(src >= 0, ab[i + 1] / ab[src.clamp_min(0)], torch.full((len(i),), float("nan"), dtype=_F64))
+            setattr(self, names[0], ratio.sqrt())
+            setattr(self, names[1], (1.0 - ratio).sqrt())
+        return [self._tab(n_, device) for n_ in names]
+
+    @staticmethod
+    def _inpaint_mask(mask, shape, device):
+        """The mask as the kernel reads it: fp32 [1 or B][H * W], 1 = keep the known pixel, 0 = generate, from ``[H, W]``, ``[1, 1, H, W]``
+        or ``[B, 1, H, W]`` of dtype bool, uint8 or float.  ValueError for another shape, NaN or a value outside [0, 1]."""
+        B, _, H, W = shape
+        m = torch.as_tensor(mask)
+        if tuple(m.shape) == (H, W):
+            m = m.reshape(1, H * W)
+        elif tuple(m.shape) in ((1, 1, H, W), (B, 1, H, W)):
+            m = m.reshape(m.shape[0], H * W)
+        else:
+            raise ValueError(f"expected a mask of shape [{H}, {W}], [1, 1, {H}, {W}] or [{B}, 1, {H}, {W}], got {tuple(m.shape)}")
+        if not (m.dtype in (torch.bool, torch.uint8) or m.dtype.is_floating_point):
+            raise ValueError(f"expected a bool, uint8 or floating-point mask, got {m.dtype}")
+        m = m.to(torch.float32)
+        if not bool(((m >= 0) & (m <= 1)).all()):                                           # (NaN compares false)
+            raise ValueError("mask values lie in [0, 1]: 1 = keep the known pixel, 0 = generate")
+        return m.to(device).contiguous()
+
+    def _inpaint_state(self, denoise_fn, shape, dev, rng, external_z, kind):
+        """Buffers and the two step bodies of an inpainting chain.  "down": network, two draws (z of the reverse step, then e of the
+        re-noising), the masked step in place, t -= 1.  "up" (kind's j > 0): t += j, one draw, `ddpm_q_jump` in place."""
+        _, j, mask_rows, form = kind
+        B, n, hw = shape[0], shape[1] * shape[2] * shape[3], shape[2] * shape[3]
+        S = self._num_steps()
+        x_t = torch.zeros(shape, dtype=torch.float32, device=dev)
+        z, e, x_known = torch.zeros_like(x_t), torch.zeros_like(x_t), torch.zeros_like(x_t)
+        mask = torch.zeros((mask_rows, hw), dtype=torch.float32, device=dev)
+        t = torch.full((B,), S - 1, dtype=torch.int64, device=dev)
+        y = None if form is None else torch.zeros((B,), dtype=torch.int64, device=dev)
+        mode = self._var_mode()
+        tabs = self._lv_tabs(dev) if mode else [self._tab(n_, dev).data_ptr() for n_ in _STEP_TABLES] + [0]
+        tabs = tabs + [self._tab(n_, dev).data_ptr() for n_ in ("sqrt_alphas_bar_prev", "sqrt_one_minus_alphas_bar_prev")]
+        code, clip, T = _MEAN_CODE[self.model_mean_type], int(bool(self.clip_sampling)), len(self.posterior_mean_coef1)
+        jump = [tb.data_ptr() for tb in self._jump_tables(j, dev)] if j else None
+
+        def down(cut=None):
+            out = (denoise_fn(x_t, self._model_t(t)) if y is None else denoise_fn(x_t, self._model_t(t), y)).contiguous().float()
+            if self.learned_var:
+                self._check_two_halves(out, x_t)
+            elif out.shape != x_t.shape:
+                raise ValueError(f"the network returned {tuple(out.shape)} for an input of {tuple(x_t.shape)}")
+            if not external_z:
+                z.normal_(generator=rng)
+                e.normal_(generator=rng)
+            _hip.call("ddpm_p_sample_step_masked", x_t.data_ptr(), out.data_ptr(), z.data_ptr(), x_known.data_ptr(), e.data_ptr(), mask.data_ptr(),
+                      t.data_ptr(), *tabs, x_t.data_ptr(), B, n, hw, mask_rows, out[0].numel(), code, clip, mode, T, _hip.stream())    # in place
+            _hip.call("ddpm_add_i64", t.data_ptr(), B, -1, _hip.stream())
+
+        def up(cut=None):
+            _hip.call("ddpm_add_i64", t.data_ptr(), B, j, _hip.stream())
+            if not external_z:
+                z.normal_(generator=rng)
+            _hip.call("ddpm_q_jump", x_t.data_ptr(), z.data_ptr(), t.data_ptr(), *jump, x_t.data_ptr(), B, n, T, _hip.stream())       # in place
+
+        return {"x_t": x_t, "z": z, "e": e, "x_known": x_known, "mask": mask, "t": t, "y": y, "rng": rng, "down": down, "up": up if j else None,
+                "ref": lambda: denoise_fn}
+
+    def _capture_inpaint_steps(self, denoise_fn, shape, device, default_rng, external_z, kind):
+        """One cache entry, two graphs over the same buffers, replayed by the host in schedule order."""
+        rng = None if default_rng else torch.Generator(device)
+        ent = self._inpaint_state(denoise_fn, shape, device, rng, external_z, kind)
+        for name in ("down", "up"):
+            if ent[name] is not None:
+                graph = self._capture_step(device, rng, ent[name], "inpainting " + name)
+                if graph is None:
+                    return None
+                ent[name] = graph.replay
+        return ent
+
+    def inpaint(self, denoise_fn, x_known, mask, jump_length=1, resamples=1, start=None, seed=None, noise=None, y=None, z_stream=None):
+        """Fill the region of ``x_known`` ([B, C, H, W] in [-1, 1]) where ``mask`` is 0 and keep it where ``mask`` is 1 (RePaint, Lugmayr
+        et al. 2022): ``[B, C, H, W]`` float32 on ``x_known``'s device, whose known region is the source image itself.  ``mask``: ``[H, W]``,
+        ``[1, 1, H, W]`` or ``[B, 1, H, W]``, bool, uint8 or float in [0, 1] (a soft value blends the two regions), broadcast over channels.
+        At every level the known region is re-noised from ``x_known`` and the unknown one comes from the reverse step — one fused kernel
+        behind the network (csrc/inpaint.hip).  ``jump_length`` / ``resamples``: the chain jumps back up ``jump_length`` levels and comes
+        down again ``resamples`` times so that the two regions harmonise (``repaint_schedule``; 1 = the plain replacement method).
+        ``start`` = None: the state begins as x_T (a draw, or ``noise``) at index S - 1; ``start`` = i: as ``q_sample(x_known, i)`` on one
+        draw (or ``noise``) in place of the x_T draw.  RNG order: the initial draw, then per reverse step z, then e, and one draw per
+        jump, from a generator seeded with ``seed`` on the device (else the default one); ``z_stream`` (parity tests) supplies exactly
+        those tensors in that order.  ``y``: class labels of a class-conditional network at guidance scale 1.  Learned-variance models are
+        served.  The two step bodies are captured once and replayed in schedule order like the sampling step (same cache, same fallback to
+        the eager loop, which issues the same launches one by one and gives the same bits)."""
+        form = self._guidance_form(denoise_fn, y, 1.0)              # None or ("cond",), by the rule p_sample and edit go through
+        with torch.inference_mode(), self._time_tables(denoise_fn):
+            return self._inpaint_impl(denoise_fn, x_known, mask, int(jump_length), int(resamples), start, seed, noise, y, z_stream, form)
+
+    def _inpaint_impl(self, denoise_fn, x_known, mask, j, r, start, seed, noise, y, z_stream, form):
+        x_known, = self._prep(x_known)
+        if x_known.ndim != 4:
+            raise ValueError(f"expected x_known of shape [B, C, H, W], got {tuple(x_known.shape)}")
+        if noise is not None and z_stream is not None:
+            raise ValueError("z_stream supplies the initial draw as its first tensor: give noise or z_stream, not both")
+        dev, shape, S = x_known.device, tuple(x_known.shape), self._num_steps()
+        B = shape[0]
+        ops = repaint_schedule(S, j, r, start)
+        top = S - 1 if start is None else int(start)
+        m = self._inpaint_mask(mask, shape, dev)
+        if form is not None:
+            y = torch.as_tensor(y).to(device=dev, dtype=torch.int64).contiguous()
+            if y.shape != (B,):
+                raise ValueError(f"expected class labels y of shape [{B}], got {tuple(y.shape)}")
+        kind = ("inpaint", j if "up" in ops else 0, m.shape[0], form)
+        external = z_stream is not None
+        ent = None
+        if (ops.count("down") >= 4 and dev.type == "cuda" and os.environ.get("DDPM_TORCH_AMD_GRAPH", "1") != "0"
+                and not torch.cuda.is_current_stream_capturing()):
+            ent = self._graph_entry(denoise_fn, shape, dev, default_rng=seed is None, external_z=external, kind=kind)
+        if ent is not None:
+            for eng in self._engines_of(denoise_fn) or ():
+                eng.ensure_fresh()
+        else:
+            ent = self._inpaint_state(denoise_fn, shape, dev, torch.Generator(dev) if seed is not None else None, external, kind)
+        rng = ent["rng"]
+        if rng is not None:
+            rng.manual_seed(seed)
+        x_t, z = ent["x_t"], ent["z"]
+        ent["x_known"].copy_(x_known)
+        ent["mask"].copy_(m)
+        if form is not None:
+            ent["y"].copy_(y)
+        if external:
+            first = next(z_stream).to(x_t)
+        elif noise is not None:
+            first = noise.to(x_t)
+        else:
+            first = z.normal_(generator=rng)                      # the initial draw first, then z and e per reverse step, one draw per jump
+        ent["t"].fill_(top)
+        if start is None:
+            x_t.copy_(first)
+        else:
+            x_t.copy_(self.q_sample(x_known, ent["t"], noise=first.contiguous()))
+        for op in ops:
+            if external:
+                z.copy_(next(z_stream))
+                if op == "down":
+                    ent["e"].copy_(next(z_stream))
+            ent[op]()
+        return x_t.clone()
+
+    def edit(self, denoise_fn, x_0, start, seed=None, y=None):
+        """SDEdit-style editing: ``q_sample(x_0, start)`` on one draw, then the sampling step from index ``start`` down — the existing
+        (captured) sampling step with ``t`` filled to ``start`` and run ``start + 1`` times.  RNG order: the q_sample draw, then one z
+        per step.  Equals ``inpaint`` with an all-zero mask and the same ``start`` bit for bit when both are given the same draws.
+        ``y``: class labels at guidance scale 1.  Returns ``[B, C, H, W]`` float32 on ``x_0``'s device."""
+        x_0, = self._prep(x_0)
+        start = int(start)
+        if not 0 <= start <= self._num_steps() - 1:
+            raise ValueError(f"the chain starts at an index in [0, {self._num_steps() - 1}], got {start}")
+        with torch.inference_mode():
+            return self._sample_loop(denoise_fn, tuple(x_0.shape), x_0.device, None, seed, y=y, edit=(x_0, start))
 
     # ------------------------------------------------------------------ negative log-likelihood in bits per dimension
     # t = 0 likelihood of the evaluation: 0 = discretized Gaussian (functions.py:49-65); the 2-D toy subclass uses 1, the continuous one

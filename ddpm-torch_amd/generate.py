@@ -11,6 +11,13 @@ prints the error.  Both need ``--use-ddim --eta 0``.
 
     python generate.py --dataset celeba --use-ddim --interpolate 9 --total-size 16 --seed 0
     python generate.py --dataset celeba --use-ddim --reconstruct --source faces.pt
+
+Conditioning a chain on pixels (``GaussianDiffusion.inpaint`` / ``edit``; either sampler): ``--inpaint MASK`` fills the part of every
+``--source`` image the mask leaves open (RePaint; ``--jump-length`` / ``--resamples`` for its resampling) and writes source | masked source |
+result, ``--edit-start I`` starts the chain from the source noised to index I (SDEdit) and writes source | result.
+
+    python generate.py --dataset celeba --inpaint left --source faces.pt --jump-length 10 --resamples 10 --seed 0
+    python generate.py --dataset celeba --use-ddim --edit-start 20 --source faces.pt
 """
 import argparse
 import json
@@ -63,10 +70,28 @@ def parse_args(argv=None):
         "pairs of drawn latents, or the consecutive pairs of --source), one grid picture per pair; needs --use-ddim --eta 0")
     add("--reconstruct", action="store_true", help="encode every --source image and decode it again; writes input | reconstruction and prints "
         "the mean squared error per dimension on the [0, 1] scale (Song et al. 2020, Table 2)")
-    add("--source", default="", type=str, help="images for --interpolate / --reconstruct: a tensor file ([N, C, H, W], uint8 or float in [-1, 1]) "
-        "or a folder of pictures at the dataset's resolution")
+    add("--source", default="", type=str, help="images for --interpolate / --reconstruct / --inpaint / --edit-start: a tensor file ([N, C, H, W], "
+        "uint8 or float in [-1, 1]) or a folder of pictures at the dataset's resolution")
+    add("--inpaint", default="", type=str, metavar="MASK", help="fill the masked region of every --source image: left | right | top | bottom "
+        "(keep that half), center (generate the central half-side square), or a tensor / image file holding the mask (1 = keep, 0 = generate)")
+    add("--jump-length", default=1, type=int, metavar="J", help="--inpaint: levels a RePaint chain jumps back up before it comes down again")
+    add("--resamples", default=1, type=int, metavar="R", help="--inpaint: times every stretch of J levels is walked (1 = no jump)")
+    add("--edit-start", default=None, type=int, metavar="I", help="start the chain from every --source image noised to index I (SDEdit); "
+        "with --inpaint: where the inpainting chain starts")
     args = p.parse_args(argv)
-    if args.interpolate or args.reconstruct:
+    if args.inpaint or args.edit_start is not None:
+        what = "--inpaint" if args.inpaint else "--edit-start"
+        if not args.source:
+            p.error(f"{what} requires --source")
+        if args.interpolate or args.reconstruct:
+            p.error(f"{what} and --interpolate / --reconstruct are separate runs")
+        if args.guidance_scale != 1.0:
+            p.error(f"{what} samples at --guidance-scale 1")
+        if args.num_gpus > 1:
+            p.error(f"{what} runs on one GPU")
+        if args.jump_length < 1 or args.resamples < 1:
+            p.error("--jump-length and --resamples are at least 1")
+    elif args.interpolate or args.reconstruct:
         what = "--interpolate" if args.interpolate else "--reconstruct"
         if not args.use_ddim or args.eta != 0:
             p.error(f"{what} runs the deterministic sampler both ways: it requires --use-ddim --eta 0")
@@ -79,7 +104,7 @@ def parse_args(argv=None):
         if args.num_gpus > 1:
             p.error(f"{what} runs on one GPU")
     elif args.source:
-        p.error("--source is read by --interpolate and --reconstruct only")
+        p.error("--source is read by --interpolate, --reconstruct, --inpaint and --edit-start only")
     if args.guidance_scale != 1.0 and not args.labels:
         p.error("--guidance-scale guides towards the classes of --labels")
     if args.labels and (args.interpolate or args.reconstruct):
@@ -262,8 +287,73 @@ def invert(args):
     return out_dir
 
 
+MASK_NAMES = ("left", "right", "top", "bottom", "center")
+
+
+def mask_of(spec, shape):
+    """``--inpaint MASK`` as a float [H, W] (or [1 | N, 1, H, W] from a file) mask, 1 = keep: a half-image name keeps that half, "center"
+    generates the central half-side square; anything else is a tensor file or a picture (grey level / 255)."""
+    H, W = shape[1], shape[2]
+    if spec in MASK_NAMES:
+        m = torch.zeros(H, W)
+        if spec == "left":
+            m[:, :W // 2] = 1
+        elif spec == "right":
+            m[:, W - W // 2:] = 1
+        elif spec == "top":
+            m[:H // 2] = 1
+        elif spec == "bottom":
+            m[H - H // 2:] = 1
+        else:
+            m[:] = 1
+            m[H // 4:H // 4 + H // 2, W // 4:W // 4 + W // 2] = 0
+        return m
+    if not os.path.isfile(spec):
+        raise ValueError(f"--inpaint {spec!r}: expected one of {', '.join(MASK_NAMES)} or a mask file")
+    if spec.lower().endswith((".png", ".jpg", ".jpeg", ".bmp")):
+        import numpy as np
+        from PIL import Image
+        return torch.from_numpy(np.asarray(Image.open(spec).convert("L")).copy()).float() / 255.0
+    m = torch.load(spec, map_location="cpu")
+    if not torch.is_tensor(m):
+        raise ValueError(f"--inpaint {spec}: expected a tensor, got {type(m).__name__}")
+    return m
+
+
+def condition(args):
+    """--inpaint / --edit-start: deterministic file names (inpaint_00000.png, ...), so a seeded run repeats byte for byte."""
+    from ddpm_torch.utils import save_image_grid
+    process, model, device, shape, out_dir = build(args)
+    os.makedirs(out_dir, exist_ok=True)
+    src = load_source(args.source, shape)
+    mask = mask_of(args.inpaint, shape) if args.inpaint else None
+    num_classes = next((m.num_classes for m in model.modules() if getattr(m, "num_classes", None) is not None), None)
+    done = chain = 0
+    for i in range(0, len(src), args.batch_size):
+        x = src[i:i + args.batch_size].to(device)
+        y = labels_of(args.labels, num_classes, done, len(x), device) if args.labels else None
+        seed = None if args.seed is None else args.seed + chain
+        if mask is None:
+            out = process.edit(model, x, args.edit_start, seed=seed, y=y)
+            panels = [x, out]
+        else:
+            m = mask[i:i + len(x)] if mask.ndim == 4 and mask.shape[0] > 1 else mask
+            out = process.inpaint(model, x, m, jump_length=args.jump_length, resamples=args.resamples, start=args.edit_start, seed=seed, y=y)
+            shown = m.to(device).float().reshape((-1, 1) + tuple(shape[1:]))
+            panels = [x, x * shown, out]                          # the open region of the masked source is mid-grey
+        for j in range(len(x)):
+            save_image_grid(torch.stack([p[j] for p in panels]), os.path.join(out_dir, f"inpaint_{done + j:05d}.png"), nrow=len(panels))
+        done += len(x)
+        chain += 1
+        print(f"\r{done}/{len(src)}", end="", flush=True)
+    print()
+    return out_dir
+
+
 def main(argv=None):
     args = parse_args(argv)
+    if args.inpaint or args.edit_start is not None:
+        return condition(args)
     if args.interpolate or args.reconstruct:
         return invert(args)
     if args.num_gpus > 1:

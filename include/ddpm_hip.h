@@ -382,6 +382,42 @@ int ddpm_add_i64(long long* t, int B, long long delta, void* stream);
 int ddpm_ddim_encode_step(const float* x, const float* model_out, const long long* t, const float* cx, const float* ce,
                           const float* sqrt_recip_ab_prev, const float* sqrt_recip_m1_ab_prev, float* x_next, float* pred_x0,
                           int B, int n, int S, void* stream);
+/* Inpainting and image editing (csrc/inpaint.hip; RePaint: Lugmayr et al., CVPR 2022, Algorithm 1).  fp32; t is int64; every product and
+ * sum is rounded on its own (no contraction) except the two fused operations of ddpm_p_sample_step's update.  Static LDS only, no atomics,
+ * no allocation: each is capturable as a first call.
+ * ddpm_p_sample_step_masked: one reverse step whose known region is re-noised from a source image.  x_t, z, x_known, e, x_prev are [B][n];
+ *   model_out rows are out_pitch floats apart, out_pitch = n, or 2n for a 2C-channel network (mean output | v); var_mode 1 | 2 needs 2n and
+ *   reads v at row[n + i] exactly as ddpm_p_sample_step_lv does, var_mode 0 with 2n reads the mean half alone (a DDIM on such a model).
+ *   mask is [mask_rows][hw], mask_rows = 1 (one mask for the batch) or B, n % hw == 0: element i of sample b uses
+ *   m = mask[mask_rows == 1 ? 0 : b][i % hw] (the mask is broadcast over channels), values in [0, 1], 1 = keep the known pixel, 0 = generate.
+ *     u = x_prev of ddpm_p_sample_step (var_mode 0, logvar_lo the fixed table) / ddpm_p_sample_step_lv (var_mode 1 | 2, logvar_lo = lv_min,
+ *         logvar_hi = lv_max) on the same x_t, model_out, z, t, tables, mean_type, clip: the same coefficients, noise mask 1[t>0],
+ *         expf(0.5f * lv) and variance policy, so the same bits
+ *     k = sqrt_ab_prev[t] * x_known + sqrt_1mab_prev[t] * e                  (two products and one sum, each rounded)
+ *     x_prev = u where m == 0;  k where m == 1;  m * k + (1 - m) * u otherwise (1 - m formed once; two products and a sum, three roundings)
+ *   The two exact cases are selects: NaN in x_known or e under m == 0, or in x_t, model_out or z under m == 1, does not reach the output.
+ *   sqrt_ab_prev[t] = sqrt(ab[t-1]), sqrt_1mab_prev[t] = sqrt(1 - ab[t-1]) with ab[-1] = 1: the level the step arrives at, so at t = 0 the
+ *   tables give 1 * x_known + 0 * e and the known region of the final image is the source image itself (up to the sign of a zero).
+ *   There is no pred_x0 output.  x_prev may be x_t (an element is read once, then written, by one lane).  A sample whose t is outside
+ *   [0, T) gets a row of NaN, no table is read for it and no other sample is touched.  grid = (column blocks, B).  A sample whose row bases
+ *   (x_t, the mean half, the v half when read, z, x_known, e, x_prev and its mask row) are all 16-byte aligned, with hw % 4 == 0, is moved
+ *   16 bytes per lane, any other one element-wise; both paths give the same bits.
+ *   Status: a required pointer NULL DDPM_ERR_NULL (logvar_lo may be NULL in var_mode 1 only, logvar_hi is required in var_mode 2 only, as
+ *   in ddpm_p_sample_step_lv); B, n, hw or T <= 0, B > 65535, n % hw != 0, mask_rows not in {1, B}, out_pitch not in {n, 2n}, var_mode 1 | 2
+ *   with out_pitch != 2n, mean_type or var_mode outside 0..2 DDPM_ERR_SHAPE; a pointer that is not a multiple of its element size
+ *   DDPM_ERR_ALIGN.
+ * ddpm_q_jump: the forward process across j levels, x_out = ja[t] * x + jb[t] * z (two products and a sum, each rounded), with t the index
+ *   the state ARRIVES at: ja[i] = sqrt(ab[i] / ab[i-j]), jb[i] = sqrt(1 - ab[i] / ab[i-j]), formed in fp64 on the host (the ratio of two
+ *   fp32 table entries would lose about three digits of 1 - a at small betas).  x, z, x_out are [B][n], the tables have length T.  x_out may
+ *   be x (ddpm_q_sample cannot serve: its operands are restrict-qualified and it has no 16-byte path).  Bad t, the 16-byte and the
+ *   element-wise path (a scalar tail after n / 4 * 4 elements) and the status codes are those of the masked step. */
+int ddpm_p_sample_step_masked(const float* x_t, const float* model_out, const float* z, const float* x_known, const float* e,
+                              const float* mask, const long long* t, const float* sqrt_recip_ab, const float* sqrt_recip_m1_ab,
+                              const float* post_coef1, const float* post_coef2, const float* logvar_lo, const float* logvar_hi,
+                              const float* sqrt_ab_prev, const float* sqrt_1mab_prev, float* x_prev, int B, int n, int hw,
+                              int mask_rows, int out_pitch, int mean_type, int clip, int var_mode, int T, void* stream);
+int ddpm_q_jump(const float* x, const float* z, const long long* t, const float* ja, const float* jb, float* x_out, int B, int n, int T,
+                void* stream);
 /* Spherical interpolation of latents (Song et al. 2020 eq. 67), per pair p over the whole flattened sample: a, b [P][n], alpha [K],
  * out [P][K][n], fp32.
  *   c = clamp(<a,b> / (|a| |b|), -1, 1),  th = acos(c)
